@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — suggest-step throughput of the HIP GP-posterior + acquisition engine on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--no-cpu-baseline] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input (BASELINE.json metric,
 configs[2] = C3 when it fits one GPU): fit the GP at fixed theta (K, Cholesky, W = L^-1, alpha), then
@@ -658,6 +658,29 @@ def emit_failed(args, n_gpus, why):
                       "config": {"workload": args.config or "C4", "collective": "FAILED"}, "error": why}), flush=True)
 
 
+DUMP_MAX_VALUES = 1 << 20   # acquisition values written whole up to this many (8 MB), a fixed sample of this size beyond
+
+
+def dump_outputs(d, best, ys=None):
+    """--dump-outputs: the timed path's answer of its last step as float64 .npy files, so that two builds can be compared
+    output for output (the inputs depend on the arguments alone).  best = (index, value, top-k indices, top-k values) as a
+    caller of the arg-best receives it; ys = the acquisition value of every candidate (a seeded sample of a larger set,
+    with the candidate indices it holds)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"best_index": np.array([best[0]], dtype=np.float64), "best_value": np.array([best[1]], dtype=np.float64),
+              "topk_index": np.asarray(best[2], dtype=np.float64), "topk_value": np.asarray(best[3], dtype=np.float64)}
+    if ys is not None:
+        ys = np.asarray(ys, dtype=np.float64)
+        if ys.size > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.RandomState(0).choice(ys.size, DUMP_MAX_VALUES, replace=False))
+            arrays["acq_values_index"] = idx.astype(np.float64)
+            ys = ys[idx]
+        arrays["acq_values"] = ys
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), a)
+    log(f"[bench] wrote {', '.join(sorted(arrays))} to {d}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -671,7 +694,11 @@ def main():
     ap.add_argument("--suggest-only", action="store_true", help="(child of a multi-rank run) print only the suggest_ms object")
     ap.add_argument("--no-extra-configs", action="store_true",
                     help="skip the other BASELINE.json configs (C2, C4 shard 0, C5 fp32 shard 0) run after the default headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # collectives wait with a deadline (comm.hip); the closing barrier of a multi-rank run has to outlast rank 0's child process
     os.environ.setdefault("GPBO_COMM_TIMEOUT_S", "300")
@@ -821,6 +848,12 @@ def main():
         kern_ms["posterior_main"] += post_ms[0] - tm["posterior_main"]   # both GPs' posterior launches
     barrier_max(0.0)
     elapsed = barrier_max(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        ys = None
+        if mode != "ranks":   # the acquisition values behind that arg-best, read back outside the timed region
+            ys = eng.acq_argbest(w.acq, w.acq_param, 0.0 if y_max is None else y_max, lb_c, ub_c, k_seeds=0,
+                                 return_values=True)[4]
+        dump_outputs(args.dump_outputs, best, ys)
     per_rank = None
     if mode == "ranks":
         # every rank's stage times of its last step, gathered as (value, rank) records over the same RCCL communicator

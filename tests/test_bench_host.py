@@ -239,3 +239,27 @@ def test_the_summary_is_the_last_key_material_and_stays_small():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.index('out["summary"] = summary_of(out)') < src.index("print(json.dumps(out), flush=True)")
     assert src.count('out["') and src[src.index('out["summary"] = summary_of(out)'):src.index("print(json.dumps(out), flush=True)")].count('out["') <= 2
+
+
+def test_dump_outputs_writes_float_arrays_within_the_size_bound(tmp_path):
+    """--dump-outputs: the arg-best as a caller receives it plus the acquisition values, float64 .npy files; a candidate set
+    larger than the bound is written as a fixed sample (the same indices every run) with the indices it holds."""
+    b = _bench()
+    ys = np.random.RandomState(3).randn(b.DUMP_MAX_VALUES + 5)
+    best = (7, -1.5, np.array([7, 2, 9]), np.array([-1.5, -1.0, 0.25]))
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), best, ys)
+    names = sorted(p[:-4] for p in os.listdir(tmp_path / "a"))
+    assert names == ["acq_values", "acq_values_index", "best_index", "best_value", "topk_index", "topk_value"]
+    total = 0
+    for n in names:
+        a, a2 = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, a2)
+        total += a.nbytes
+    assert total <= 64 << 20
+    idx = np.load(tmp_path / "a" / "acq_values_index.npy").astype(np.int64)
+    assert idx.size == b.DUMP_MAX_VALUES and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "acq_values.npy"), ys[idx])
+    assert np.load(tmp_path / "a" / "best_index.npy")[0] == 7
+    b.dump_outputs(str(tmp_path / "c"), best, None)
+    assert sorted(os.listdir(tmp_path / "c")) == ["best_index.npy", "best_value.npy", "topk_index.npy", "topk_value.npy"]

@@ -1,5 +1,5 @@
-"""CPU: host-side mirror of the reference interface (space, acquisition orchestration, merge rules),
-checked against the reference itself when /root/reference is mounted."""
+"""CPU: host-side mirror of the reference interface (space, acquisition orchestration, merge rules), checked against what
+the reference itself returns (tests/golden/reference_host.npz, written by oracle/gen_reference_host.py)."""
 import numpy as np
 import pytest
 
@@ -7,9 +7,8 @@ from bayesianoptimization_amd import fused_acquisition as A
 from bayesianoptimization_amd import workloads as W
 from bayesianoptimization_amd.distributed import merge_best, shard_range
 from bayesianoptimization_amd.float_space import FloatSpace, ensure_rng
-from oracle.refenv import have_reference, import_reference
-
-needs_ref = pytest.mark.skipif(not have_reference(), reason="reference not mounted (GPU box)")
+from conftest import load_golden
+from oracle.gen_reference_host import untext
 
 
 def test_ensure_rng():
@@ -64,18 +63,15 @@ def test_floatspace_protocol_and_target_max():
     assert sp.random_sample(0, 3).shape == (2,)
 
 
-@needs_ref
 def test_candidate_stream_equals_reference():
-    import_reference()
-    from bayes_opt.target_space import TargetSpace
-
+    """TargetSpace(None, pbounds).random_sample(777, RandomState(7)) and .bounds of the reference, stored."""
+    g = load_golden("reference_host")
     for w in (W.C1, W.C2, W.C5S):
-        ts = TargetSpace(None, w.pbounds())
-        a = ts.random_sample(777, np.random.RandomState(7))
+        a = g[f"cand_{w.name}"]
         b = FloatSpace(w.pbounds()).random_sample(777, np.random.RandomState(7))
         c = W.make_candidates(w.bounds_array(), 777, 7)
         assert np.array_equal(a, b) and np.array_equal(a, c)
-        assert np.array_equal(ts.bounds, FloatSpace(w.pbounds()).bounds)
+        assert np.array_equal(g[f"bounds_{w.name}"], FloatSpace(w.pbounds()).bounds)
 
 
 def _mk_spaces(w, n=40):
@@ -85,37 +81,28 @@ def _mk_spaces(w, n=40):
     return sp, X[:n], y[:n]
 
 
-@needs_ref
 @pytest.mark.parametrize("kind", ["ucb", "ei", "poi"])
 @pytest.mark.parametrize("n_smart", [0, 3])
 def test_host_orchestration_equals_reference(kind, n_smart):
-    """Same GP object, same seeds: the restated suggest()/_acq_min/_smart_minimize give the SAME point
-    as bayes_opt's (non-fused path, plain sklearn GP), and consume the RandomState identically."""
-    import_reference()
-    from bayes_opt import acquisition as RA
-    from bayes_opt.target_space import TargetSpace
+    """Same GP, same seeds: the restated suggest()/_acq_min/_smart_minimize give the SAME points as bayes_opt's (non-fused
+    path, plain sklearn GP; its two suggestions stored), and consume the RandomState identically."""
     from sklearn.gaussian_process import GaussianProcessRegressor
     from sklearn.gaussian_process.kernels import Matern
 
+    g = load_golden("reference_host")
+    key = f"orch_{kind}_{n_smart}"
     w = W.P1
     sp, X, y = _mk_spaces(w)
-    ts = TargetSpace(None, w.pbounds())
-    for i in range(len(y)):
-        ts.register(X[i], y[i])
     mine = {"ucb": A.UpperConfidenceBound(kappa=1.7, exploration_decay=0.9), "ei": A.ExpectedImprovement(xi=0.02),
             "poi": A.ProbabilityOfImprovement(xi=0.02)}[kind]
-    ref = {"ucb": RA.UpperConfidenceBound(kappa=1.7, exploration_decay=0.9), "ei": RA.ExpectedImprovement(xi=0.02),
-           "poi": RA.ProbabilityOfImprovement(xi=0.02)}[kind]
-    r1, r2 = np.random.RandomState(11), np.random.RandomState(11)
+    r1 = np.random.RandomState(11)
     gp1 = GaussianProcessRegressor(kernel=Matern(nu=2.5, length_scale=0.4), alpha=1e-6, normalize_y=True, optimizer=None)
-    gp2 = GaussianProcessRegressor(kernel=Matern(nu=2.5, length_scale=0.4), alpha=1e-6, normalize_y=True, optimizer=None)
-    for _ in range(2):
+    for x2 in g[key + "_x"]:
         x1 = mine.suggest(gp1, sp, n_random=500, n_smart=n_smart, random_state=r1)
-        x2 = ref.suggest(gp2, ts, n_random=500, n_smart=n_smart, random_state=r2)
         assert np.array_equal(x1, x2)
-    assert r1.uniform() == r2.uniform()  # identical stream position
-    assert mine.i == ref.i == 2
-    assert mine.get_acquisition_params() == ref.get_acquisition_params()
+    assert r1.uniform() == g[key + "_next_uniform"][0]  # identical stream position
+    assert mine.i == g[key + "_i"][0] == 2
+    assert mine.get_acquisition_params() == untext(g[key + "_params"])
 
 
 def test_error_behaviour_matches_reference_contract():

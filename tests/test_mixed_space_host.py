@@ -2,7 +2,8 @@
 
 * `MixedSpace` — the stand-in the GPU box uses, where bayes_opt is not installed — against the reference's TargetSpace
   (bayes_opt/target_space.py:237-301, 340-347, 565-603; parameter.py:237-449): same bounds, masks, samples, RandomState
-  consumption and kernel_transform (its categorical batch behaviour included), bit for bit.
+  consumption and kernel_transform (its categorical batch behaviour included), bit for bit; what the reference returns is
+  stored in tests/golden/reference_host.npz (oracle/gen_reference_host.py).
 * the host half of the device assembly (`GpEngine.generate_candidates_mixed`): float runs go to the device generator with
   the stream state threaded through, int / categorical parameters are drawn by their own `random_sample` from exactly the
   position the device hands back.  Here the two C entry points are replaced by NumPy stand-ins (RandomState itself), so the
@@ -10,7 +11,6 @@
   (tests/test_gpu_seams.py does that on the GPU).
 * `_mixed_groups_on_device`: which spaces qualify."""
 import ctypes as C
-import warnings
 
 import numpy as np
 import pytest
@@ -18,46 +18,39 @@ import pytest
 from bayesianoptimization_amd import fused_acquisition as A
 from bayesianoptimization_amd.engine import GpEngine
 from bayesianoptimization_amd.float_space import FloatSpace, MixedSpace
-from oracle.refenv import have_reference, import_reference
+from conftest import load_golden
+from oracle.gen_reference_host import MIXED_N, untext
 
 PB = {"a": (0.0, 2.0), "n": (-3, 7, int), "b": (1.0, 4.0), "c": ("x", "y", "z"), "e": (5.0, 6.0), "f": (0.0, 1.0), "k": (0, 1, int)}
 
 
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference")
 def test_mixed_space_stand_in_is_the_reference_target_space():
-    import_reference()
-    from bayes_opt.target_space import TargetSpace
-
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        ts = TargetSpace(None, PB)
+    g = load_golden("reference_host")
     ms = MixedSpace(PB)
-    assert ts.keys == ms.keys and ts.dim == ms.dim == 9
-    assert np.array_equal(ts.bounds, ms.bounds)
-    assert all(np.array_equal(ts.masks[k], ms.masks[k]) for k in ts.keys)
-    assert np.array_equal(ts.continuous_dimensions, ms.continuous_dimensions)
-    for n in (0, 1, 7, 5000):
-        r1, r2 = np.random.RandomState(5), np.random.RandomState(5)
-        a, b = ts.random_sample(n, r1), ms.random_sample(n, r2)
-        assert np.array_equal(a, b) and r1.uniform() == r2.uniform()
-        assert np.array_equal(ts.kernel_transform(a), ms.kernel_transform(b))
+    assert untext(g["mixed_keys"]) == ms.keys and g["mixed_dim"][0] == ms.dim == 9
+    assert np.array_equal(g["mixed_bounds"], ms.bounds)
+    assert all(np.array_equal(g[f"mixed_mask_{k}"], ms.masks[k]) for k in ms.keys)
+    assert np.array_equal(g["mixed_continuous_dimensions"], ms.continuous_dimensions)
+    for n in MIXED_N:
+        r2 = np.random.RandomState(5)
+        a, b = g[f"mixed_sample_{n}"], ms.random_sample(n, r2)
+        assert np.array_equal(a, b) and g[f"mixed_sample_{n}_next_uniform"][0] == r2.uniform()
+        assert np.array_equal(g[f"mixed_transform_{n}"], ms.kernel_transform(b))
     # the categorical transform's batch behaviour (parameter.py:446-449): one row keeps its own one-hot, a batch gets every
     # column that is some row's argmax
     x = ms.random_sample(3, np.random.RandomState(1))
     assert np.array_equal(ms.kernel_transform(x[0])[0, 4:7], x[0, 4:7])
     assert ms.kernel_transform(ms.random_sample(500, 2))[:, 4:7].min() == 1.0
-    for k in ts.keys:
-        assert type(ts._params_config[k]).__name__ == type(ms._params_config[k]).__name__
+    assert untext(g["mixed_param_types"]) == {k: type(ms._params_config[k]).__name__ for k in ms.keys}
     # and the reference's own TargetSpace qualifies for the device assembly exactly like the stand-in
     eng = _engine_over(_NumpyLib())
-    g_ref = A._mixed_groups_on_device([_Gp(eng, ts.kernel_transform)], ts, np.random.RandomState(0), 10**5)
     g_ms = A._mixed_groups_on_device([_Gp(eng, ms.kernel_transform)], ms, np.random.RandomState(0), 10**5)
-    assert g_ref is not None and [(g[0], g[1], g[2]) for g in g_ref] == [(g[0], g[1], g[2]) for g in g_ms]
-    assert all(np.array_equal(a[3], b[3]) and np.array_equal(a[4], b[4]) for a, b in zip(g_ref, g_ms))
-    r1, r2 = np.random.RandomState(9), np.random.RandomState(9)
-    want = ts.random_sample(3000, r1)
-    eng.generate_candidates_mixed(3000, g_ref, r2)
-    assert np.array_equal(eng._lib.X, want) and r1.uniform() == r2.uniform()
+    assert g_ms is not None and untext(g["mixed_groups"]) == [[gi[0], gi[1], gi[2]] for gi in g_ms]
+    assert all(np.array_equal(g[f"mixed_group_{j}_lo"], gi[3]) and np.array_equal(g[f"mixed_group_{j}_hi"], gi[4])
+               for j, gi in enumerate(g_ms))
+    r2 = np.random.RandomState(9)
+    eng.generate_candidates_mixed(3000, g_ms, r2)
+    assert np.array_equal(eng._lib.X, g["mixed_sample_3000_seed9"]) and g["mixed_sample_3000_seed9_next_uniform"][0] == r2.uniform()
 
 
 class _NumpyLib:
