@@ -149,6 +149,8 @@ class HipGPR(GaussianProcessRegressor):
     # -- outside the device path ------------------------------------------------------------------
     #: True after a fit that the device path does not cover: every numeric method is then the base class's
     _host_mode = False
+    #: True while `_fit_on_host` runs scikit-learn's fit: its theta search must not reach the engine either
+    _host_fitting = False
 
     def _unsupported_reason(self, kernel, y=None, X=None):
         """Why this configuration is outside the device path (None when it is inside)."""
@@ -203,11 +205,17 @@ class HipGPR(GaussianProcessRegressor):
         # The device state goes first (a host model must never read an engine slot through the lazy L_ / alpha_), the flag last:
         # if the base fit raises (NaN input, a kernel matrix that is not positive definite) the estimator is left UNFITTED —
         # no X_train_ of an earlier device fit next to `_host_mode` — and not as a host model without its attributes.
+        # `_host_fitting` keeps the base fit's theta search (its own log_marginal_likelihood calls, after it has set X_train_)
+        # off the device for the whole fit: this model is outside the device path (width > GPBO_MAX_DIM, several targets).
         self._held = None
         for k in ("_kind", "_ls", "_L_cache", "_alpha_cache", "log_marginal_likelihood_value_", "_lml_lazy", "X_train_", "y_train_"):
             self.__dict__.pop(k, None)
         self._host_mode = False
-        out = GaussianProcessRegressor.fit(self, X, y)
+        self._host_fitting = True
+        try:
+            out = GaussianProcessRegressor.fit(self, X, y)
+        finally:
+            self._host_fitting = False
         self._host_mode = True
         return out
 
@@ -239,7 +247,7 @@ class HipGPR(GaussianProcessRegressor):
 
     # -- log marginal likelihood ---------------------------------------------------------------------
     def _device_lml_ok(self, kernel) -> bool:
-        if self.lml_on_device is False or not hasattr(self, "X_train_") or self._host_mode:
+        if self.lml_on_device is False or not hasattr(self, "X_train_") or self._host_mode or self._host_fitting:
             return False
         if self.lml_on_device == "auto" and self.X_train_.shape[0] < LML_DEVICE_MIN_N:
             return False

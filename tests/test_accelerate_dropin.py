@@ -542,3 +542,94 @@ def test_a_space_wider_than_the_engine_degrades_to_the_reference_trajectory():
     assert np.array_equal(mine.space.target, ref.space.target)
     assert np.array_equal(mine._gp.kernel_.theta, ref._gp.kernel_.theta)
     assert ref._random_state.uniform() == mine._random_state.uniform()
+
+
+@needs_ref
+def test_a_space_wider_than_the_engine_degrades_to_the_reference_trajectory_with_the_default_lml_setting():
+    """The test above with accelerate()'s default lml_on_device ("auto"): the theta search of scikit-learn's host fit must not
+    reach the engine either (it used to: the base fit sets X_train_ and then calls log_marginal_likelihood, which went to
+    gpbo_lml — GPBO_ERR_UNSUPPORTED at 81 columns, a NotImplementedError from inside suggest())."""
+    import_reference()
+    from bayes_opt import BayesianOptimization
+
+    from bayesianoptimization_amd import accelerate
+    from bayesianoptimization_amd._lib import MAX_DIM
+
+    cats = tuple(f"v{i:02d}" for i in range(16))
+    pb = {f"c{j}": cats for j in range(5)}
+    pb["x"] = (0.0, 1.0)
+
+    def f(x, **c):
+        return -(x - 0.3) ** 2 + 0.1 * sum(cats.index(v) == 3 + j for j, v in enumerate(c[k] for k in sorted(c)))
+
+    ref = BayesianOptimization(f=f, pbounds=pb, random_state=5, verbose=0)
+    mine = BayesianOptimization(f=f, pbounds=pb, random_state=5, verbose=0)
+    eng = FakeEngine()
+    with pytest.warns(UserWarning, match="81 columns in kernel space"):
+        accelerate(mine, engine=eng)
+    assert mine._gp.lml_on_device == "auto"
+    assert mine._gp._device_width(mine._space.random_sample(2, random_state=np.random.RandomState(0))) == 81 > MAX_DIM
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        mine.maximize(init_points=3, n_iter=3)
+    assert not [w for w in seen if "HIP path" in str(w.message)]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        ref.maximize(init_points=3, n_iter=3)
+    assert mine._gp._host_mode and not [c for c in eng.calls if c[0] in ("fit", "posterior", "lml", "lml_batch")]
+    assert np.array_equal(mine.space.params, ref.space.params)
+    assert np.array_equal(mine.space.target, ref.space.target)
+    assert np.array_equal(mine._gp.kernel_.theta, ref._gp.kernel_.theta)
+    assert ref._random_state.uniform() == mine._random_state.uniform()
+
+
+def _host_fit_pair(X, y, kernel):
+    """A default HipGPR (lml_on_device="auto") on a FakeEngine and scikit-learn's estimator, same hyper-parameters and seed."""
+    from sklearn.gaussian_process import GaussianProcessRegressor
+
+    from bayesianoptimization_amd.gpr import HipGPR
+
+    kw = dict(kernel=kernel, alpha=1e-6, normalize_y=True, n_restarts_optimizer=2, random_state=3)
+    sk = GaussianProcessRegressor(**kw).fit(X, y)
+    eng = FakeEngine()
+    gp = HipGPR(engine=eng, **kw)
+    assert gp.lml_on_device == "auto"
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        gp.fit(X, y)
+    assert len([w for w in seen if "HIP path" in str(w.message)]) == 1
+    return sk, gp, eng
+
+
+def _assert_host_fit_is_sklearns(sk, gp, eng, Xq):
+    assert gp._host_mode
+    assert not [c for c in eng.calls if c[0] in ("fit", "lml", "lml_batch", "posterior")], eng.calls
+    assert np.array_equal(gp.kernel_.theta, sk.kernel_.theta)
+    assert np.array_equal(gp.L_, sk.L_) and np.array_equal(gp.alpha_, sk.alpha_)
+    assert gp.log_marginal_likelihood_value_ == sk.log_marginal_likelihood_value_
+    for a, b in zip(gp.predict(Xq, return_std=True), sk.predict(Xq, return_std=True)):
+        assert np.array_equal(a, b)
+
+
+def test_a_host_fit_wider_than_the_engine_keeps_its_theta_search_on_the_host():
+    """65 columns with the default lml_on_device="auto": scikit-learn's whole fit, theta search included, bit for bit — no gpbo_lml
+    (which refuses d > 64) in between."""
+    from sklearn.gaussian_process.kernels import Matern
+
+    rng = np.random.RandomState(0)
+    X = rng.uniform(size=(30, 65))
+    y = np.sin(X @ rng.uniform(-0.5, 0.5, 65))
+    sk, gp, eng = _host_fit_pair(X, y, Matern(nu=2.5, length_scale=2.0))
+    _assert_host_fit_is_sklearns(sk, gp, eng, rng.uniform(size=(7, 65)))
+
+
+def test_a_host_fit_of_two_targets_keeps_its_theta_search_on_the_host():
+    """y of shape (20, 2) with the default lml_on_device="auto": scikit-learn's multi-target fit, bit for bit — the engine's LML
+    (single target) never sees the (20, 2) y."""
+    from sklearn.gaussian_process.kernels import Matern
+
+    rng = np.random.RandomState(1)
+    X = rng.uniform(size=(20, 3))
+    y = np.column_stack([np.sin(3 * X.sum(1)), np.cos(2 * X[:, 0])])
+    sk, gp, eng = _host_fit_pair(X, y, Matern(nu=2.5, length_scale=[0.5, 0.7, 0.9]))
+    _assert_host_fit_is_sklearns(sk, gp, eng, rng.uniform(size=(5, 3)))
