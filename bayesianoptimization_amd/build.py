@@ -34,7 +34,7 @@ SOURCES = {
     "posterior_kernel_v2.hip": [],
     "posterior_small.hip": [],
     "polish.hip": [],                          # gpbo_polish_seeds: the local-search stage as one C call (host optimiser, device evaluations)
-    "polish_fused.hip": [],                    # ... and as one launch for NP <= 256: one workgroup per local search (NP <= 128: thread = training point), evaluations + optimiser inside
+    "polish_fused.hip": [],                    # ... and as one launch for NP <= 512: one workgroup per local search (NP <= 128: thread = training point), evaluations + optimiser inside
     "posterior_kernel_f32.hip": [],
     "posterior_cov.hip": [],
     "lml_kernels.hip": [],

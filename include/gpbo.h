@@ -235,14 +235,14 @@ int gpbo_predict_grad(gpbo_ctx* ctx, int slot, const double* Xc, int64_t M, int 
  * from the posteriors of slots 0..n_constraints and their input gradients (as gpbo_predict_grad), and the optimiser
  * arithmetic (a projected L-BFGS with L-BFGS-B's stopping rule as SciPy configures it: 10 corrections, projected gradient
  * 1e-5, relative reduction 1e7 eps, 20 line-search steps, max_iter <= 0 -> 15000 iterations) runs on the host in between.
- * One model of at most 256 (padded) observations: the runs are one launch, a workgroup each, evaluations and optimiser on the
+ * One model of at most 512 (padded) observations: the runs are one launch, a workgroup each, evaluations and optimiser on the
  * device — the same optimiser arithmetic, the same evaluation arithmetic, the same results (bit for bit for UCB).
  * Not the reference's iterates: parity is statistical (acquisition value at the returned point).
  * y_mean / y_std: (1 + n_constraints,) the targets' normalisation per slot; seeds (n_seeds,d), clipped into the box;
  * box_lo < box_hi (d,).  Outputs per seed: x_out (n_seeds,d) inside the box, f_out, status_out (0: projected gradient
  * below tolerance, 1: relative reduction below tolerance / no further progress, 2: iteration limit or a non-finite start —
  * SciPy's success = False), n_rounds_out (optional) = batched evaluations issued by the lockstep path, or — one model of
- * NP <= 256, where the whole stage is ONE launch (a workgroup per run) — the longest run's evaluation count; n_iter_out /
+ * NP <= 512, where the whole stage is ONE launch (a workgroup per run) — the longest run's evaluation count; n_iter_out /
  * n_eval_out (optional, per seed) = accepted steps / objective evaluations, SciPy's nit / nfev.  The one-launch form returns when
  * its longest run has stopped: the calling thread and the context's stream are held for that long (a run is bounded by
  * 4 * max_iter + 64 evaluations of 4-40 us each; with the default max_iter = 15 000 a pathological run is ~1 s) — callers that

@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 from bayesianoptimization_amd import workloads as W
+from conftest import rel_err
 from oracle import gp_oracle as O
 
 
@@ -203,6 +204,25 @@ class FakeEngine:
         nan = np.isnan(ys)
         order = np.lexsort((np.arange(len(ys)), np.where(nan, np.inf, ys) + 0.0, nan))[:k_seeds]
         return bi + index_offset, bv, order + index_offset, ys[order], (ys if return_values else None)
+
+
+def assert_same_model(engine, X, yn, kernel, ls, noise, ym, ys, Xc, tol=1e-9):
+    """The slot's model equals (to rounding) the oracle's from-scratch fit of (X, yn): K, L, W, alpha, posterior.  Returns the
+    worst error / bar."""
+    n = X.shape[0]
+    gp = O.fit_fixed_theta(kernel, X, yn, ls, noise, normalize_y=False)
+    K = O.kernel_matrix(kernel, X, None, ls)
+    K[np.diag_indices_from(K)] += noise
+    errs = {"K": (rel_err(engine.get_K(n), K), 1e-14), "L": (rel_err(engine.get_L(n), gp.L), tol),
+            "WL-I": (rel_err(engine.get_Linv(n) @ gp.L, np.eye(n)), 100 * tol),
+            "alpha": (rel_err(engine.get_alpha(n), gp.alpha), 100 * tol)}
+    mu, sd = engine.predict(Xc, y_mean=ym, y_std=ys)
+    mu_o, sd_o = O.predict(gp, Xc)
+    errs["mu"] = (rel_err(mu, ys * mu_o + ym), tol)
+    errs["sd"] = (rel_err(sd, ys * sd_o), tol)
+    for k, (e, bar) in errs.items():
+        assert e < bar, f"{k} {e:.2e} over its bar {bar:.0e}"
+    return max(e / bar for e, bar in errs.values())
 
 
 def philox4x32_10_uniform(M, d, lo, hi, seed):

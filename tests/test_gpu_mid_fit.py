@@ -154,7 +154,7 @@ def test_strip_overlapped_fits_append_and_not_pd(debug_engine):
 
 
 def test_product_library_uses_the_strip_path_and_agrees_with_the_debug_build(engine, debug_engine):
-    """The product has no switch: its 128 < NP <= 512 fits ARE the strip path.  Same bits as the debug build's."""
+    """The product has no switch: its 64 < NP <= 768 fits ARE the strip path.  Same bits as the debug build's."""
     X, yn, ls, Xc = problem(333, 5, 11, True)
     with H.fit_paths(fused=None, mid=None):
         ref = fit_state(debug_engine, X, yn, O.MATERN25, ls, Xc)

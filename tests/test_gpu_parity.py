@@ -7,6 +7,7 @@ import pytest
 from bayesianoptimization_amd import _lib
 from bayesianoptimization_amd import workloads as W
 from conftest import rel_err
+from helpers import assert_same_model as _assert_same_model
 from helpers import oracle_case
 from oracle import gp_oracle as O
 
@@ -570,21 +571,6 @@ def test_kstar_slab_loop_equals_single_slab(engine):
 
 
 # ---- gpbo_fit_append ---------------------------------------------------------------------
-def _assert_same_model(engine, X, yn, kernel, ls, noise, ym, ys, Xc, tol=1e-9):
-    """The slot's model equals (to rounding) the oracle's from-scratch fit of (X, yn): K, L, W, alpha, posterior."""
-    n = X.shape[0]
-    gp = O.fit_fixed_theta(kernel, X, yn, ls, noise, normalize_y=False)
-    K = O.kernel_matrix(kernel, X, None, ls)
-    K[np.diag_indices_from(K)] += noise
-    assert rel_err(engine.get_K(n), K) < 1e-14
-    assert rel_err(engine.get_L(n), gp.L) < tol
-    assert rel_err(engine.get_Linv(n) @ gp.L, np.eye(n)) < 100 * tol
-    assert rel_err(engine.get_alpha(n), gp.alpha) < 100 * tol
-    mu, sd = engine.predict(Xc, y_mean=ym, y_std=ys)
-    mu_o, sd_o = O.predict(gp, Xc)
-    assert rel_err(mu, ys * mu_o + ym) < tol and rel_err(sd, ys * sd_o) < tol
-
-
 @pytest.mark.parametrize("kernel,ls", [(O.MATERN25, 0.9), (O.RBF, 1.3)])
 @pytest.mark.parametrize("n0,steps", [(100, [1, 3, 1]), (126, [1, 1, 5]), (128, [1]), (60, [20]), (200, [0, 2, 0])])
 def test_fit_append_equals_full_fit(engine, kernel, ls, n0, steps):
