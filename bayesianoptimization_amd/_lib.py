@@ -23,6 +23,7 @@ ABI_VERSION = 2
 
 _c_double_p = C.POINTER(C.c_double)
 _c_int64_p = C.POINTER(C.c_int64)
+_c_int_p = C.POINTER(C.c_int)
 
 # name -> (restype, argtypes); must list every symbol include/gpbo.h declares (tests check this)
 SIGNATURES = {
@@ -109,6 +110,9 @@ SIGNATURES = {
     "gpbo_polish_seeds": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, _c_double_p, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int, _c_double_p,
                                     _c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gpbo_evolve_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _c_int_p,
+                                    _c_int_p, _c_int_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_uint32), _c_int_p, _c_double_p, _c_double_p, _c_int_p, _c_int_p, _c_int_p]),
     "gpbo_mfma_f64_peak": (C.c_int, [C.c_void_p, C.c_int, _c_double_p]),
     "gpbo_mfma_f64_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _c_double_p]),
     "gpbo_hbm_copy_peak": (C.c_int, [C.c_void_p, C.c_int64, _c_double_p]),
@@ -132,6 +136,12 @@ DEBUG_SIGNATURES = {
                                         _c_double_p]),
     "gpbo_hybrid_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_double_p]),
     "gpbo_debug_fail_next_acq": (C.c_int, [C.c_void_p]),
+    "gpbo_debug_evolve_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _c_int_p,
+                                         _c_int_p, _c_int_p, _c_double_p, C.c_int, C.c_int, _c_double_p]),
+    "gpbo_debug_evolve_walk": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p,
+                                         _c_int_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(C.c_uint32), _c_int_p, _c_double_p, _c_double_p, _c_int_p, _c_int_p, _c_int_p,
+                                         _c_int_p]),
     "gpbo_debug_polish_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _c_double_p, C.c_int, C.c_int,
                                          C.c_int, _c_double_p]),
 }

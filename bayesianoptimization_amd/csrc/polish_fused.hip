@@ -25,6 +25,7 @@
 
 #include "gpbo_internal.h"
 #include "polish_opt.h"
+#include "posterior_rows.h"
 
 namespace gpbo {
 
@@ -233,10 +234,6 @@ __global__ __launch_bounds__(256) void transpose_w_kernel(const double* __restri
 }
 
 // ---- thread = training point (NP <= 512) ---------------------------------------------------------------------------------
-#ifndef GPBO_PR_INFLIGHT
-#define GPBO_PR_INFLIGHT 16
-#endif
-constexpr int PR_INFLIGHT = GPBO_PR_INFLIGHT;      // 16-byte loads in flight per lane in the walks over W in memory (128 is a multiple)
 constexpr int PR_LDS_NP = 128;       // W fits the LDS up to here (a padded square: 132 KB at 128)
 constexpr int PR_MAX_NP = 512;       // ... and is streamed from memory above (W for the column walk, its transpose for the row walk): 8 waves,
                                      // 256 VGPRs each (12 waves for NP = 768 would spill the optimiser's registers to scratch)
@@ -318,13 +315,8 @@ __global__ __launch_bounds__(WLDS ? PR_LDS_NP : PR_MAX_NP) void polish_rows_kern
     // ---- k*_i and the gradient factor f_i of this thread's point
     double fi;
     {
-      const double* xr = Xs + (int64_t)tid * xld;
-      double d2 = 0.0;
-      for (int t = 0; t < DP; ++t) {
-        const double df = xs[t] - xr[t];
-        d2 = fma(df, df, d2);
-      }
-      const double kv = gpbo_kernel_value<KERNEL>(d2);
+      double d2;
+      const double kv = pr_kstar<KERNEL>(xs, Xs + (int64_t)tid * xld, DP, d2);
       if (KERNEL == GPBO_KERNEL_MATERN25) {
         const double sq = gpbo_sqrt_pos(d2) * 2.23606797749978969641;      // sqrt(5) r
         fi = -1.66666666666666666667 * (1.0 + sq) * gpbo_exp_nonpos(-sq);
@@ -338,14 +330,7 @@ __global__ __launch_bounds__(WLDS ? PR_LDS_NP : PR_MAX_NP) void polish_rows_kern
     // ---- v = W k* and u = W^T v, then every point's two gradient weights and its terms of |v|^2 and k* . alpha
     if (WLDS) {
       // thread i: row i of W for v_i (zeros above the diagonal: the whole row), column i for u_i
-      double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-      for (int k = 0; k < NP; k += 4) {
-        v0 = fma(wrow[k], ks[k], v0);
-        v1 = fma(wrow[k + 1], ks[k + 1], v1);
-        v2 = fma(wrow[k + 2], ks[k + 2], v2);
-        v3 = fma(wrow[k + 3], ks[k + 3], v3);
-      }
-      const double v = (tid < N) ? (v0 + v1) + (v2 + v3) : 0.0;
+      const double v = (tid < N) ? pr_row_lds(wrow, ks, NP) : 0.0;
       vs[tid] = v;
       pp[2 * tid] = v * v;
       pp[2 * tid + 1] = ks[tid] * al_i;
@@ -366,25 +351,7 @@ __global__ __launch_bounds__(WLDS ? PR_LDS_NP : PR_MAX_NP) void polish_rows_kern
       // start at 128 w): the zeros of the triangle are never loaded.  The sums come back through LDS to the points' own threads.
       typedef double d2 __attribute__((ext_vector_type(2)));
       const int ld2 = NP / 2;
-      if (tid < ld2) {
-        const d2* __restrict__ wt = reinterpret_cast<const d2*>(a.Wt) + tid;      // Wt[k][2 tid .. 2 tid + 1] = W[2 tid ..][k]
-        const int kend = min(NP, 128 * (wave + 1));
-        double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
-        for (int k = 0; k < kend; k += PR_INFLIGHT) {
-          d2 w[PR_INFLIGHT];
-#pragma unroll
-          for (int e = 0; e < PR_INFLIGHT; ++e) w[e] = wt[(int64_t)(k + e) * ld2];
-#pragma unroll
-          for (int e = 0; e < PR_INFLIGHT; e += 2) {
-            a0 = fma(w[e].x, ks[k + e], a0);
-            b0 = fma(w[e].y, ks[k + e], b0);
-            a1 = fma(w[e + 1].x, ks[k + e + 1], a1);
-            b1 = fma(w[e + 1].y, ks[k + e + 1], b1);
-          }
-        }
-        vs[2 * tid] = (2 * tid < N) ? a0 + a1 : 0.0;
-        vs[2 * tid + 1] = (2 * tid + 1 < N) ? b0 + b1 : 0.0;
-      }
+      pr_rows_mem(a.Wt, ks, NP, N, tid, wave, vs);
       __syncthreads();
       pp[2 * tid] = vs[tid] * vs[tid];
       pp[2 * tid + 1] = ks[tid] * al_i;
@@ -487,6 +454,15 @@ __global__ __launch_bounds__(WLDS ? PR_LDS_NP : PR_MAX_NP) void polish_rows_kern
 
 }  // namespace
 
+int ensure_w_transposed(gpbo_ctx* ctx, Model& m) {
+  if (!m.wt_valid) {
+    transpose_w_kernel<<<dim3((unsigned)(m.NP / 64), (unsigned)(m.NP / 64)), dim3(256), 0, ctx->stream>>>(m.W, m.K, (int)m.NP);
+    GPBO_HIP(ctx, hipGetLastError());
+    m.wt_valid = true;
+  }
+  return GPBO_OK;
+}
+
 // Largest padded size the one launch serves with W in memory (debug build: GPBO_POLISH_FUSED_MAX_NP read per call — the crossover
 // against the lockstep rounds, scripts/r06_polish_fused_ab.py: at N = 512 a run of ~50 evaluations already loses to them, 2.46
 // against 2.13 ms — and 0 = never, the lockstep path alone: the checker's switch, with GPBO_POLISH_FUSED=0)
@@ -558,11 +534,7 @@ int launch_polish_fused(gpbo_ctx* ctx, Model& m, int acq, double acq_param, doub
   if (rows_mode == 2) {
     // the transposed copy for the row walk lives in the slot's K buffer (a fit assembles K straight into L; gpbo_get_K and the LML
     // path, which write K, invalidate it): made once per fit
-    if (!m.wt_valid) {
-      transpose_w_kernel<<<dim3((unsigned)(m.NP / 64), (unsigned)(m.NP / 64)), dim3(256), 0, ctx->stream>>>(m.W, m.K, (int)m.NP);
-      GPBO_HIP(ctx, hipGetLastError());
-      m.wt_valid = true;
-    }
+    if (const int rc = ensure_w_transposed(ctx, m)) return rc;
     a.Wt = m.K;
     if (m.kernel == GPBO_KERNEL_MATERN25) polish_rows_kernel<GPBO_KERNEL_MATERN25, false><<<grid, rows_block, lds, ctx->stream>>>(a);
     else polish_rows_kernel<GPBO_KERNEL_RBF, false><<<grid, rows_block, lds, ctx->stream>>>(a);

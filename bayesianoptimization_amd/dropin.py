@@ -132,7 +132,8 @@ def warm_up(engine, bounds, acquisition=None, kernel=None, n_restarts_optimizer:
 
 
 def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=None, precision: str = "f64",
-               devices=None, local_search: str = "auto", lml_on_device="auto", warm: bool = True):
+               devices=None, local_search: str = "auto", lml_on_device="auto", warm: bool = True,
+               mixed_search: str = "reference"):
     """Swap the GP(s) and the acquisition function of `optimizer` in place; returns `optimizer`.
 
     `devices=[0, 1, ...]`: shard the random stage of every suggest() over these GPUs from this ONE process (GroupEngine:
@@ -157,12 +158,19 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
     transform) and stock UCB / EI / POI policies; mixed spaces and custom policies keep the reference-shaped stage.
     "device" asks for the same explicitly; "reference" keeps SciPy's L-BFGS-B over finite differences, iterate for iterate
     the reference's local searches (bayes_opt/acquisition.py:364-374).
+    `mixed_search`: the differential evolution that ends every suggest() on a space with IntParameter / CategoricalParameter
+    columns (bayes_opt/acquisition.py:375-396).  "reference" (default): SciPy's DifferentialEvolutionSolver, one device round
+    trip per trial.  "device": the same walk, draw for draw on the optimizer's RandomState, with the trials evaluated on the
+    device (gpbo_evolve_mixed) wherever it applies — one model without constraint GPs, stock UCB / EI / POI (also under GPHedge
+    and ConstantLiar), at most 512 observations, SciPy 1.15.x; the energies agree with the host's to rounding.
     `warm` (default True): run `warm_up` once per engine and dimension — five synthetic suggest() calls (~0.3 s) that load the
     code objects, allocate and launch every small-N path, so that no suggest() of the user's loop carries a first-use spike.
     The optimizer's RandomState is not touched.
     """
     if local_search not in ("auto", "reference", "device"):
         raise ValueError("local_search must be 'auto', 'reference' or 'device'")
+    if mixed_search not in ("reference", "device"):
+        raise ValueError("mixed_search must be 'reference' or 'device'")
     if engine is None:
         engine = shared_engine(tuple(devices)) if devices is not None else shared_engine(device)
     space = optimizer._space
@@ -199,6 +207,11 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
         for f in [fn, getattr(fn, "base_acquisition", None), *getattr(fn, "base_acquisitions", [])]:
             if isinstance(f, A.AcquisitionFunction):
                 f.device_polish = (local_search == "device")
+    if mixed_search == "device":
+        fn = optimizer._acquisition_function
+        for f in [fn, getattr(fn, "base_acquisition", None), *getattr(fn, "base_acquisitions", [])]:
+            if isinstance(f, A.AcquisitionFunction):
+                f.device_evolve = True
     from .engine import GpEngine
 
     if warm and isinstance(engine, GpEngine) and transform is None and not too_wide and not engine.__dict__.get("_warmed", {}).get(width):

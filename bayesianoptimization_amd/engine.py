@@ -514,6 +514,74 @@ class GpEngine:
         self._resident = False
         return x, f, status, rounds.value
 
+    @staticmethod
+    def _groups_arrays(groups):
+        n = len(groups)
+        return ((C.c_int * n)(*[int(g[0]) for g in groups]), (C.c_int * n)(*[int(g[1]) for g in groups]),
+                (C.c_int * n)(*[int(g[2]) for g in groups]), n)
+
+    def evolve_mixed(self, acq: int, param: float, y_max, y_mean: float, y_std: float, groups, bounds, init, random_state,
+                     maxiter: int = 1000):
+        """gpbo_evolve_mixed: `DifferentialEvolutionSolver(func, bounds, init=init, polish=False, rng=random_state).solve()` of a
+        mixed-space smart stage (SciPy 1.15, best1bin) with the walk and its evaluations — -base_acq of slot 0's posterior at
+        kernel_transform(x), `groups` = [(kind, col0, ncols, ...)] as for transform_candidates — on the device.  Returns
+        (x, fun, nit, nfev, success); `random_state` (a legacy MT19937 RandomState) is left where SciPy's solver would leave it."""
+        self._settle(0)
+        name, key, pos, has_gauss, cached = random_state.get_state(legacy=True)
+        if name != "MT19937":
+            raise TypeError("evolve_mixed needs an MT19937 RandomState")
+        bounds = np.asarray(bounds, dtype=np.float64)
+        lo, hi = np.ascontiguousarray(bounds[:, 0]), np.ascontiguousarray(bounds[:, 1])
+        init = np.ascontiguousarray(init, dtype=np.float64)
+        S, D = init.shape
+        kinds, col0, ncols, n = self._groups_arrays(groups)
+        key = np.ascontiguousarray(key, dtype=np.uint32).copy()
+        cpos = C.c_int(int(pos))
+        x = np.empty(D)
+        f, nit, nfev, ok = C.c_double(0.0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.gpbo_evolve_mixed(
+            self._h, int(acq), float(param), float(0.0 if y_max is None else y_max), float(y_mean), float(y_std), n, kinds, col0,
+            ncols, dptr(lo), dptr(hi), dptr(init), S, D, int(maxiter), key.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(cpos),
+            dptr(x), C.byref(f), C.byref(nit), C.byref(nfev), C.byref(ok)))
+        random_state.set_state((name, key, cpos.value, has_gauss, cached))
+        return x, f.value, nit.value, nfev.value, bool(ok.value)
+
+    def debug_evolve_eval(self, acq: int, param: float, y_max, y_mean: float, y_std: float, groups, points):
+        """gpbo_debug_evolve_eval: the device walk's objective at each row of `points` (n, D)."""
+        self._need_debug("debug_evolve_eval")
+        self._settle(0)
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        n, D = points.shape
+        kinds, col0, ncols, ng = self._groups_arrays(groups)
+        out = np.empty(n)
+        self._check(self._lib.gpbo_debug_evolve_eval(self._h, int(acq), float(param), float(0.0 if y_max is None else y_max),
+                                                     float(y_mean), float(y_std), ng, kinds, col0, ncols, dptr(points), n, D,
+                                                     dptr(out)))
+        return out
+
+    def debug_evolve_walk(self, weights, targets, groups, bounds, init, key, pos, maxiter=1000, budget=256,
+                          nan_below=-np.inf, inf_above=np.inf):
+        """gpbo_debug_evolve_walk: the device walk over the analytic objective (tests/de_walk.py: analytic).  Returns a dict
+        with x, fun, nit, nfev, success, key, pos, launches."""
+        self._need_debug("debug_evolve_walk")
+        bounds = np.asarray(bounds, dtype=np.float64)
+        lo, hi = np.ascontiguousarray(bounds[:, 0]), np.ascontiguousarray(bounds[:, 1])
+        init = np.ascontiguousarray(init, dtype=np.float64)
+        S, D = init.shape
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        a = np.ascontiguousarray(targets, dtype=np.float64)
+        kinds, col0, ncols, n = self._groups_arrays(groups)
+        key = np.ascontiguousarray(key, dtype=np.uint32).copy()
+        cpos = C.c_int(int(pos))
+        x = np.empty(D)
+        f, nit, nfev, ok, launches = C.c_double(0.0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.gpbo_debug_evolve_walk(
+            self._h, dptr(w), dptr(a), float(nan_below), float(inf_above), n, kinds, col0, ncols, dptr(lo), dptr(hi), dptr(init),
+            S, D, int(maxiter), int(budget), key.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(cpos), dptr(x), C.byref(f),
+            C.byref(nit), C.byref(nfev), C.byref(ok), C.byref(launches)))
+        return {"x": x, "fun": f.value, "nit": nit.value, "nfev": nfev.value, "success": bool(ok.value), "key": key,
+                "pos": cpos.value, "launches": launches.value}
+
     # -- acquisition -----------------------------------------------------------------------------
     def acq_argbest(self, acq: int, param: float, y_max: float = 0.0, lb=None, ub=None, k_seeds: int = 0,
                     index_offset: int = 0, return_values: bool = False):

@@ -158,9 +158,18 @@ def _mixed_groups_on_device(chain, space, random_state, n_random):
     eng = chain[0]._engine()
     if not getattr(eng, "mixed_device_sampling", False) or not hasattr(eng, "generate_candidates_mixed"):
         return None
+    if n_random * space.bounds.shape[0] < 4096:
+        return None
+    return _mixed_space_groups(chain, space, random_state)
+
+
+def _mixed_space_groups(chain, space, random_state):
+    """The space half of `_mixed_groups_on_device` (no engine, no batch size): the column groups when the space holds only the
+    reference's three parameter kinds, at least one non-float, in key order, sampled by the stock loop on an MT19937
+    RandomState, and every GP's input transform is this space's kernel_transform; else None."""
     config = getattr(space, "_params_config", None)
     masks = getattr(space, "masks", None)
-    if config is None or masks is None or n_random * space.bounds.shape[0] < 4096:
+    if config is None or masks is None:
         return None
     if not isinstance(random_state, np.random.RandomState) or random_state.get_state()[0] != "MT19937":
         return None
@@ -186,6 +195,20 @@ def _mixed_groups_on_device(chain, space, random_state, n_random):
     if col != space.bounds.shape[0] or all(g[0] == 0 for g in groups) or col > 64:
         return None
     return groups
+
+
+#: the SciPy releases whose DifferentialEvolutionSolver walk gpbo_evolve_mixed reproduces draw for draw (tests/test_evolve_host.py)
+_DEVICE_DE_SCIPY = ((1, 15),)
+
+
+def _scipy_de_validated() -> bool:
+    import scipy
+
+    try:
+        major, minor = (int(v) for v in scipy.__version__.split(".")[:2])
+    except ValueError:
+        return False
+    return (major, minor) in _DEVICE_DE_SCIPY
 
 
 def _fused_models(gp, constraint):
@@ -242,6 +265,13 @@ class AcquisitionFunction(abc.ABC):
     #: False: SciPy's L-BFGS-B over (batched) finite differences, iterate for iterate the reference's local searches
     #: (bayes_opt/acquisition.py:364-374).
     device_polish = "auto"
+    #: the differential evolution of a mixed space's local-search stage (bayes_opt/acquisition.py:375-396).  False (default):
+    #: SciPy's DifferentialEvolutionSolver with one objective call — one device round trip — per trial.  True: the same walk,
+    #: draw for draw on the same RandomState, with its evaluations on the device (gpbo_evolve_mixed: one workgroup, a few
+    #: launches per suggest) whenever it applies — one engine-backed model without constraint, a stock UCB / EI / POI policy,
+    #: a space of the reference's parameter classes transformed by its own kernel_transform, at most 512 observations, an
+    #: MT19937 RandomState and SciPy 1.15.x; otherwise SciPy's solver.  The energies agree with the host's to rounding.
+    device_evolve = False
     _acq_kind: int | None = None     # engine acquisition id of the stock policies; None = host formula only
 
     def __init__(self, random_state=None) -> None:
@@ -517,6 +547,17 @@ class AcquisitionFunction(abc.ABC):
                 winner = (res.x, np.squeeze(res.fun))
         return winner
 
+    def _device_evolve_groups(self, space, random_state):
+        """Column groups when `device_evolve` applies to this suggest() (see its comment), else None."""
+        chain = getattr(self, "_fused", None)
+        if not self.device_evolve or chain is None or len(chain) != 1 or type(self) not in _STOCK_POLICIES:
+            return None
+        if not hasattr(chain[0]._engine(), "evolve_mixed") or chain[0].X_train_.shape[0] > 512 or not _scipy_de_validated():
+            return None
+        if not isinstance(random_state, np.random.RandomState) or random_state.get_state(legacy=False)["bit_generator"] != "MT19937":
+            return None
+        return _mixed_space_groups(chain, space, random_state)
+
     def _evolve_mixed(self, acq, space, x_seeds, random_state, is_cont, box):
         import scipy
         from packaging import version
@@ -526,13 +567,25 @@ class AcquisitionFunction(abc.ABC):
         n_keep = min(len(x_seeds), len(population))
         if n_keep > 0:
             population[:n_keep] = x_seeds[:n_keep]
-        rng_kw = "seed" if version.parse(scipy.__version__) < version.parse("1.15.0") else "rng"
-        solver = DifferentialEvolutionSolver(func=acq, bounds=space.bounds, polish=False, init=population,
-                                             **{rng_kw: random_state})
-        found = solver.solve()
-        if not found.success:
-            raise RuntimeError(f"Differential evolution optimization failed. Message: {found.message}")
-        x_best, f_best = found.x, np.squeeze(found.fun)
+        groups = self._device_evolve_groups(space, random_state)
+        if groups is not None:
+            model = self._fused[0]
+            model._ensure_resident()
+            x_best, _, _, _, success = model._engine().evolve_mixed(
+                self._acq_kind, self._acq_param(), getattr(self, "y_max", None), float(model._y_train_mean),
+                float(model._y_train_std), groups, space.bounds, population, random_state)
+            if not success:
+                raise RuntimeError("Differential evolution optimization failed. Message: "
+                                   "Maximum number of iterations has been exceeded.")
+            f_best = np.squeeze(acq(x_best))        # the host objective's value at the point, as SciPy's found.fun holds it
+        else:
+            rng_kw = "seed" if version.parse(scipy.__version__) < version.parse("1.15.0") else "rng"
+            solver = DifferentialEvolutionSolver(func=acq, bounds=space.bounds, polish=False, init=population,
+                                                 **{rng_kw: random_state})
+            found = solver.solve()
+            if not found.success:
+                raise RuntimeError(f"Differential evolution optimization failed. Message: {found.message}")
+            x_best, f_best = found.x, np.squeeze(found.fun)
         if any(is_cont):
             frozen = x_best.copy()
 
@@ -810,3 +863,6 @@ class GPHedge(AcquisitionFunction):
         self.gains = np.array(params["gains"])
         pc = params["previous_candidates"]
         self.previous_candidates = None if pc is None else np.array(pc)
+
+
+_STOCK_POLICIES = (UpperConfidenceBound, ExpectedImprovement, ProbabilityOfImprovement)

@@ -254,6 +254,26 @@ int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, double y_max, in
                       const double* box_lo, const double* box_hi, int max_iter, double* x_out, double* f_out, int* status_out,
                       int* n_rounds_out, int* n_iter_out, int* n_eval_out);
 
+/* The differential evolution of a mixed-space smart stage as ONE call.  Replaces the solver the reference runs when a space has
+ * IntParameter / CategoricalParameter columns (bayes_opt/acquisition.py:375-396: DifferentialEvolutionSolver(func=acq, bounds,
+ * init=population, polish=False, rng=random_state).solve(), SciPy 1.15: best1bin, mutation (0.5, 1) dithered, recombination 0.7,
+ * updating 'immediate', tol 0.01, atol 0) over the objective
+ *   f(x) = -base_acq(mu0, sd0) at kernel_transform(x)   (slot 0, no constraint GPs; acquisition.py:198-217, target_space.py:340-347)
+ * with the walk AND its evaluations on the device: one workgroup holds the solver's state and evaluates each trial as the posterior of
+ * its one point (thread = training point), launches of a bounded number of evaluations repeated until the run ends.  Every draw is
+ * the one SciPy makes from the legacy RandomState whose MT19937 state is key[624] / *pos (both come back advanced, as
+ * gpbo_generate_candidate_columns_mt19937's).  Column groups as gpbo_transform_candidates: kind[g] 0 float (identity), 1 int (rint),
+ * 2 categorical (one-hot at the first argmax), covering columns [col0[g], col0[g] + ncols[g]) of D <= 64 exactly once.  bounds_lo /
+ * bounds_hi (D,): the space's bounds; init (S, D), S in [5, 1024]: the initial population in parameter space (clipped into the box);
+ * maxiter >= 1 generations.  Outputs: x_out (D,) the best member, f_out its energy, nit_out / nfev_out SciPy's nit / nfev,
+ * success_out 0 when maxiter ended the run.  The energies agree with the host's to rounding, so the walk is the host solver's
+ * wherever no comparison of two energies falls within it.  Slot 0 of at most 512 (padded) observations, fp64 whatever the fit's
+ * precision. */
+int gpbo_evolve_mixed(gpbo_ctx* ctx, int acq, double acq_param, double y_max, double y_mean, double y_std, int n_groups,
+                      const int* kind, const int* col0, const int* ncols, const double* bounds_lo, const double* bounds_hi,
+                      const double* init, int S, int D, int maxiter, unsigned* key, int* pos, double* x_out, double* f_out,
+                      int* nit_out, int* nfev_out, int* success_out);
+
 /* ---- acquisition + arg-best ------------------------------------------------------------- */
 /* Replaces the _get_acq closure + base_acq + argmin/min/argsort[:k]
  * (bayes_opt/acquisition.py:198-217, 485, 660-661, 847-849, 312-317) and, when n_constraints > 0,
@@ -385,6 +405,19 @@ int gpbo_debug_minimize_box(gpbo_fg_callback fg, void* user, const double* seeds
  * dmu/dx (d) | dsd/dx (d)] — what gpbo_predict_grad's six kernels compute, from the one kernel (the tests require the same bits). */
 int gpbo_debug_polish_eval(gpbo_ctx* ctx, int acq, double acq_param, double y_max, double y_mean, double y_std, const double* points,
                            int n, int d, int repeat, double* out);
+
+/* gpbo_evolve_mixed's objective at each of n points (n, D) in parameter space (transform, posterior of slot 0, -base_acq),
+ * evaluated by the kernel of the device walk: out (n,). */
+int gpbo_debug_evolve_eval(gpbo_ctx* ctx, int acq, double acq_param, double y_max, double y_mean, double y_std, int n_groups,
+                           const int* kind, const int* col0, const int* ncols, const double* points, int n, int D, double* out);
+/* gpbo_evolve_mixed's walk over a fixed analytic objective the host can reproduce bit for bit: f(x) = sum_t w_t (g_t - a_t)^2 left
+ * to right without contraction, g_t = rint(x_t) on int columns and x_t elsewhere; NaN where x_0 < nan_below, +inf where
+ * x_0 > inf_above.  budget = evaluations per launch; launches_out (optional) = launches the run took. */
+int gpbo_debug_evolve_walk(gpbo_ctx* ctx, const double* weights, const double* targets, double nan_below, double inf_above,
+                           int n_groups, const int* kind, const int* col0, const int* ncols, const double* bounds_lo,
+                           const double* bounds_hi, const double* init, int S, int D, int maxiter, int budget, unsigned* key,
+                           int* pos, double* x_out, double* f_out, int* nit_out, int* nfev_out, int* success_out,
+                           int* launches_out);
 
 /* Multi-GPU failure path, self-test seam (no device needed): a group of workers without contexts, and a job in which
  * rank `fail_rank` returns `fail_code` and rank `hang_rank` sleeps `hang_ms` (either may be -1). */
