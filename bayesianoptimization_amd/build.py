@@ -29,7 +29,7 @@ ARCH = "gfx950"
 SOURCES = {
     "gpbo_api.hip": [],
     "fit_kernels.hip": [],
-    "chol_kernels.hip": os.environ.get("GPBO_CHOL_EXTRA_FLAGS", "").split(),   # probe builds (scripts/archive/r03_*): -D switches
+    "chol_kernels.hip": [],
     "posterior_kernel.hip": [],
     "posterior_kernel_v2.hip": [],
     "posterior_small.hip": [],

@@ -447,8 +447,7 @@ static bool select_v2_enabled() {
 // `acq` (v2 only): the values are made by the block stage itself from the models' mu / sd (and stored to ctx->ys)
 static int enqueue_select(gpbo_ctx* ctx, int64_t M, int npass, bool v2, SelState** st_out, Key** picks_out, const AcqDev* acq = nullptr) {
   int rc;
-  const char* ie = dbg_env("GPBO_SELECT_ITEMS");      // debug build: 16 = rounds 2-5 (A/B)
-  const int items = v2 ? ((ie && atoi(ie) == 16) ? 16 : (M <= ((int64_t)1 << 18) ? 4 : 16)) : SEL_ITEMS;
+  const int items = v2 ? (M <= ((int64_t)1 << 18) ? 4 : 16) : SEL_ITEMS;
   const int nblocks = (int)((M + SEL_BLOCK * items - 1) / (SEL_BLOCK * items));
   // scratch layout: SelState | picks[npass] | partial[nblocks][npass] | nan_partial[nblocks]
   const int64_t bytes = sizeof(SelState) + sizeof(Key) * (npass + (int64_t)nblocks * npass) + sizeof(int64_t) * nblocks + 64;
@@ -493,14 +492,13 @@ static int enqueue_acq_select(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_
   d.acq = a.acq; d.param = a.param; d.y_max = a.y_max; d.n_constraints = a.n_constraints;
   for (int j = 0; j < GPBO_MAX_MODELS; ++j) { d.lb[j] = a.lb[j]; d.ub[j] = a.ub[j]; d.mu[j] = a.mu[j]; d.sd[j] = a.sd[j]; }
   // one or two picks: the passes are the shorter chain (k = 1: 11 us against 16, profiles/r03_select_probe.json)
+  // v2 makes the values in its block stage; the two-pass form reads them from a separate acq_kernel launch
   const bool v2 = select_v2_enabled() && npass >= 3;
-  const char* fe = dbg_env("GPBO_SELECT_FUSED_ACQ");      // debug build: 0 = the separate acq_kernel launch of rounds 1-5 (A/B)
-  const bool fused_acq = v2 && !(fe && fe[0] == '0');
-  if (!fused_acq) {
+  if (!v2) {
     acq_kernel<<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream>>>(d, M, ctx->ys);
     GPBO_HIP(ctx, hipGetLastError());
   }
-  if ((rc = enqueue_select(ctx, M, npass, v2, st_out, picks_out, fused_acq ? &d : nullptr))) return rc;
+  if ((rc = enqueue_select(ctx, M, npass, v2, st_out, picks_out, v2 ? &d : nullptr))) return rc;
   *npass_out = npass;
   return GPBO_OK;
 }

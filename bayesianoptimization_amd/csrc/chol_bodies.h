@@ -34,15 +34,11 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 // compiler has to keep the order.
 #define GPBO_LDS_ORDER() asm volatile("" ::: "memory")
 #define GPBO_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#ifndef GPBO_CHOL_POLL_SLEEP
-#define GPBO_CHOL_POLL_SLEEP 8      // x 64 cycles between two looks at a marker, cut short by the owner's s_wakeup
-#endif
+constexpr int CHOL_POLL_SLEEP = 8;   // x 64 cycles between two looks at a marker, cut short by the owner's s_wakeup
 #ifndef GPBO_CHOL_DEFER_MATE
 #define GPBO_CHOL_DEFER_MATE 1
 #endif
-#ifndef GPBO_CHOL_WAKE_MASK
-#define GPBO_CHOL_WAKE_MASK 1       // the owner wakes the sleepers behind every column jj with (jj & mask) == mask: every second one
-#endif
+constexpr int CHOL_WAKE_MASK = 1;    // the owner wakes the sleepers behind every column jj with (jj & mask) == mask: every second one
 
 // a[c] -= l * m_c and (the riding row) a2[c] -= l2 * m_c for N of the wave's own columns, m_c = the value of l in lane
 // C0 + c (the rows of the wave's diagonal 8x8 block sit in lanes 0..7): v_readlane_b32 into FIXED scalar registers,
@@ -189,7 +185,7 @@ __device__ __forceinline__ void factor_block8(double (&a)[8], double (&a2)[8], d
           if (i == 0) *broken = 1;
           break;
         }
-        __builtin_amdgcn_s_sleep(GPBO_CHOL_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(CHOL_POLL_SLEEP);
         GPBO_LDS_ORDER();
       }
       GPBO_LDS_ORDER();
@@ -239,7 +235,7 @@ __device__ __forceinline__ void factor_block8(double (&a)[8], double (&a2)[8], d
     GPBO_LDS_ORDER();
     col[jj * DS + 64] = rs;
     GPBO_LDS_ORDER();
-    if ((jj & GPBO_CHOL_WAKE_MASK) == GPBO_CHOL_WAKE_MASK) asm volatile("s_wakeup" ::: "memory");      // the store is in the LDS queue before any reader woken by this can queue its read
+    if ((jj & CHOL_WAKE_MASK) == CHOL_WAKE_MASK) asm volatile("s_wakeup" ::: "memory");      // the store is in the LDS queue before any reader woken by this can queue its read
     GPBO_SCHED_FENCE();
     switch (jj) {     // jj is a compile-time constant of the unrolled loop: only its own case survives
       case 0: bcast_fma_from<1, FOLLOW>(a, a2, l, l2); break;

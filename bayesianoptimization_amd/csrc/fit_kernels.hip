@@ -366,12 +366,10 @@ int launch_gemm(gpbo_ctx* ctx, const GemmArgs& g_in) {
   // workgroup slot (512) ends on its longest tiles while most CUs idle, so such products take the 64x64 tiles (4x as
   // many, each a quarter of the work, handed out longest first).  Measured (r02 fit probe): W = L^-1 at N = 4096
   // 0.93 -> 0.82 ms; with deeper grids (N = 8192: 1024 tiles) the 128x128 kernel wins, 3.91 vs 4.11 ms.
-  // GPBO_TRI64=0 turns the rule off (A/B runs).
-  static const bool tri64 = !(dbg_env("GPBO_TRI64") && dbg_env("GPBO_TRI64")[0] == '0');
   const bool triangular = g.a_lower || g.b_lower || g.k_from_tile;
   // ... and W^T W (k_from_tile: the first tile's k-loop is the whole N) takes them while one 128x128 tile per slot would make that
   // tile the launch: N = 4096, 528 tiles: 1.04 ms, the longest tile alone 1.05 ms at a 512th of the chip's rate
-  static const int tri64_limit = dbg_env("GPBO_TRI64_LIMIT") ? atoi(dbg_env("GPBO_TRI64_LIMIT")) : 600;
+  constexpr int tri64_limit = 600;
   // Lower-only square products (W^T W, the SYRK-shaped trailing updates): a 1-D grid of the LIVE tiles in lower-triangle order
   // instead of the square grid whose upper half exits at once.  The hardware deals workgroups to the 8 XCDs by id mod 8; in the
   // square grid that is the column tile mod 8, and column c of a lower triangle has nt - c live tiles: XCD 0 carried 38 % more
@@ -405,7 +403,7 @@ int launch_gemm(gpbo_ctx* ctx, const GemmArgs& g_in) {
       return GPBO_OK;
     }
   }
-  const bool prefer64 = tri64 && triangular && (blocks128 < 512 || (g.k_from_tile && blocks128 < tri64_limit));
+  const bool prefer64 = triangular && (blocks128 < 512 || (g.k_from_tile && blocks128 < tri64_limit));
   if (gemm128_enabled() && !prefer64 && g.m >= 128 && g.n >= 128 && g.k >= 256 && blocks128 >= 192) {
     constexpr size_t lds = (size_t)4 * G2_TILE * sizeof(double);   // 65 536 B
     if (!(ctx->func_attrs & ATTR_GEMM128)) {

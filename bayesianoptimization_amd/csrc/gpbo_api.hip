@@ -14,19 +14,6 @@ static std::mutex g_err_mu;
 // hipGraph captures are taken one at a time, process-wide, and not while another context of the process allocates or uploads
 // theta-search inputs (shared side): see gpbo_lml_batch.
 static std::shared_mutex g_capture_mu;
-#ifndef GPBO_CAPTURE_MODE
-#define GPBO_CAPTURE_MODE hipStreamCaptureModeThreadLocal
-#endif
-#ifdef GPBO_CAPTURE_NOLOCK           // experiment builds (scripts/archive/r04_capture_stress.sh)
-#define CAPTURE_LOCK
-#else
-#define CAPTURE_LOCK std::unique_lock<std::shared_mutex> capture_lock(g_capture_mu)
-#endif
-#ifdef GPBO_CAPTURE_TRACE
-#define CAPTURE_TRACE(...) fprintf(stderr, __VA_ARGS__)
-#else
-#define CAPTURE_TRACE(...) ((void)0)
-#endif
 static std::string g_err;
 
 void set_global_error(const std::string& s) {
@@ -750,19 +737,12 @@ int lml_upload_inputs(gpbo_ctx* ctx, const double* X, const double* y_norm, int6
   // On the context's own (non-blocking) stream, never the legacy stream: a synchronous hipMemcpy on one thread while another
   // thread's context captures its evaluation graph invalidates that capture on this runtime ("would make the legacy stream
   // depend on a capturing blocking stream"; seen with the lanes of a device group, one thread per device).
-#ifndef GPBO_CAPTURE_NOLOCK
   std::shared_lock<std::shared_mutex> not_while_capturing(g_capture_mu);
-#endif
   if ((rc = ensure(ctx, &ctx->lml_X, &ctx->cap_lml_X, N * d))) return rc;
   if ((rc = ensure(ctx, &ctx->lml_y, &ctx->cap_lml_y, N))) return rc;
-#ifdef GPBO_LML_SYNC_UPLOAD          // experiment builds (scripts/archive/r04_capture_stress.sh): the legacy-stream copies of rounds 2-3
-  GPBO_HIP(ctx, hipMemcpy(ctx->lml_X, X, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice));
-  GPBO_HIP(ctx, hipMemcpy(ctx->lml_y, y_norm, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-#else
   GPBO_HIP(ctx, hipMemcpyAsync(ctx->lml_X, X, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   GPBO_HIP(ctx, hipMemcpyAsync(ctx->lml_y, y_norm, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-#endif
   ctx->lml_N = N; ctx->lml_d = d;
   return GPBO_OK;
 }
@@ -927,8 +907,7 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
     ctx->pinned = window;
     ctx->lanes = gl; ctx->lane_stride = stride;
     ctx->no_timing = true;
-    static const bool la_lanes = dbg_env("GPBO_CHOL_LA_LANES") && dbg_env("GPBO_CHOL_LA_LANES")[0] == '1';
-    ctx->no_lookahead = n_groups > 1 && !la_lanes;
+    ctx->no_lookahead = n_groups > 1;
     const bool fused = use_fused(m);     // one launch for the whole group: nothing to capture
     // ... and the strip path's ~17 launches are enqueued faster than the device runs them: replaying them from a graph bought nothing
     // at a fixed shape (six lanes at N = 512: 0.292 ms replayed, 0.283 launched) and cost a maximize() loop — whose N grows by one
@@ -976,8 +955,8 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
           // Captures of different contexts (the lanes of a device group run on one thread per device) are taken one at a
           // time, process-wide: concurrent captures were seen to invalidate each other on this runtime
           // (tests/test_gpu_sharded.py, three virtual ranks).  A capture is ~1 ms of host work once per problem shape.
-          CAPTURE_LOCK;
-          e = hipStreamBeginCapture(ctx->stream, GPBO_CAPTURE_MODE);
+          std::unique_lock<std::shared_mutex> capture_lock(g_capture_mu);
+          e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
           if (e == hipSuccess) {
             crc = enqueue(&oh, &ih);
             e = hipStreamEndCapture(ctx->stream, &graph);
@@ -995,7 +974,6 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
           if (key.exec) { (void)hipGraphExecDestroy(key.exec); key.exec = nullptr; }
           (void)hipGetLastError();
           ctx->lml_graph_off = true;
-          CAPTURE_TRACE("gpbo: lml graph capture failed on device %d (hip %d, rc %d): direct launches from now on\n", ctx->device, (int)e, crc);
           // an invalidated capture can outlive hipStreamEndCapture on this runtime: the direct launches below need a live stream
           hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
           if (hipStreamIsCapturing(ctx->stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone) {
@@ -1006,7 +984,6 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
               (void)hipStreamDestroy(ctx->lml_stream[g]);
               ctx->lml_stream[g] = fresh;
               ctx->stream = fresh;
-              CAPTURE_TRACE("gpbo: replaced the stream the dead capture sat on (device %d)\n", ctx->device);
             }
           }
         }

@@ -123,8 +123,7 @@ __global__ __launch_bounds__(512) void mt19937_uniform_kernel(const unsigned* __
                                                               const MtChunk* __restrict__ chunks,
                                                               const unsigned* __restrict__ states,
                                                               const double* __restrict__ lohi, double* __restrict__ out,
-                                                              unsigned* __restrict__ key_out,
-                                                              int skip) {   // 1 = no emission, 2 = no regeneration (timing probes)
+                                                              unsigned* __restrict__ key_out) {
   __shared__ unsigned ring[MT_RING][MT_N];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -143,15 +142,13 @@ __global__ __launch_bounds__(512) void mt19937_uniform_kernel(const unsigned* __
   const int64_t n_steps = (my_blocks + MT_GROUP - 1) / MT_GROUP;
   for (int64_t step = 0; step <= n_steps; ++step) {
     if (generator) {
-      if (!(skip & 2)) {
-        for (int j = 1; j <= MT_GROUP; ++j) {
-          const int64_t b = bs + step * MT_GROUP + j;          // block to produce, from block b - 1
-          if (b > be) break;
-          mt_regenerate(ring[(b - 1) & (MT_RING - 1)], ring[b & (MT_RING - 1)], lane);
-          GPBO_WAVE_SYNC();
-        }
+      for (int j = 1; j <= MT_GROUP; ++j) {
+        const int64_t b = bs + step * MT_GROUP + j;          // block to produce, from block b - 1
+        if (b > be) break;
+        mt_regenerate(ring[(b - 1) & (MT_RING - 1)], ring[b & (MT_RING - 1)], lane);
+        GPBO_WAVE_SYNC();
       }
-    } else if (!(skip & 1)) {
+    } else {
       // Doubles whose SECOND word lies in the previous group of blocks (the start block itself in the first step), cut to
       // [t_begin, t_end).  Their stream indices are contiguous, so the emitting lanes simply split [t_lo, t_hi); the two
       // words of double t sit at virtual positions v1 = pos0 + 2t and v1 + 1, located in the ring relative to b_first.
@@ -303,8 +300,7 @@ static int mt_generate_rows(gpbo_ctx* ctx, int64_t M, int d, int64_t r0, int64_t
     if ((rc = mt_jump_states(ctx, dkey, stride, max_k, polys_dev, n_states, seq_dev, states_dev, windows_dev))) return rc;
   }
   mt19937_uniform_kernel<<<dim3((unsigned)chunks.size()), dim3(512), 0, ctx->stream>>>(
-      dkey, pos, chunks_dev, states_dev, (const double*)ctx->red, ctx->stage, key_out_dev,
-      dbg_env("GPBO_MT_PROBE") ? atoi(dbg_env("GPBO_MT_PROBE")) : 0);
+      dkey, pos, chunks_dev, states_dev, (const double*)ctx->red, ctx->stage, key_out_dev);
   GPBO_HIP(ctx, hipGetLastError());
   transpose_stream_kernel<<<dim3((unsigned)((Mloc + 255) / 256)), dim3(256), 0, ctx->stream>>>(ctx->stage, Mloc, d, ctx->Xc, d_total, col0);
   GPBO_HIP(ctx, hipGetLastError());

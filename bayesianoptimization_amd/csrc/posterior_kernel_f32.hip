@@ -12,7 +12,6 @@
 // with 32 train points per stage.  The reference has no fp32 path (everything is float64,
 // bayes_opt/target_space.py:95-96): this mode trades ~1e-3 relative accuracy on sigma for throughput and is
 // checked against the fp64 goldens with that tolerance (tests/test_gpu_f32.py).
-#include <cstdlib>
 #include <type_traits>
 
 #include "gpbo_internal.h"
@@ -22,15 +21,12 @@ namespace gpbo {
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 
-// Which f32 MFMA the big chunks (NP >= 512) run on: v_mfma_f32_32x32x2_f32 (default) or v_mfma_f32_16x16x4_f32
-// (GPBO_F32_MFMA=16; NP < 512 always).  Same rate, same operand bytes per flop — the 32x32 form is HALF the MFMA
-// instructions (64 cycles each instead of 32), which leaves the issue slots the LDS reads, the slab / W loads and the
-// barrier need: the 16x16 kernel ran its matrix pipe 81 % busy.  The two forms want W packed differently.
-static bool f32_use_mfma32(int64_t NP) {
-  static const bool off = dbg_env("GPBO_F32_MFMA") && atoi(dbg_env("GPBO_F32_MFMA")) == 16;
-  static const bool rt2 = dbg_env("GPBO_F32_RT") && dbg_env("GPBO_F32_RT")[0] == '2';
-  return !off && !rt2 && NP >= 512;
-}
+// Which f32 MFMA the posterior GEMM runs on: v_mfma_f32_32x32x2_f32 in 512-row chunks for NP >= 512
+// (posterior_kernel_f32x), v_mfma_f32_16x16x4_f32 in 256-row chunks below (posterior_kernel_f32).  Same rate, same operand
+// bytes per flop — the 32x32 form is HALF the MFMA instructions (64 cycles each instead of 32), which leaves the issue slots
+// the LDS reads, the slab / W loads and the barrier need: the 16x16 kernel ran its matrix pipe 81 % busy.  The two forms want
+// W packed differently.
+static bool f32_use_mfma32(int64_t NP) { return NP >= 512; }
 
 constexpr int F32_CANDS = 64;
 constexpr int F32_BK = 32;
@@ -154,11 +150,10 @@ __global__ __launch_bounds__(256) void kstar_gen_f32_kernel(const double* __rest
   if (live) mu_part[(int64_t)blockIdx.y * Mp + m0 + ml] = mu;
 }
 
-// RT = 16-row MFMA tiles per wave: 2 (wave = 32 rows, workgroup chunk = 256 rows) or 4 (64 rows / 512 rows: half
-// the LDS B-fragment reads and slab re-reads per MFMA).  p.nchunks counts chunks of 8 * 16 * RT rows.
-template <int RT>
+// Wave = 32 rows = two 16-row MFMA tiles, workgroup chunk = 256 rows; p.nchunks counts chunks of 256 rows.
 __global__ __launch_bounds__(512, 4) void posterior_kernel_f32(PostArgsF32 p) {
   __shared__ __attribute__((aligned(16))) float Ks[2 * F32_BK * F32_STRIDE];   // 20 KiB
+  constexpr int RT = 2;                   // 16-row MFMA tiles per wave
   constexpr int WROWS = 16 * RT;          // rows per wave
   constexpr int CROWS = 8 * WROWS;        // rows per workgroup chunk
 
@@ -178,7 +173,6 @@ __global__ __launch_bounds__(512, 4) void posterior_kernel_f32(PostArgsF32 p) {
   const int wrow_ld = active ? wrow0 : (NP - WROWS);    // inactive waves stream valid rows; their sums are dropped
   // packed layout is per 32-row slab: [slab32][quad][tile2][lane] float4
   const f4* wp0 = reinterpret_cast<const f4*>(p.Wp) + (int64_t)(wrow_ld / 32) * quads * 128 + lane;
-  const f4* wp1 = wp0 + quads * 128;                    // second 32-row slab (RT == 4)
 
   f4 acc[RT][4];
 #pragma unroll
@@ -200,10 +194,6 @@ __global__ __launch_bounds__(512, 4) void posterior_kernel_f32(PostArgsF32 p) {
   auto loadA = [&](int kquad, f4(&a)[RT]) {
     a[0] = wp0[((int64_t)kquad * 2 + 0) * 64];
     a[1] = wp0[((int64_t)kquad * 2 + 1) * 64];
-    if constexpr (RT == 4) {
-      a[2] = wp1[((int64_t)kquad * 2 + 0) * 64];
-      a[3] = wp1[((int64_t)kquad * 2 + 1) * 64];
-    }
   };
   auto mma_quad = [&](int buf, int qq, const f4(&a)[RT]) {
 #pragma unroll
@@ -481,16 +471,12 @@ int launch_posterior_f32(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, int* 
     PostArgsF32 a;
     a.Wp = m.Wp32; a.Kst = kst; a.part = ctx->part; a.NP = (int)m.NP; a.Mp = Mp;
     a.n_ctiles = (int)(ldk / F32_CANDS); a.ldk = ldk; a.m0 = m0;
-    // wave tile: 64 rows (chunks of 512 rows) by default; GPBO_F32_RT=2 selects 32 rows (chunks of 256)
-    const char* e = dbg_env("GPBO_F32_RT");
-    const bool rt2 = (e && e[0] == '2') || m.NP < 512;
     const bool mf32 = f32_use_mfma32(m.NP);     // (the packed W of this fit was laid out for the same choice)
-    a.nchunks = rt2 ? nchunks : (int)((m.NP + 511) / 512);
+    a.nchunks = mf32 ? (int)((m.NP + 511) / 512) : nchunks;
     const int64_t nblocks = (int64_t)a.n_ctiles * a.nchunks;
     if (nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
     if (mf32) posterior_kernel_f32x<32><<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);
-    else if (rt2) posterior_kernel_f32<2><<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);
-    else posterior_kernel_f32<4><<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);
+    else posterior_kernel_f32<<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);
     GPBO_HIP(ctx, hipGetLastError());
     *part_chunks = a.nchunks;
   }

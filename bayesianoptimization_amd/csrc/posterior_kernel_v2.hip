@@ -14,7 +14,6 @@
 //
 // Same math, same reduction order per row chunk as v1 up to the candidate-tile width; results are
 // deterministic.  Replaces the same reference lines as posterior_kernel.hip (_gpr.py:443-494).
-#include <cstdlib>
 #include <type_traits>
 
 #include "gpbo_internal.h"
@@ -55,7 +54,6 @@ constexpr int BUF_FLAGS = 0x00020000;   // gfx9 buffer descriptor word 3: raw bu
 // GEN = 1: k* generated in the kernel (fused).  GEN = 2: k* read from a slab materialised by
 // kstar_gen_kernel (the fp64 VALU work of the generation shares the FP64 datapath with the MFMAs — measured:
 // 31 % of the fused kernel's time at C3 — so paying it once per candidate instead of once per row chunk wins).
-// GEN = 0 is a timing-only ablation (k* replaced by a constant; results are wrong): GPBO_POST_ABLATE_GEN=1.
 // BK = train points per LDS stage (one s_barrier per stage): 16, or 32 for the slab kernel (half the barriers; the
 // triangular cut-off of a 16-row tile then rounds up to 32 columns — zeros of the packed W, a few per cent more MFMAs
 // in the diagonal chunk only).
@@ -65,8 +63,9 @@ constexpr int BUF_FLAGS = 0x00020000;   // gfx9 buffer descriptor word 3: raw bu
 // 268 MB round trip at N = 512, M = 65 536 and a second launch (C2: 0.09 + 0.29 ms).
 template <int DP, int KERNEL, int GEN, int BK = POST_BK, int WAVES = 8>
 __global__ __launch_bounds__(WAVES * 64, 4) void posterior_kernel_v2(PostArgs2 p) {
-  static_assert(BK == 16 || BK == 32 || BK == 64, "stages of 16, 32 or 64 train points");
-  static_assert(WAVES == 8 || (WAVES == 16 && GEN == 1 && (BK == 32 || BK == 64)), "the 16-wave form is the fused kernel with 32- or 64-point stages");
+  static_assert(GEN == 1 || GEN == 2, "k* generated in the kernel or read from a slab");
+  static_assert(BK == 16 || BK == 32, "stages of 16 or 32 train points");
+  static_assert(WAVES == 8 || (WAVES == 16 && GEN == 1 && BK == 32), "the 16-wave form is the fused kernel with 32-point stages");
   constexpr int NT = WAVES * 64;                   // threads
   constexpr int ROWS = WAVES * 32;                 // rows of W per workgroup (wave = two 16-row tiles)
   constexpr int E = BK / WAVES;                    // stage elements per thread (lane = candidate, wave = E train points)
@@ -140,11 +139,6 @@ __global__ __launch_bounds__(WAVES * 64, 4) void posterior_kernel_v2(PostArgs2 p
   // generation role: candidate = lane, train points E*wave .. E*wave + E - 1 of the stage
   auto gen_compute = [&](int stage, double (&kv)[E], double mu_weight) {
     const int j0 = stage * BK + wave * E;
-    if constexpr (GEN == 0) {
-      kv[0] = 1e-3 * lane;
-      kv[1] = 2e-3 * lane + stage;
-      return;
-    }
     if constexpr (GEN == 2) {
       const double* src = p.Kst + (int64_t)j0 * p.ldk + (int64_t)ct * V2_CANDS;       // wave-uniform
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(src), 0, 0x7fffffff, BUF_FLAGS);
@@ -408,8 +402,7 @@ int launch_posterior_v3(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks) {
   // k* workspace: the candidate set is walked slab by slab; a slab only has to be wide enough to fill the chip
   // (4e9 B = 121 984 candidates at N = 4096 = 1906 candidate tiles x 16 row chunks per launch); measured at C3: one 34 GB
   // slab 263.7 ms, eight 4 GB slabs 264.4 ms (round 1 A/B) — the big workspace bought nothing.  GPBO_KSTAR_GB overrides.
-  // 32 train points per stage: 262.9 vs 264.0 ms per C3 launch (round-2 A/B, same box, same run); GPBO_POST_BK=16 restores 16
-  static const int post_bk = (dbg_env("GPBO_POST_BK") && atoi(dbg_env("GPBO_POST_BK")) == 16) ? 16 : 32;
+  // 32 train points per stage: 262.9 vs 264.0 ms per C3 launch (round-2 A/B, same box, same run)
   const int64_t budget = kstar_slab_budget_bytes(ctx, Mp * m.NP * 8);
   int64_t ms = budget / (m.NP * 8);
   // the slab kernel addresses a stage's rows as 32-bit buffer offsets: 3 rows of ldk doubles must stay below 2^31 bytes
@@ -430,13 +423,8 @@ int launch_posterior_v3(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks) {
     a.n_ctiles = (int)(ldk / V2_CANDS); a.Kst = ctx->kst; a.ldk = ldk; a.m0 = m0;
     const int64_t nblocks = (int64_t)a.n_ctiles * nchunks;
     if (nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
-    if (post_bk == 32) {
-      const size_t lds = (size_t)(2 * 32 * V2_STRIDE) * sizeof(double);
-      posterior_kernel_v2<4, 0, 2, 32><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
-    } else {
-      const size_t lds = (size_t)(2 * POST_BK * V2_STRIDE) * sizeof(double);
-      posterior_kernel_v2<4, 0, 2><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
-    }
+    const size_t lds = (size_t)(2 * 32 * V2_STRIDE) * sizeof(double);
+    posterior_kernel_v2<4, 0, 2, 32><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
     GPBO_HIP(ctx, hipGetLastError());
   }
   return GPBO_OK;
@@ -445,14 +433,6 @@ int launch_posterior_v3(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks) {
 template <int DP, int KERNEL>
 static int launch_v2_t(gpbo_ctx* ctx, const PostArgs2& a, int64_t nblocks) {
   const size_t lds = (size_t)(2 * POST_BK * V2_STRIDE + DP * V2_CANDS) * sizeof(double);
-#ifdef GPBO_DEBUG   // timing-only ablation (k* replaced by a constant: WRONG results) — scripts/ablate_gen.py, debug build only
-  const char* ab = dbg_env("GPBO_POST_ABLATE_GEN");
-  if (ab && ab[0] == '1') {
-    posterior_kernel_v2<DP, KERNEL, 0><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
-    GPBO_HIP(ctx, hipGetLastError());
-    return GPBO_OK;
-  }
-#endif
   posterior_kernel_v2<DP, KERNEL, 1><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
@@ -474,21 +454,6 @@ static int launch_v2_k(gpbo_ctx* ctx, int DP, const PostArgs2& a, int64_t nblock
 // chunks the sum-of-squares partials are split into (what posterior_finalize_kernel sums over).
 template <int DP, int KERNEL>
 static int launch_v4_t(gpbo_ctx* ctx, const PostArgs2& a, int64_t nblocks) {
-#ifdef GPBO_DEBUG   // experiment (round 5): 64-point stages = half the workgroup barriers of the 1024-thread workgroup; GPBO_POST_V4_BK=64
-  if (dbg_env("GPBO_POST_V4_BK") && atoi(dbg_env("GPBO_POST_V4_BK")) == 64) {
-    const size_t lds64 = (size_t)(2 * 64 * V2_STRIDE + DP * V2_CANDS) * sizeof(double);
-    static bool attr[6] = {false, false, false, false, false, false};
-    const int ai = KERNEL * 3 + (DP <= 8 ? 0 : DP <= 16 ? 1 : 2);
-    if (!attr[ai]) {
-      GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(posterior_kernel_v2<DP, KERNEL, 1, 64, 16>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * 64 * V2_STRIDE + 64 * V2_CANDS) * 8));
-      attr[ai] = true;
-    }
-    posterior_kernel_v2<DP, KERNEL, 1, 64, 16><<<dim3((unsigned)nblocks), dim3(1024), lds64, ctx->stream>>>(a);
-    GPBO_HIP(ctx, hipGetLastError());
-    return GPBO_OK;
-  }
-#endif
   const size_t lds = (size_t)(2 * 32 * V2_STRIDE + DP * V2_CANDS) * sizeof(double);
   posterior_kernel_v2<DP, KERNEL, 1, 32, 16><<<dim3((unsigned)nblocks), dim3(1024), lds, ctx->stream>>>(a);
   GPBO_HIP(ctx, hipGetLastError());

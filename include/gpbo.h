@@ -390,7 +390,7 @@ int gpbo_hbm_copy_peak(gpbo_ctx* ctx, int64_t bytes, double* gbps);
 /* ==== DEBUG BUILD ONLY (-DGPBO_DEBUG: bayesianoptimization_amd/libgpbo_dbg.so) ==========================================
  * Self-test seams, single-kernel timers and micro-benchmarks the tests and scripts/ use.  The product library
  * (libgpbo.so) exports none of them, reads none of the A/B environment switches (GPBO_CHOL_*, GPBO_POST_*, GPBO_SMALL_MAX,
- * GPBO_SELECT_V2*, GPBO_MT_*, GPBO_F32_*, GPBO_GEMM128, GPBO_TRI64*, GPBO_LML_GRAPH, GPBO_POLISH_FUSED*) and contains no scratch-using kernel. */
+ * GPBO_SELECT_V2*, GPBO_MT_*, GPBO_GEMM128, GPBO_TRI_GRID, GPBO_LML_GRAPH, GPBO_POLISH_FUSED*) and contains no scratch-using kernel. */
 #ifdef GPBO_DEBUG
 /* The optimiser of gpbo_polish_seeds alone, over a host objective (self-test seam: no device, no context): `fg` is called
  * once per lockstep round with the trial points of the runs that are still alive — x (n_live,d) -> f (n_live), g (n_live,d) —

@@ -62,11 +62,17 @@ def test_debug_entry_points_live_in_the_debug_library_only():
 
 
 ENV_ALLOW_LIST = {"GPBO_KSTAR_GB", "GPBO_COMM_TIMEOUT_S", "GPBO_GROUP_TIMEOUT_S", "GPBO_GROUP_HOST_MERGE"}
+# switches and build macros of kernel experiments that were measured and not adopted (rounds 2-6): retired with their code paths
+RETIRED = {"GPBO_CHOL_FUSED_STEP", "GPBO_CHOL_SQUARE_TILES", "GPBO_CHOL_LA_CUS", "GPBO_CHOL_LA_LANES", "GPBO_POST_ABLATE_GEN",
+           "GPBO_POST_V4_BK", "GPBO_POST_BK", "GPBO_F32_MFMA", "GPBO_F32_RT", "GPBO_SELECT_ITEMS", "GPBO_SELECT_FUSED_ACQ",
+           "GPBO_TRI64", "GPBO_TRI64_LIMIT", "GPBO_MT_PROBE", "GPBO_CAPTURE_NOLOCK", "GPBO_CAPTURE_TRACE", "GPBO_LML_SYNC_UPLOAD",
+           "GPBO_CAPTURE_MODE", "GPBO_CHOL_POLL_SLEEP", "GPBO_CHOL_WAKE_MASK"}
 
 
-def test_the_product_reads_only_the_documented_environment_variables():
+def test_the_product_reads_only_the_documented_variables_and_no_retired_switch():
     """No switch that changes a result, or selects a retired kernel, survives in the product: every getenv() in csrc/ is
-    either one of the four documented variables or sits behind dbg_env(), which is a constant NULL without -DGPBO_DEBUG."""
+    either one of the four documented variables or sits behind dbg_env(), which is a constant NULL without -DGPBO_DEBUG.
+    And no RETIRED switch is left in the sources or in either library."""
     csrc = os.path.join(ROOT, "bayesianoptimization_amd", "csrc")
     direct, debug_only = set(), set()
     for fn in sorted(os.listdir(csrc)):
@@ -88,10 +94,18 @@ def test_the_product_reads_only_the_documented_environment_variables():
     for name in debug_only:
         assert name.encode() + b"\0" not in blob, f"{name} is still read by the product library"
         assert name.encode() in dblob
-    for name in ("GPBO_POST_ABLATE_GEN", "GPBO_CHOL_OUTER", "GPBO_SELECT_V2"):
+    for name in ("GPBO_POST_KERNEL", "GPBO_CHOL_OUTER", "GPBO_SELECT_V2"):
         assert name in debug_only
     for name in ENV_ALLOW_LIST:
         assert name.encode() in blob
+    # the retired switches are gone: not in the sources (comments included), not in either library
+    inc = os.path.join(ROOT, "include")
+    for path in [os.path.join(csrc, fn) for fn in sorted(os.listdir(csrc))] + [os.path.join(inc, fn) for fn in sorted(os.listdir(inc))]:
+        src = open(path).read()
+        for name in RETIRED:
+            assert name not in src, f"{name} is still named in {os.path.relpath(path, ROOT)}"
+    for name in RETIRED:
+        assert name.encode() not in blob and name.encode() not in dblob, f"{name} is still in a library"
 
 
 def _gfx950_code_objects(so_path):
