@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py — suggest-step throughput of the HIP GP-posterior + acquisition engine on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-suggest] [--no-extra-configs]]
 
 A "step" is one pass of the hot path over one batch of synthetic input (BASELINE.json metric,
 configs[2] = C3 when it fits one GPU): fit the GP at fixed theta (K, Cholesky, W = L^-1, alpha), then
@@ -18,6 +19,11 @@ per GPU over RCCL.  Two ways to own the GPUs, same kernels, same exchange:
 
 No torch anywhere: the product path is ctypes -> libgpbo.so (HIP).  If RCCL cannot be brought up the line says
 `"collective": "FAILED"` and the exit status is non-zero — there is no fallback transport.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: its roofline and step breakdown
+are the HIP events of the timed steps themselves.  Everything that takes work of its own goes behind --full: the measured
+matrix peak (MFMA probes) and the PMC traffic from profiles/, the stage timings of one fit alone when the fits overlap, parity
+with the reference's goldens, the CPU baseline, the other BASELINE.json configs and the ms/suggest measurements.
 """
 from __future__ import annotations
 
@@ -689,11 +695,15 @@ def main():
     ap.add_argument("--config", default=None,
                     help="BASELINE.json config; default: C3 on one GPU, C4 (= C3's GP with EI, 2^20 candidates per GPU, "
                          "8 x 2^20 at --gpus 8) when sharded")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-suggest", action="store_true", help="skip the ms/suggest measurement after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline does not need: measured peak, PMC traffic, "
+                         "parity with the reference, CPU baseline, the other BASELINE.json configs, ms/suggest")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-suggest", action="store_true", help="(with --full) skip the ms/suggest measurement after the timed region")
     ap.add_argument("--suggest-only", action="store_true", help="(child of a multi-rank run) print only the suggest_ms object")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the other BASELINE.json configs (C2, C4 shard 0, C5 fp32 shard 0) run after the default headline")
+                    help="(with --full) skip the other BASELINE.json configs (C2, C4 shard 0, C5 fp32 shard 0) run after the "
+                         "default headline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
@@ -826,9 +836,9 @@ def main():
     for _ in range(args.warmup):
         step()
     fit_probe = None
-    if overlap:
+    if overlap and args.full:
         # stage timings of ONE fit on the main stream (the overlapped fits are not bracketed by the timing events); outside
-        # the timed region
+        # the timed region.  A plain run has no fit stage timings to quote (null in the line)
         eng.fit(X, yn, w.kernel, w.length_scale, w.noise, slot=0, precision=prec)
         fit_probe = dict(eng.last_timings())
     kern_ms = {"fit": 0.0, "posterior_main": 0.0, "posterior_finalize": 0.0, "acq_argbest": 0.0, "kmat": 0.0,
@@ -951,88 +961,95 @@ def main():
             # `fit`, `kmat`, `cholesky`, `trtri` above = n_gp x ONE fit measured alone on the main stream; in the timed steps
             # the fits of the GPs run side by side:
             out["step_breakdown_ms"]["fits_overlapped_wall"] = kern_ms_overlapped[0] / steps
-            out["roofline_fit"]["note"] = ("stage timings of one fit measured alone (outside the timed region); in the timed steps "
-                                           "the two GPs' fits are enqueued side by side: step_breakdown_ms.fits_overlapped_wall")
-        if mode == "single":
-            try:
-                mp = measured_peak(eng, prec)
-                out["roofline"].update(mp)
-                out["roofline"]["frac_of_measured"] = achieved / mp["peak_measured"]
-                out["roofline"]["frac_at_sustained_clock"] = achieved / mp["peak_at_sustained_clock"]
-            except Exception as e:  # noqa: BLE001
-                log(f"[bench] measured peak not available: {e!r}")
-        # HBM traffic of the dominant kernels: separate rocprofv3 --pmc passes of this very command, summarised in profiles/
-        try:
-            pm, note = pmc_summary_for(w)
-            out["roofline"]["traffic_note"] = note
-            if pm is not None:
-                keys = [k_ for k_ in pm if "posterior_kernel" in k_ or "kstar_gen" in k_]
-                out["roofline"]["traffic"] = sum(pm[k_].get("fetch_bytes_corrected_x2", 0.0) * pm[k_].get("launches_per_step", 1)
-                                                 + pm[k_].get("write_bytes", 0.0) * pm[k_].get("launches_per_step", 1) for k_ in keys)
-                out["roofline"]["traffic_algorithmic"] = (w.d + 1) * 8 * M * n_gp + n_gp * w.N * w.N * 4
-                busy = [pm[k_].get("mfma_pipe_busy_frac") for k_ in keys if "posterior_kernel" in k_ and pm[k_].get("mfma_pipe_busy_frac")]
-                out["roofline"]["mfma_pipe_busy_frac_pmc"] = max(busy) if busy else None
-                for k_ in pm:
-                    if k_.startswith("_"):
-                        continue
-                    if "gemm128" in k_ and pm[k_].get("mfma_pipe_busy_frac") is not None:
-                        out["roofline_fit"].setdefault("trailing_update_mfma_busy", {})[k_[:60]] = pm[k_]["mfma_pipe_busy_frac"]
-        except Exception as e:  # noqa: BLE001
-            log(f"[bench] PMC summary not usable: {e!r}")
-        # parity with the reference's answer for exactly this job (any n_gpus)
-        g = reference_golden(w.name, n_gpus, M)
-        if g is not None:
-            top10 = np.asarray(best[2], dtype=np.int64)
-            out["parity"] = {"argmin_equals_reference": bool(int(best[0]) == g["argmin"]),
-                             "top10_equals_reference": bool(np.array_equal(top10, g["top_idx"][:10])),
-                             "argmin_in_reference_top16": bool(int(best[0]) in set(g["top_idx"][:16].tolist())),
-                             "min_rel_err": float(abs(best[1] - g["min"]) / abs(g["min"])),
-                             "reference": g["source"],
-                             "arithmetic": "fp32 posterior vs the fp64 reference" if prec else "fp64"}
-        if mode == "single" and not args.no_cpu_baseline:
-            try:
-                _, _, _, _, gpu_ys = eng.acq_argbest(w.acq, w.acq_param, 0.0 if y_max is None else y_max, lb_c, ub_c,
-                                                     k_seeds=0, return_values=True)
-                out["cpu_baseline"] = cpu_baseline(w, X, y, c, Xc, y_max, gpu_ys)
-            except Exception as e:
-                log(f"[bench] cpu_baseline failed: {e!r}")
-                out["cpu_baseline"] = None
-        if mode == "single" and args.config is None and not args.no_extra_configs:
-            # every other BASELINE.json config, in the line the driver records (5 steps each, the CPU path beside each on a
-            # bounded sample: C1 / C2 whole or 3 chunks, the two big shards 2 chunks)
-            out["configs"] = {}
-            for key, nm, cpu_chunks in (("C1", "C1", 1), ("C2", "C2", 3), ("C4_s0", "C4", 2), ("C5_f32_s0", "C5", 2)):
+            if fit_probe is None:     # plain run: no fit was measured alone, and the overlapped fits carry no stage events
+                out["step_breakdown_ms"].update({k_: None for k_ in ("fit", "kmat", "cholesky", "trtri")})
+                out["roofline_fit"] = {"note": "the two GPs' fits run side by side: stage timings of one fit alone with --full"}
+            else:
+                out["roofline_fit"]["note"] = ("stage timings of one fit measured alone (outside the timed region); in the timed "
+                                               "steps the two GPs' fits are enqueued side by side: "
+                                               "step_breakdown_ms.fits_overlapped_wall")
+        if args.full:
+            if mode == "single":
                 try:
-                    out["configs"][key] = run_extra_config(eng, nm, cpu_chunks=cpu_chunks)
+                    mp = measured_peak(eng, prec)
+                    out["roofline"].update(mp)
+                    out["roofline"]["frac_of_measured"] = achieved / mp["peak_measured"]
+                    out["roofline"]["frac_at_sustained_clock"] = achieved / mp["peak_at_sustained_clock"]
                 except Exception as e:  # noqa: BLE001
-                    log(f"[bench] extra config {key} failed: {e!r}")
-                    out["configs"][key] = {"error": repr(e)}
-            eng.set_candidates(Xc)
-        if mode in ("single", "group") and not w.constrained and not args.no_suggest:
-            # the other half of BASELINE.json's metric, ms/suggest: whole suggest() calls through the drop-in seams
-            # (refit at fixed theta, candidates drawn from the caller's RandomState on the device, posterior, acquisition,
-            # arg-best; with the reference's default 10 local searches and without) — outside the timed region above
+                    log(f"[bench] measured peak not available: {e!r}")
+            # HBM traffic of the dominant kernels: separate rocprofv3 --pmc passes of this very command, summarised in profiles/
             try:
-                # group mode: the same seams over the device group, as accelerate(optimizer, devices=[...]) installs it
-                # (one process, candidates sharded over the GPUs, n_random = the whole job's candidates)
-                out["suggest_ms"] = suggest_latency(w, X, y, eng, M * n_gpus)
-                if mode == "group":
-                    out["suggest_ms"]["engine"] = f"GroupEngine over {n_gpus} device(s), n_random = {M * n_gpus}"
+                pm, note = pmc_summary_for(w)
+                out["roofline"]["traffic_note"] = note
+                if pm is not None:
+                    keys = [k_ for k_ in pm if "posterior_kernel" in k_ or "kstar_gen" in k_]
+                    out["roofline"]["traffic"] = sum(pm[k_].get("fetch_bytes_corrected_x2", 0.0) * pm[k_].get("launches_per_step", 1)
+                                                     + pm[k_].get("write_bytes", 0.0) * pm[k_].get("launches_per_step", 1) for k_ in keys)
+                    out["roofline"]["traffic_algorithmic"] = (w.d + 1) * 8 * M * n_gp + n_gp * w.N * w.N * 4
+                    busy = [pm[k_].get("mfma_pipe_busy_frac") for k_ in keys
+                            if "posterior_kernel" in k_ and pm[k_].get("mfma_pipe_busy_frac")]
+                    out["roofline"]["mfma_pipe_busy_frac_pmc"] = max(busy) if busy else None
+                    for k_ in pm:
+                        if k_.startswith("_"):
+                            continue
+                        if "gemm128" in k_ and pm[k_].get("mfma_pipe_busy_frac") is not None:
+                            out["roofline_fit"].setdefault("trailing_update_mfma_busy", {})[k_[:60]] = pm[k_]["mfma_pipe_busy_frac"]
             except Exception as e:  # noqa: BLE001
-                log(f"[bench] suggest latency failed: {e!r}")
-        if mode == "ranks" and not w.constrained and not args.no_suggest:
-            # ms/suggest for the same N GPUs: BayesianOptimization.suggest() is ONE process (accelerate(devices=[...]) ->
-            # GroupEngine), so rank 0 measures it in a child process that owns all N devices while the other ranks idle at
-            # the closing barrier; a child that fails or exceeds its deadline costs only this key
-            out["suggest_ms"] = suggest_in_child(n_gpus, w.name)
-        if mode in ("single", "group") and not w.constrained and not args.no_suggest:
-            # ... and the same suggest() with the job's candidates FIXED at the config's own M (2^20), however many GPUs share it
-            try:
-                out["suggest_ms_fixed_total"] = suggest_fixed_total(w, X, eng, M, n_gpus, mode)
-            except Exception as e:  # noqa: BLE001
-                out["suggest_ms_fixed_total"] = {"error": repr(e)}
-        elif mode == "ranks" and isinstance(out.get("suggest_ms"), dict) and "fixed_total" in out["suggest_ms"]:
-            out["suggest_ms_fixed_total"] = out["suggest_ms"].pop("fixed_total")
+                log(f"[bench] PMC summary not usable: {e!r}")
+            # parity with the reference's answer for exactly this job (any n_gpus)
+            g = reference_golden(w.name, n_gpus, M)
+            if g is not None:
+                top10 = np.asarray(best[2], dtype=np.int64)
+                out["parity"] = {"argmin_equals_reference": bool(int(best[0]) == g["argmin"]),
+                                 "top10_equals_reference": bool(np.array_equal(top10, g["top_idx"][:10])),
+                                 "argmin_in_reference_top16": bool(int(best[0]) in set(g["top_idx"][:16].tolist())),
+                                 "min_rel_err": float(abs(best[1] - g["min"]) / abs(g["min"])),
+                                 "reference": g["source"],
+                                 "arithmetic": "fp32 posterior vs the fp64 reference" if prec else "fp64"}
+            if mode == "single" and not args.no_cpu_baseline:
+                try:
+                    _, _, _, _, gpu_ys = eng.acq_argbest(w.acq, w.acq_param, 0.0 if y_max is None else y_max, lb_c, ub_c,
+                                                         k_seeds=0, return_values=True)
+                    out["cpu_baseline"] = cpu_baseline(w, X, y, c, Xc, y_max, gpu_ys)
+                except Exception as e:
+                    log(f"[bench] cpu_baseline failed: {e!r}")
+                    out["cpu_baseline"] = None
+            if mode == "single" and args.config is None and not args.no_extra_configs:
+                # every other BASELINE.json config, in the line the driver records (5 steps each, the CPU path beside each on a
+                # bounded sample: C1 / C2 whole or 3 chunks, the two big shards 2 chunks)
+                out["configs"] = {}
+                for key, nm, cpu_chunks in (("C1", "C1", 1), ("C2", "C2", 3), ("C4_s0", "C4", 2), ("C5_f32_s0", "C5", 2)):
+                    try:
+                        out["configs"][key] = run_extra_config(eng, nm, cpu_chunks=cpu_chunks)
+                    except Exception as e:  # noqa: BLE001
+                        log(f"[bench] extra config {key} failed: {e!r}")
+                        out["configs"][key] = {"error": repr(e)}
+                eng.set_candidates(Xc)
+            if mode in ("single", "group") and not w.constrained and not args.no_suggest:
+                # the other half of BASELINE.json's metric, ms/suggest: whole suggest() calls through the drop-in seams
+                # (refit at fixed theta, candidates drawn from the caller's RandomState on the device, posterior, acquisition,
+                # arg-best; with the reference's default 10 local searches and without) — outside the timed region above
+                try:
+                    # group mode: the same seams over the device group, as accelerate(optimizer, devices=[...]) installs it
+                    # (one process, candidates sharded over the GPUs, n_random = the whole job's candidates)
+                    out["suggest_ms"] = suggest_latency(w, X, y, eng, M * n_gpus)
+                    if mode == "group":
+                        out["suggest_ms"]["engine"] = f"GroupEngine over {n_gpus} device(s), n_random = {M * n_gpus}"
+                except Exception as e:  # noqa: BLE001
+                    log(f"[bench] suggest latency failed: {e!r}")
+            if mode == "ranks" and not w.constrained and not args.no_suggest:
+                # ms/suggest for the same N GPUs: BayesianOptimization.suggest() is ONE process (accelerate(devices=[...]) ->
+                # GroupEngine), so rank 0 measures it in a child process that owns all N devices while the other ranks idle at
+                # the closing barrier; a child that fails or exceeds its deadline costs only this key
+                out["suggest_ms"] = suggest_in_child(n_gpus, w.name)
+            if mode in ("single", "group") and not w.constrained and not args.no_suggest:
+                # ... and the same suggest() with the job's candidates FIXED at the config's own M (2^20), however many GPUs share it
+                try:
+                    out["suggest_ms_fixed_total"] = suggest_fixed_total(w, X, eng, M, n_gpus, mode)
+                except Exception as e:  # noqa: BLE001
+                    out["suggest_ms_fixed_total"] = {"error": repr(e)}
+            elif mode == "ranks" and isinstance(out.get("suggest_ms"), dict) and "fixed_total" in out["suggest_ms"]:
+                out["suggest_ms_fixed_total"] = out["suggest_ms"].pop("fixed_total")
         try:
             out["summary"] = summary_of(out)       # LAST key: survives a record that keeps only the line's tail
         except Exception as e:  # noqa: BLE001

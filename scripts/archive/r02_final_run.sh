@@ -11,10 +11,10 @@ for c in C3 C5; do
   bash scripts/profile_pmc.sh final/pmc_$c --config $c > $F/pmc_$c.log 2>&1
   cp $F/pmc_$c/summary.json profiles/r02_pmc_$c.json; cp $F/pmc_$c/summary.txt profiles/r02_pmc_$c.txt
 done
-python bench.py > $F/bench_C3.json 2> $F/bench_C3.err
-python bench.py --config C5 > $F/bench_C5.json 2> $F/bench_C5.err
-python bench.py --config C4 --no-cpu-baseline --no-suggest > $F/bench_C4_1gpu.json 2> $F/bench_C4_1gpu.err
-GPBO_BENCH_DEVICES=0,0 python bench.py --gpus 2 --no-cpu-baseline --no-suggest > $F/bench_C4_group2_virtual.json 2> $F/bench_C4_group2_virtual.err
+python bench.py --full > $F/bench_C3.json 2> $F/bench_C3.err
+python bench.py --full --config C5 > $F/bench_C5.json 2> $F/bench_C5.err
+python bench.py --full --config C4 --no-cpu-baseline --no-suggest > $F/bench_C4_1gpu.json 2> $F/bench_C4_1gpu.err
+GPBO_BENCH_DEVICES=0,0 python bench.py --full --gpus 2 --no-cpu-baseline --no-suggest > $F/bench_C4_group2_virtual.json 2> $F/bench_C4_group2_virtual.err
 python scripts/config_table.py > $F/config_table.log 2>&1; cp gpurun_out/config_table.json $F/ 2>/dev/null
 python scripts/archive/r02_fit_probe.py > $F/fit_probe.log 2>&1; cp gpurun_out/r02_fit_probe.json $F/ 2>/dev/null
 python scripts/theta_search_timing.py > $F/theta.log 2>&1; cp gpurun_out/theta_search_timing.json $F/ 2>/dev/null

@@ -12,7 +12,7 @@ timeout 900 python -m pytest tests -x -q -m gpu > $F/pytest.log 2>&1; echo "pyte
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $F/smoke.log 2>&1; tail -1 $F/smoke.log
 bash scripts/profile_pmc.sh final3/pmc_C3 --config C3 > $F/pmc_C3.log 2>&1
 cp $F/pmc_C3/summary.json profiles/r03_pmc_C3.json; cp $F/pmc_C3/summary.txt profiles/r03_pmc_C3.txt
-timeout 300 python bench.py > $F/bench_default.json 2> $F/bench_default.err
+timeout 300 python bench.py --full > $F/bench_default.json 2> $F/bench_default.err
 python - "$F/bench_default.json" <<'PY'
 import json, sys
 try:

@@ -13,6 +13,6 @@ tail -12 $O/lml_crossover.log
 tail -5 $O/theta_search_timing.log
 ( time timeout 400 scripts/archive/r04_kmat_pmc.sh r04a/kmat_pmc ) > $O/kmat_pmc.log 2>&1
 tail -40 $O/kmat_pmc.log
-( time timeout 400 python bench.py ) > $O/bench_default.json 2> $O/bench_default.err
+( time timeout 400 python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err
 tail -c 3000 $O/bench_default.json
 tail -5 $O/bench_default.err

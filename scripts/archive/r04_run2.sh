@@ -7,7 +7,7 @@ O=gpurun_out/r04b
 tail -12 $O/pytest_gpu.log
 ( time timeout 200 python scripts/archive/r04_post_small_np_ab.py ) > $O/post_ab.log 2>&1
 tail -8 $O/post_ab.log
-( time timeout 400 python bench.py --no-cpu-baseline ) > $O/bench_default.json 2> $O/bench_default.err
+( time timeout 400 python bench.py --full --no-cpu-baseline ) > $O/bench_default.json 2> $O/bench_default.err
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r04b/bench_default.json'))

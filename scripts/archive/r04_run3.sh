@@ -15,7 +15,7 @@ for k,v in d.items():
 PY
 ( time timeout 100 python scripts/archive/r03_kmat_probe.py ) > $O/kmat_probe.log 2>&1
 tail -3 $O/kmat_probe.log
-( time timeout 400 python bench.py --no-cpu-baseline ) > $O/bench_default.json 2> $O/bench_default.err
+( time timeout 400 python bench.py --full --no-cpu-baseline ) > $O/bench_default.json 2> $O/bench_default.err
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r04c/bench_default.json'))

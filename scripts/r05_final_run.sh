@@ -13,7 +13,7 @@ bash scripts/profile_pmc.sh r05f/pmc_C3 --config C3 > $F/pmc_C3.log 2>&1
 cp $F/pmc_C3/summary.json profiles/r05_pmc_C3.json; cp $F/pmc_C3/summary.txt profiles/r05_pmc_C3.txt
 bash scripts/profile_pmc.sh r05f/pmc_C2 --config C2 > $F/pmc_C2.log 2>&1
 cp $F/pmc_C2/summary.json profiles/r05_pmc_C2.json; cp $F/pmc_C2/summary.txt profiles/r05_pmc_C2.txt
-( time timeout 500 python bench.py ) > $F/bench_default.json 2> $F/bench_default.err
+( time timeout 500 python bench.py --full ) > $F/bench_default.json 2> $F/bench_default.err
 python - "$F/bench_default.json" <<'PY'
 import json, sys
 try:
@@ -32,7 +32,7 @@ try:
 except Exception as e:
     print("ERR", e)
 PY
-( time GPBO_BENCH_DEVICES=0,0 timeout 400 python bench.py --gpus 2 ) > $F/bench_C4_group2_virtual.json 2> $F/bench_C4_group2_virtual.err
+( time GPBO_BENCH_DEVICES=0,0 timeout 400 python bench.py --full --gpus 2 ) > $F/bench_C4_group2_virtual.json 2> $F/bench_C4_group2_virtual.err
 tail -c 600 $F/bench_C4_group2_virtual.json; tail -2 $F/bench_C4_group2_virtual.err
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $F/c2_trace -o t -- python bench.py --config C2 --steps 20 --warmup 3 --no-cpu-baseline --no-suggest > $F/c2_trace.json 2> $F/c2_trace.err
 timeout 300 bash scripts/r05_pmc_C2_posterior.sh > $F/pmc_C2_posterior.log 2>&1; cp gpurun_out/r05_pmc_C2_posterior_summary.* $F/ 2>/dev/null

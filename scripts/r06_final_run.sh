@@ -14,7 +14,7 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')
 bash scripts/profile_pmc.sh r06f/pmc_C3 --config C3 > $F/pmc_C3.log 2>&1
 cp $F/pmc_C3/summary.json profiles/r06_pmc_C3.json; cp $F/pmc_C3/summary.txt profiles/r06_pmc_C3.txt
 bash scripts/profile_pmc.sh r06f/pmc_C2 --config C2 > $F/pmc_C2.log 2>&1
-( time timeout 600 python bench.py ) > $F/bench_default.json 2> $F/bench_default.err
+( time timeout 600 python bench.py --full ) > $F/bench_default.json 2> $F/bench_default.err
 python - "$F/bench_default.json" <<'PY'
 import json, sys
 try:
@@ -25,7 +25,7 @@ try:
 except Exception as e:
     print("ERR", e)
 PY
-( time GPBO_BENCH_DEVICES=0,0,0,0,0,0,0,0 timeout 600 python bench.py --gpus 8 ) > $F/bench_C4_group8_virtual.json 2> $F/bench_C4_group8_virtual.err
+( time GPBO_BENCH_DEVICES=0,0,0,0,0,0,0,0 timeout 600 python bench.py --full --gpus 8 ) > $F/bench_C4_group8_virtual.json 2> $F/bench_C4_group8_virtual.err
 tail -c 500 $F/bench_C4_group8_virtual.json; tail -2 $F/bench_C4_group8_virtual.err
 timeout 400 bash scripts/r06_lml_evidence.sh r06f/lml > $F/lml_evidence.log 2>&1
 python scripts/r06_lml_timeline.py $F/lml/trace_4096/t_kernel_trace.csv > $F/lml_4096_timeline.txt 2>/dev/null
