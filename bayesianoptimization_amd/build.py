@@ -32,6 +32,7 @@ SOURCES = {
     "chol_kernels.hip": [],
     "posterior_kernel.hip": [],
     "posterior_kernel_v2.hip": [],
+    "posterior_i8.hip": [],                    # the slab GEMM on int8 matrix cores (fixed-point digit planes, exact level sums)
     "posterior_small.hip": [],
     "polish.hip": [],                          # gpbo_polish_seeds: the local-search stage as one C call (host optimiser, device evaluations)
     "polish_fused.hip": [],                    # ... and as one launch for NP <= 512: one workgroup per local search (NP <= 128: thread = training point), evaluations + optimiser inside

@@ -34,6 +34,8 @@ static void free_model(Model& m) {
     *p = nullptr;
   }
   if (m.Wp32) (void)hipFree(m.Wp32);
+  if (m.Wd) (void)hipFree(m.Wd);
+  if (m.wscale) (void)hipFree(m.wscale);
   m = Model();
 }
 
@@ -439,6 +441,7 @@ static int prepare_model(gpbo_ctx* ctx, Model& m, const char* who, bool have_inp
 
   m.fitted = false;
   m.wp_packed = false;     // (set by the small fit paths at enqueue time; a failure before finish_enqueue must not leave it behind)
+  m.wd_valid = false;      // W is about to change: the int8 digit planes of the old one must not be used
   m.wt_valid = false;      // (K no longer holds the transpose of this slot's W)
   m.M_post = -1;
   const int64_t NP = round_up(N, NB);
@@ -493,6 +496,7 @@ static int finish_enqueue(gpbo_ctx* ctx, Model& m) {
   int rc;
   if (!m.wp_packed && (rc = launch_pack_w(ctx, m))) return rc;
   m.wp_packed = false;
+  m.wd_valid = false;              // W changed: the int8 digit planes are re-packed by the next posterior that uses them
   if (m.precision == GPBO_F32) {   // fp32 posterior: W rounded to fp32 in f32-MFMA fragment order (fit itself is fp64)
     if ((rc = ensure(ctx, &m.Wp32, &m.cap_Wp32, m.NP * m.NP))) return rc;
     if ((rc = launch_pack_w32(ctx, m))) return rc;

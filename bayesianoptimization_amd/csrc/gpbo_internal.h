@@ -42,6 +42,11 @@ struct Model {
   double* Wp = nullptr;    // NP*NP doubles, MFMA-fragment packed W for the posterior kernel
   float* Wp32 = nullptr;   // NP*NP floats, W rounded to fp32 in v_mfma_f32_16x16x4_f32 fragment order (precision F32)
   int64_t cap_Wp32 = 0;
+  uint4* Wd = nullptr;     // int8 digit planes of W, row-scaled (posterior_i8.hip), packed on first use after a fit
+  int64_t cap_Wd = 0;
+  double* wscale = nullptr; // [NP] power of two per row of W for the int8 GEMM's epilogue, then NP ints: the row exponents
+  int64_t cap_wscale = 0;
+  bool wd_valid = false;   // Wd / wscale hold the current fit's W
   double* dinv = nullptr;  // [NP/NB][NB][NB] inverses of the diagonal blocks of L
   double* tmp = nullptr;   // NP*NP/2 doubles workspace (trtri)
   double* yn = nullptr;    // [NP] normalised targets, zero padded
@@ -403,6 +408,9 @@ int launch_posterior_v2(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, const 
 int launch_posterior_v3(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks);
 int launch_posterior_v4(gpbo_ctx* ctx, Model& m, int64_t Mp, int* part_chunks, const PostEnds* ends = nullptr);   // fused, 512-row chunks (NP <= 1024)
 int launch_kstar_slab(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks);
+int launch_kstar_digits(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks);  // posterior_kernel_v2.hip
+bool posterior_i8_serves(const Model& m);                                                   // posterior_i8.hip
+int launch_posterior_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, int* part_chunks);
 // posterior_cov.hip
 int launch_posterior_cov(gpbo_ctx* ctx, Model& m, int64_t M, double y_std, double** cov_dev, int64_t* ld_cov);
 // posterior_kernel_f32.hip

@@ -9,7 +9,8 @@
 //   M <= small_batch_limit(NP)   posterior_small.hip      batched GEMV (latency path: predicts of the host optimisers)
 //   precision F32                posterior_kernel_f32.hip fp32 k* slab + v_mfma_f32_16x16x4_f32 GEMM
 //   NP <= 512 (<= 2 row chunks)  posterior_kernel_v2.hip  GEN = 1: k* generated inside the MFMA kernel
-//   otherwise                    posterior_kernel_v2.hip  GEN = 2: k* slab generated once + MFMA GEMM ("v3")
+//   otherwise                    posterior_kernel_v2.hip  GEN = 2: k* slab generated once + MFMA GEMM ("v3"),
+//     from NP = 2048 on          posterior_i8.hip         the same slab as int8 digit planes + int8 MFMA GEMM
 // The row-chunk partial sums every path writes are combined in a fixed order by posterior_finalize_kernel,
 // so results are run-to-run deterministic.  (The first version of the fused kernel — 128 candidates x 256
 // rows per workgroup, 2 waves/SIMD, 403 ms per C3 launch — is in the git history; docs/LAB_NOTEBOOK.md §4.1.)
@@ -18,6 +19,7 @@
 
 #include "gpbo_internal.h"
 #include "fit_bodies.h"
+#include "i8_digits.h"
 
 namespace gpbo {
 
@@ -114,7 +116,11 @@ int launch_posterior(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y
   // mu / sd itself); from there to 32 768 candidates the 8-wave kernel's two workgroups per CU fill the chip better than either.
   if (nchunks == 2 && Mp >= 9216 && Mp <= 16384) path = 4;
   else if (nchunks == 2 && Mp > 16384 && Mp < 32768) path = 2;
+  // fp64 models on the slab route from NP = 2048 on: the GEMM on int8 matrix cores (posterior_i8.hip), by NP alone — never by M,
+  // so that a candidate's mu / sd do not depend on the batch it comes in.
+  if (path == 3 && !use_f32 && posterior_i8_serves(m)) path = 8;
   if (kv && (kv[0] == '2' || kv[0] == '3' || (kv[0] == '4' && m.NP <= 1024))) path = kv[0] - '0';
+  if (kv && kv[0] == '8' && !use_f32 && m.NP > 512 && m.NP <= I8_NP_MAX) path = 8;
   const bool use_v2 = path == 2, use_v4 = path == 4;
   const char* sm = dbg_env("GPBO_POST_SMALL");
   const bool small = M <= small_batch_limit(m.NP) && !(sm && sm[0] == '0');
@@ -148,14 +154,16 @@ int launch_posterior(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y
   // Why v4 gains only 6 % where the slab traffic and a launch go away: its floor is the GEMM at the matrix pipe's 0.95
   // (0.25 ms) + one generation of k* on the same datapath (~0.09 ms); one 1024-thread workgroup per CU also means every
   // s_barrier stalls the whole CU (the 16-wave slab kernel measured 3 % slower at C3 for the same reason).
-  // GPBO_POST_KERNEL=2|3|4 forces a path (debug build: A/B runs; 4 only up to NP = 1024).
-  const int n_mu = (use_f32 || path == 3) ? nchunks : 1;
+  // GPBO_POST_KERNEL=2|3|4 forces a path (debug build: A/B runs; 4 only up to NP = 1024); 8 forces the int8 GEMM (fp64 models,
+  // 512 < NP <= 16384) and 3 the fp64 slab GEMM where the int8 one would run.
+  const int n_mu = (use_f32 || path == 3 || path == 8) ? nchunks : 1;
   PostEnds ends{ctx->Xc, m.ls, m.d, M, y_mean, y_std, m.mu, m.sd, ctx->negvar};
   ev_begin(ctx, T_POST_MAIN);
   int part_chunks = nchunks;   // row chunks the sum-of-squares partials are split into (fp32 path, v4: 512-row chunks)
   if (use_f32) rc = launch_posterior_f32(ctx, m, Mp, nchunks, &part_chunks);
   else if (use_v2) rc = launch_posterior_v2(ctx, m, Mp, nchunks, fuse_ends ? &ends : nullptr);
   else if (use_v4) rc = launch_posterior_v4(ctx, m, Mp, &part_chunks, fuse_ends ? &ends : nullptr);
+  else if (path == 8) rc = launch_posterior_i8(ctx, m, Mp, nchunks, &part_chunks);
   else rc = launch_posterior_v3(ctx, m, Mp, nchunks);
   ev_end(ctx, T_POST_MAIN);
   if (rc) return rc;

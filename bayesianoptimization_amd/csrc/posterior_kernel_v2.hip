@@ -18,6 +18,7 @@
 
 #include "gpbo_internal.h"
 #include "fit_bodies.h"
+#include "i8_digits.h"
 
 namespace gpbo {
 
@@ -313,8 +314,12 @@ __global__ __launch_bounds__(WAVES * 64, 4) void posterior_kernel_v2(PostArgs2 p
 // through LDS 64 at a time and read back as broadcasts (every lane the same address): as scalar loads straight from
 // memory each pair of points cost the wave four s_load_dwordx16 + s_waitcnt round trips per iteration, which left the
 // fp64 VALU — the unit this kernel is bound by — idle about 40 % of the time (14.2 ms per C3 pass).
+// DIG = S > 0 (posterior_i8.hip): the same k* values and partial means, but the slab holds the S int8 digit planes of
+// k* (i8_digits.h) in the B-operand order of v_mfma_i32_32x32x32_i8 — [candidate block of 32][32 train points][plane]
+// [lane] 16 bytes, lane 32 h + c = candidate c, train points 16 h ... 16 h + 15 — written as one 16-byte store per plane
+// and 16 train points.
 constexpr int GEN_CH = 64;
-template <int DP, int KERNEL>
+template <int DP, int KERNEL, int DIG = 0>
 __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict__ Xs, const double* __restrict__ alpha,
                                                         const double* __restrict__ Xcs, double* __restrict__ Kst,
                                                         int64_t ldk, int NP, double* __restrict__ mu_part,
@@ -344,7 +349,43 @@ __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict
       if (threadIdx.x < GEN_CH) al[threadIdx.x] = alpha[kc + threadIdx.x];
     }
     __syncthreads();
-    if (live) {
+    if (DIG > 0 && live) {
+      // 16 train points at a time: the digit planes of 16 k* values are one 16-byte operand chunk per plane
+      uint4* Kd = reinterpret_cast<uint4*>(Kst) + ((ml >> 5) * (int64_t)(NP / 32) * DIG) * 64 + (ml & 31);
+#pragma unroll 1
+      for (int kg = 0; kg < GEN_CH; kg += 16) {
+        constexpr int DS = DIG > 0 ? DIG : 5;   // (the fp64 instantiations compile this branch too)
+        uint32_t w[DS][4] = {};
+#pragma unroll
+        for (int kk = kg; kk < kg + 16; kk += 2) {
+          const double* xr = xs + kk * DP;
+          double d2a = 0.0, d2b = 0.0;
+#pragma unroll
+          for (int t = 0; t < DP; ++t) {
+            const double da = xc[t] - xr[t], db = xc[t] - xr[DP + t];
+            d2a = fma(da, da, d2a);
+            d2b = fma(db, db, d2b);
+          }
+          const double ka = gpbo_kernel_value<KERNEL>(d2a), kb = gpbo_kernel_value<KERNEL>(d2b);
+          mu = fma(ka, al[kk], mu);
+          mu = fma(kb, al[kk + 1], mu);
+          const int64_t qa = i8_quantize<DS>(ka), qb = i8_quantize<DS>(kb);
+          const int j = kk - kg;
+#pragma unroll
+          for (int t = 0; t < DIG; ++t) {
+            w[t][j >> 2] |= (uint32_t)((qa >> (8 * (DIG - 1 - t))) & 255) << (8 * (j & 3));
+            w[t][j >> 2] |= (uint32_t)((qb >> (8 * (DIG - 1 - t))) & 255) << (8 * ((j + 1) & 3));
+          }
+        }
+        const int k = kc + kg;   // multiple of 16
+        uint4* dst = Kd + ((int64_t)(k >> 5) * DIG) * 64 + ((k >> 4) & 1) * 32;
+#pragma unroll
+        for (int t = 0; t < DIG; ++t) {
+          const uint32_t x = t ? 0x80808080u : 0u;   // planes below the leading one: byte - 128 (i8_digit_byte)
+          dst[t * 64] = make_uint4(w[t][0] ^ x, w[t][1] ^ x, w[t][2] ^ x, w[t][3] ^ x);
+        }
+      }
+    } else if (live) {
 #pragma unroll 2
       for (int kk = 0; kk < GEN_CH; kk += 2) {
         const double* xr = xs + kk * DP;           // the same address in every lane: LDS broadcast
@@ -386,6 +427,33 @@ static int launch_gen_k(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64
     case 64: return launch_gen_t<64, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
   }
   GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: unsupported padded dimension");
+}
+
+template <int DP, int KERNEL>
+static int launch_gen_dig_t(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
+  dim3 grid((unsigned)((ldk + 255) / 256), (unsigned)nchunks);
+  kstar_gen_kernel<DP, KERNEL, I8_S><<<grid, dim3(256), 0, ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, static_cast<double*>(Kd), ldk,
+                                                                          (int)m.NP, ctx->mu_part, Mp, m0);
+  GPBO_HIP(ctx, hipGetLastError());
+  return GPBO_OK;
+}
+
+template <int KERNEL>
+static int launch_gen_dig_k(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
+  switch (m.DP) {
+    case 4: return launch_gen_dig_t<4, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
+    case 8: return launch_gen_dig_t<8, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
+    case 16: return launch_gen_dig_t<16, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
+    case 32: return launch_gen_dig_t<32, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
+    case 64: return launch_gen_dig_t<64, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
+  }
+  GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: unsupported padded dimension");
+}
+
+// the I8_S int8 digit planes of the k* slab (ldk a multiple of 32) + the same partial means as launch_kstar_slab
+int launch_kstar_digits(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
+  if (m.kernel == GPBO_KERNEL_MATERN25) return launch_gen_dig_k<GPBO_KERNEL_MATERN25>(ctx, m, Kd, ldk, Mp, m0, nchunks);
+  return launch_gen_dig_k<GPBO_KERNEL_RBF>(ctx, m, Kd, ldk, Mp, m0, nchunks);
 }
 
 // k* slab [NP][ldk] (+ partial means) for candidates [m0, m0 + ldk) of the scaled set ctx->Xcs — also used by the
