@@ -10,13 +10,14 @@
 #include <string>
 #include <vector>
 
+#include <type_traits>
+
 #include "gpbo.h"
+#include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 
 namespace gpbo {
 
 constexpr int NB = 64;          // Cholesky / inverse block size (one MFMA GEMM tile edge)
-constexpr int POST_ROWS = 256;  // W rows owned by one posterior workgroup (8 waves x 32 rows)
-constexpr int POST_CANDS = 128; // candidate padding granule (Mp = round_up(M, 128); kernels tile 64 candidates)
 constexpr int POST_BK = 16;     // train points (k) per LDS stage of the fp64 kernels
 
 enum TimingSlot {
@@ -135,11 +136,11 @@ struct gpbo_ctx {
   int64_t cap_mt_desc = 0;
   double* Xcs = nullptr;   // [Mp][DP] scaled/padded workspace
   int64_t cap_Xcs = 0;
-  double* part = nullptr;  // [nchunks][Mp] partial |W k*|^2
+  double* part = nullptr;  // [PostPlan::part_chunks][Mp] partial |W k*|^2 (the GEMV paths: their own scratch layout)
   int64_t cap_part = 0;
-  double* mu_part = nullptr;  // [nchunks][Mp] (v3: one partial mean per 256-train-point chunk) or [Mp]
+  double* mu_part = nullptr;  // [PostPlan::mu_chunks][Mp]: one partial mean per 256-train-point chunk (slab paths) or [Mp]
   int64_t cap_mu_part = 0;
-  double* kst = nullptr;   // materialised k* slab [NP][slab width] (posterior v3)
+  double* kst = nullptr;   // materialised k* slab [NP][slab width] (the posterior's slab paths)
   int64_t cap_kst = 0;
   double* ys = nullptr;    // [M] negated acquisition values
   int64_t cap_ys = 0;
@@ -317,6 +318,27 @@ __device__ __forceinline__ double gpbo_kernel_value(double d2) {
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 inline int pad_dim(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : 64; }
 
+// Template instance dispatch of the posterior launchers: f(kernel) / f(dp, kernel) with std::integral_constant arguments for the
+// model's kernel type (GPBO_KERNEL_MATERN25, anything else RBF) and padded dimension (pad_dim's values).
+template <typename F>
+int with_kernel(int kernel, F&& f) {
+  if (kernel == GPBO_KERNEL_MATERN25) return f(std::integral_constant<int, GPBO_KERNEL_MATERN25>{});
+  return f(std::integral_constant<int, GPBO_KERNEL_RBF>{});
+}
+template <typename F>
+int with_dp_kernel(gpbo_ctx* ctx, int DP, int kernel, F&& f) {
+  return with_kernel(kernel, [&](auto k) -> int {
+    switch (DP) {
+      case 4: return f(std::integral_constant<int, 4>{}, k);
+      case 8: return f(std::integral_constant<int, 8>{}, k);
+      case 16: return f(std::integral_constant<int, 16>{}, k);
+      case 32: return f(std::integral_constant<int, 32>{}, k);
+      case 64: return f(std::integral_constant<int, 64>{}, k);
+    }
+    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: unsupported padded dimension");
+  });
+}
+
 template <typename T>
 int ensure(gpbo_ctx* ctx, T** p, int64_t* cap, int64_t need) {
   if (need <= *cap && *p) return GPBO_OK;
@@ -332,9 +354,11 @@ int ensure(gpbo_ctx* ctx, T** p, int64_t* cap, int64_t need) {
   return GPBO_OK;
 }
 
-// k* slab budget in bytes: GPBO_KSTAR_GB (default 4), clipped to 80 % of what the device could give the slab —
-// hipMemGetInfo is asked only when the slab buffer would have to grow (it costs tens of microseconds per call).
-int64_t kstar_slab_budget_bytes(gpbo_ctx* ctx, int64_t want_bytes_if_unlimited);   // posterior_kernel.hip
+// Candidates per k* slab of a slab walk (posterior_kernel.hip): what the workspace budget holds at bytes_per_cand — GPBO_KSTAR_GB
+// (default 4 GB), clipped to 80 % of what the device could give the slab; hipMemGetInfo is asked only when the slab buffer would
+// have to grow (it costs tens of microseconds per call) — and at most `cap` and `preferred`, rounded down to 128, at most Mp.
+// Below 128 the caller decides: the fp64 / fp32 walks fail, the int8 walk takes 128.
+int64_t kstar_slab_width(gpbo_ctx* ctx, int64_t Mp, int64_t bytes_per_cand, int64_t cap, int64_t preferred = INT64_MAX);
 
 // ---- launchers implemented in the kernel translation units ---------------------------------
 // fit_kernels.hip
@@ -404,18 +428,17 @@ struct PostEnds {
   double* sd;
   int* negvar;
 };
-int launch_posterior_v2(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, const PostEnds* ends = nullptr);
-int launch_posterior_v3(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks);
-int launch_posterior_v4(gpbo_ctx* ctx, Model& m, int64_t Mp, int* part_chunks, const PostEnds* ends = nullptr);   // fused, 512-row chunks (NP <= 1024)
+// The launchers of the paths (PostPath: posterior_plan.h); plan_posterior sizes their grids and ctx->part / ctx->mu_part.
+int launch_posterior_fused(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan, const PostEnds& ends);   // Fused256, Fused512
+int launch_posterior_slab(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan);                          // SlabF64
 int launch_kstar_slab(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks);
 int launch_kstar_digits(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks);  // posterior_kernel_v2.hip
-bool posterior_i8_serves(const Model& m);                                                   // posterior_i8.hip
-int launch_posterior_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, int* part_chunks);
+int launch_posterior_slab_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan);                       // posterior_i8.hip
 // posterior_cov.hip
 int launch_posterior_cov(gpbo_ctx* ctx, Model& m, int64_t M, double y_std, double** cov_dev, int64_t* ld_cov);
 // posterior_kernel_f32.hip
 int launch_pack_w32(gpbo_ctx* ctx, Model& m);
-int launch_posterior_f32(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, int* part_chunks);
+int launch_posterior_slab_f32(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan);
 // acq_kernels.hip
 struct AcqArgs {
   int acq; double param; double y_max; int n_constraints;

@@ -19,6 +19,8 @@
 // The level sums are exact, so v_i is the correctly rounded value of the truncated digit product whatever the tiling; the
 // sum of squares is then taken in a fixed order per 128-row chunk, as the fp64 kernels do per 256-row chunk.  mu (k* . alpha)
 // is computed by kstar_gen_kernel exactly as on the fp64 path.
+#include <algorithm>
+
 #include "gpbo_internal.h"
 #include "i8_digits.h"
 
@@ -27,7 +29,6 @@ namespace gpbo {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-constexpr int I8_ROWS = 128;   // rows of W per workgroup (4 waves x 32)
 constexpr int I8_CANDS = 64;   // candidates per workgroup (2 blocks of 32)
 constexpr int I8_BUF_FLAGS = 0x00020000;   // gfx9 buffer descriptor word 3: raw buffer, 32-bit data format
 
@@ -201,45 +202,31 @@ __global__ __launch_bounds__(256, 1) void posterior_i8_kernel(I8Args p) {
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------------
-// fp64 models on the k* slab route from this NP on (posterior_kernel.hip's path rule); the int32 level sums bound NP.
-// ms per posterior pass, M = 2^20, d = 16, Matern-2.5 (debug build, GPBO_POST_KERNEL=3 | 8, one MI355X):
-//   NP = 1536: fp64 slab 40.0, int8 35.9;  2048: 68.0 / 56.6;  3072: 145.7 / 116.5;  4096: 255.8 / 196.5.
-// The int8 GEMM wins from 1536 on; the rule starts at 2048, the smallest NP the suite checks it at (the ill-conditioned N = 2000
-// case of test_gpu_conditioning.py); NP <= 1024 keeps the fp64 kernels that the three-kernel parity test pins.
-constexpr int64_t I8_NP_MIN = 2048;
-bool posterior_i8_serves(const Model& m) { return m.precision != GPBO_F32 && m.NP >= I8_NP_MIN && m.NP <= I8_NP_MAX; }
-
-// Slab loop as launch_posterior_v3, but the slab is S bytes per element and sized so that the 32 row chunks re-read it from the
-// 256 MB Infinity Cache rather than from HBM (GPBO_KSTAR_GB still caps it).  *part_chunks = NP / 128 (rounded up).
+// SlabI8 (posterior_plan.h): the slab walk of launch_posterior_slab, but the slab is S bytes per element and sized so that the
+// 32 row chunks re-read it from the 256 MB Infinity Cache rather than from HBM (GPBO_KSTAR_GB still caps it).
 // C3 posterior pass per slab size (debug build, GPBO_I8_SLAB_MB): 128 MB 204.4 ms (241 slab pairs: the generation kernel's grid
 // of 272 workgroups leaves the chip half idle), 256 MB 196.6, 512 MB 211.1, 1 GB 211.0, 2 GB 215.5, 4 GB 216.0 (the re-reads
 // miss the cache).
-int launch_posterior_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, int* part_chunks) {
+int launch_posterior_slab_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
   if (m.NP > I8_NP_MAX || m.NP % 64) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: the int8 GEMM serves NP <= 16384");
   int rc;
   if (!m.wd_valid && (rc = pack_wd(ctx, m))) return rc;
-  const int nch = (int)((m.NP + I8_ROWS - 1) / I8_ROWS);
-  if ((rc = ensure(ctx, &ctx->part, &ctx->cap_part, (int64_t)nch * Mp))) return rc;
   const int64_t per_cand = m.NP * I8_S;          // bytes of one candidate's digit planes
   const char* sm = dbg_env("GPBO_I8_SLAB_MB");      // debug build: slab size A/B
-  int64_t ms = (int64_t)((sm && atof(sm) > 0.0) ? atof(sm) : 256.0) * 1000 * 1000 / per_cand;
-  const int64_t budget = kstar_slab_budget_bytes(ctx, Mp * per_cand);
-  if (ms > budget / per_cand) ms = budget / per_cand;
-  ms = ms / 128 * 128;
-  if (ms < 128) ms = 128;
-  if (ms > Mp) ms = Mp;
+  const int64_t mb = (int64_t)((sm && atof(sm) > 0.0) ? atof(sm) : 256.0);
+  // no cap: the kernel's buffer offsets start at its own candidate tile; below 128 candidates the walk still takes 128
+  const int64_t ms = std::max<int64_t>(kstar_slab_width(ctx, Mp, per_cand, INT64_MAX, mb * 1000 * 1000 / per_cand), 128);
   if ((rc = ensure(ctx, &ctx->kst, &ctx->cap_kst, (ms * per_cand + 7) / 8))) return rc;
   for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
     const int64_t ldk = (Mp - m0 < ms) ? (Mp - m0) : ms;
-    if ((rc = launch_kstar_digits(ctx, m, ctx->kst, ldk, Mp, m0, nchunks))) return rc;
+    if ((rc = launch_kstar_digits(ctx, m, ctx->kst, ldk, Mp, m0, plan.mu_chunks))) return rc;
     I8Args a;
     a.Wd = m.Wd; a.wscale = m.wscale; a.Kd = reinterpret_cast<const uint4*>(ctx->kst); a.part = ctx->part;
-    a.NP = (int)m.NP; a.Mp = Mp; a.nchunks = nch; a.n_ctiles = (int)(ldk / I8_CANDS); a.m0 = m0;
-    const int64_t nblocks = (int64_t)a.n_ctiles * nch;
+    a.NP = (int)m.NP; a.Mp = Mp; a.nchunks = plan.part_chunks; a.n_ctiles = (int)(ldk / I8_CANDS); a.m0 = m0;
+    const int64_t nblocks = (int64_t)a.n_ctiles * a.nchunks;
     posterior_i8_kernel<I8_S><<<dim3((unsigned)nblocks), dim3(256), 0, ctx->stream>>>(a);
     GPBO_HIP(ctx, hipGetLastError());
   }
-  *part_chunks = nch;
   return GPBO_OK;
 }
 

@@ -21,13 +21,6 @@ namespace gpbo {
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 
-// Which f32 MFMA the posterior GEMM runs on: v_mfma_f32_32x32x2_f32 in 512-row chunks for NP >= 512
-// (posterior_kernel_f32x), v_mfma_f32_16x16x4_f32 in 256-row chunks below (posterior_kernel_f32).  Same rate, same operand
-// bytes per flop — the 32x32 form is HALF the MFMA instructions (64 cycles each instead of 32), which leaves the issue slots
-// the LDS reads, the slab / W loads and the barrier need: the 16x16 kernel ran its matrix pipe 81 % busy.  The two forms want
-// W packed differently.
-static bool f32_use_mfma32(int64_t NP) { return NP >= 512; }
-
 constexpr int F32_CANDS = 64;
 constexpr int F32_BK = 32;
 constexpr int F32_STRIDE = 80;   // floats per k-row of the stage tile: 64 + 16 -> the two k-rows of a 32-lane group 16 banks apart
@@ -430,55 +423,34 @@ __global__ __launch_bounds__(512, 4) void posterior_kernel_f32x(PostArgsF32 p) {
   }
 }
 
-template <int DP, int KERNEL>
-static int launch_gen32_t(gpbo_ctx* ctx, Model& m, float* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  dim3 grid((unsigned)((ldk + 255) / 256), (unsigned)nchunks);
-  kstar_gen_f32_kernel<DP, KERNEL><<<grid, dim3(256), 0, ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, Kst, ldk, (int)m.NP,
-                                                                          ctx->mu_part, Mp, m0);
-  GPBO_HIP(ctx, hipGetLastError());
-  return GPBO_OK;
-}
-
-template <int KERNEL>
-static int launch_gen32_k(gpbo_ctx* ctx, Model& m, float* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  switch (m.DP) {
-    case 4: return launch_gen32_t<4, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-    case 8: return launch_gen32_t<8, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-    case 16: return launch_gen32_t<16, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-    case 32: return launch_gen32_t<32, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-    case 64: return launch_gen32_t<64, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-  }
-  GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: unsupported padded dimension");
-}
-
-// fp32 pipeline per candidate slab; the slab buffer (ctx->kst, sized in doubles) is shared with the fp64 path.
-int launch_posterior_f32(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, int* part_chunks) {
-  *part_chunks = nchunks;
-  const int64_t budget = kstar_slab_budget_bytes(ctx, Mp * m.NP * 4);   // as the fp64 path (posterior_kernel_v2.hip)
-  int64_t ms = budget / (m.NP * 4);
-  if (ms > (int64_t)160 * 1000 * 1000) ms = (int64_t)160 * 1000 * 1000;   // 32-bit buffer offsets of a stage's rows (f32x kernel)
-  ms = ms / 128 * 128;
+// SlabF32 per candidate slab (the walk of launch_posterior_slab); the slab buffer (ctx->kst, sized in doubles) is shared with the
+// fp64 path.  The GEMM runs on the MFMA form f32_use_mfma32 picks (posterior_plan.h), in plan.part_chunks row chunks.
+int launch_posterior_slab_f32(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
+  // 32-bit buffer offsets of a stage's rows (f32x kernel)
+  const int64_t ms = kstar_slab_width(ctx, Mp, m.NP * 4, (int64_t)160 * 1000 * 1000);
   if (ms < 128) GPBO_FAIL(ctx, GPBO_ERR_HIP, "posterior: not enough device memory for one k* slab");
-  if (ms > Mp) ms = Mp;
   int rc;
   if ((rc = ensure(ctx, &ctx->kst, &ctx->cap_kst, (ms * m.NP + 1) / 2))) return rc;
   float* kst = reinterpret_cast<float*>(ctx->kst);
   for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
     const int64_t ldk = (Mp - m0 < ms) ? (Mp - m0) : ms;
-    if (m.kernel == GPBO_KERNEL_MATERN25) rc = launch_gen32_k<GPBO_KERNEL_MATERN25>(ctx, m, kst, ldk, Mp, m0, nchunks);
-    else rc = launch_gen32_k<GPBO_KERNEL_RBF>(ctx, m, kst, ldk, Mp, m0, nchunks);
+    rc = with_dp_kernel(ctx, m.DP, m.kernel, [&](auto dp, auto k) {
+      kstar_gen_f32_kernel<decltype(dp)::value, decltype(k)::value><<<dim3((unsigned)((ldk + 255) / 256), (unsigned)plan.mu_chunks),
+                                                                      dim3(256), 0, ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, kst, ldk,
+                                                                                                   (int)m.NP, ctx->mu_part, Mp, m0);
+      GPBO_HIP(ctx, hipGetLastError());
+      return GPBO_OK;
+    });
     if (rc) return rc;
     PostArgsF32 a;
     a.Wp = m.Wp32; a.Kst = kst; a.part = ctx->part; a.NP = (int)m.NP; a.Mp = Mp;
     a.n_ctiles = (int)(ldk / F32_CANDS); a.ldk = ldk; a.m0 = m0;
-    const bool mf32 = f32_use_mfma32(m.NP);     // (the packed W of this fit was laid out for the same choice)
-    a.nchunks = mf32 ? (int)((m.NP + 511) / 512) : nchunks;
+    a.nchunks = plan.part_chunks;
     const int64_t nblocks = (int64_t)a.n_ctiles * a.nchunks;
     if (nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
-    if (mf32) posterior_kernel_f32x<32><<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);
+    if (f32_use_mfma32(m.NP)) posterior_kernel_f32x<32><<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);   // (W packed for it)
     else posterior_kernel_f32<<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);
     GPBO_HIP(ctx, hipGetLastError());
-    *part_chunks = a.nchunks;
   }
   return GPBO_OK;
 }

@@ -1,5 +1,6 @@
 // posterior_kernel_v2 — the posterior MFMA kernel tiled for FOUR waves per SIMD (v1, 2 waves/SIMD, is in the git
-// history), with the k* operand either generated in-kernel (GEN = 1) or read from a slab (GEN = 2, "v3").
+// history), with the k* operand either generated in-kernel (GEN = 1: the Fused256 / Fused512 paths of posterior_plan.h) or
+// read from a slab (GEN = 2: SlabF64).
 //
 // Why: the in-tree probe (gpbo_mfma_f64_probe) shows that on gfx950 a SIMD only reaches the
 // 64-cycle issue cadence of v_mfma_f64_16x16x4_f64 when >= 4 waves feed it (1 wave: 140 cycles per
@@ -58,7 +59,7 @@ constexpr int BUF_FLAGS = 0x00020000;   // gfx9 buffer descriptor word 3: raw bu
 // BK = train points per LDS stage (one s_barrier per stage): 16, or 32 for the slab kernel (half the barriers; the
 // triangular cut-off of a 16-row tile then rounds up to 32 columns — zeros of the packed W, a few per cent more MFMAs
 // in the diagonal chunk only).
-// WAVES = 8: 256-row chunks, two workgroups per CU.  WAVES = 16 (round 4, GEN = 1 only, "v4"): 512-row chunks, ONE 1024-thread
+// WAVES = 8: 256-row chunks, two workgroups per CU.  WAVES = 16 (round 4, GEN = 1 only, Fused512): 512-row chunks, ONE 1024-thread
 // workgroup per CU — for NP <= 1024 a candidate tile's k* is then generated once (NP <= 512) or 1.5 times (NP <= 1024)
 // instead of once per 256-row chunk (1.5 / 2.5 times) and never crosses HBM: the slab route generates it once too, but pays a
 // 268 MB round trip at N = 512, M = 65 536 and a second launch (C2: 0.09 + 0.29 ms).
@@ -408,89 +409,56 @@ __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict
   if (live) mu_part[(int64_t)blockIdx.y * Mp + m0 + ml] = mu;
 }
 
-template <int DP, int KERNEL>
-static int launch_gen_t(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  dim3 grid((unsigned)((ldk + 255) / 256), (unsigned)nchunks);
-  kstar_gen_kernel<DP, KERNEL><<<grid, dim3(256), 0, ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, Kst, ldk, (int)m.NP,
-                                                                      ctx->mu_part, Mp, m0);
-  GPBO_HIP(ctx, hipGetLastError());
-  return GPBO_OK;
-}
-
-template <int KERNEL>
-static int launch_gen_k(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  switch (m.DP) {
-    case 4: return launch_gen_t<4, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-    case 8: return launch_gen_t<8, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-    case 16: return launch_gen_t<16, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-    case 32: return launch_gen_t<32, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-    case 64: return launch_gen_t<64, KERNEL>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-  }
-  GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: unsupported padded dimension");
-}
-
-template <int DP, int KERNEL>
-static int launch_gen_dig_t(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  dim3 grid((unsigned)((ldk + 255) / 256), (unsigned)nchunks);
-  kstar_gen_kernel<DP, KERNEL, I8_S><<<grid, dim3(256), 0, ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, static_cast<double*>(Kd), ldk,
-                                                                          (int)m.NP, ctx->mu_part, Mp, m0);
-  GPBO_HIP(ctx, hipGetLastError());
-  return GPBO_OK;
-}
-
-template <int KERNEL>
-static int launch_gen_dig_k(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  switch (m.DP) {
-    case 4: return launch_gen_dig_t<4, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
-    case 8: return launch_gen_dig_t<8, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
-    case 16: return launch_gen_dig_t<16, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
-    case 32: return launch_gen_dig_t<32, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
-    case 64: return launch_gen_dig_t<64, KERNEL>(ctx, m, Kd, ldk, Mp, m0, nchunks);
-  }
-  GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: unsupported padded dimension");
+template <int DIG>
+static int launch_gen(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
+  return with_dp_kernel(ctx, m.DP, m.kernel, [&](auto dp, auto k) {
+    kstar_gen_kernel<decltype(dp)::value, decltype(k)::value, DIG><<<dim3((unsigned)((ldk + 255) / 256), (unsigned)nchunks), dim3(256), 0,
+                                                                     ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, Kst, ldk, (int)m.NP,
+                                                                                    ctx->mu_part, Mp, m0);
+    GPBO_HIP(ctx, hipGetLastError());
+    return GPBO_OK;
+  });
 }
 
 // the I8_S int8 digit planes of the k* slab (ldk a multiple of 32) + the same partial means as launch_kstar_slab
 int launch_kstar_digits(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  if (m.kernel == GPBO_KERNEL_MATERN25) return launch_gen_dig_k<GPBO_KERNEL_MATERN25>(ctx, m, Kd, ldk, Mp, m0, nchunks);
-  return launch_gen_dig_k<GPBO_KERNEL_RBF>(ctx, m, Kd, ldk, Mp, m0, nchunks);
+  return launch_gen<I8_S>(ctx, m, static_cast<double*>(Kd), ldk, Mp, m0, nchunks);
 }
 
 // k* slab [NP][ldk] (+ partial means) for candidates [m0, m0 + ldk) of the scaled set ctx->Xcs — also used by the
 // covariance path (posterior_cov.hip)
 int launch_kstar_slab(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  if (m.kernel == GPBO_KERNEL_MATERN25) return launch_gen_k<GPBO_KERNEL_MATERN25>(ctx, m, Kst, ldk, Mp, m0, nchunks);
-  return launch_gen_k<GPBO_KERNEL_RBF>(ctx, m, Kst, ldk, Mp, m0, nchunks);
+  return launch_gen<0>(ctx, m, Kst, ldk, Mp, m0, nchunks);
 }
 
-// Two-kernel pipeline per candidate slab: kstar_gen_kernel -> posterior_kernel_v2<.., GEN = 2>.
-// The slab width is bounded by a workspace budget (default 4 GB, GPBO_KSTAR_GB to override); mu partials
-// need nchunks x Mp doubles in ctx->mu_part (allocated by the caller).
-int launch_posterior_v3(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks) {
-  // k* workspace: the candidate set is walked slab by slab; a slab only has to be wide enough to fill the chip
-  // (4e9 B = 121 984 candidates at N = 4096 = 1906 candidate tiles x 16 row chunks per launch); measured at C3: one 34 GB
-  // slab 263.7 ms, eight 4 GB slabs 264.4 ms (round 1 A/B) — the big workspace bought nothing.  GPBO_KSTAR_GB overrides.
-  // 32 train points per stage: 262.9 vs 264.0 ms per C3 launch (round-2 A/B, same box, same run)
-  const int64_t budget = kstar_slab_budget_bytes(ctx, Mp * m.NP * 8);
-  int64_t ms = budget / (m.NP * 8);
+// The kernel's arguments for ncands candidates in nchunks row chunks (no slab, no fused ends) and its grid size.
+static int post_args(gpbo_ctx* ctx, const Model& m, int64_t Mp, int nchunks, int64_t ncands, PostArgs2* a, int64_t* nblocks) {
+  a->Wp = m.Wp; a->Xs = m.Xs; a->alpha = m.alpha; a->Xcs = ctx->Xcs; a->part = ctx->part;
+  a->mu_part = ctx->mu_part; a->NP = (int)m.NP; a->Mp = Mp; a->nchunks = nchunks;
+  a->n_ctiles = (int)(ncands / V2_CANDS);
+  a->Kst = nullptr; a->ldk = 0; a->m0 = 0;
+  *nblocks = (int64_t)a->n_ctiles * nchunks;
+  if (*nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
+  return GPBO_OK;
+}
+
+// SlabF64: kstar_gen_kernel -> posterior_kernel_v2<.., GEN = 2> per candidate slab.  The slab width is bounded by the workspace
+// budget (kstar_slab_width); a slab only has to be wide enough to fill the chip (4e9 B = 121 984 candidates at N = 4096 = 1906
+// candidate tiles x 16 row chunks per launch); measured at C3: one 34 GB slab 263.7 ms, eight 4 GB slabs 264.4 ms (round 1
+// A/B) — the big workspace bought nothing.  32 train points per stage: 262.9 vs 264.0 ms per C3 launch (round-2 A/B).
+int launch_posterior_slab(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
   // the slab kernel addresses a stage's rows as 32-bit buffer offsets: 3 rows of ldk doubles must stay below 2^31 bytes
-  if (ms > (int64_t)80 * 1000 * 1000) ms = (int64_t)80 * 1000 * 1000;
-  ms = ms / 128 * 128;
+  const int64_t ms = kstar_slab_width(ctx, Mp, m.NP * 8, (int64_t)80 * 1000 * 1000);
   if (ms < 128) GPBO_FAIL(ctx, GPBO_ERR_HIP, "posterior: not enough device memory for one k* slab");
-  if (ms > Mp) ms = Mp;
   int rc;
   if ((rc = ensure(ctx, &ctx->kst, &ctx->cap_kst, ms * m.NP))) return rc;
   for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
     const int64_t ldk = (Mp - m0 < ms) ? (Mp - m0) : ms;
-    if (m.kernel == GPBO_KERNEL_MATERN25) rc = launch_gen_k<GPBO_KERNEL_MATERN25>(ctx, m, ctx->kst, ldk, Mp, m0, nchunks);
-    else rc = launch_gen_k<GPBO_KERNEL_RBF>(ctx, m, ctx->kst, ldk, Mp, m0, nchunks);
-    if (rc) return rc;
+    if ((rc = launch_kstar_slab(ctx, m, ctx->kst, ldk, Mp, m0, plan.mu_chunks))) return rc;
     PostArgs2 a;
-    a.Wp = m.Wp; a.Xs = m.Xs; a.alpha = m.alpha; a.Xcs = ctx->Xcs; a.part = ctx->part;
-    a.mu_part = ctx->mu_part; a.NP = (int)m.NP; a.Mp = Mp; a.nchunks = nchunks;
-    a.n_ctiles = (int)(ldk / V2_CANDS); a.Kst = ctx->kst; a.ldk = ldk; a.m0 = m0;
-    const int64_t nblocks = (int64_t)a.n_ctiles * nchunks;
-    if (nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
+    int64_t nblocks;
+    if ((rc = post_args(ctx, m, Mp, plan.part_chunks, ldk, &a, &nblocks))) return rc;
+    a.Kst = ctx->kst; a.ldk = ldk; a.m0 = m0;
     const size_t lds = (size_t)(2 * 32 * V2_STRIDE) * sizeof(double);
     posterior_kernel_v2<4, 0, 2, 32><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
     GPBO_HIP(ctx, hipGetLastError());
@@ -498,75 +466,28 @@ int launch_posterior_v3(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks) {
   return GPBO_OK;
 }
 
-template <int DP, int KERNEL>
-static int launch_v2_t(gpbo_ctx* ctx, const PostArgs2& a, int64_t nblocks) {
-  const size_t lds = (size_t)(2 * POST_BK * V2_STRIDE + DP * V2_CANDS) * sizeof(double);
-  posterior_kernel_v2<DP, KERNEL, 1><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
-  GPBO_HIP(ctx, hipGetLastError());
-  return GPBO_OK;
-}
-
-template <int KERNEL>
-static int launch_v2_k(gpbo_ctx* ctx, int DP, const PostArgs2& a, int64_t nblocks) {
-  switch (DP) {
-    case 4: return launch_v2_t<4, KERNEL>(ctx, a, nblocks);
-    case 8: return launch_v2_t<8, KERNEL>(ctx, a, nblocks);
-    case 16: return launch_v2_t<16, KERNEL>(ctx, a, nblocks);
-    case 32: return launch_v2_t<32, KERNEL>(ctx, a, nblocks);
-    case 64: return launch_v2_t<64, KERNEL>(ctx, a, nblocks);
-  }
-  GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: unsupported padded dimension");
-}
-
-// "v4": the fused kernel in its 16-wave form, 512-row chunks (NP <= 1024: at most two).  *part_chunks = the number of row
-// chunks the sum-of-squares partials are split into (what posterior_finalize_kernel sums over).
-template <int DP, int KERNEL>
-static int launch_v4_t(gpbo_ctx* ctx, const PostArgs2& a, int64_t nblocks) {
-  const size_t lds = (size_t)(2 * 32 * V2_STRIDE + DP * V2_CANDS) * sizeof(double);
-  posterior_kernel_v2<DP, KERNEL, 1, 32, 16><<<dim3((unsigned)nblocks), dim3(1024), lds, ctx->stream>>>(a);
-  GPBO_HIP(ctx, hipGetLastError());
-  return GPBO_OK;
-}
-template <int KERNEL>
-static int launch_v4_k(gpbo_ctx* ctx, int DP, const PostArgs2& a, int64_t nblocks) {
-  switch (DP) {
-    case 4: return launch_v4_t<4, KERNEL>(ctx, a, nblocks);
-    case 8: return launch_v4_t<8, KERNEL>(ctx, a, nblocks);
-    case 16: return launch_v4_t<16, KERNEL>(ctx, a, nblocks);
-    case 32: return launch_v4_t<32, KERNEL>(ctx, a, nblocks);
-    case 64: return launch_v4_t<64, KERNEL>(ctx, a, nblocks);
-  }
-  GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: unsupported padded dimension");
-}
-int launch_posterior_v4(gpbo_ctx* ctx, Model& m, int64_t Mp, int* part_chunks, const PostEnds* ends) {
-  const int nch = (int)((m.NP + 511) / 512);
-  if (ends && nch != 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "posterior: fused ends need one row chunk");
+// Fused256 (8 waves, 256-row chunks) and Fused512 (16 waves, 512-row chunks; NP <= 1024: at most two), the ends fused when
+// the plan says so (one row chunk).  Mp must be a multiple of 64.
+int launch_posterior_fused(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan, const PostEnds& ends) {
+  if (plan.fuse_ends && plan.part_chunks != 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "posterior: fused ends need one row chunk");
   PostArgs2 a;
-  if (ends) { a.fuse_ends = 1; a.ends = *ends; }
-  a.Wp = m.Wp; a.Xs = m.Xs; a.alpha = m.alpha; a.Xcs = ctx->Xcs; a.part = ctx->part;
-  a.mu_part = ctx->mu_part; a.NP = (int)m.NP; a.Mp = Mp; a.nchunks = nch;
-  a.n_ctiles = (int)(Mp / V2_CANDS);
-  a.Kst = nullptr; a.ldk = 0; a.m0 = 0;
-  const int64_t nblocks = (int64_t)a.n_ctiles * nch;
-  if (nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
-  *part_chunks = nch;
-  if (m.kernel == GPBO_KERNEL_MATERN25) return launch_v4_k<GPBO_KERNEL_MATERN25>(ctx, m.DP, a, nblocks);
-  return launch_v4_k<GPBO_KERNEL_RBF>(ctx, m.DP, a, nblocks);
-}
-
-// Mp must be a multiple of 128 (the v1 tile) — also a multiple of 64.
-int launch_posterior_v2(gpbo_ctx* ctx, Model& m, int64_t Mp, int nchunks, const PostEnds* ends) {
-  if (ends && nchunks != 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "posterior: fused ends need one row chunk");
-  PostArgs2 a;
-  if (ends) { a.fuse_ends = 1; a.ends = *ends; }
-  a.Wp = m.Wp; a.Xs = m.Xs; a.alpha = m.alpha; a.Xcs = ctx->Xcs; a.part = ctx->part;
-  a.mu_part = ctx->mu_part; a.NP = (int)m.NP; a.Mp = Mp; a.nchunks = nchunks;
-  a.n_ctiles = (int)(Mp / V2_CANDS);
-  a.Kst = nullptr; a.ldk = 0; a.m0 = 0;
-  const int64_t nblocks = (int64_t)a.n_ctiles * nchunks;
-  if (nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
-  if (m.kernel == GPBO_KERNEL_MATERN25) return launch_v2_k<GPBO_KERNEL_MATERN25>(ctx, m.DP, a, nblocks);
-  return launch_v2_k<GPBO_KERNEL_RBF>(ctx, m.DP, a, nblocks);
+  int64_t nblocks;
+  int rc;
+  if ((rc = post_args(ctx, m, Mp, plan.part_chunks, Mp, &a, &nblocks))) return rc;
+  if (plan.fuse_ends) { a.fuse_ends = 1; a.ends = ends; }
+  const bool wide = plan.path == PostPath::Fused512;
+  return with_dp_kernel(ctx, m.DP, m.kernel, [&](auto dp, auto k) {
+    constexpr int DP = decltype(dp)::value, KERNEL = decltype(k)::value;
+    if (wide) {
+      const size_t lds = (size_t)(2 * 32 * V2_STRIDE + DP * V2_CANDS) * sizeof(double);
+      posterior_kernel_v2<DP, KERNEL, 1, 32, 16><<<dim3((unsigned)nblocks), dim3(1024), lds, ctx->stream>>>(a);
+    } else {
+      const size_t lds = (size_t)(2 * POST_BK * V2_STRIDE + DP * V2_CANDS) * sizeof(double);
+      posterior_kernel_v2<DP, KERNEL, 1><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
+    }
+    GPBO_HIP(ctx, hipGetLastError());
+    return GPBO_OK;
+  });
 }
 
 }  // namespace gpbo

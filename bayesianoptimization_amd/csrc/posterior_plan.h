@@ -1,0 +1,107 @@
+// Which device path a posterior pass takes (posterior_kernel.hip's launch_posterior), as a pure function of plain values.
+// Host-only and free of HIP: tests/test_posterior_plan_host.py compiles it with the system C++ compiler and pins the rule on
+// both sides of every edge.  The debug switches (GPBO_POST_KERNEL, GPBO_POST_SMALL, GPBO_POST_FUSE_ENDS) are read by the caller
+// and come in already parsed.
+#pragma once
+
+#include <cstdint>
+
+namespace gpbo {
+
+constexpr int POST_ROWS = 256;       // W rows owned by one posterior workgroup (8 waves x 32 rows)
+constexpr int POST_ROWS_WIDE = 512;  // ... by the 16-wave fused kernel and by the fp32 kernel on 32x32 MFMAs
+constexpr int POST_CANDS = 128;      // candidate padding granule (Mp = round_up(M, 128); kernels tile 64 candidates)
+constexpr int I8_ROWS = 128;         // rows of W per workgroup of the int8 GEMM (4 waves x 32)
+constexpr int64_t I8_NP_MIN = 2048;  // fp64 models take the int8 GEMM from this NP on ...
+constexpr int I8_NP_MAX = 16384;     // ... up to this one: i8_digits.h's int32 level sums bound it
+
+enum class PostPath {
+  Small,     // batched GEMV                                       posterior_small.hip
+  Fused256,  // k* generated inside the MFMA kernel, 8 waves       posterior_kernel_v2.hip (GEN = 1)
+  Fused512,  // ... 16 waves, 512-row chunks                       posterior_kernel_v2.hip (GEN = 1, WAVES = 16)
+  SlabF64,   // k* slab + fp64 MFMA GEMM                           posterior_kernel_v2.hip (GEN = 2)
+  SlabI8,    // k* slab as int8 digit planes + int8 MFMA GEMM      posterior_i8.hip
+  SlabF32,   // fp32 k* slab + fp32 MFMA GEMM                      posterior_kernel_f32.hip
+};
+
+struct PostPlan {
+  PostPath path;
+  bool fuse_ends;   // the fused kernel takes the raw candidates and writes mu / sd itself: no prescale, no finalize launch
+  int part_chunks;  // rows of sum-of-squares partials (ctx->part) the finalize kernel sums
+  int mu_chunks;    // rows of mean partials (ctx->mu_part)
+};
+
+// The fp32 GEMM runs on v_mfma_f32_32x32x2_f32 in 512-row chunks from NP = 512 on, on v_mfma_f32_16x16x4_f32 in 256-row chunks
+// below.  Same rate, same operand bytes per flop; the 32x32 form is half the MFMA instructions (64 cycles each instead of 32),
+// which leaves the issue slots the LDS reads, the slab / W loads and the barrier need: the 16x16 kernel ran its matrix pipe 81 %
+// busy.  The two forms want W packed differently (launch_pack_w32).
+inline bool f32_use_mfma32(int64_t NP) { return NP >= POST_ROWS_WIDE; }
+
+// fp64 models on the slab route take the int8 GEMM by NP alone, never by M, so that a candidate's mu / sd do not depend on the
+// batch it comes in; the int32 level sums bound NP from above.
+inline bool posterior_i8_serves(int64_t NP) { return NP >= I8_NP_MIN && NP <= I8_NP_MAX; }
+
+// The rule: plan_posterior, first match wins (nchunks = 256-row chunks, Mp = M padded to 128, the GEMV limit small_batch_limit).
+// Why.  The slab route as soon as k* would be generated more than once: the fp64 VALU work of the generation runs instead of
+// MFMAs, not beside them, and the slab GEMM's loop carries no other VALU work.  For 384 <= NP <= 512 and a batch that fills the
+// chip, Fused512 (round 4): ONE 16-wave workgroup covers all rows, so k* is generated once and never crosses HBM (the slab
+// route: a 268 MB round trip and a second launch at C2).  Measured at M = 65 536 (scripts/r04_post_small_np_ab.py,
+// profiles/r04_post_small_np_ab.json; round 2: scripts/archive/r02_small_n_posterior_ab.py), ms for Fused256 / SlabF64 / Fused512:
+//   NP = 512, d = 8 : 0.406 / 0.374 / 0.352 (0.58 / 0.62 / 0.66 of the fp64 matrix peak)            -> Fused512
+//   NP = 448, d = 8 : 0.357 / 0.332 / 0.327                                                         -> Fused512
+//   NP = 1024, d = 16: 1.48 / 1.19 / 1.31 (two 512-row chunks: k* generated 1.5 times)               -> SlabF64
+//   NP = 768, d = 16, M = 2^18: SlabF64 2.87, Fused512 4.72 (a ragged second chunk of 16 waves, half of them idle)
+//   NP = 512, M = 8192: 0.073 / 0.115 / 0.087 (a grid of 128 workgroups does not fill the chip)    -> Fused256
+//   NP = 256: Fused256 0.12 vs SlabF64 0.14 (one chunk: nothing is generated twice).
+// Fused512 gains only 6 % where the slab traffic and a launch go away: its floor is the GEMM at the matrix pipe's 0.95 (0.25 ms)
+// + one generation of k* on the same datapath (~0.09 ms); one 1024-thread workgroup per CU also means every s_barrier stalls the
+// whole CU (the 16-wave slab kernel measured 3 % slower at C3 for the same reason).
+// Two row chunks and a batch around bayes_opt's DEFAULT n_random = 10 000 (round 6, scripts/r06_post_10k_ab.py,
+// profiles/r06_post_10k_ab.json; ms at M = 10 000 / 20 000 for N = 300, 384, 450, 512; SlabF64 was the rule's choice then):
+//   SlabF64 0.125-0.147 / 0.16-0.19;  Fused256 0.092-0.113 / 0.12-0.17;  Fused512 0.080-0.100 / 0.14-0.18
+// 144 ... 256 candidate tiles are one 16-wave workgroup per CU in ONE round; from there to 32 768 candidates the 8-wave kernel's
+// two workgroups per CU fill the chip better than either.
+// The int8 GEMM, ms per posterior pass, M = 2^20, d = 16, Matern-2.5 (debug build, GPBO_POST_KERNEL=3 | 8, one MI355X):
+//   NP = 1536: SlabF64 40.0, SlabI8 35.9;  2048: 68.0 / 56.6;  3072: 145.7 / 116.5;  4096: 255.8 / 196.5.
+// It wins from 1536 on; the rule starts at 2048, the smallest NP the suite checks it at (the ill-conditioned N = 2000 case of
+// test_gpu_conditioning.py); NP <= 1024 keeps the fp64 kernels that the three-kernel parity test pins.
+// A fused kernel whose workgroups hold ALL rows of their candidates (one row chunk) takes the raw candidates in and writes mu / sd
+// itself (round 6: three launches -> one).
+//
+// Debug overrides (parsed by the caller): force_kernel = GPBO_POST_KERNEL's digit — 2 Fused256, 3 SlabF64 (always), 4 Fused512
+// (NP <= 1024), 8 SlabI8 (512 < NP <= I8_NP_MAX); never for fp32 models, never past the Small row.  no_small: GPBO_POST_SMALL=0.
+// no_fuse_ends: GPBO_POST_FUSE_ENDS=0 (the three launches).
+inline PostPlan plan_posterior(int64_t NP, int64_t M, bool f32, int64_t gemv_limit, int force_kernel = 0, bool no_small = false,
+                               bool no_fuse_ends = false) {
+  const int nchunks = (int)((NP + POST_ROWS - 1) / POST_ROWS);
+  const int64_t Mp = (M + POST_CANDS - 1) / POST_CANDS * POST_CANDS;
+  if (M <= gemv_limit && !no_small) return {PostPath::Small, false, 0, 0};
+  if (f32)
+    return {PostPath::SlabF32, false, f32_use_mfma32(NP) ? (int)((NP + POST_ROWS_WIDE - 1) / POST_ROWS_WIDE) : nchunks, nchunks};
+  PostPath path;
+  if (nchunks <= 1) path = PostPath::Fused256;
+  else if (nchunks == 2) {
+    if (Mp < 8192) path = PostPath::Fused256;
+    else if (Mp < 9216) path = PostPath::SlabF64;
+    else if (Mp <= 16384) path = PostPath::Fused512;
+    else if (Mp < 32768) path = PostPath::Fused256;
+    else path = NP >= 384 ? PostPath::Fused512 : PostPath::SlabF64;
+  } else path = posterior_i8_serves(NP) ? PostPath::SlabI8 : PostPath::SlabF64;
+  switch (force_kernel) {
+    case 2: path = PostPath::Fused256; break;
+    case 3: path = PostPath::SlabF64; break;
+    case 4: if (NP <= 1024) path = PostPath::Fused512; break;
+    case 8: if (NP > 512 && NP <= I8_NP_MAX) path = PostPath::SlabI8; break;
+  }
+  PostPlan p{path, false, nchunks, nchunks};
+  if (path == PostPath::Fused256 || path == PostPath::Fused512) {
+    if (path == PostPath::Fused512) p.part_chunks = (int)((NP + POST_ROWS_WIDE - 1) / POST_ROWS_WIDE);
+    p.mu_chunks = 1;
+    p.fuse_ends = p.part_chunks == 1 && !no_fuse_ends;
+  } else if (path == PostPath::SlabI8) {
+    p.part_chunks = (int)((NP + I8_ROWS - 1) / I8_ROWS);
+  }
+  return p;
+}
+
+}  // namespace gpbo

@@ -138,10 +138,10 @@ int launch_posterior_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, double
   double* ks = ctx->part;
   double* vsq = ctx->part + rows * m.NP;
   const dim3 kgrid((unsigned)((m.NP + 255) / 256), (unsigned)((M + 15) / 16));
-  if (m.kernel == GPBO_KERNEL_MATERN25)
-    kstar_small_kernel<GPBO_KERNEL_MATERN25><<<kgrid, dim3(256), 0, ctx->stream>>>(m.Xs, ctx->Xcs, m.DP, m.NP, M, ks);
-  else
-    kstar_small_kernel<GPBO_KERNEL_RBF><<<kgrid, dim3(256), 0, ctx->stream>>>(m.Xs, ctx->Xcs, m.DP, m.NP, M, ks);
+  with_kernel(m.kernel, [&](auto k) {
+    kstar_small_kernel<decltype(k)::value><<<kgrid, dim3(256), 0, ctx->stream>>>(m.Xs, ctx->Xcs, m.DP, m.NP, M, ks);
+    return GPBO_OK;
+  });
   GPBO_HIP(ctx, hipGetLastError());
   // passes of up to 16 candidates (the row order of the dot products does not depend on the pass width, so a
   // candidate's result is bitwise the same whether it is evaluated alone or inside a batch)
@@ -441,10 +441,10 @@ int launch_posterior_grad_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, d
   double* partial = vb + rows * m.NP;
   double* gpart = partial + (int64_t)n_splits * M * m.NP;
   const dim3 kgrid((unsigned)((m.NP + 255) / 256), (unsigned)((M + 15) / 16));
-  if (m.kernel == GPBO_KERNEL_MATERN25)
-    kstar_grad_small_kernel<GPBO_KERNEL_MATERN25><<<kgrid, dim3(256), 0, ctx->stream>>>(m.Xs, ctx->Xcs, m.DP, m.NP, m.N, M, ks, fs);
-  else
-    kstar_grad_small_kernel<GPBO_KERNEL_RBF><<<kgrid, dim3(256), 0, ctx->stream>>>(m.Xs, ctx->Xcs, m.DP, m.NP, m.N, M, ks, fs);
+  with_kernel(m.kernel, [&](auto k) {
+    kstar_grad_small_kernel<decltype(k)::value><<<kgrid, dim3(256), 0, ctx->stream>>>(m.Xs, ctx->Xcs, m.DP, m.NP, m.N, M, ks, fs);
+    return GPBO_OK;
+  });
   GPBO_HIP(ctx, hipGetLastError());
   // v = W k*: passes of 8 candidates (a padded last pass reads/writes scratch rows that exist: rows = M + 16)
   {
