@@ -252,7 +252,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int nblk = (int)(a.NP / NB);
   fs_inputs(a, lo, zl);
   fs_kmat<KERNEL>(a, lo, fs_smem);
-  // Cholesky: launch_cholesky128's schedule with ONE outer panel (what chol_outer_width gives up to NP = 2048), every launch of it a
+  // Cholesky: launch_cholesky128's schedule with ONE outer panel (what chol_outer gives up to NP = 2048), every launch of it a
   // phase of this workgroup
   for (int kb = 0; kb < nblk; kb += 2) {
     const int nb = (nblk - kb >= 2) ? 2 : 1;
@@ -272,17 +272,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if (fs_tid() == 0) a.info_out[(int64_t)zl * a.info_pitch] = a.info[lo * 2];
 }
 
-// Largest padded size the fused kernel serves: 64 in the product.  (At NP = 128 — still one diagonal workgroup plus a handful of
-// tiles — the strip path of mid_fit.hip is faster, 50 against 79 us per fit and 94 against 118 per LML + gradient; at NP = 64 the
-// one launch wins the LML evaluation, 67 against 74 us, and loses 5 us on the fit: profiles/r05_small_fit_timing.json.  Debug
-// build: GPBO_FUSED_MAX_NP = 0 / 64 / 128 / ... up to FUSED_NP_CAP, read per call, for the bitwise A/B tests and the crossover
-// measurement.)
-int fused_max_np() {
-  int v = FUSED_NP_DEFAULT;
-  if (const char* e = dbg_env("GPBO_FUSED_MAX_NP")) v = atoi(e);
-  if (v > FUSED_NP_CAP) v = FUSED_NP_CAP;
-  return v;
-}
+// Largest padded size the fused kernel serves (fit_plan.h: the default, the cap and the measurement behind them).
+int fused_max_np() { return fused_max_from(env_override(dbg_env("GPBO_FUSED_MAX_NP"))); }
 
 int launch_fused_small(gpbo_ctx* ctx, Model& m, int mode, int src, int n_ls, const double* X, const double* y, const double* ls_in,
                        double* scal, int* info_out, int64_t info_pitch, double* out, int64_t out_pitch) {

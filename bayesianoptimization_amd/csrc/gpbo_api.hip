@@ -1,6 +1,7 @@
 // C-ABI entry points of libgpbo (see include/gpbo.h for the contract and the reference call each
 // function replaces).  Host-side orchestration only: every numeric step is a HIP kernel launched
 // on the context's stream.
+#include <array>
 #include <cmath>
 #include <mutex>
 #include <shared_mutex>
@@ -27,6 +28,11 @@ static int check_slot(gpbo_ctx* ctx, int slot) {
   return GPBO_OK;
 }
 
+// m's buffers in the order of fit_plan.h's table (FitBuf, the per-model part)
+static std::array<double**, FB_MODEL_COUNT> model_buffers(Model& m) {
+  return {&m.ls, &m.Xs, &m.K, &m.L, &m.W, &m.dinv, &m.tmp, &m.yn, &m.tvec, &m.alpha};
+}
+
 static void free_model(Model& m) {
   double** ptrs[] = {&m.ls, &m.Xs, &m.K, &m.L, &m.W, &m.Wp, &m.dinv, &m.tmp, &m.yn, &m.tvec, &m.alpha, &m.mu, &m.sd};
   for (double** p : ptrs) {
@@ -45,19 +51,10 @@ static int alloc_model(gpbo_ctx* ctx, Model& m, int64_t NP, int DP) {
   m.mu = m.sd = nullptr;
   free_model(m);
   m.mu = mu; m.sd = sd; m.cap_M = cap_M;
-  const size_t sq = (size_t)NP * NP * sizeof(double);
-  const int64_t tmp_elems = std::max<int64_t>(NP * NP / 2, NP * (int64_t)GPBO_MAX_DIM);
-  GPBO_HIP(ctx, hipMalloc((void**)&m.ls, GPBO_MAX_DIM * sizeof(double)));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.Xs, (size_t)NP * DP * sizeof(double)));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.K, sq));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.L, sq));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.W, sq));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.Wp, sq));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.dinv, (size_t)(NP / NB) * NB * NB * sizeof(double)));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.tmp, (size_t)tmp_elems * sizeof(double)));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.yn, (size_t)NP * sizeof(double)));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.tvec, (size_t)NP * sizeof(double)));
-  GPBO_HIP(ctx, hipMalloc((void**)&m.alpha, (size_t)NP * sizeof(double)));
+  const FitBuffers sizes = fit_buffers(NP, DP);
+  const auto buf = model_buffers(m);
+  for (int i = 0; i < FB_MODEL_COUNT; ++i) GPBO_HIP(ctx, hipMalloc((void**)buf[i], (size_t)sizes.size[i] * sizeof(double)));
+  GPBO_HIP(ctx, hipMalloc((void**)&m.Wp, (size_t)NP * NP * sizeof(double)));
   m.cap_NP = NP;
   m.cap_DP = DP;
   return GPBO_OK;
@@ -68,19 +65,9 @@ static int alloc_model(gpbo_ctx* ctx, Model& m, int64_t NP, int DP) {
 // inside `outer`-column panels; the matrix right of a panel gets ONE rank-`outer` update per panel, so the trailing
 // matrix is read and written N / outer times instead of N / 128 times.  (Round 2's 64-column schedules — potrf_diag_kernel /
 // chol_step_kernel — were retired in round 4.)
-static int chol_outer_width(int64_t NP) {
-  // Outer panel width by size (scripts/archive/r03_chol_probe.py, round-3 schedule): up to NP = 2048 one panel — the rank-128
-  // updates of the steps reach the whole trailing matrix, whose traffic is still small, and no latency-bound
-  // rank-`outer` GEMM stands between the steps (NP = 1024: 0.312 -> 0.283 ms, 2048: 0.683 -> 0.618); 1024 up to NP = 4096
-  // (1.70 -> 1.66-1.68); 512 beyond (8192: 6.0 against 6.36 with 1024), where the trailing matrix no longer fits the
-  // caches and every pass over it counts.
-  int outer = NP <= 2048 ? (int)round_up(NP, 2 * NB) : (NP <= 4096 ? 1024 : 512);
-  if (const char* e = dbg_env("GPBO_CHOL_OUTER")) outer = atoi(e);
-  if (outer < 2 * NB || outer % (2 * NB)) outer = 2 * NB;
-  return outer;
+static int cholesky(gpbo_ctx* ctx, Model& m, long long* stamps = nullptr) {
+  return launch_cholesky128(ctx, m, chol_outer(m.NP, env_override(dbg_env("GPBO_CHOL_OUTER"))), stamps);
 }
-
-static int cholesky(gpbo_ctx* ctx, Model& m) { return launch_cholesky128(ctx, m, chol_outer_width(m.NP), nullptr); }
 
 // W = L^-1 by recursive doubling from the inverted 64x64 diagonal blocks:
 //   [[A,0],[C,B]]^-1 = [[A^-1,0],[-B^-1 C A^-1, B^-1]]  — two batched GEMMs per level.
@@ -281,10 +268,6 @@ int gpbo_device_info(gpbo_ctx* ctx, char* buf, int buflen) {
   return GPBO_OK;
 }
 
-// Shared by gpbo_fit and gpbo_lml: validate, upload, K, Cholesky, W = L^-1, alpha — all queued on the
-// stream; the potrf info word is copied to pinned memory (valid after the next stream sync).
-// Copies/fills that act on one buffer of EVERY lane (lane mode: the buffers of lane l sit l * lane_stride doubles
-// behind lane 0's; host staging areas are arrays with `host_pitch` bytes per lane).
 // The look-ahead side stream + events that belong to `main` (a stream about to be destroyed).
 static void drop_lookahead(gpbo_ctx* ctx, hipStream_t main) {
   for (size_t i = 0; i < ctx->lookahead.size();) {
@@ -295,6 +278,8 @@ static void drop_lookahead(gpbo_ctx* ctx, hipStream_t main) {
   }
 }
 
+// Copies/fills that act on one buffer of EVERY lane (lane mode: the buffers of lane l sit l * lane_stride doubles
+// behind lane 0's; host staging areas are arrays with `host_pitch` bytes per lane).
 static hipError_t lane_memset(gpbo_ctx* ctx, void* p, size_t bytes) {
   if (ctx->lanes == 1) return hipMemsetAsync(p, 0, bytes, ctx->stream);
   return hipMemset2DAsync(p, (size_t)ctx->lane_stride * sizeof(double), 0, bytes, (size_t)ctx->lanes, ctx->stream);
@@ -310,28 +295,8 @@ static hipError_t lane_d2h(gpbo_ctx* ctx, void* dst_host, size_t host_pitch, con
                           hipMemcpyDeviceToHost, ctx->stream);
 }
 
-// Host staging: single lane = window 0 of the pinned allocation (PIN_LS / PIN_INFO / PIN_LML_OUT, gpbo_internal.h);
-// lane mode = one window per group with per-lane pitches: length scales at +0, info words at PIN_LANE_INFO, LML scalars
-// at PIN_LANE_OUT.
-constexpr size_t PIN_LS_PITCH = PIN_LS_BYTES;
-constexpr size_t PIN_INFO_PITCH = 8;
-constexpr size_t PIN_OUT_PITCH = PIN_LML_OUT_BYTES;
-constexpr size_t PIN_LANE_WINDOW = PIN_WINDOW, PIN_LANE_INFO = 4096, PIN_LANE_OUT = 8192;   // lane-mode layout inside a group's window
-static_assert(GPBO_LML_BATCH_MAX * PIN_LS_PITCH <= PIN_LANE_INFO, "lane length scales overlap the lane info words");
-static_assert(PIN_LANE_INFO + GPBO_LML_BATCH_MAX * PIN_INFO_PITCH <= PIN_LANE_OUT, "lane info words overlap the lane LML scalars");
-static_assert(PIN_LANE_OUT + GPBO_LML_BATCH_MAX * PIN_OUT_PITCH <= PIN_WINDOW, "lane LML scalars leave the window");
-
-// Small problems (NP <= fused_max_np()): the whole fit — or LML evaluation — as ONE launch of one workgroup per model
-// (fused_small.hip; bitwise the multi-launch sequence below).  mode 0: fit incl. the packed W; 1 / 2: LML value / value + gradient.
-// src 0: raw inputs (host arrays staged through pinned memory the kernel reads directly, or device arrays X_dev / y_dev) and the
-// length scales of the pinned window; src 1: the model's resident Xs / yn / ls.  The pivot word and the LML scalars land in the
-// pinned words *info_host / *out_host (valid after the stream has drained) without copy nodes.
-static bool use_fused(const Model& m) { return m.NP <= fused_max_np(); }
-// fused_max_np() < NP <= mid_max_np(): the strip path (mid_fit.hip)
-static bool use_mid(const Model& m) { return !use_fused(m) && m.NP <= mid_max_np(); }
-
-// the address the device sees a word of the pinned window allocation at
-static char* pinned_dev(gpbo_ctx* ctx, void* host) { return ctx->pinned_base_dev + ((char*)host - (char*)ctx->pinned_base); }
+// The size tier of a model's fit (fit_plan.h; the two limits are read per call: debug-build switches)
+static FitTier tier_of(const Model& m) { return fit_tier(m.NP, fused_max_np(), mid_max_np()); }
 
 // X (N, d) | y (N) of a small host-side fit copied into the pinned staging window that belongs to ctx->pinned's window (0: the
 // context's own stream, every such call ends with a stream synchronisation; 1 + slot: a gpbo_fit_begin in flight); the first
@@ -350,6 +315,11 @@ static int stage_small_inputs(gpbo_ctx* ctx, const Model& m, const double* X, co
   return GPBO_OK;
 }
 
+// Small problems (FitTier::Fused): the whole fit — or LML evaluation — as ONE launch of one workgroup per model
+// (fused_small.hip; bitwise the multi-launch sequence below).  mode 0: fit incl. the packed W; 1 / 2: LML value / value + gradient.
+// src 0: raw inputs (host arrays staged through pinned memory the kernel reads directly, or device arrays X_dev / y_dev) and the
+// length scales of the pinned window; src 1: the model's resident Xs / yn / ls.  The pivot word and the LML scalars land in the
+// pinned words *info_host / *out_host (valid after the stream has drained) without copy nodes.
 static int enqueue_fused(gpbo_ctx* ctx, Model& m, const double* X, const double* y_norm, const double* X_dev, const double* y_dev,
                          double noise, int mode, int n_ls, int src, int** info_host, double** out_host) {
   int rc;
@@ -358,25 +328,26 @@ static int enqueue_fused(gpbo_ctx* ctx, Model& m, const double* X, const double*
   if (src == 0 && !X_dev && (rc = stage_small_inputs(ctx, m, X, y_norm, &Xd, &yd))) return rc;
   double* scal = m.tmp;
   if (mode != 0) {
+    // (a lane group of gpbo_lml_batch has pointed red / cap_red at its slab's FB_SCAL region, which has exactly this size: nothing
+    // grows there, and its LaunchScope puts back a pointer that is still the context's)
     char* p = (char*)ctx->red;
     int64_t cap = ctx->cap_red;
-    if ((rc = ensure(ctx, &p, &cap, (int64_t)(8 + GPBO_MAX_DIM) * 8))) return rc;
+    if ((rc = ensure(ctx, &p, &cap, FIT_SCAL_DOUBLES * (int64_t)sizeof(double)))) return rc;
     ctx->red = p;
     ctx->cap_red = cap;
     scal = (double*)ctx->red;
   }
-  int* info_h = (int*)((char*)ctx->pinned + (ctx->lanes == 1 ? PIN_INFO : PIN_LANE_INFO));
-  double* out_h = (double*)((char*)ctx->pinned + (ctx->lanes == 1 ? PIN_LML_OUT : PIN_LANE_OUT));
+  const PinLane h = pin_lane(ctx->pinned);
   ev_begin(ctx, T_FIT);
   if (!ctx->no_timing) ctx->ev[T_KMAT].used = ctx->ev[T_CHOL].used = ctx->ev[T_TRTRI].used = false;   // one kernel: no phase events
-  if ((rc = launch_fused_small(ctx, m, mode, src, n_ls, Xd, yd, (const double*)pinned_dev(ctx, ctx->pinned), scal,
-                               (int*)pinned_dev(ctx, info_h), (int64_t)(PIN_INFO_PITCH / sizeof(int)),
-                               mode ? (double*)pinned_dev(ctx, out_h) : nullptr, (int64_t)(PIN_OUT_PITCH / sizeof(double)))))
+  if ((rc = launch_fused_small(ctx, m, mode, src, n_ls, Xd, yd, pinned_dev(ctx, h.ls), scal, pinned_dev(ctx, h.info),
+                               (int64_t)(PIN_INFO_PITCH / sizeof(int)), mode ? pinned_dev(ctx, h.out) : nullptr,
+                               (int64_t)(PIN_OUT_PITCH / sizeof(double)))))
     return rc;
   if (mode == 0) m.wp_packed = true;
   else ev_end(ctx, T_FIT);
-  *info_host = info_h;
-  if (out_host) *out_host = out_h;
+  *info_host = h.info;
+  if (out_host) *out_host = h.out;
   return GPBO_OK;
 }
 
@@ -389,8 +360,8 @@ static int factor_mid(gpbo_ctx* ctx, Model& m, double noise, bool pack, int** in
   if ((rc = launch_kmat_q(ctx, m, noise, m.L))) return rc;
   if ((rc = cholesky(ctx, m))) return rc;
   if ((rc = launch_w_strip(ctx, m, pack))) return rc;
-  int* info_h = (int*)((char*)ctx->pinned + (ctx->lanes == 1 ? PIN_INFO : PIN_LANE_INFO));
-  if ((rc = launch_alpha_strip(ctx, m, (int*)pinned_dev(ctx, info_h), (int64_t)(PIN_INFO_PITCH / sizeof(int))))) return rc;
+  int* info_h = pin_lane(ctx->pinned).info;
+  if ((rc = launch_alpha_strip(ctx, m, pinned_dev(ctx, info_h), (int64_t)(PIN_INFO_PITCH / sizeof(int))))) return rc;
   if (pack && m.Wp) m.wp_packed = true;
   *info_host = info_h;
   return GPBO_OK;
@@ -399,17 +370,18 @@ static int factor_mid(gpbo_ctx* ctx, Model& m, double noise, bool pack, int** in
 // K, L, W = L^-1 and alpha from the device-resident scaled inputs m.Xs / targets m.yn (m.N, m.NP, m.kernel set).
 static int factor_resident(gpbo_ctx* ctx, Model& m, double noise, int** info_host, bool pack = true) {
   int rc;
-  if (use_fused(m)) return enqueue_fused(ctx, m, nullptr, nullptr, nullptr, nullptr, noise, 0, 0, 1, info_host, nullptr);   // (gpbo_fit_append's rebuild)
+  const FitTier tier = tier_of(m);
+  if (tier == FitTier::Fused) return enqueue_fused(ctx, m, nullptr, nullptr, nullptr, nullptr, noise, 0, 0, 1, info_host, nullptr);   // (gpbo_fit_append's rebuild)
   m.noise = noise;
   GPBO_HIP(ctx, lane_memset(ctx, ctx->info_dev, sizeof(int)));
-  if (use_mid(m)) return factor_mid(ctx, m, noise, pack, info_host);
+  if (tier == FitTier::Strip) return factor_mid(ctx, m, noise, pack, info_host);
   ev_begin(ctx, T_KMAT);
   if ((rc = launch_kmat(ctx, m, noise, m.L))) return rc;   // straight into the buffer the Cholesky factorises in place
   ev_end(ctx, T_KMAT);
   ev_begin(ctx, T_CHOL);
   if ((rc = cholesky(ctx, m))) return rc;
   ev_end(ctx, T_CHOL);
-  int* info_h = (int*)((char*)ctx->pinned + (ctx->lanes == 1 ? PIN_INFO : PIN_LANE_INFO));   // lane mode: one word per PIN_INFO_PITCH
+  int* info_h = pin_lane(ctx->pinned).info;   // one word per lane, PIN_INFO_PITCH apart
   GPBO_HIP(ctx, lane_d2h(ctx, info_h, PIN_INFO_PITCH, ctx->info_dev, sizeof(int)));
   // W and alpha are issued before the info check resolves (harmless on failure)
   ev_begin(ctx, T_TRTRI);
@@ -420,23 +392,37 @@ static int factor_resident(gpbo_ctx* ctx, Model& m, double noise, int** info_hos
   return GPBO_OK;
 }
 
+// The shape / kernel / length-scale / noise checks of a fit or LML entry point (n_theta sets of n_ls length scales).
+static int check_gp_args(gpbo_ctx* ctx, const char* who, int64_t N, int d, int kernel, const double* length_scales, int n_theta,
+                         int n_ls, double noise) {
+  const auto w = [who] { return std::string(who); };     // (built on a failure only)
+  if (N < 1 || N > (1 << 16)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w() + ": N out of range [1, 65536]");
+  if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, w() + ": d out of range [1, 64]");
+  if (kernel != GPBO_KERNEL_RBF && kernel != GPBO_KERNEL_MATERN25)
+    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, w() + ": kernel must be RBF or Matern(nu=2.5)");
+  if (n_ls != 1 && n_ls != d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w() + ": length_scale must have 1 or d entries");
+  for (int64_t t = 0; t < (int64_t)n_theta * n_ls; ++t)
+    if (!(length_scales[t] > 0.0) || !std::isfinite(length_scales[t]))
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, w() + ": length_scale must be positive and finite");
+  if (!(noise >= 0.0)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w() + ": noise must be >= 0");
+  return GPBO_OK;
+}
+
+// lane l's length scales into the window's staging words: one value for every dimension or one per dimension, 1 beyond d
+static void stage_length_scales(void* window, int l, const double* length_scale, int n_ls, int d) {
+  double* ls_h = pin_lane(window, l).ls;
+  for (int t = 0; t < GPBO_MAX_DIM; ++t) ls_h[t] = (t < d) ? (n_ls == 1 ? length_scale[0] : length_scale[t]) : 1.0;
+}
+
 // Argument checks, buffers and descriptor of a fit; the scaled length scales go to the pinned staging words.  Nothing
 // is enqueued (so this part stays outside a stream capture).
 static int prepare_model(gpbo_ctx* ctx, Model& m, const char* who, bool have_inputs, int64_t N, int d, int kernel,
                          const double* length_scale, int n_ls, double noise, int precision) {
   int rc;
-  std::string w(who);
-  if (!have_inputs || !length_scale) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": NULL input");
-  if (N < 1 || N > (1 << 16)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": N out of range [1, 65536]");
-  if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, w + ": d out of range [1, 64]");
-  if (kernel != GPBO_KERNEL_RBF && kernel != GPBO_KERNEL_MATERN25)
-    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, w + ": kernel must be RBF or Matern(nu=2.5)");
-  if (n_ls != 1 && n_ls != d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": length_scale must have 1 or d entries");
-  if (precision != GPBO_F64 && precision != GPBO_F32) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, w + ": precision must be GPBO_F64 or GPBO_F32");
-  for (int t = 0; t < n_ls; ++t)
-    if (!(length_scale[t] > 0.0) || !std::isfinite(length_scale[t]))
-      GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": length_scale must be positive and finite");
-  if (!(noise >= 0.0)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": noise must be >= 0");
+  if (!have_inputs || !length_scale) GPBO_FAIL(ctx, GPBO_ERR_INVALID, std::string(who) + ": NULL input");
+  if ((rc = check_gp_args(ctx, who, N, d, kernel, length_scale, 1, n_ls, noise))) return rc;
+  if (precision != GPBO_F64 && precision != GPBO_F32)
+    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, std::string(who) + ": precision must be GPBO_F64 or GPBO_F32");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
 
   m.fitted = false;
@@ -448,8 +434,7 @@ static int prepare_model(gpbo_ctx* ctx, Model& m, const char* who, bool have_inp
   const int DP = pad_dim(d);
   if ((rc = alloc_model(ctx, m, NP, DP))) return rc;
   m.N = N; m.NP = NP; m.d = d; m.DP = DP; m.kernel = kernel; m.precision = precision;
-  double* ls_h = (double*)ctx->pinned;
-  for (int t = 0; t < GPBO_MAX_DIM; ++t) ls_h[t] = (t < d) ? (n_ls == 1 ? length_scale[0] : length_scale[t]) : 1.0;
+  stage_length_scales(ctx->pinned, 0, length_scale, n_ls, d);
   return GPBO_OK;
 }
 
@@ -459,16 +444,17 @@ static int enqueue_factor(gpbo_ctx* ctx, Model& m, const double* X, const double
                           const double* y_dev, double noise, int** info_host, bool pack = true) {
   int rc;
   const int64_t N = m.N, NP = m.NP;
-  if (use_fused(m)) return enqueue_fused(ctx, m, X, y_norm, X_dev, y_dev, noise, 0, 0, 0, info_host, nullptr);
-  if (use_mid(m)) {      // inputs straight from pinned host memory (or the resident device copies): no copy / fill nodes
+  const FitTier tier = tier_of(m);
+  if (tier == FitTier::Fused) return enqueue_fused(ctx, m, X, y_norm, X_dev, y_dev, noise, 0, 0, 0, info_host, nullptr);
+  if (tier == FitTier::Strip) {      // inputs straight from pinned host memory (or the resident device copies): no copy / fill nodes
     const double *Xd = X_dev, *yd = y_dev;
     if (!X_dev && (rc = stage_small_inputs(ctx, m, X, y_norm, &Xd, &yd))) return rc;
     ev_begin(ctx, T_FIT);
-    if ((rc = launch_mid_inputs(ctx, m, Xd, yd, (const double*)pinned_dev(ctx, ctx->pinned)))) return rc;
+    if ((rc = launch_mid_inputs(ctx, m, Xd, yd, pinned_dev(ctx, pin_lane(ctx->pinned).ls)))) return rc;
     return factor_mid(ctx, m, noise, pack, info_host);
   }
   ev_begin(ctx, T_FIT);
-  GPBO_HIP(ctx, lane_h2d(ctx, m.ls, ctx->pinned, PIN_LS_PITCH, GPBO_MAX_DIM * sizeof(double)));
+  GPBO_HIP(ctx, lane_h2d(ctx, m.ls, pin_lane(ctx->pinned).ls, PIN_LS_PITCH, GPBO_MAX_DIM * sizeof(double)));
   GPBO_HIP(ctx, lane_memset(ctx, m.yn, (size_t)NP * sizeof(double)));
   if (X_dev) {
     for (int l = 0; l < ctx->lanes; ++l)     // every lane gets the same targets
@@ -481,14 +467,6 @@ static int enqueue_factor(gpbo_ctx* ctx, Model& m, const double* X, const double
     if ((rc = launch_prescale(ctx, m.tmp, N, m.d, m.DP, m.ls, m.Xs, NP))) return rc;
   }
   return factor_resident(ctx, m, noise, info_host, pack);
-}
-
-static int factorize(gpbo_ctx* ctx, Model& m, const char* who, const double* X, const double* y_norm, int64_t N,
-                     int d, int kernel, const double* length_scale, int n_ls, double noise, int precision,
-                     int** info_host) {
-  int rc = prepare_model(ctx, m, who, X && y_norm, N, d, kernel, length_scale, n_ls, noise, precision);
-  if (rc) return rc;
-  return enqueue_factor(ctx, m, X, y_norm, nullptr, nullptr, noise, info_host);
 }
 
 // Tail shared by the fit entry points: pack W for the posterior kernels (enqueue), then wait and resolve the pivot check.
@@ -547,9 +525,10 @@ int gpbo_fit(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int
   int rc = check_slot(ctx, slot);
   if (rc) return rc;
   if ((rc = no_pending_fit(ctx, slot, "gpbo_fit"))) return rc;
-  rc = factorize(ctx, ctx->models[slot], "gpbo_fit", X, y_norm, N, d, kernel, length_scale, n_ls, noise, precision, &info_h);
-  if (rc) return rc;
-  return finish_fit(ctx, ctx->models[slot], info_h, info);
+  Model& m = ctx->models[slot];
+  if ((rc = prepare_model(ctx, m, "gpbo_fit", X && y_norm, N, d, kernel, length_scale, n_ls, noise, precision))) return rc;
+  if ((rc = enqueue_factor(ctx, m, X, y_norm, nullptr, nullptr, noise, &info_h))) return rc;
+  return finish_fit(ctx, m, info_h, info);
 }
 
 int gpbo_fit_begin(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int64_t N, int d, int kernel,
@@ -560,20 +539,19 @@ int gpbo_fit_begin(gpbo_ctx* ctx, int slot, const double* X, const double* y_nor
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
   if (!ctx->slot_stream[slot]) GPBO_HIP(ctx, hipStreamCreateWithFlags(&ctx->slot_stream[slot], hipStreamNonBlocking));
   if (!ctx->info_slots) GPBO_HIP(ctx, hipMalloc((void**)&ctx->info_slots, GPBO_MAX_MODELS * sizeof(int)));
-  // the slot's own stream, pinned window and pivot word for the duration of the enqueue (as a gpbo_lml_batch group)
-  hipStream_t stream0 = ctx->stream;
-  void* pinned0 = ctx->pinned;
-  int* info0 = ctx->info_dev;
-  const bool timing0 = ctx->no_timing;
-  ctx->stream = ctx->slot_stream[slot];
-  ctx->pinned = (char*)pinned0 + PIN_LANE_WINDOW * (size_t)(1 + slot);
-  ctx->info_dev = ctx->info_slots + slot;
-  ctx->no_timing = true;            // the timing events belong to the main stream's calls
   int* info_h = nullptr;
-  Model& m = ctx->models[slot];
-  rc = factorize(ctx, m, "gpbo_fit_begin", X, y_norm, N, d, kernel, length_scale, n_ls, noise, precision, &info_h);
-  if (rc == GPBO_OK) rc = finish_enqueue(ctx, m);
-  ctx->stream = stream0; ctx->pinned = pinned0; ctx->info_dev = info0; ctx->no_timing = timing0;
+  {
+    // the slot's own stream, pinned window and pivot word for the duration of the enqueue (as a gpbo_lml_batch group)
+    LaunchScope scope(ctx);
+    ctx->stream = ctx->slot_stream[slot];
+    ctx->pinned = pin_window(ctx, 1 + slot);
+    ctx->info_dev = ctx->info_slots + slot;
+    ctx->no_timing = true;            // the timing events belong to the main stream's calls
+    Model& m = ctx->models[slot];
+    rc = prepare_model(ctx, m, "gpbo_fit_begin", X && y_norm, N, d, kernel, length_scale, n_ls, noise, precision);
+    if (rc == GPBO_OK) rc = enqueue_factor(ctx, m, X, y_norm, nullptr, nullptr, noise, &info_h);
+    if (rc == GPBO_OK) rc = finish_enqueue(ctx, m);
+  }
   if (rc) {
     (void)hipStreamSynchronize(ctx->slot_stream[slot]);     // nothing of a half-enqueued fit may still be running
     return rc;
@@ -619,7 +597,7 @@ int gpbo_fit_append(gpbo_ctx* ctx, int slot, const double* x_new, int64_t n_new,
     double* keep = nullptr;
     GPBO_HIP(ctx, hipMalloc((void**)&keep, (size_t)N0 * m.DP * sizeof(double)));
     GPBO_HIP(ctx, hipMemcpyAsync(keep, m.Xs, (size_t)N0 * m.DP * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    double* ls_h = (double*)ctx->pinned;
+    double* ls_h = pin_lane(ctx->pinned).ls;
     GPBO_HIP(ctx, hipMemcpyAsync(ls_h, m.ls, GPBO_MAX_DIM * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int DP = m.DP;
@@ -650,7 +628,7 @@ int gpbo_fit_append(gpbo_ctx* ctx, int slot, const double* x_new, int64_t n_new,
     for (int64_t j = N0; j < n_total; ++j)
       if ((rc = launch_append_row(ctx, m, j))) return rc;
     m.N = n_total;
-    info_h = (int*)((char*)ctx->pinned + PIN_INFO);
+    info_h = pin_lane(ctx->pinned).info;
     GPBO_HIP(ctx, hipMemcpyAsync(info_h, ctx->info_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = launch_trmv(ctx, m))) return rc;
   }
@@ -661,17 +639,15 @@ int gpbo_fit_append(gpbo_ctx* ctx, int slot, const double* x_new, int64_t n_new,
 // terms, K^-1 = W^T W and the gradient reduction, and the copy of the results to the pinned words *out_host.
 static int lml_tail(gpbo_ctx* ctx, Model& m, int n_ls, int eval_gradient, double** out_host) {
   int rc;
-  // the kernels write the scalars into the pinned words themselves (lane mode: PIN_OUT_PITCH bytes per lane): no copy node
-  double* out_h = (double*)((char*)ctx->pinned + (ctx->lanes == 1 ? PIN_LML_OUT : PIN_LANE_OUT));
-  double* out_d = (double*)pinned_dev(ctx, out_h);
+  // the kernels write the scalars into the pinned words themselves (PIN_OUT_PITCH bytes per lane): no copy node
+  double* out_h = pin_lane(ctx->pinned).out;
+  double* out_d = pinned_dev(ctx, out_h);
   const int64_t pitch = (int64_t)(PIN_OUT_PITCH / sizeof(double));
   if (!eval_gradient && (rc = launch_lml_terms(ctx, m, out_d, pitch))) return rc;
   if (eval_gradient) {
-    if (m.NP <= mid_max_np()) {
-      // small problems: K^-1 tile by tile inside the gradient launch (kinv_grad_kernel), the two LML terms in its final launch
+    if (kinv_in_grad_launch(tier_of(m))) {      // kinv_grad_kernel; the two LML terms in its final launch
       if ((rc = launch_lml_grad(ctx, m, n_ls, nullptr, m.tmp, out_d, pitch, true))) return rc;
-    } else {
-      // K^-1 = W^T W (lower tiles) into the K buffer, then the trace reduction; partials go to m.tmp
+    } else {                                    // the W^T W GEMM into the K buffer, then the trace reduction; partials go to m.tmp
       GemmArgs g{};
       g.m = (int)m.NP; g.n = (int)m.NP; g.k = (int)m.NP; g.alpha = 1.0; g.beta = 0.0;
       g.A = m.W; g.lda = m.NP; g.a_trans = 1;
@@ -686,15 +662,15 @@ static int lml_tail(gpbo_ctx* ctx, Model& m, int n_ls, int eval_gradient, double
   return GPBO_OK;
 }
 
-// One log-marginal-likelihood evaluation enqueued on ctx->stream into model m; results land in the pinned words
-// *out_host (yT alpha, sum log L_ii, gradient...) and *info_host once the stream has drained.
-static int lml_enqueue(gpbo_ctx* ctx, Model& m, const double* X, const double* y_norm, int64_t N, int d, int kernel,
-                       const double* length_scale, int n_ls, double noise, int eval_gradient, double** out_host,
-                       int** info_host) {
-  int rc = prepare_model(ctx, m, "gpbo_lml", X && y_norm, N, d, kernel, length_scale, n_ls, noise, GPBO_F64);
+// One log-marginal-likelihood evaluation of the prepared model m (and, in lane mode, of ctx->lanes models) enqueued on ctx->stream,
+// inputs from the host (X, y_norm) or resident on the device (X_dev, y_dev): the one fused launch, or factorisation + tail.  Results
+// land in the pinned words *out_host (yT alpha, sum log L_ii, gradient...) and *info_host once the stream has drained.
+static int enqueue_lml(gpbo_ctx* ctx, Model& m, const double* X, const double* y_norm, const double* X_dev, const double* y_dev,
+                       double noise, int n_ls, int eval_gradient, double** out_host, int** info_host) {
+  if (tier_of(m) == FitTier::Fused)
+    return enqueue_fused(ctx, m, X, y_norm, X_dev, y_dev, noise, eval_gradient ? 2 : 1, n_ls, 0, info_host, out_host);
+  int rc = enqueue_factor(ctx, m, X, y_norm, X_dev, y_dev, noise, info_host, false);
   if (rc) return rc;
-  if (use_fused(m)) return enqueue_fused(ctx, m, X, y_norm, nullptr, nullptr, noise, eval_gradient ? 2 : 1, n_ls, 0, info_host, out_host);
-  if ((rc = enqueue_factor(ctx, m, X, y_norm, nullptr, nullptr, noise, info_host, false))) return rc;
   return lml_tail(ctx, m, n_ls, eval_gradient, out_host);
 }
 
@@ -721,8 +697,9 @@ int gpbo_lml(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int
   int* info_h = nullptr;
   double* out_h = nullptr;
   // the slot is left "unfitted": its W is not packed for the posterior kernel
-  rc = lml_enqueue(ctx, ctx->models[slot], X, y_norm, N, d, kernel, length_scale, n_ls, noise, eval_gradient, &out_h, &info_h);
-  if (rc) return rc;
+  Model& m = ctx->models[slot];
+  if ((rc = prepare_model(ctx, m, "gpbo_lml", X && y_norm, N, d, kernel, length_scale, n_ls, noise, GPBO_F64))) return rc;
+  if ((rc = enqueue_lml(ctx, m, X, y_norm, nullptr, nullptr, noise, n_ls, eval_gradient, &out_h, &info_h))) return rc;
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   lml_finish(out_h, info_h, N, n_ls, eval_gradient, lml, grad, info);
   return GPBO_OK;
@@ -807,6 +784,77 @@ static int pick_lane_streams(gpbo_ctx* ctx, int n_groups) {
   ctx->lane_streams_picked = n_groups;
   return GPBO_OK;
 }
+
+// The graph pool of gpbo_lml_batch (ctx->lml_lane).  An evaluation is ~60 short launches: the second time the same problem shape
+// comes by, the group's sequence is captured into a hipGraph and from then on replayed with one launch.
+
+// The pool's entry for `key` — seen: the one that has run it — or the entry that takes it in: an unused one, else the least
+// recently used, emptied (seen == false).  Either way it is now the most recently used.
+static LmlLane& lml_lane_find(gpbo_ctx* ctx, const LmlKey& key) {
+  LmlLane* found = nullptr;
+  LmlLane* victim = &ctx->lml_lane[0];
+  for (auto& e : ctx->lml_lane) {
+    if (e.seen && e.key == key) {
+      found = &e;
+      break;
+    }
+    if ((!e.seen && victim->seen) || (e.seen == victim->seen && e.used < victim->used)) victim = &e;
+  }
+  LmlLane& e = found ? *found : *victim;
+  if (!found) {
+    if (e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; }
+    e.seen = false;
+  }
+  e.used = ++ctx->lml_lane_clock;
+  return e;
+}
+
+static LmlKey lml_lane_key(const gpbo_ctx* ctx, const Model& m, int n_ls, int eval_gradient, int group, const double* gbase) {
+  LmlKey k;
+  k.N = m.N; k.d = m.d; k.kernel = m.kernel; k.n_ls = n_ls; k.eval_gradient = eval_gradient; k.noise = m.noise;
+  k.lanes = ctx->lanes; k.group = group; k.X = ctx->lml_X; k.y = ctx->lml_y; k.K = gbase;
+  return k;
+}
+
+// Group g's evaluation of m captured on ctx->stream (== ctx->lml_stream[g]) and instantiated into e.exec.  Failure leaves e.exec
+// null, turns graphs off for the context and leaves ctx->stream a live stream for the direct launches that follow.
+static void lml_lane_capture(gpbo_ctx* ctx, LmlLane& e, int g, Model& m, int n_ls, int eval_gradient) {
+  hipGraph_t graph = nullptr;
+  double* oh = nullptr; int* ih = nullptr;
+  bool instantiated = false;
+  {
+    // Captures of different contexts (the lanes of a device group run on one thread per device) are taken one at a
+    // time, process-wide: concurrent captures were seen to invalidate each other on this runtime
+    // (tests/test_gpu_sharded.py, three virtual ranks).  A capture is ~1 ms of host work once per problem shape.
+    std::unique_lock<std::shared_mutex> capture_lock(g_capture_mu);
+    int crc = GPBO_ERR_HIP;
+    hipError_t err = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
+    if (err == hipSuccess) {
+      crc = enqueue_lml(ctx, m, nullptr, nullptr, ctx->lml_X, ctx->lml_y, m.noise, n_ls, eval_gradient, &oh, &ih);
+      err = hipStreamEndCapture(ctx->stream, &graph);
+    }
+    instantiated = err == hipSuccess && crc == GPBO_OK && graph &&
+                   hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0) == hipSuccess && e.exec;
+  }
+  if (graph) (void)hipGraphDestroy(graph);
+  if (instantiated) return;
+  // capture is not available for this sequence on this runtime: direct launches from now on
+  if (e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; }
+  (void)hipGetLastError();
+  ctx->lml_graph_off = true;
+  // an invalidated capture can outlive hipStreamEndCapture on this runtime: the direct launches need a live stream
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(ctx->stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone) {
+    (void)hipGetLastError();
+    hipStream_t fresh = nullptr;
+    if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) == hipSuccess) {
+      drop_lookahead(ctx, ctx->lml_stream[g]);
+      (void)hipStreamDestroy(ctx->lml_stream[g]);
+      ctx->lml_stream[g] = fresh;
+      ctx->stream = fresh;     // (the group's LaunchScope puts the context's own stream back)
+    }
+  }
+}
 }  // namespace gpbo
 
 extern "C" {
@@ -818,204 +866,70 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
   if (n_theta < 1 || n_theta > GPBO_LML_BATCH_MAX) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch: n_theta out of range [1, 8]");
   if (!lml || !length_scales || (eval_gradient && !grad) || (!X) != (!y_norm))
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch: NULL argument");
-  {
-    int rcw = wait_all_pending_fits(ctx);   // their pinned windows are the ones the lane groups are about to use
-    if (rcw) return rcw;
-  }
+  int rc = wait_all_pending_fits(ctx);   // their pinned windows are the ones the lane groups are about to use
+  if (rc) return rc;
   const bool reuse_inputs = !X;     // X == y_norm == NULL: the inputs of the previous call are still on the device
   if (reuse_inputs && (ctx->lml_N != N || ctx->lml_d != d))
     GPBO_FAIL(ctx, GPBO_ERR_STATE, "gpbo_lml_batch: no resident inputs of this shape (pass X and y_norm)");
-  if (N < 1 || N > (1 << 16)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch: N out of range [1, 65536]");
-  if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "gpbo_lml_batch: d out of range [1, 64]");
-  if (kernel != GPBO_KERNEL_RBF && kernel != GPBO_KERNEL_MATERN25)
-    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "gpbo_lml_batch: kernel must be RBF or Matern(nu=2.5)");
-  if (n_ls != 1 && n_ls != d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch: length_scale must have 1 or d entries");
-  if (!(noise >= 0.0)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch: noise must be >= 0");
-  for (int64_t t = 0; t < (int64_t)n_theta * n_ls; ++t)
-    if (!(length_scales[t] > 0.0) || !std::isfinite(length_scales[t]))
-      GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch: length_scale must be positive and finite");
+  if ((rc = check_gp_args(ctx, "gpbo_lml_batch", N, d, kernel, length_scales, n_theta, n_ls, noise))) return rc;
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
 
   // One slab, one layout per lane: every kernel of the evaluation runs ONCE for all lanes (lane = a grid dimension,
   // lane l's buffers l * stride doubles behind lane 0's) — the command processor sees ~60 dispatches per batch, not
   // ~60 per theta.  Model slots and their fits are not touched.
   const int64_t NP = round_up(N, NB);
-  const int DP = pad_dim(d);
-  auto up = [](int64_t v) { return round_up(v, 32); };
-  int64_t off = 0;
-  const int64_t o_ls = off;    off += up(GPBO_MAX_DIM);
-  const int64_t o_Xs = off;    off += up(NP * DP);
-  const int64_t o_K = off;     off += up(NP * NP);
-  const int64_t o_L = off;     off += up(NP * NP);
-  const int64_t o_W = off;     off += up(NP * NP);
-  const int64_t o_dinv = off;  off += up((NP / NB) * NB * NB);
-  const int64_t o_tmp = off;   off += up(std::max<int64_t>(NP * NP / 2, NP * (int64_t)GPBO_MAX_DIM));
-  const int64_t o_yn = off;    off += up(NP);
-  const int64_t o_tvec = off;  off += up(NP);
-  const int64_t o_alpha = off; off += up(NP);
-  const int64_t o_scal = off;  off += up(8 + GPBO_MAX_DIM);
-  const int64_t o_info = off;  off += 32;
-  const int64_t stride = off;
-  int rc;
+  const FitBuffers sizes = fit_buffers(NP, pad_dim(d));
+  const LaneSlab slab = lane_slab(sizes);
   {
     std::shared_lock<std::shared_mutex> not_while_capturing(g_capture_mu);      // (hipMalloc / hipFree when the slab grows)
-    if ((rc = ensure(ctx, &ctx->lml_slab, &ctx->cap_lml_slab, stride * n_theta))) return rc;
+    if ((rc = ensure(ctx, &ctx->lml_slab, &ctx->cap_lml_slab, slab.stride * n_theta))) return rc;
   }
   if (!reuse_inputs && (rc = lml_upload_inputs(ctx, X, y_norm, N, d))) return rc;
-  double* base = ctx->lml_slab;
-  // Lanes are processed in groups: a group runs the launch sequence once for its lanes on its own stream.  Small
-  // problems are dispatch-bound (every kernel is tiny): ONE group of all lanes.  From NP = 2048 on the big GEMMs fill
-  // the chip by themselves and what is left to win is hiding one lane's latency-bound steps (the diagonal-block
-  // kernels) behind another lane's GEMMs — which a SECOND stream does and a third does not: three lanes on three streams
-  // take what two take plus one alone (2.16 against 1.22 + 0.94 ms at N = 2048; it is not the hardware queues — four streams of
-  // one-workgroup kernels do run side by side, scripts/probes/stream_queues.hip — but what two evaluations in the same phase
-  // leave free of the chip).  So: two groups, and inside a group lane = a grid dimension, where the chain's launches are
-  // shared (the diagonal blocks of all its lanes factor side by side in one step launch).  Until round 6: one lane per group
-  // from NP = 2048 on.  profiles/r06_lanes_grouping.json, ms for 3 / 4 / 6 lanes:
-  //   N = 2048: one lane per group 2.16 / 2.36 / 2.72, two groups 1.48 / 1.72 / 2.25;  N = 3072: 4.01 / 4.63 / 5.78 -> 3.17 / 3.82 / 5.31
-  //   N = 4096: 5.59 / 8.33 / 11.14 -> (three lanes on three streams stay) / 7.19 / 10.01 with two lanes per group;  N = 6144: 21.5 -> 18.9 at 4
-  int per_group = n_theta;
-  if (NP >= 4096) per_group = (n_theta <= 3) ? 1 : 2;
-  else if (NP >= 2048) per_group = (n_theta + 1) / 2;
-  if (const char* e = dbg_env("GPBO_LML_PER_GROUP")) per_group = std::max(1, std::min(atoi(e), n_theta));   // A/B runs (debug build)
-  const int n_groups = (n_theta + per_group - 1) / per_group;
-  if ((rc = pick_lane_streams(ctx, n_groups))) return rc;
+  // the lanes in groups, a group's launch sequence once for its lanes on its own stream (fit_plan.h)
+  const LaneGroups groups = lane_groups(NP, n_theta, env_override(dbg_env("GPBO_LML_PER_GROUP")));
+  if ((rc = pick_lane_streams(ctx, groups.n_groups))) return rc;
   static const bool graphs_allowed = !(dbg_env("GPBO_LML_GRAPH") && dbg_env("GPBO_LML_GRAPH")[0] == '0');
-  hipStream_t stream0 = ctx->stream;
-  void* red0 = ctx->red; int64_t cap_red0 = ctx->cap_red;
-  int* info0 = ctx->info_dev;
-  void* pinned0 = ctx->pinned;
-  auto restore = [&]() {
-    ctx->stream = stream0; ctx->red = red0; ctx->cap_red = cap_red0; ctx->info_dev = info0; ctx->pinned = pinned0;
-    ctx->lanes = 1; ctx->lane_stride = 0; ctx->no_timing = false; ctx->no_lookahead = false;
-  };
-  rc = GPBO_OK;
-  for (int g = 0; g < n_groups && rc == GPBO_OK; ++g) {
-    const int l0 = g * per_group;
-    const int gl = std::min(per_group, n_theta - l0);             // lanes of this group
-    double* gbase = base + (int64_t)l0 * stride;
-    Model m;     // a view of the group's first lane (not owning)
-    m.N = N; m.NP = NP; m.d = d; m.DP = DP; m.kernel = kernel; m.precision = GPBO_F64; m.noise = noise;
-    m.ls = gbase + o_ls; m.Xs = gbase + o_Xs; m.K = gbase + o_K; m.L = gbase + o_L; m.W = gbase + o_W;
-    m.dinv = gbase + o_dinv; m.tmp = gbase + o_tmp; m.yn = gbase + o_yn; m.tvec = gbase + o_tvec; m.alpha = gbase + o_alpha;
-    // theta enters through the pinned length-scale words ([lane][64]) that the sequence's first copy reads
-    char* window = (char*)pinned0 + PIN_LANE_WINDOW * (size_t)(1 + g);
-    double* ls_h = (double*)window;
-    for (int l = 0; l < gl; ++l)
-      for (int t = 0; t < GPBO_MAX_DIM; ++t)
-        ls_h[l * GPBO_MAX_DIM + t] =
-            (t < d) ? (n_ls == 1 ? length_scales[l0 + l] : length_scales[(int64_t)(l0 + l) * n_ls + t]) : 1.0;
+  for (int g = 0; g < groups.n_groups && rc == GPBO_OK; ++g) {
+    const int l0 = g * groups.per_group;
+    double* gbase = ctx->lml_slab + (int64_t)l0 * slab.stride;
+    LaunchScope scope(ctx);      // the group's stream, pinned window, scratch (exactly FIT_SCAL_DOUBLES: enqueue_fused) and lanes
     ctx->stream = ctx->lml_stream[g];
-    ctx->red = gbase + o_scal; ctx->cap_red = (8 + GPBO_MAX_DIM) * 8;
-    ctx->info_dev = (int*)(gbase + o_info);
-    ctx->pinned = window;
-    ctx->lanes = gl; ctx->lane_stride = stride;
+    ctx->pinned = pin_window(ctx, 1 + g);
+    ctx->red = gbase + slab.off[FB_SCAL]; ctx->cap_red = sizes.size[FB_SCAL] * (int64_t)sizeof(double);
+    ctx->info_dev = (int*)(gbase + slab.off[FB_INFO]);
+    ctx->lanes = std::min(groups.per_group, n_theta - l0); ctx->lane_stride = slab.stride;
     ctx->no_timing = true;
-    ctx->no_lookahead = n_groups > 1;
-    const bool fused = use_fused(m);     // one launch for the whole group: nothing to capture
-    // ... and the strip path's ~17 launches are enqueued faster than the device runs them: replaying them from a graph bought nothing
-    // at a fixed shape (six lanes at N = 512: 0.292 ms replayed, 0.283 launched) and cost a maximize() loop — whose N grows by one
-    // per step, a new shape every call — ~1 ms of capture + instantiation per suggest() (profiles/r05_maximize_loop.json)
-    const bool no_graph = fused || use_mid(m);
-    auto enqueue = [&](double** oh, int** ih) {
-      if (fused) return enqueue_fused(ctx, m, nullptr, nullptr, ctx->lml_X, ctx->lml_y, noise, eval_gradient ? 2 : 1, n_ls, 0, ih, oh);
-      int r = enqueue_factor(ctx, m, nullptr, nullptr, ctx->lml_X, ctx->lml_y, noise, ih, false);
-      if (r == GPBO_OK) r = lml_tail(ctx, m, n_ls, eval_gradient, oh);
-      return r;
-    };
-    // An evaluation is ~60 short launches: the second time the same problem shape comes by, the group's sequence is
-    // captured into a hipGraph and from then on replayed with one launch.
-    LmlLane* found = nullptr;
-    LmlLane* victim = &ctx->lml_lane[0];
-    for (auto& e : ctx->lml_lane) {
-      if (e.seen && e.N == N && e.d == d && e.kernel == kernel && e.n_ls == n_ls && e.eval_gradient == eval_gradient &&
-          e.noise == noise && e.lanes == gl && e.group == g && e.X == ctx->lml_X && e.y == ctx->lml_y && e.K == gbase) {
-        found = &e;
-        break;
-      }
-      if ((!e.seen && victim->seen) || (e.seen == victim->seen && e.used < victim->used)) victim = &e;
+    ctx->no_lookahead = groups.n_groups > 1;
+    Model m;     // a view of the group's first lane (not owning)
+    m.N = N; m.NP = NP; m.d = d; m.DP = pad_dim(d); m.kernel = kernel; m.precision = GPBO_F64; m.noise = noise;
+    const auto buf = model_buffers(m);
+    for (int i = 0; i < FB_MODEL_COUNT; ++i) *buf[i] = gbase + slab.off[i];
+    // theta enters through the pinned length-scale words ([lane][64]) that the sequence's first copy reads
+    for (int l = 0; l < ctx->lanes; ++l) stage_length_scales(ctx->pinned, l, length_scales + (int64_t)(l0 + l) * n_ls, n_ls, d);
+    const LmlKey key = lml_lane_key(ctx, m, n_ls, eval_gradient, g, gbase);
+    LmlLane& e = lml_lane_find(ctx, key);
+    const bool graph = e.seen && graph_eligible(tier_of(m));      // from the second sighting on
+    if (!graph && e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; }
+    if (graph && !e.exec && graphs_allowed && !ctx->lml_graph_off) lml_lane_capture(ctx, e, g, m, n_ls, eval_gradient);
+    if (graph && e.exec) {
+      GPBO_HIP(ctx, hipGraphLaunch(e.exec, ctx->stream));
+      continue;
     }
-    const bool same = found != nullptr;
-    LmlLane& key = same ? *found : *victim;
-    if (!same) {
-      if (key.exec) { (void)hipGraphExecDestroy(key.exec); key.exec = nullptr; }
-      key.seen = false;
-    }
-    key.used = ++ctx->lml_lane_clock;
-    bool launched = false;
-    if (same && key.exec && !no_graph) {
-      hipError_t e = hipGraphLaunch(key.exec, ctx->stream);
-      if (e != hipSuccess) { restore(); GPBO_HIP(ctx, e); }
-      launched = true;
-    } else {
-      if (key.exec) { (void)hipGraphExecDestroy(key.exec); key.exec = nullptr; }
-      if (same && graphs_allowed && !ctx->lml_graph_off && !no_graph) {
-        hipGraph_t graph = nullptr;
-        double* oh = nullptr; int* ih = nullptr;
-        hipError_t e;
-        int crc = GPBO_ERR_HIP;
-        bool instantiated = false;
-        {
-          // Captures of different contexts (the lanes of a device group run on one thread per device) are taken one at a
-          // time, process-wide: concurrent captures were seen to invalidate each other on this runtime
-          // (tests/test_gpu_sharded.py, three virtual ranks).  A capture is ~1 ms of host work once per problem shape.
-          std::unique_lock<std::shared_mutex> capture_lock(g_capture_mu);
-          e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-          if (e == hipSuccess) {
-            crc = enqueue(&oh, &ih);
-            e = hipStreamEndCapture(ctx->stream, &graph);
-          }
-          instantiated = e == hipSuccess && crc == GPBO_OK && graph &&
-                         hipGraphInstantiate(&key.exec, graph, nullptr, nullptr, 0) == hipSuccess && key.exec;
-        }
-        if (instantiated) {
-          (void)hipGraphDestroy(graph);
-          e = hipGraphLaunch(key.exec, ctx->stream);
-          if (e != hipSuccess) { restore(); GPBO_HIP(ctx, e); }
-          launched = true;
-        } else {   // capture is not available for this sequence on this runtime: direct launches from now on
-          if (graph) (void)hipGraphDestroy(graph);
-          if (key.exec) { (void)hipGraphExecDestroy(key.exec); key.exec = nullptr; }
-          (void)hipGetLastError();
-          ctx->lml_graph_off = true;
-          // an invalidated capture can outlive hipStreamEndCapture on this runtime: the direct launches below need a live stream
-          hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-          if (hipStreamIsCapturing(ctx->stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            hipStream_t fresh = nullptr;
-            if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) == hipSuccess) {
-              drop_lookahead(ctx, ctx->lml_stream[g]);
-              (void)hipStreamDestroy(ctx->lml_stream[g]);
-              ctx->lml_stream[g] = fresh;
-              ctx->stream = fresh;
-            }
-          }
-        }
-      }
-    }
-    if (!launched) {
-      double* oh = nullptr; int* ih = nullptr;
-      rc = enqueue(&oh, &ih);
-      key.seen = (rc == GPBO_OK);
-      key.N = N; key.d = d; key.kernel = kernel; key.n_ls = n_ls; key.eval_gradient = eval_gradient; key.noise = noise;
-      key.lanes = gl; key.group = g; key.X = ctx->lml_X; key.y = ctx->lml_y; key.K = gbase;
-    }
+    double* oh = nullptr; int* ih = nullptr;
+    rc = enqueue_lml(ctx, m, nullptr, nullptr, ctx->lml_X, ctx->lml_y, noise, n_ls, eval_gradient, &oh, &ih);
+    e.key = key;
+    e.seen = (rc == GPBO_OK);
   }
-  restore();
-  for (int g = 0; g < n_groups; ++g) {
-    hipError_t e = hipStreamSynchronize(ctx->lml_stream[g]);
-    if (e != hipSuccess && rc == GPBO_OK) GPBO_HIP(ctx, e);
+  for (int g = 0; g < groups.n_groups; ++g) {
+    hipError_t err = hipStreamSynchronize(ctx->lml_stream[g]);
+    if (err != hipSuccess && rc == GPBO_OK) GPBO_HIP(ctx, err);
   }
   if (rc) return rc;
   for (int i = 0; i < n_theta; ++i) {
-    const int g = i / per_group, l = i - g * per_group;
-    const int gl = std::min(per_group, n_theta - g * per_group);
-    const char* window = (const char*)ctx->pinned + PIN_LANE_WINDOW * (size_t)(1 + g);
-    const char* out_h = window + (gl == 1 ? PIN_LML_OUT : PIN_LANE_OUT);      // where lml_tail / factor_resident put the
-    const char* info_h = window + (gl == 1 ? PIN_INFO : PIN_LANE_INFO);    // results (single / lane mode)
+    const int g = i / groups.per_group;
+    const PinLane h = pin_lane(pin_window(ctx, 1 + g), i - g * groups.per_group);
     if (info) info[i] = 0;
-    lml_finish((const double*)(out_h + (size_t)l * PIN_OUT_PITCH), (const int*)(info_h + (size_t)l * PIN_INFO_PITCH), N,
-               n_ls, eval_gradient, lml + i, eval_gradient ? grad + (size_t)i * n_ls : nullptr, info ? info + i : nullptr);
+    lml_finish(h.out, h.info, N, n_ls, eval_gradient, lml + i, eval_gradient ? grad + (size_t)i * n_ls : nullptr, info ? info + i : nullptr);
   }
   return GPBO_OK;
 }
@@ -1035,7 +949,7 @@ int gpbo_get_K(gpbo_ctx* ctx, int slot, double* out) {
   // device-resident scaled inputs (same kernel, same bits)
   Model& m = ctx->models[slot];
   m.wt_valid = false;
-  if ((rc = use_mid(m) ? launch_kmat_q(ctx, m, m.noise, m.K) : launch_kmat(ctx, m, m.noise, m.K))) return rc;   // the fit's own kernel
+  if ((rc = tier_of(m) == FitTier::Strip ? launch_kmat_q(ctx, m, m.noise, m.K) : launch_kmat(ctx, m, m.noise, m.K))) return rc;   // the fit's own kernel
   return copy_square(ctx, m, m.K, out, 0);
 }
 int gpbo_get_L(gpbo_ctx* ctx, int slot, double* out) {
@@ -1234,7 +1148,7 @@ int gpbo_debug_cholesky(gpbo_ctx* ctx, const double* A, int64_t n, int variant, 
     (void)hipMemcpyAsync(m.L, m.K, sq, hipMemcpyDeviceToDevice, ctx->stream);
     (void)hipMemsetAsync(ctx->info_dev, 0, sizeof(int), ctx->stream);
     (void)hipEventRecord(e0, ctx->stream);
-    rc = launch_cholesky128(ctx, m, chol_outer_width(m.NP), it == iters - 1 ? stamps_dev : nullptr);   // stamps: the last (warm) run
+    rc = cholesky(ctx, m, it == iters - 1 ? stamps_dev : nullptr);   // stamps: the last (warm) run
     (void)hipEventRecord(e1, ctx->stream);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return done(GPBO_ERR_HIP);
     float ms = 0.f;

@@ -13,11 +13,11 @@
 #include <type_traits>
 
 #include "gpbo.h"
+#include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 
 namespace gpbo {
 
-constexpr int NB = 64;          // Cholesky / inverse block size (one MFMA GEMM tile edge)
 constexpr int POST_BK = 16;     // train points (k) per LDS stage of the fp64 kernels
 
 enum TimingSlot {
@@ -63,13 +63,20 @@ struct Model {
 // gpbo_lml_batch, per lane group it has run: the problem shape and, from the second run on, the captured launch sequence.  A pool
 // looked up by the whole key: the lanes of a call are dealt to groups by their number (gpbo_api.hip), and a theta search's rounds
 // come with 6, 6, 5, 3, 2, 1, 1 ... live runs — every grouping it passes through keeps its graphs.
-struct LmlLane {
-  hipGraphExec_t exec = nullptr;
-  bool seen = false;
+struct LmlKey {
   int64_t N = 0;
   int d = 0, kernel = 0, n_ls = 0, eval_gradient = 0, lanes = 0, group = 0;
   double noise = 0.0;
-  const void* X = nullptr; const void* y = nullptr; const void* K = nullptr;
+  const void* X = nullptr; const void* y = nullptr; const void* K = nullptr;   // the resident inputs and the group's slab
+  bool operator==(const LmlKey& o) const {
+    return N == o.N && d == o.d && kernel == o.kernel && n_ls == o.n_ls && eval_gradient == o.eval_gradient && noise == o.noise &&
+           lanes == o.lanes && group == o.group && X == o.X && y == o.y && K == o.K;
+  }
+};
+struct LmlLane {
+  LmlKey key;
+  hipGraphExec_t exec = nullptr;
+  bool seen = false;      // the key's sequence has been launched directly once: the next sighting captures it
   uint64_t used = 0;      // the pool's clock at its last use (the least recently used entry is the one replaced)
 };
 constexpr int LML_GRAPH_POOL = 24;
@@ -147,7 +154,7 @@ struct gpbo_ctx {
   void* red = nullptr;     // reduction scratch
   int64_t cap_red = 0;
   int* info_dev = nullptr; // potrf info word
-  void* pinned = nullptr;  // pinned host staging: window 0 = fit/LML words (PIN_* below), windows 1..8 = gpbo_lml_batch groups
+  void* pinned = nullptr;  // pinned host staging: window 0 = fit/LML words (PIN_* below), windows 1..8 = gpbo_fit_begin slots / gpbo_lml_batch groups
   void* pinned_base = nullptr;      // the allocation `pinned` points into (never re-pointed) and the address the device sees it at:
   char* pinned_base_dev = nullptr;  // fused_small.hip reads length scales from it and writes pivot word / LML scalars into it
   void* fused_stage = nullptr;      // pinned: X / y of a small host-side fit per window (FUSED_STAGE_BYTES each), read by the fused kernel
@@ -184,10 +191,6 @@ namespace gpbo {
 constexpr size_t SMALL_PIN_IN = 128 * 1024, SMALL_PIN_OUT = 32 * 1024;   // bytes: candidates in; mu, sd out (each)
 constexpr size_t SMALL_PIN_BYTES = SMALL_PIN_IN + 2 * SMALL_PIN_OUT;
 constexpr unsigned ATTR_GEMM128 = 4u, ATTR_CHOL128 = 16u, ATTR_FUSED = 32u, ATTR_MID = 64u, ATTR_KINV_GRAD = 128u, ATTR_POLISH_FUSED = 256u, ATTR_GEMM_FAT = 512u, ATTR_EVOLVE = 2048u;
-// fused_small.hip: the whole fit / LML evaluation of a problem of NP <= fused_max_np() as one launch of one workgroup per model
-constexpr int FUSED_NP_DEFAULT = 64, FUSED_NP_CAP = 512;
-// mid_fit.hip: fused_max_np() < NP <= mid_max_np(): the strip algorithms, ~15 launches
-constexpr int MID_NP_DEFAULT = 768, MID_NP_CAP = 1024;
 // the local searches of gpbo_polish_seeds as one launch (polish_fused.hip): up to this padded size, one model — the kernel's own
 // limit: at N = 512 the launch still beats the lockstep rounds (profiles/r06_polish_fused_ab.json: 0.36-0.48 against 0.53-0.59 ms for
 // 8-10 evaluations, 2.09 against 2.13 for 48)
@@ -199,20 +202,31 @@ constexpr size_t FUSED_STAGE_BYTES = ((size_t)STAGE_NP_CAP * GPBO_MAX_DIM + STAG
 
 // ---- pinned host staging layout -------------------------------------------------------------------------------
 // ONE allocation of PIN_WINDOWS windows of PIN_WINDOW bytes.  Window 0 (ctx->pinned) carries the words of a fit /
-// LML evaluation; gpbo_lml_batch re-points ctx->pinned at windows 1..GPBO_LML_BATCH_MAX for its groups (their own
-// sub-layout, PIN_LANE_* in gpbo_api.hip); the LAST window (ctx->pinned_aux) belongs to the selection and candidate
-// entry points, so that no two subsystems share a byte whatever stays in flight.
+// LML evaluation; gpbo_fit_begin re-points ctx->pinned at window 1 + slot and gpbo_lml_batch at windows
+// 1..GPBO_LML_BATCH_MAX for its groups (LaunchScope below); the LAST window (ctx->pinned_aux) belongs to the selection
+// and candidate entry points, so that no two subsystems share a byte whatever stays in flight.
 constexpr size_t PIN_WINDOW = 16384;
 constexpr int PIN_WINDOWS = 2 + GPBO_LML_BATCH_MAX;
-// window 0
-constexpr size_t PIN_LS = 0;                                         // [GPBO_MAX_DIM] doubles: length scales
-constexpr size_t PIN_LS_BYTES = GPBO_MAX_DIM * sizeof(double);
-constexpr size_t PIN_INFO = 1024;                                    // potrf info word
-constexpr size_t PIN_LML_OUT = 2048;                                 // yT alpha, sum log L_ii, gradient[GPBO_MAX_DIM]
-constexpr size_t PIN_LML_OUT_BYTES = (2 + GPBO_MAX_DIM) * sizeof(double);
-static_assert(PIN_LS + PIN_LS_BYTES <= PIN_INFO, "length scales overlap the info word");
-static_assert(PIN_INFO + sizeof(int) <= PIN_LML_OUT, "info word overlaps the LML scalars");
-static_assert(PIN_LML_OUT + PIN_LML_OUT_BYTES <= PIN_WINDOW, "LML scalars leave the window");
+// every window but the last, one layout: per lane the length scales at +0, the potrf info words at PIN_LANE_INFO, the LML
+// scalars (yT alpha, sum log L_ii, gradient[GPBO_MAX_DIM]) at PIN_LANE_OUT.  A single fit or evaluation is lane 0.
+constexpr size_t PIN_LS_PITCH = GPBO_MAX_DIM * sizeof(double);
+constexpr size_t PIN_INFO_PITCH = 8;
+constexpr size_t PIN_OUT_PITCH = (2 + GPBO_MAX_DIM) * sizeof(double);
+constexpr size_t PIN_LANE_INFO = 4096, PIN_LANE_OUT = 8192;
+static_assert(GPBO_LML_BATCH_MAX * PIN_LS_PITCH <= PIN_LANE_INFO, "lane length scales overlap the lane info words");
+static_assert(PIN_LANE_INFO + GPBO_LML_BATCH_MAX * PIN_INFO_PITCH <= PIN_LANE_OUT, "lane info words overlap the lane LML scalars");
+static_assert(PIN_LANE_OUT + GPBO_LML_BATCH_MAX * PIN_OUT_PITCH <= PIN_WINDOW, "lane LML scalars leave the window");
+// the address the device sees a word of the pinned window allocation at
+template <typename T>
+T* pinned_dev(const gpbo_ctx* ctx, T* host) { return (T*)(ctx->pinned_base_dev + ((const char*)host - (const char*)ctx->pinned_base)); }
+inline void* pin_window(const gpbo_ctx* ctx, int w) { return (char*)ctx->pinned_base + PIN_WINDOW * (size_t)w; }
+// lane l's words in a window (host addresses; the kernels take pinned_dev() of lane 0's and the pitches)
+struct PinLane { double* ls; int* info; double* out; };
+inline PinLane pin_lane(void* window, int l = 0) {
+  char* w = (char*)window;
+  return {(double*)(w + (size_t)l * PIN_LS_PITCH), (int*)(w + PIN_LANE_INFO + (size_t)l * PIN_INFO_PITCH),
+          (double*)(w + PIN_LANE_OUT + (size_t)l * PIN_OUT_PITCH)};
+}
 // aux window
 constexpr size_t PIN_AUX_SEL_OUT = 256;                              // SelState + picks[GPBO_MAX_SEEDS + 1] coming back
 constexpr size_t PIN_AUX_SEL_OUT_BYTES = 32 + 16 * (GPBO_MAX_SEEDS + 1);
@@ -222,6 +236,30 @@ static_assert(PIN_AUX_SEL_OUT + PIN_AUX_SEL_OUT_BYTES <= PIN_AUX_CAND, "selectio
 constexpr size_t PIN_AUX_NEGVAR = 8192;                              // int: a finalize kernel clipped a NEGATIVE variance (_gpr.py:479-485)
 static_assert(PIN_AUX_CAND + PIN_AUX_CAND_BYTES <= PIN_AUX_NEGVAR, "candidate staging overlaps the clipped-variance flag");
 static_assert(PIN_AUX_NEGVAR + sizeof(int) <= PIN_WINDOW, "clipped-variance flag leaves the window");
+
+// The context's launch state — where the fit / LML launchers enqueue, stage and reduce, and for how many lanes — saved on
+// construction and put back on destruction: gpbo_fit_begin and the lane groups of gpbo_lml_batch point it at a stream, a pinned
+// window and scratch of their own for the duration of an enqueue, and every exit from that scope leaves the context as it was.
+struct LaunchScope {
+  gpbo_ctx* const ctx;
+  const hipStream_t stream;
+  void* const pinned;
+  int* const info_dev;
+  void* const red;
+  const int64_t cap_red;
+  const int lanes;
+  const int64_t lane_stride;
+  const bool no_timing, no_lookahead;
+  explicit LaunchScope(gpbo_ctx* c)
+      : ctx(c), stream(c->stream), pinned(c->pinned), info_dev(c->info_dev), red(c->red), cap_red(c->cap_red), lanes(c->lanes),
+        lane_stride(c->lane_stride), no_timing(c->no_timing), no_lookahead(c->no_lookahead) {}
+  LaunchScope(const LaunchScope&) = delete;
+  LaunchScope& operator=(const LaunchScope&) = delete;
+  ~LaunchScope() {
+    ctx->stream = stream; ctx->pinned = pinned; ctx->info_dev = info_dev; ctx->red = red; ctx->cap_red = cap_red;
+    ctx->lanes = lanes; ctx->lane_stride = lane_stride; ctx->no_timing = no_timing; ctx->no_lookahead = no_lookahead;
+  }
+};
 
 void set_global_error(const std::string& s);
 
@@ -236,6 +274,8 @@ inline const char* dbg_env(const char* name) { return getenv(name); }
 #else
 inline const char* dbg_env(const char*) { return nullptr; }
 #endif
+// a debug switch's number for the rules of fit_plan.h: env_override(dbg_env("GPBO_..."))
+inline int env_override(const char* e) { return e ? atoi(e) : NO_OVERRIDE; }
 
 #define GPBO_HIP(ctx, expr)                                                                  \
   do {                                                                                       \

@@ -396,16 +396,8 @@ __global__ __launch_bounds__(256) void alpha_strip_kernel(const double* __restri
   if (s == 0 && tid == 0 && info_out) info_out[(int64_t)blockIdx.y * info_pitch] = info[lo * 2];
 }
 
-// Largest padded size the strip path serves (fused_max_np() < NP <= mid_max_np()).  The strip's LDS image caps it at 1024; the
-// default (768) is where one lane stops beating the multi-launch path (profiles/r05_small_fit_timing.json: fit 0.31 vs 0.39 ms at
-// 768, 0.44 vs 0.49 at 1024 but a resident lane 0.52 vs 0.51 there).  (Debug build:
-// GPBO_MID_MAX_NP = 0 ... 1024 read per call, for the A/B tests and the crossover measurement.)
-int mid_max_np() {
-  int v = MID_NP_DEFAULT;
-  if (const char* e = dbg_env("GPBO_MID_MAX_NP")) v = atoi(e);
-  if (v > MID_NP_CAP) v = MID_NP_CAP;
-  return v;
-}
+// Largest padded size the strip path serves (fit_plan.h: the default, the cap and the measurement behind them).
+int mid_max_np() { return mid_max_from(env_override(dbg_env("GPBO_MID_MAX_NP"))); }
 
 int launch_w_strip(gpbo_ctx* ctx, Model& m, bool pack) {
   if (!(ctx->func_attrs & ATTR_MID)) {
