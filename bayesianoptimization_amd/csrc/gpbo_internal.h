@@ -98,6 +98,7 @@ struct LookAhead {
 
 struct gpbo_ctx {
   int device = 0;
+  int compute_units = 0;   // of the device, asked once (launch_posterior_slab_i8: the slab width that fills them)
   hipStream_t stream = nullptr;
   std::string err;
   gpbo::Model models[GPBO_MAX_MODELS];

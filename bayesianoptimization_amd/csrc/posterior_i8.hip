@@ -202,20 +202,19 @@ __global__ __launch_bounds__(256, 1) void posterior_i8_kernel(I8Args p) {
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------------
-// SlabI8 (posterior_plan.h): the slab walk of launch_posterior_slab, but the slab is S bytes per element and sized so that the
-// 32 row chunks re-read it from the 256 MB Infinity Cache rather than from HBM (GPBO_KSTAR_GB still caps it).
-// C3 posterior pass per slab size (debug build, GPBO_I8_SLAB_MB): 128 MB 204.4 ms (241 slab pairs: the generation kernel's grid
-// of 272 workgroups leaves the chip half idle), 256 MB 196.6, 512 MB 211.1, 1 GB 211.0, 2 GB 215.5, 4 GB 216.0 (the re-reads
-// miss the cache).
+// SlabI8 (posterior_plan.h): the slab walk of launch_posterior_slab, but the slab is S bytes per element and its width comes from
+// i8_slab_width: small enough that the 32 row chunks re-read it from the 256 MB Infinity Cache rather than from HBM, and such that
+// the generation's grid ends with the device's compute units full (GPBO_KSTAR_GB still caps it).  The byte bound I8_SLAB_BYTES is
+// a constant of the rule: the debug build's slab-size switch (GPBO_I8_SLAB_MB, which produced the table quoted there) went with
+// the plain byte rule, so another bound is probed by rebuilding.
 int launch_posterior_slab_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
   if (m.NP > I8_NP_MAX || m.NP % 64) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: the int8 GEMM serves NP <= 16384");
   int rc;
   if (!m.wd_valid && (rc = pack_wd(ctx, m))) return rc;
   const int64_t per_cand = m.NP * I8_S;          // bytes of one candidate's digit planes
-  const char* sm = dbg_env("GPBO_I8_SLAB_MB");      // debug build: slab size A/B
-  const int64_t mb = (int64_t)((sm && atof(sm) > 0.0) ? atof(sm) : 256.0);
-  // no cap: the kernel's buffer offsets start at its own candidate tile; below 128 candidates the walk still takes 128
-  const int64_t ms = std::max<int64_t>(kstar_slab_width(ctx, Mp, per_cand, INT64_MAX, mb * 1000 * 1000 / per_cand), 128);
+  if (!ctx->compute_units) GPBO_HIP(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  // no cap: the kernel's buffer offsets start at its own candidate tile
+  const int64_t ms = i8_slab_width(m.NP, per_cand, kstar_slab_width(ctx, Mp, per_cand, INT64_MAX), ctx->compute_units);
   if ((rc = ensure(ctx, &ctx->kst, &ctx->cap_kst, (ms * per_cand + 7) / 8))) return rc;
   for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
     const int64_t ldk = (Mp - m0 < ms) ? (Mp - m0) : ms;

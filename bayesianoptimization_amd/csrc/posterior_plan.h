@@ -41,6 +41,41 @@ inline bool f32_use_mfma32(int64_t NP) { return NP >= POST_ROWS_WIDE; }
 // batch it comes in; the int32 level sums bound NP from above.
 inline bool posterior_i8_serves(int64_t NP) { return NP >= I8_NP_MIN && NP <= I8_NP_MAX; }
 
+// SlabI8's slab width in candidates (one launch of kstar_gen_kernel<.., DIG> + one of the int8 GEMM per slab), from NP, the bytes of
+// one candidate's digit planes (NP x S), the width the workspace budget grants (kstar_slab_width: a multiple of 128, <= Mp) and the
+// device's compute units.
+// Two things bound it.  The GEMM's 32 row chunks re-read the slab, so it has to stay in the 256 MB Infinity Cache (C3 pass per slab
+// size, measured with the plain byte rule: 128 MB 204.4 ms, 256 MB 196.6, 512 MB 211.1, 1 GB 211.0, 4 GB 216.0).  And the generation's
+// grid should end with the chip full: it launches ceil(width / 256) x ceil(NP / 256) equal workgroups at 1.3 - 1.5 waves per SIMD and
+// lasts as long as the CUs that get one more than the others.  Below the byte bound, down to half of it, the rule takes the width (a
+// multiple of 256) whose generation grid fills the largest share of its last round over the compute units, the widest one among
+// equals.  The GEMM's grid (ceil(NP / 128) x width / 64 workgroups, one per CU) is 8 times the generation's when NP is a multiple of
+// 256 and then ends full with it; its workgroups are of unequal cost (triangular, heaviest first), so for it "full" is an
+// approximation, and at other NP (2112: 17 x 224 = 14.9 per CU) the rule does not look at it at all.
+// C3 (NP = 4096, 16 chunks): 8928 candidates fit; 8832 (the plain multiple of 128) is 35 x 16 = 560 workgroups = 0.73 of three rounds,
+// 8192 is 512 = exactly two.  Measured on one MI355X, plain rule -> this one, profiles/i8_lds_ab.json:
+//   C3 kernel totals per pass, three alternating traced runs of 25 passes per arm (medians; ranges 0.15 / 0.15 and 0.86 / 0.53):
+//     generation 23.15 -> 18.54 ms, GEMM 174.45 -> 171.76 ms (every run of the new arm below every run of the old one);
+//     bench.py C3 on another box, three runs per arm: 193.5 -> 186.2 ms per step.
+//   Posterior pass (M = 2^20, d = 16, medians of three), width and ms: NP = 1536: 23 808 -> 21 760, 35.9 -> 34.3;
+//     2048: 17 792 -> 16 384, 57.2 -> 55.4;  2112 (9 chunks: 17 % more launches): 17 280 -> 14 336, 61.1 -> 59.8;
+//     3072: 11 904 -> 10 752, 116.8 -> 113.2;  4096: 8832 -> 8192, 197.1 -> 189.4.
+// Generating four slabs per launch instead (C3: 35 328 candidates, the GEMM walking sub-slabs of 8832) took the generation to 15.3 ms
+// but cost the GEMM 4.9 ms: every sub-slab's first row chunk then reads its digits from HBM.
+constexpr int64_t I8_SLAB_BYTES = 256 * 1000 * 1000;
+inline int64_t i8_slab_width(int64_t NP, int64_t bytes_per_cand, int64_t granted, int64_t compute_units) {
+  const int64_t chunks = (NP + POST_ROWS - 1) / POST_ROWS;
+  const int64_t kmax = I8_SLAB_BYTES / bytes_per_cand / 256;
+  int64_t width = I8_SLAB_BYTES / bytes_per_cand / 128 * 128;   // less than 256 candidates fit: the plain multiple of 128
+  int64_t best_wgs = 0, best_cap = 1;
+  for (int64_t k = kmax; k >= 1 && 2 * k > kmax; --k) {
+    const int64_t wgs = k * chunks, cap = (wgs + compute_units - 1) / compute_units * compute_units;
+    if (wgs * best_cap > best_wgs * cap) { best_wgs = wgs; best_cap = cap; width = 256 * k; }
+  }
+  if (granted < width) width = granted;
+  return width < 128 ? 128 : width;   // below 128 candidates the walk still takes 128
+}
+
 // The rule: plan_posterior, first match wins (nchunks = 256-row chunks, Mp = M padded to 128, the GEMV limit small_batch_limit).
 // Why.  The slab route as soon as k* would be generated more than once: the fp64 VALU work of the generation runs instead of
 // MFMAs, not beside them, and the slab GEMM's loop carries no other VALU work.  For 384 <= NP <= 512 and a batch that fills the
