@@ -35,7 +35,7 @@ SOURCES = {
     "posterior_i8.hip": [],                    # the slab GEMM on int8 matrix cores (fixed-point digit planes, exact level sums)
     "posterior_small.hip": [],
     "polish.hip": [],                          # gpbo_polish_seeds: the local-search stage as one C call (host optimiser, device evaluations)
-    "polish_fused.hip": [],                    # ... and as one launch for NP <= 512: one workgroup per local search (NP <= 128: thread = training point), evaluations + optimiser inside
+    "polish_fused.hip": [],                    # ... and as one launch for NP <= 512: one workgroup per local search (thread = training point; W in LDS up to NP = 128, streamed above: search_plan.h), evaluations + optimiser inside
     "evolve.hip": ["-ffp-contract=off"],     # gpbo_evolve_mixed: the mixed-space differential evolution as one workgroup (scaling and mutation round as NumPy)
     "posterior_kernel_f32.hip": [],
     "posterior_cov.hip": [],

@@ -18,7 +18,7 @@
 //              most maxiter generations (success = false)
 // The objective at a trial x: TargetSpace.kernel_transform per column group (identity / rint / one-hot at the first argmax, row-local for
 // one row), the posterior of slot 0 with thread = training point (posterior_rows.h, the evaluation of polish_fused.hip: W in LDS for
-// NP <= 128 when it fits, its transposed copy streamed from memory up to 512), then -base_acq(mu, sd) with the acquisition kernels'
+// NP <= 128 when it fits, its transposed copy streamed from memory up to 512: search_plan.h's plan_evolve), then -base_acq(mu, sd) with the acquisition kernels'
 // formulas (acq_formulas.h).  Values agree with the host's objective to rounding; the walk is the host solver's as long as no
 // comparison of two energies falls within that rounding.
 // Wave 0 runs the solver (every lane the same uniform steps; lane t holds coordinate t); the state — population, energies, index
@@ -37,14 +37,7 @@ namespace gpbo {
 
 namespace {
 
-constexpr int EV_LDS_NP = 128;           // W in LDS up to here (when it fits beside the solver's state)
-constexpr int EV_MAX_NP = 512;
-constexpr int EV_MAX_S = 1024;
-constexpr size_t EV_LDS_CAP = 160 * 1024;
-
 enum EvPhase { PH_PASS = 0, PH_GEN = 1, PH_SCALE = 2, PH_CAND = 3, PH_DONE = 4 };
-// integer state words in device memory
-enum EvInt { I_POS = 0, I_PHASE, I_EV, I_THEN, I_C, I_NIT, I_NFEV, I_STATUS, I_COUNT = 8 };
 
 struct EvolveArgs {
   // objective: slot 0's posterior (analytic = 0) or the debug walk's analytic sum (analytic = 1)
@@ -78,13 +71,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double ev_lane(double v, int i) {      // v of lane i (i uniform), in every lane
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), i);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), i);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
 }
 
 // ---- MT19937 on wave 0 (every lane the same value) ------------------------------------------------------------------------------
@@ -149,7 +135,7 @@ __device__ int ev_argmin(const double* E, int S, int lane) {
   for (int l = 0; l < 64; ++l) {
     const int bn = __builtin_amdgcn_readlane(nan_at, l);
     const int bi = __builtin_amdgcn_readlane(best, l);
-    const double v = ev_lane(bv, l);
+    const double v = pr_lane(bv, l);
     if (bn >= 0 && (gnan < 0 || bn < gnan)) gnan = bn;
     if (bi >= 0 && (gbest < 0 || v < gv || (v == gv && bi < gbest))) { gbest = bi; gv = v; }
   }
@@ -157,8 +143,7 @@ __device__ int ev_argmin(const double* E, int S, int lane) {
 }
 
 // NumPy's pairwise float64 sum of f(E[i]) (8 accumulators up to 128 values, halves above), uniform over wave 0.  The recursion runs
-// on an explicit stack in LDS (frames: lo, n, state; partial sums), post-order: left half, right half, left + right.
-constexpr int EV_STACK = 16;
+// on an explicit stack in LDS (EV_STACK frames: lo, n, state; partial sums), post-order: left half, right half, left + right.
 template <class F>
 __device__ double ev_pairwise(const double* E, int n0, int* frames, double* acc, F f) {
 #pragma clang fp contract(off)
@@ -264,34 +249,23 @@ __device__ double ev_analytic(const EvolveArgs& a, const double* px) {
 }
 
 template <int KERNEL, bool WLDS>
-__global__ __launch_bounds__(EV_MAX_NP) void evolve_kernel(const EvolveArgs a) {
+__global__ __launch_bounds__(SEARCH_MAX_NP) void evolve_kernel(const EvolveArgs a) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) double ev_smem[];
   const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int NP = a.analytic ? 0 : a.NP, N = a.N, D = a.D, S = a.S, DP = a.DP;
   const int WLD = NP + 1;
-  double* Wl = ev_smem;
-  double* xs = Wl + (WLDS ? NP * WLD : 0);   // [64]
-  double* ls_s = xs + 64;                    // [64]
-  double* px = ls_s + 64;                    // [64] the point in parameter space
-  double* ks = px + 64;                      // [NP]
-  double* vs = ks + NP;                      // [NP]
-  double* pp = vs + NP;                      // [2 NP]
-  double* E = pp + 2 * NP;                   // [S]
-  double* misc = E + S;                      // [8]: [0] the energy, [1] stop flag
-  double* stk_acc = misc + 8;                // [EV_STACK] partial sums of the pairwise summation
-  double* popl = stk_acc + EV_STACK;         // [S][D] when the population fits
-  unsigned* key = (unsigned*)(popl + (a.pop_lds ? (size_t)S * D : 0));      // [624]
-  int* perm = (int*)(key + 624);             // [S]
-  int* frames = perm + S;                    // [EV_STACK][3] its frames
+  const EvolveLds L = evolve_lds(NP, S, D, WLDS, a.pop_lds != 0);
+  double *Wl = ev_smem + L.W, *xs = ev_smem + L.xs, *ls_s = ev_smem + L.ls, *px = ev_smem + L.px, *ks = ev_smem + L.ks,
+         *vs = ev_smem + L.vs, *pp = ev_smem + L.pp, *E = ev_smem + L.E, *misc = ev_smem + L.misc, *stk_acc = ev_smem + L.acc,
+         *popl = ev_smem + L.pop;
+  int* const words = (int*)ev_smem;
+  unsigned* key = (unsigned*)(words + L.key);
+  int *perm = words + L.perm, *frames = words + L.frames;
   double* pop = a.pop_lds ? popl : a.pop;
 
   if (!a.analytic) {
-    if (WLDS)
-      for (int e = tid; e < NP * NP; e += NP) {
-        const int i = e / NP, k = e - i * NP;
-        Wl[i * WLD + k] = a.W[e];
-      }
+    if (WLDS) pr_load_w(Wl, a.W, NP, tid);
     if (tid < 64) ls_s[tid] = (tid < D) ? a.ls[tid] : 1.0;
   }
   const int nthr = (int)blockDim.x;
@@ -466,8 +440,8 @@ __global__ __launch_bounds__(EV_MAX_NP) void evolve_kernel(const EvolveArgs a) {
         s2 += __shfl_xor(s2, off);
         mm += __shfl_xor(mm, off);
       }
-      s2 = ev_lane(s2, 0);
-      mm = ev_lane(mm, 0);
+      s2 = pr_lane(s2, 0);
+      mm = pr_lane(mm, 0);
       double var = 1.0 - s2;
       if (var < 0.0) var = 0.0;
       const double sd = sqrt(var * (a.y_std * a.y_std));
@@ -498,194 +472,166 @@ __global__ __launch_bounds__(EV_MAX_NP) void evolve_kernel(const EvolveArgs a) {
   }
 }
 
-size_t ev_lds_bytes(int NP, int S, int D, bool wlds, bool pop_lds) {
-  return ((size_t)(wlds ? NP * (NP + 1) : 0) + 192 + 4 * (size_t)NP + S + 8 + EV_STACK + (pop_lds ? (size_t)S * D : 0)) * sizeof(double) +
-         (624 + (size_t)S + 3 * EV_STACK) * sizeof(int);
-}
+// What run_evolve is asked for.  The objective: slot 0's posterior under an acquisition (model), or — model = nullptr — the debug
+// walk's analytic sum (aw, aa, thresholds).
+struct EvolveObjective {
+  Model* model = nullptr;
+  int acq = 0;
+  double acq_param = 0.0, y_max = 0.0, y_mean = 0.0, y_std = 1.0;
+  const double *aw = nullptr, *aa = nullptr;      // (D,) weights and targets
+  double nan_below = 0.0, inf_above = 0.0;
+};
+// ... the space (column groups, bounds), the run (initial population, generations, the caller's MT19937 state) and where the result
+// goes; or eval_n > 0 (debug): the objective at eval_n points, no run.
+struct EvolveRun {
+  int n_groups = 0;
+  const int *kind = nullptr, *col0 = nullptr, *ncols = nullptr;
+  const double *lo = nullptr, *hi = nullptr, *init = nullptr;
+  int S = 0, D = 0, maxiter = 0;
+  int budget = 0;      // evaluations per launch of the analytic objective (a model: the plan's): a launch ends at the first candidate boundary after them
+  unsigned* key = nullptr;
+  int* pos = nullptr;
+  double *x_out = nullptr, *f_out = nullptr;
+  int *nit_out = nullptr, *nfev_out = nullptr, *success_out = nullptr, *launches_out = nullptr;
+  const double* eval_x = nullptr;
+  int eval_n = 0;
+  double* eval_out = nullptr;
+};
 
-}  // namespace
+struct DeviceBlock {      // freed on every way out
+  char* p = nullptr;
+  ~DeviceBlock() { (void)hipFree(p); }
+};
 
-// Device side of gpbo_evolve_mixed / the debug entries.  model = nullptr: the analytic objective (aw, aa, thresholds).
-// Evaluations per launch: a launch ends at the first candidate boundary after `budget` of them.
-int run_evolve(gpbo_ctx* ctx, Model* model, int acq, double acq_param, double y_max, double y_mean, double y_std, const double* aw,
-               const double* aa, double nan_below, double inf_above, int n_groups, const int* kind, const int* col0, const int* ncols,
-               const double* lo, const double* hi, const double* init, int S, int D, int maxiter, int budget, unsigned* key, int* pos,
-               double* x_out, double* f_out, int* nit_out, int* nfev_out, int* success_out, const double* eval_x, int eval_n,
-               double* eval_out, int* launches_out) {
-  if (D < 1 || D > GPBO_MAX_DIM || S < 5 || S > EV_MAX_S || n_groups < 1 || n_groups > D || maxiter < 1 || budget < 1)
+// Device side of gpbo_evolve_mixed / the debug entries.
+int run_evolve(gpbo_ctx* ctx, const EvolveObjective& o, const EvolveRun& r) {
+  const int S = r.S, D = r.D, eval_n = r.eval_n;
+  Model* const model = o.model;
+  if (D < 1 || D > GPBO_MAX_DIM || S < 5 || S > EV_MAX_S || r.n_groups < 1 || r.n_groups > D || r.maxiter < 1 || (!model && r.budget < 1))
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve: D in [1, 64], S in [5, 1024], maxiter >= 1 and one group per parameter");
   std::vector<int> ck(D, -1), cg0(D, 0), cgn(D, 1);
-  for (int g = 0; g < n_groups; ++g) {
-    if (kind[g] < 0 || kind[g] > 2 || ncols[g] < 1 || col0[g] < 0 || col0[g] + ncols[g] > D)
+  for (int g = 0; g < r.n_groups; ++g) {
+    if (r.kind[g] < 0 || r.kind[g] > 2 || r.ncols[g] < 1 || r.col0[g] < 0 || r.col0[g] + r.ncols[g] > D)
       GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve: bad column group");
-    for (int t = col0[g]; t < col0[g] + ncols[g]; ++t) {
+    for (int t = r.col0[g]; t < r.col0[g] + r.ncols[g]; ++t) {
       if (ck[t] >= 0) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve: column groups overlap");
-      ck[t] = kind[g]; cg0[t] = col0[g]; cgn[t] = ncols[g];
+      ck[t] = r.kind[g]; cg0[t] = r.col0[g]; cgn[t] = r.ncols[g];
     }
   }
   for (int t = 0; t < D; ++t)
     if (ck[t] < 0) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve: the column groups leave a column out");
-  if (*pos < 0 || *pos > 624) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve: MT19937 position outside [0, 624]");
-  int mode = 0;      // 1: W in LDS, 2: W in memory
-  bool pop_lds = false;
+  if (*r.pos < 0 || *r.pos > 624) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve: MT19937 position outside [0, 624]");
   if (model) {
-    Model& m = *model;
-    if (!m.fitted || m.d != D) GPBO_FAIL(ctx, GPBO_ERR_STATE, "evolve: slot 0 is not fitted for this width");
+    if (!model->fitted || model->d != D) GPBO_FAIL(ctx, GPBO_ERR_STATE, "evolve: slot 0 is not fitted for this width");
     if (ctx->pending_info[0]) GPBO_FAIL(ctx, GPBO_ERR_STATE, "evolve: a fit of slot 0 is still in flight (gpbo_fit_wait)");
-    if (m.NP > EV_MAX_NP || m.NP > polish_fused_max_np()) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "evolve: more than 512 (padded) observations");
-    pop_lds = ev_lds_bytes((int)m.NP, S, D, m.NP <= EV_LDS_NP, true) <= EV_LDS_CAP;
-    if (m.NP <= EV_LDS_NP && ev_lds_bytes((int)m.NP, S, D, true, pop_lds) <= EV_LDS_CAP) mode = 1;
-    else {
-      pop_lds = ev_lds_bytes((int)m.NP, S, D, false, true) <= EV_LDS_CAP;
-      if (ev_lds_bytes((int)m.NP, S, D, false, pop_lds) <= EV_LDS_CAP) mode = 2;
-    }
-    if (!mode) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "evolve: the solver's state does not fit the LDS");
-  } else {
-    pop_lds = ev_lds_bytes(0, S, D, false, true) <= EV_LDS_CAP;
+  }
+  const int NP = model ? (int)model->NP : 0;
+  const EvolvePlan plan = plan_evolve(NP, S, D, search_np_override(), !model);
+  if (plan.mode == SearchMode::NotServed) {
+    if (NP > search_max_np(search_np_override())) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "evolve: more than 512 (padded) observations");
+    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "evolve: the solver's state does not fit the LDS");
   }
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
   // host-side scaling of SciPy's solver and the initial population
   std::vector<double> arg1(D), arg2(D), recip(D);
   for (int t = 0; t < D; ++t) {
-    arg1[t] = 0.5 * (lo[t] + hi[t]);
-    arg2[t] = std::fabs(lo[t] - hi[t]);
-    const double r = 1.0 / arg2[t];
-    recip[t] = std::isfinite(r) ? r : 0.0;
+    arg1[t] = 0.5 * (r.lo[t] + r.hi[t]);
+    arg2[t] = std::fabs(r.lo[t] - r.hi[t]);
+    const double rc = 1.0 / arg2[t];
+    recip[t] = std::isfinite(rc) ? rc : 0.0;
   }
-  // device block: doubles [pop S D | E S | arg1 D | arg2 D | aw D | aa D | eval_x | eval_out | scale] then ints [ist 8 | perm S | ck D |
-  // cg0 D | cgn D] then the key
-  const size_t nd = (size_t)S * D + S + 4 * (size_t)D + (size_t)eval_n * D + eval_n + 1;
-  const size_t ni = I_COUNT + (size_t)S + 3 * (size_t)D + 624;
-  const size_t bytes = nd * sizeof(double) + ni * sizeof(int);
-  std::vector<char> h(bytes);
+  // the run's block (search_plan.h): its host image, then the same layout over the device copy
+  const EvolveBlock b = evolve_block(S, D, eval_n);
+  std::vector<char> h(b.bytes);
   double* hd = (double*)h.data();
-  double* h_pop = hd;
-  double* h_E = h_pop + (size_t)S * D;
-  double* h_a1 = h_E + S;
-  double* h_a2 = h_a1 + D;
-  double* h_aw = h_a2 + D;
-  double* h_aa = h_aw + D;
-  double* h_ex = h_aa + D;
-  double* h_eo = h_ex + (size_t)eval_n * D;
-  double* h_sc = h_eo + eval_n;
-  int* hi_ = (int*)(hd + nd);
-  int* h_ist = hi_;
-  int* h_perm = h_ist + I_COUNT;
-  int* h_ck = h_perm + S;
-  int* h_cg0 = h_ck + D;
-  int* h_cgn = h_cg0 + D;
-  unsigned* h_key = (unsigned*)(h_cgn + D);
+  int* hw = (int*)h.data();
   for (int s = 0; s < S; ++s)
     for (int t = 0; t < D; ++t) {
-      const double u = (init ? (init[(size_t)s * D + t] - arg1[t]) * recip[t] + 0.5 : 0.0);
-      h_pop[(size_t)s * D + t] = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);      // np.clip: NaN stays NaN
+      const double u = (r.init ? (r.init[(size_t)s * D + t] - arg1[t]) * recip[t] + 0.5 : 0.0);
+      hd[b.pop + (size_t)s * D + t] = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);      // np.clip: NaN stays NaN
     }
-  for (int s = 0; s < S; ++s) { h_E[s] = INFINITY; h_perm[s] = s; }
+  for (int s = 0; s < S; ++s) { hd[b.E + s] = INFINITY; hw[b.perm + s] = s; }
   for (int t = 0; t < D; ++t) {
-    h_a1[t] = arg1[t]; h_a2[t] = arg2[t];
-    h_aw[t] = aw ? aw[t] : 0.0; h_aa[t] = aa ? aa[t] : 0.0;
-    h_ck[t] = ck[t]; h_cg0[t] = cg0[t]; h_cgn[t] = cgn[t];
+    hd[b.arg1 + t] = arg1[t]; hd[b.arg2 + t] = arg2[t];
+    hd[b.aw + t] = o.aw ? o.aw[t] : 0.0; hd[b.aa + t] = o.aa ? o.aa[t] : 0.0;
+    hw[b.ckind + t] = ck[t]; hw[b.cg0 + t] = cg0[t]; hw[b.cgn + t] = cgn[t];
   }
-  if (eval_n) std::copy(eval_x, eval_x + (size_t)eval_n * D, h_ex);
-  h_sc[0] = 0.0;
-  h_ist[I_POS] = *pos; h_ist[I_PHASE] = PH_PASS; h_ist[I_EV] = 0; h_ist[I_THEN] = PH_GEN; h_ist[I_C] = 0; h_ist[I_NIT] = 0;
+  if (eval_n) std::copy(r.eval_x, r.eval_x + (size_t)eval_n * D, hd + b.eval_x);
+  hd[b.scale] = 0.0;
+  int* h_ist = hw + b.ist;
+  h_ist[I_POS] = *r.pos; h_ist[I_PHASE] = PH_PASS; h_ist[I_EV] = 0; h_ist[I_THEN] = PH_GEN; h_ist[I_C] = 0; h_ist[I_NIT] = 0;
   h_ist[I_NFEV] = 0; h_ist[I_STATUS] = 0;
-  std::copy(key, key + 624, h_key);
-  char* dblock = nullptr;
-  GPBO_HIP(ctx, hipMalloc(&dblock, bytes));
-  auto release = [&]() { (void)hipFree(dblock); };
-  {
-    hipError_t e = hipMemcpyAsync(dblock, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { release(); GPBO_HIP(ctx, e); }
-  }
-  double* dd = (double*)dblock;
-  int* di = (int*)(dd + nd);
+  std::copy(r.key, r.key + 624, (unsigned*)(hw + b.key));
+  DeviceBlock dblock;
+  GPBO_HIP(ctx, hipMalloc(&dblock.p, b.bytes));
+  GPBO_HIP(ctx, hipMemcpyAsync(dblock.p, h.data(), b.bytes, hipMemcpyHostToDevice, ctx->stream));
+  double* dd = (double*)dblock.p;
+  int* dw = (int*)dblock.p;
   EvolveArgs a{};
   a.analytic = model ? 0 : 1;
-  a.D = D; a.S = S; a.maxiter = maxiter; a.budget = budget;
-  a.pop = dd; a.energies = dd + (size_t)S * D; a.arg1 = a.energies + S; a.arg2 = a.arg1 + D; a.aw = a.arg2 + D; a.aa = a.aw + D;
-  a.eval_x = a.aa + D; a.eval_out = (double*)a.eval_x + (size_t)eval_n * D; a.scale = a.eval_out + eval_n;
-  a.ist = di; a.perm = di + I_COUNT; a.ckind = a.perm + S; a.cg0 = a.ckind + D; a.cgn = a.cg0 + D;
-  a.mt = (unsigned*)(a.cgn + D);
+  a.D = D; a.S = S; a.maxiter = r.maxiter; a.budget = model ? plan.evals_per_launch : r.budget;
+  a.pop = dd + b.pop; a.energies = dd + b.E; a.arg1 = dd + b.arg1; a.arg2 = dd + b.arg2; a.aw = dd + b.aw; a.aa = dd + b.aa;
+  a.eval_x = dd + b.eval_x; a.eval_out = dd + b.eval_out; a.scale = dd + b.scale;
+  a.ist = dw + b.ist; a.perm = dw + b.perm; a.ckind = dw + b.ckind; a.cg0 = dw + b.cg0; a.cgn = dw + b.cgn;
+  a.mt = (unsigned*)(dw + b.key);
   a.eval_n = eval_n;
-  a.nan_below = nan_below; a.inf_above = inf_above;
-  a.pop_lds = pop_lds ? 1 : 0;
-  a.acq = acq; a.acq_param = acq_param; a.y_max = y_max; a.y_mean = y_mean; a.y_std = y_std;
-  size_t lds;
+  a.nan_below = o.nan_below; a.inf_above = o.inf_above;
+  a.pop_lds = plan.pop_lds ? 1 : 0;
+  a.acq = o.acq; a.acq_param = o.acq_param; a.y_max = o.y_max; a.y_mean = o.y_mean; a.y_std = o.y_std;
   dim3 block(64);
-  int kern = 0;
   if (model) {
     Model& m = *model;
     a.W = m.W; a.Xs = m.Xs; a.alpha = m.alpha; a.ls = m.ls;
-    a.NP = (int)m.NP; a.N = (int)m.N; a.DP = m.DP;
-    kern = m.kernel;
+    a.NP = NP; a.N = (int)m.N; a.DP = m.DP;
     block = dim3((unsigned)m.NP);
-    if (mode == 2) {
-      int rc = ensure_w_transposed(ctx, m);
-      if (rc) { release(); return rc; }
+    if (plan.mode == SearchMode::WInMemory) {
+      if (const int rc = ensure_w_transposed(ctx, m)) return rc;
       a.Wt = m.K;
     }
-    lds = ev_lds_bytes((int)m.NP, S, D, mode == 1, pop_lds);
-  } else {
-    a.DP = 0;
-    lds = ev_lds_bytes(0, S, D, false, pop_lds);
   }
   if (!(ctx->func_attrs & ATTR_EVOLVE)) {
-    const void* ks[4] = {reinterpret_cast<const void*>(evolve_kernel<GPBO_KERNEL_MATERN25, true>),
-                         reinterpret_cast<const void*>(evolve_kernel<GPBO_KERNEL_RBF, true>),
-                         reinterpret_cast<const void*>(evolve_kernel<GPBO_KERNEL_MATERN25, false>),
-                         reinterpret_cast<const void*>(evolve_kernel<GPBO_KERNEL_RBF, false>)};
-    for (const void* k : ks) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EV_LDS_CAP);
-      if (e != hipSuccess) { release(); GPBO_HIP(ctx, e); }
-    }
+    const int rc = for_each_kernel_wlds([&](auto k, auto wlds) -> int {
+      GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(evolve_kernel<decltype(k)::value, decltype(wlds)::value>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, SEARCH_LDS_BYTES));
+      return GPBO_OK;
+    });
+    if (rc) return rc;
     ctx->func_attrs |= ATTR_EVOLVE;
   }
   int launches = 0;
   int st[I_COUNT];
   for (;;) {
-    if (mode == 1) {
-      if (kern == GPBO_KERNEL_MATERN25) evolve_kernel<GPBO_KERNEL_MATERN25, true><<<dim3(1), block, lds, ctx->stream>>>(a);
-      else evolve_kernel<GPBO_KERNEL_RBF, true><<<dim3(1), block, lds, ctx->stream>>>(a);
-    } else {
-      if (kern == GPBO_KERNEL_MATERN25) evolve_kernel<GPBO_KERNEL_MATERN25, false><<<dim3(1), block, lds, ctx->stream>>>(a);
-      else evolve_kernel<GPBO_KERNEL_RBF, false><<<dim3(1), block, lds, ctx->stream>>>(a);
-    }
+    with_kernel_wlds(model ? model->kernel : 0, plan.mode == SearchMode::WInLds, [&](auto k, auto wlds) -> int {
+      evolve_kernel<decltype(k)::value, decltype(wlds)::value><<<dim3(1), block, (size_t)plan.lds_bytes, ctx->stream>>>(a);
+      return GPBO_OK;
+    });
     ++launches;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(st, di, sizeof(st), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { release(); GPBO_HIP(ctx, e); }
+    GPBO_HIP(ctx, hipGetLastError());
+    GPBO_HIP(ctx, hipMemcpyAsync(st, a.ist, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (eval_n > 0 || st[I_PHASE] == PH_DONE) break;
   }
-  {
-    hipError_t e = hipMemcpy(h.data(), dblock, bytes, hipMemcpyDeviceToHost);
-    release();
-    GPBO_HIP(ctx, e);
-  }
-  if (launches_out) *launches_out = launches;
+  GPBO_HIP(ctx, hipMemcpy(h.data(), dblock.p, b.bytes, hipMemcpyDeviceToHost));
+  if (r.launches_out) *r.launches_out = launches;
   if (eval_n > 0) {
-    std::copy(h_eo, h_eo + eval_n, eval_out);
+    std::copy(hd + b.eval_out, hd + b.eval_out + eval_n, r.eval_out);
     return GPBO_OK;
   }
-  std::copy(h_key, h_key + 624, key);
-  *pos = h_ist[I_POS];
-  for (int t = 0; t < D; ++t) x_out[t] = arg1[t] + (h_pop[t] - 0.5) * arg2[t];
-  *f_out = h_E[0];
-  *nit_out = h_ist[I_NIT];
-  *nfev_out = h_ist[I_NFEV];
-  *success_out = h_ist[I_STATUS] == 1 ? 1 : 0;
+  std::copy((unsigned*)(hw + b.key), (unsigned*)(hw + b.key) + 624, r.key);
+  *r.pos = h_ist[I_POS];
+  for (int t = 0; t < D; ++t) r.x_out[t] = arg1[t] + (hd[b.pop + t] - 0.5) * arg2[t];
+  *r.f_out = hd[b.E];
+  *r.nit_out = h_ist[I_NIT];
+  *r.nfev_out = h_ist[I_NFEV];
+  *r.success_out = h_ist[I_STATUS] == 1 ? 1 : 0;
   return GPBO_OK;
 }
+
+}  // namespace
 
 }  // namespace gpbo
 
 using namespace gpbo;
-
-namespace {
-// Evaluations per launch: ~2 ms of work at the per-evaluation cost of each size band (3-6 us up to NP = 128, 16-41 us up to 512)
-int evolve_budget(const Model& m) { return m.NP <= 128 ? 384 : (m.NP <= 256 ? 96 : 48); }
-}  // namespace
 
 extern "C" int gpbo_evolve_mixed(gpbo_ctx* ctx, int acq, double acq_param, double y_max, double y_mean, double y_std, int n_groups,
                                  const int* kind, const int* col0, const int* ncols, const double* bounds_lo, const double* bounds_hi,
@@ -696,10 +642,16 @@ extern "C" int gpbo_evolve_mixed(gpbo_ctx* ctx, int acq, double acq_param, doubl
       !success_out)
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: NULL argument");
   if (acq != GPBO_ACQ_UCB && acq != GPBO_ACQ_EI && acq != GPBO_ACQ_POI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: unknown acquisition");
-  Model& m = ctx->models[0];
-  return run_evolve(ctx, &m, acq, acq_param, y_max, y_mean, y_std, nullptr, nullptr, 0.0, 0.0, n_groups, kind, col0, ncols, bounds_lo,
-                    bounds_hi, init, S, D, maxiter, m.fitted ? evolve_budget(m) : 1, key, pos, x_out, f_out, nit_out, nfev_out,
-                    success_out, nullptr, 0, nullptr, nullptr);
+  EvolveObjective o;
+  o.model = &ctx->models[0];
+  o.acq = acq; o.acq_param = acq_param; o.y_max = y_max; o.y_mean = y_mean; o.y_std = y_std;
+  EvolveRun r;
+  r.n_groups = n_groups; r.kind = kind; r.col0 = col0; r.ncols = ncols;
+  r.lo = bounds_lo; r.hi = bounds_hi; r.init = init;
+  r.S = S; r.D = D; r.maxiter = maxiter;
+  r.key = key; r.pos = pos;
+  r.x_out = x_out; r.f_out = f_out; r.nit_out = nit_out; r.nfev_out = nfev_out; r.success_out = success_out;
+  return run_evolve(ctx, o, r);
 }
 
 #ifdef GPBO_DEBUG
@@ -709,11 +661,17 @@ extern "C" int gpbo_debug_evolve_eval(gpbo_ctx* ctx, int acq, double acq_param, 
   if (!ctx || !kind || !col0 || !ncols || !points || !out || n < 1) return GPBO_ERR_INVALID;
   std::vector<double> lo(D, 0.0), hi(D, 1.0);
   unsigned key[624] = {};
-  int pos = 624, nit = 0, nfev = 0, ok = 0;
-  double x[GPBO_MAX_DIM], f;
-  Model& m = ctx->models[0];
-  return run_evolve(ctx, &m, acq, acq_param, y_max, y_mean, y_std, nullptr, nullptr, 0.0, 0.0, n_groups, kind, col0, ncols, lo.data(),
-                    hi.data(), nullptr, 5, D, 1, 1, key, &pos, x, &f, &nit, &nfev, &ok, points, n, out, nullptr);
+  int pos = 624;
+  EvolveObjective o;
+  o.model = &ctx->models[0];
+  o.acq = acq; o.acq_param = acq_param; o.y_max = y_max; o.y_mean = y_mean; o.y_std = y_std;
+  EvolveRun r;      // the smallest legal run around the points: nothing of it is stepped
+  r.n_groups = n_groups; r.kind = kind; r.col0 = col0; r.ncols = ncols;
+  r.lo = lo.data(); r.hi = hi.data();
+  r.S = 5; r.D = D; r.maxiter = 1;
+  r.key = key; r.pos = &pos;
+  r.eval_x = points; r.eval_n = n; r.eval_out = out;
+  return run_evolve(ctx, o, r);
 }
 
 extern "C" int gpbo_debug_evolve_walk(gpbo_ctx* ctx, const double* weights, const double* targets, double nan_below, double inf_above,
@@ -724,8 +682,14 @@ extern "C" int gpbo_debug_evolve_walk(gpbo_ctx* ctx, const double* weights, cons
   if (!ctx || !weights || !targets || !kind || !col0 || !ncols || !bounds_lo || !bounds_hi || !init || !key || !pos || !x_out ||
       !f_out || !nit_out || !nfev_out || !success_out)
     return GPBO_ERR_INVALID;
-  return run_evolve(ctx, nullptr, 0, 0.0, 0.0, 0.0, 1.0, weights, targets, nan_below, inf_above, n_groups, kind, col0, ncols, bounds_lo,
-                    bounds_hi, init, S, D, maxiter, budget, key, pos, x_out, f_out, nit_out, nfev_out, success_out, nullptr, 0, nullptr,
-                    launches_out);
+  EvolveObjective o;
+  o.aw = weights; o.aa = targets; o.nan_below = nan_below; o.inf_above = inf_above;
+  EvolveRun r;
+  r.n_groups = n_groups; r.kind = kind; r.col0 = col0; r.ncols = ncols;
+  r.lo = bounds_lo; r.hi = bounds_hi; r.init = init;
+  r.S = S; r.D = D; r.maxiter = maxiter; r.budget = budget;
+  r.key = key; r.pos = pos;
+  r.x_out = x_out; r.f_out = f_out; r.nit_out = nit_out; r.nfev_out = nfev_out; r.success_out = success_out; r.launches_out = launches_out;
+  return run_evolve(ctx, o, r);
 }
 #endif  // GPBO_DEBUG

@@ -15,6 +15,7 @@
 #include "gpbo.h"
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
+#include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
 
 namespace gpbo {
 
@@ -192,10 +193,6 @@ namespace gpbo {
 constexpr size_t SMALL_PIN_IN = 128 * 1024, SMALL_PIN_OUT = 32 * 1024;   // bytes: candidates in; mu, sd out (each)
 constexpr size_t SMALL_PIN_BYTES = SMALL_PIN_IN + 2 * SMALL_PIN_OUT;
 constexpr unsigned ATTR_GEMM128 = 4u, ATTR_CHOL128 = 16u, ATTR_FUSED = 32u, ATTR_MID = 64u, ATTR_KINV_GRAD = 128u, ATTR_POLISH_FUSED = 256u, ATTR_GEMM_FAT = 512u, ATTR_EVOLVE = 2048u;
-// the local searches of gpbo_polish_seeds as one launch (polish_fused.hip): up to this padded size, one model — the kernel's own
-// limit: at N = 512 the launch still beats the lockstep rounds (profiles/r06_polish_fused_ab.json: 0.36-0.48 against 0.53-0.59 ms for
-// 8-10 evaluations, 2.09 against 2.13 for 48)
-constexpr int POLISH_FUSED_NP_DEFAULT = 512;
 // pinned staging of a small host-side fit's X (N, d) | y (N), read by the first kernel directly (one window per PIN window)
 constexpr int STAGE_NP_CAP = MID_NP_CAP;
 static_assert(STAGE_NP_CAP >= FUSED_NP_CAP, "the staging window serves both small paths");
@@ -275,8 +272,10 @@ inline const char* dbg_env(const char* name) { return getenv(name); }
 #else
 inline const char* dbg_env(const char*) { return nullptr; }
 #endif
-// a debug switch's number for the rules of fit_plan.h: env_override(dbg_env("GPBO_..."))
+// a debug switch's number for the rules of fit_plan.h / search_plan.h: env_override(dbg_env("GPBO_..."))
 inline int env_override(const char* e) { return e ? atoi(e) : NO_OVERRIDE; }
+// the size cap of the one-launch searches (search_plan.h: search_max_np), local searches and evolution alike
+inline int search_np_override() { return env_override(dbg_env("GPBO_POLISH_FUSED_MAX_NP")); }
 
 #define GPBO_HIP(ctx, expr)                                                                  \
   do {                                                                                       \
@@ -365,6 +364,18 @@ template <typename F>
 int with_kernel(int kernel, F&& f) {
   if (kernel == GPBO_KERNEL_MATERN25) return f(std::integral_constant<int, GPBO_KERNEL_MATERN25>{});
   return f(std::integral_constant<int, GPBO_KERNEL_RBF>{});
+}
+// ... and the four <KERNEL, WLDS> instances of the one-launch search kernels (search_plan.h: W in LDS or streamed from memory)
+template <typename F>
+int with_kernel_wlds(int kernel, bool wlds, F&& f) {
+  return with_kernel(kernel, [&](auto k) -> int { return wlds ? f(k, std::true_type{}) : f(k, std::false_type{}); });
+}
+template <typename F>
+int for_each_kernel_wlds(F&& f) {
+  for (const int kernel : {GPBO_KERNEL_MATERN25, GPBO_KERNEL_RBF})
+    for (const bool wlds : {true, false})
+      if (const int rc = with_kernel_wlds(kernel, wlds, f)) return rc;
+  return GPBO_OK;
 }
 template <typename F>
 int with_dp_kernel(gpbo_ctx* ctx, int DP, int kernel, F&& f) {
@@ -508,15 +519,13 @@ int build_acq_args(gpbo_ctx* ctx, const char* who, int acq, double acq_param, do
 // posterior_small.hip
 int launch_posterior_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, double y_std);
 int small_batch_limit(int64_t NP);   // largest M the GEMV path takes (posterior_small.hip)
-// polish_fused.hip: gpbo_polish_seeds' runs as one launch (one workgroup per run).  host_block / dev_block: the two addresses of one
-// device-visible pinned block of polish_fused_pinned_bytes(n_seeds, d); results land there (layout: polish_fused.hip).  eval_repeat = R > 0:
-// no search, R evaluations at every seed (the debug entry's timing and parity seam).
-int polish_fused_max_np();
-bool polish_fused_serves(const Model& m);
-size_t polish_fused_pinned_bytes(int n_seeds, int d);
-int launch_polish_fused(gpbo_ctx* ctx, Model& m, int acq, double acq_param, double y_max, double y_mean, double y_std, const double* seeds,
-                        int n_seeds, const double* box_lo, const double* box_hi, int max_iter, int eval_repeat, double* host_block,
-                        double* dev_block);
+// polish_fused.hip: gpbo_polish_seeds' runs as one launch (one workgroup per run) by the caller's plan (search_plan.h: plan_polish,
+// a served mode).  The seeds and the box go in and the results land in ctx->polish_pinned, a device-visible block of at least
+// block.bytes laid out by `block` (polish_block(n_seeds, d)).  eval_repeat = R > 0: no search, R evaluations at every seed (the debug
+// entry's timing and parity seam).
+int launch_polish_fused(gpbo_ctx* ctx, Model& m, const PolishPlan& plan, const PolishBlock& block, int acq, double acq_param,
+                        double y_max, double y_mean, double y_std, const double* seeds, int n_seeds, const double* box_lo,
+                        const double* box_hi, int max_iter, int eval_repeat);
 int launch_posterior_grad_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, double y_std, double* dmu_dev, double* dsd_dev,
                                 double* mu_out, double* sd_out);
 // lml_kernels.hip

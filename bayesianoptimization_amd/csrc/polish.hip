@@ -83,6 +83,29 @@ int lockstep_minimize(Eval&& eval, const double* seeds, int n_seeds, int d, cons
   return GPBO_OK;
 }
 
+inline int clamp_max_iter(int max_iter) {      // 0 or less: SciPy's 15000; the cap keeps 4 * max_iter + 64 rounds an int
+  return max_iter < 1 ? 15000 : std::min(max_iter, 100000000);
+}
+inline bool box_ok(const double* box_lo, const double* box_hi, int d) {
+  for (int i = 0; i < d; ++i)
+    if (!(box_lo[i] < box_hi[i])) return false;
+  return true;
+}
+
+// the context's device-visible pinned block (ctx->polish_pinned and its device address), grown to `bytes`
+int ensure_polish_pinned(gpbo_ctx* ctx, size_t bytes) {
+  if ((int64_t)bytes <= ctx->cap_polish_pinned) return GPBO_OK;
+  if (ctx->polish_pinned) GPBO_HIP(ctx, hipHostFree(ctx->polish_pinned));
+  ctx->polish_pinned = nullptr;
+  ctx->cap_polish_pinned = 0;
+  GPBO_HIP(ctx, hipHostMalloc(&ctx->polish_pinned, bytes, hipHostMallocDefault));
+  GPBO_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->polish_pinned_dev, ctx->polish_pinned, 0));
+  ctx->cap_polish_pinned = (int64_t)bytes;
+  return GPBO_OK;
+}
+
+PolishPlan plan_polish_for(const Model& m) { return plan_polish((int)m.NP, m.d, m.DP, search_np_override()); }
+
 }  // namespace
 
 }  // namespace gpbo
@@ -96,12 +119,9 @@ extern "C" int gpbo_debug_minimize_box(gpbo_fg_callback fg, void* user, const do
   if (!fg || !seeds || !box_lo || !box_hi || !x_out || !f_out || !status_out || n_seeds < 1 || n_seeds > GPBO_MAX_SEEDS || d < 1 ||
       d > GPBO_MAX_DIM)
     return GPBO_ERR_INVALID;
-  for (int i = 0; i < d; ++i)
-    if (!(box_lo[i] < box_hi[i])) return GPBO_ERR_INVALID;
-  if (max_iter < 1) max_iter = 15000;
-  if (max_iter > 100000000) max_iter = 100000000;      // (4 * max_iter + 64 rounds is an int)
+  if (!box_ok(box_lo, box_hi, d)) return GPBO_ERR_INVALID;
   return lockstep_minimize([&](const double* batch, int live, double* f, double* g) { return fg(batch, live, d, f, g, user); }, seeds,
-                           n_seeds, d, box_lo, box_hi, max_iter, x_out, f_out, status_out, n_rounds_out, n_iter_out, n_eval_out);
+                           n_seeds, d, box_lo, box_hi, clamp_max_iter(max_iter), x_out, f_out, status_out, n_rounds_out, n_iter_out, n_eval_out);
 }
 #endif  // GPBO_DEBUG
 
@@ -113,24 +133,16 @@ extern "C" int gpbo_debug_polish_eval(gpbo_ctx* ctx, int acq, double acq_param, 
   if (!ctx || !points || !out || n < 1 || n > GPBO_MAX_SEEDS || repeat < 1) return GPBO_ERR_INVALID;
   Model& m = ctx->models[0];
   if (!m.fitted || m.d != d) GPBO_FAIL(ctx, GPBO_ERR_STATE, "debug_polish_eval: slot 0 is not fitted for this d");
-  if (!polish_fused_serves(m)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_polish_eval: the model is outside the one-launch path's range");
+  const PolishPlan plan = plan_polish_for(m);
+  if (plan.mode == SearchMode::NotServed) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_polish_eval: the model is outside the one-launch path's range");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t need = polish_fused_pinned_bytes(n, d);
-  if ((int64_t)need > ctx->cap_polish_pinned) {
-    if (ctx->polish_pinned) GPBO_HIP(ctx, hipHostFree(ctx->polish_pinned));
-    ctx->polish_pinned = nullptr;
-    ctx->cap_polish_pinned = 0;
-    GPBO_HIP(ctx, hipHostMalloc(&ctx->polish_pinned, need, hipHostMallocDefault));
-    GPBO_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->polish_pinned_dev, ctx->polish_pinned, 0));
-    ctx->cap_polish_pinned = (int64_t)need;
-  }
+  const PolishBlock block = polish_block(n, d);
+  if (const int rc = ensure_polish_pinned(ctx, block.bytes)) return rc;
   std::vector<double> lo((size_t)d, -1e300), hi((size_t)d, 1e300);
-  const int rc = launch_polish_fused(ctx, m, acq, acq_param, y_max, y_mean, y_std, points, n, lo.data(), hi.data(), 1, repeat,
-                                     (double*)ctx->polish_pinned, (double*)ctx->polish_pinned_dev);
-  if (rc) return rc;
-  const size_t S = (size_t)n;
-  const double* dbg = (const double*)ctx->polish_pinned + 2 * S * d + 2 * (size_t)d + S;
-  std::copy(dbg, dbg + S * (4 + 3 * (size_t)d), out);
+  if (const int rc = launch_polish_fused(ctx, m, plan, block, acq, acq_param, y_max, y_mean, y_std, points, n, lo.data(), hi.data(), 1, repeat))
+    return rc;
+  const double* dbg = (const double*)ctx->polish_pinned + block.dbg;
+  std::copy(dbg, (const double*)ctx->polish_pinned + block.ints, out);
   return GPBO_OK;
 }
 #endif  // GPBO_DEBUG
@@ -146,15 +158,13 @@ extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, doubl
   if (acq != GPBO_ACQ_UCB && acq != GPBO_ACQ_EI && acq != GPBO_ACQ_POI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: unknown acquisition");
   if (n_constraints < 0 || n_constraints >= GPBO_MAX_MODELS || (n_constraints > 0 && (!lb || !ub)))
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: bad constraint arguments");
-  if (max_iter < 1) max_iter = 15000;
-  if (max_iter > 100000000) max_iter = 100000000;      // (4 * max_iter + 64 rounds is an int)
+  max_iter = clamp_max_iter(max_iter);
   for (int j = 0; j <= n_constraints; ++j) {
     if (!ctx->models[j].fitted) GPBO_FAIL(ctx, GPBO_ERR_STATE, "polish_seeds: model slot has not been fitted");
     if (ctx->models[j].d != d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: d differs from the fitted model's");
     if (ctx->pending_info[j]) GPBO_FAIL(ctx, GPBO_ERR_STATE, "polish_seeds: a fit of this slot is still in flight (gpbo_fit_wait)");
   }
-  for (int i = 0; i < d; ++i)
-    if (!(box_lo[i] < box_hi[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: every bound needs lo < hi");
+  if (!box_ok(box_lo, box_hi, d)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: every bound needs lo < hi");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
 
   const int n_models = 1 + n_constraints;
@@ -163,18 +173,12 @@ extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, doubl
   // there: a round is six launches and ONE stream synchronisation, no copy nodes (round 5; until then: H2D copy + event, D2H copy).
   const size_t per_model = (size_t)n_seeds * (2 + 2 * (size_t)d);
   const size_t pts = (size_t)n_seeds * (size_t)d;
-  // (NP <= polish_fused_max_np(), one model: the runs as ONE launch — polish_fused.hip; GPBO_POLISH_FUSED=0, debug build: never)
-  const char* pf_env = dbg_env("GPBO_POLISH_FUSED");
-  const bool fused = n_constraints == 0 && polish_fused_serves(ctx->models[0]) && !(pf_env && pf_env[0] == '0');
-  const size_t need = std::max((pts + per_model * (size_t)n_models) * sizeof(double), fused ? polish_fused_pinned_bytes(n_seeds, d) : (size_t)0);
-  if ((int64_t)need > ctx->cap_polish_pinned) {
-    if (ctx->polish_pinned) GPBO_HIP(ctx, hipHostFree(ctx->polish_pinned));
-    ctx->polish_pinned = nullptr;
-    ctx->cap_polish_pinned = 0;
-    GPBO_HIP(ctx, hipHostMalloc(&ctx->polish_pinned, need, hipHostMallocDefault));
-    GPBO_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->polish_pinned_dev, ctx->polish_pinned, 0));
-    ctx->cap_polish_pinned = (int64_t)need;
-  }
+  // (one model that search_plan.h's rule serves: the runs as ONE launch — polish_fused.hip; GPBO_POLISH_FUSED=0, debug build: never)
+  const PolishPlan plan = plan_polish_for(ctx->models[0]);
+  const PolishBlock block = polish_block(n_seeds, d);
+  const bool fused = polish_one_launch(n_constraints, plan.mode, dbg_env("GPBO_POLISH_FUSED"));
+  if (const int rc = ensure_polish_pinned(ctx, std::max((pts + per_model * (size_t)n_models) * sizeof(double), fused ? block.bytes : (size_t)0)))
+    return rc;
   double* pts_h = (double*)ctx->polish_pinned;
   double* land = pts_h + pts;
   const double* pts_d = (const double*)ctx->polish_pinned_dev;
@@ -182,21 +186,19 @@ extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, doubl
   const bool timing0 = ctx->no_timing;
 
   if (fused) {
-    const int rc = launch_polish_fused(ctx, ctx->models[0], acq, acq_param, y_max, y_mean[0], y_std[0], seeds, n_seeds, box_lo, box_hi,
-                                       max_iter, 0, (double*)ctx->polish_pinned, (double*)ctx->polish_pinned_dev);
-    if (rc) return rc;
-    const size_t S = (size_t)n_seeds;
-    const double* xo = (const double*)ctx->polish_pinned + S * d + 2 * (size_t)d;
-    const double* fo = xo + S * d;
-    const int* io = (const int*)(fo + S + S * (4 + 3 * (size_t)d));
-    std::copy(xo, xo + S * d, x_out);
-    std::copy(fo, fo + S, f_out);
+    if (const int rc = launch_polish_fused(ctx, ctx->models[0], plan, block, acq, acq_param, y_max, y_mean[0], y_std[0], seeds, n_seeds,
+                                           box_lo, box_hi, max_iter, 0))
+      return rc;
+    const double* hd = (const double*)ctx->polish_pinned;
+    const int* hw = (const int*)ctx->polish_pinned;
+    std::copy(hd + block.x, hd + block.f, x_out);
+    std::copy(hd + block.f, hd + block.dbg, f_out);
     int rounds = 0;
     for (int s = 0; s < n_seeds; ++s) {
-      status_out[s] = io[s];
-      if (n_iter_out) n_iter_out[s] = io[S + s];
-      if (n_eval_out) n_eval_out[s] = io[2 * S + s];
-      rounds = std::max(rounds, io[2 * S + s]);
+      status_out[s] = hw[block.status + s];
+      if (n_iter_out) n_iter_out[s] = hw[block.iter + s];
+      if (n_eval_out) n_eval_out[s] = hw[block.evals + s];
+      rounds = std::max(rounds, hw[block.evals + s]);
     }
     if (n_rounds_out) *n_rounds_out = rounds;      // (what the lockstep path counts: batched evaluations = the longest run's)
     return GPBO_OK;

@@ -18,7 +18,7 @@
 // (same or better acquisition value), not bit-wise"); the lockstep path is the checker (tests/test_gpu_polish_fused.py).  Round 5's
 // eight-wave kernel — the six kernels' arithmetic phase by phase, bitwise the lockstep path, nine barriers and two passes over W
 // at 25 GB/s per evaluation — is in the git history; every size it served is served faster here.
-// One model (no constraint slots).
+// One model (no constraint slots).  Which models are served, the kernel's LDS layout and the pinned block's: search_plan.h.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -52,14 +52,7 @@ struct DevPdf {
   __device__ __forceinline__ double operator()(double z) const { return exp(-0.5 * z * z) * 0.39894228040143267794; }
 };
 
-constexpr int PF_LDS_CAP = 160 * 128 - 8;      // doubles in 160 KiB, less the flag words
-
-__device__ __forceinline__ double pf_lane(double v, int i) {      // v of lane i (i uniform), in every lane
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), i);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), i);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
-}
+static_assert(POLISH_OPT_PAIRS == LBFGS_M, "search_plan.h sizes the optimiser's LDS block for polish_opt.h's correction pairs");
 
 // ---- the optimiser: polish_opt.h's steps over wave 0, lane i = variable i (d <= 64; lanes >= d carry zeros) ---------------------
 // Against the host's arithmetic: (a) a sum over the variables is a DPP butterfly inside the rows of 16
@@ -83,9 +76,9 @@ __device__ __forceinline__ double pr_sum(double v, int d) {      // lanes >= d c
   v += pr_dpp<0x4E>(v);
   v += pr_dpp<0x141>(v);
   v += pr_dpp<0x140>(v);
-  double acc = pf_lane(v, 0);
-  if (d > 16) acc += pf_lane(v, 16);
-  if (d > 32) acc = (acc + pf_lane(v, 32)) + pf_lane(v, 48);
+  double acc = pr_lane(v, 0);
+  if (d > 16) acc += pr_lane(v, 16);
+  if (d > 32) acc = (acc + pr_lane(v, 32)) + pr_lane(v, 48);
   return acc;
 }
 __device__ __forceinline__ double pr_max_abs(double v, int d) {  // max |v_i|, a NaN never wins (polish_opt.h)
@@ -95,9 +88,9 @@ __device__ __forceinline__ double pr_max_abs(double v, int d) {  // max |v_i|, a
   m = polish_max(m, pr_dpp<0x4E>(m));
   m = polish_max(m, pr_dpp<0x141>(m));
   m = polish_max(m, pr_dpp<0x140>(m));
-  double acc = pf_lane(m, 0);
-  if (d > 16) acc = polish_max(acc, pf_lane(m, 16));
-  if (d > 32) acc = polish_max(polish_max(acc, pf_lane(m, 32)), pf_lane(m, 48));
+  double acc = pr_lane(m, 0);
+  if (d > 16) acc = polish_max(acc, pr_lane(m, 16));
+  if (d > 32) acc = polish_max(polish_max(acc, pr_lane(m, 32)), pr_lane(m, 48));
   return acc;
 }
 
@@ -107,11 +100,8 @@ struct RowsRun {
   double f, alpha;
   int hist, head, iter, evals, ls, phase, status;
 };
-// LDS of the optimiser (doubles): S, Y [LBFGS_M][d] (lane i reads and writes column i) | s.y, y.y over ALL variables, rho, a
-// [LBFGS_M each] (written and read by every lane alike: program order within the one wave)
-__host__ __device__ inline int pr_opt_doubles(int d) { return 2 * LBFGS_M * d + 4 * LBFGS_M; }
-
 // one answer (ft, this lane's gradient component gt — non-finite components already 0) of the objective: polish_advance
+// (opt: the optimiser's LDS block, search_plan.h's polish_opt_doubles)
 __device__ __forceinline__ void pr_advance(RowsRun& r, double ft, double gt, int d, int lane, double* opt, int max_iter) {
 #pragma clang fp contract(off)
   double* S = opt;
@@ -234,56 +224,28 @@ __global__ __launch_bounds__(256) void transpose_w_kernel(const double* __restri
 }
 
 // ---- thread = training point (NP <= 512) ---------------------------------------------------------------------------------
-constexpr int PR_LDS_NP = 128;       // W fits the LDS up to here (a padded square: 132 KB at 128)
-constexpr int PR_MAX_NP = 512;       // ... and is streamed from memory above (W for the column walk, its transpose for the row walk): 8 waves,
-                                     // 256 VGPRs each (12 waves for NP = 768 would spill the optimiser's registers to scratch)
-// LDS (doubles): [W [NP][NP + 1]] | xs [64] | ls [64] | alpha, k*, v [NP each] | (c1, c2) [NP][2] | (v^2, k* alpha) [NP][2] | u [NP] |
-// group partials [groups][2 DP + 2] | the optimiser's block (pr_opt_doubles) | X [NP][DP + 1] (when it fits) ; then the flag word
-__host__ __device__ inline int pr_groups(int NP, int DP) { return (64 / DP) * (NP >> 6); }
-__host__ __device__ inline int pr_lds_base(int NP, int d, int DP, bool wlds) {
-  return (wlds ? NP * (NP + 1) : 0) + 128 + 8 * NP + pr_groups(NP, DP) * (2 * DP + 2) + pr_opt_doubles(d);
-}
-__host__ __device__ inline int pr_xs_stage(int NP, int d, int DP, bool wlds) {
-  const int want = NP * (DP + 1);
-  return (pr_lds_base(NP, d, DP, wlds) + want <= PF_LDS_CAP) ? want : 0;
-}
-__host__ __device__ inline int pr_lds_doubles(int NP, int d, int DP, bool wlds) {
-  return pr_lds_base(NP, d, DP, wlds) + pr_xs_stage(NP, d, DP, wlds);
-}
-
+// (the LDS layout: search_plan.h's PolishLds)
 // WLDS = false (round 6, 128 < NP <= 512): W stays in memory and both walks are COALESCED: the row walk reads the transposed copy
 // (Wt[k][i], lanes = consecutive i), the column walk reads W itself (W[i'][k], lanes = consecutive k), two rows (columns) per thread
 // with 16-byte loads, PR_INFLIGHT of them in flight per lane.  A CU pulls NP^2 / 2 * 8 B per walk at ~64 B per clock: 0.4 us at NP = 256, 1.7 us
 // at 512 — against two passes of the eight-wave kernel at 25 GB/s per CU and against the 41-75 us of a six-launch lockstep round.
 template <int KERNEL, bool WLDS>
-__global__ __launch_bounds__(WLDS ? PR_LDS_NP : PR_MAX_NP) void polish_rows_kernel(const PolishFusedArgs a) {
+__global__ __launch_bounds__(WLDS ? SEARCH_LDS_NP : SEARCH_MAX_NP) void polish_rows_kernel(const PolishFusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) double pr_smem[];
   const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int sidx = (int)blockIdx.x;
   const int NP = a.NP, N = a.N, d = a.d, DP = a.DP;
   const int WLD = NP + 1;
-  double* Wl = pr_smem;                     // [NP][NP + 1]: row walks and column walks both hit 64 different banks
-  double* xs = Wl + (WLDS ? NP * WLD : 0);  // [64] the trial point over the length scales, zero padded
-  double* ls_s = xs + 64;                   // [64]
-  double* al_s = ls_s + 64;                 // [NP] alpha
-  double* ks = al_s + NP;                   // [NP] k*
-  double* vs = ks + NP;                     // [NP] v = W k*
-  double* cc = vs + NP;                     // [NP][2] alpha_k f_k, u_k f_k
-  double* pp = cc + 2 * NP;                 // [NP][2] v_k^2, k*_k alpha_k
-  double* us = pp + 2 * NP;                 // [NP] u = W^T v (W in memory: the pair threads hand their columns' sums over)
-  double* red = us + NP;                    // [groups][2 DP + 2]
-  double* opt = red + pr_groups(NP, DP) * (2 * DP + 2);
-  double* Xl = opt + pr_opt_doubles(d);
-  const int xs_staged = pr_xs_stage(NP, d, DP, WLDS);
-  int* flag = (int*)(Xl + xs_staged);
+  const PolishLds L = polish_lds(NP, d, DP, WLDS);
+  double *Wl = pr_smem + L.W, *xs = pr_smem + L.xs, *ls_s = pr_smem + L.ls, *al_s = pr_smem + L.alpha, *ks = pr_smem + L.ks,
+         *vs = pr_smem + L.vs, *cc = pr_smem + L.cc, *pp = pr_smem + L.pp, *us = pr_smem + L.us, *red = pr_smem + L.red,
+         *opt = pr_smem + L.opt, *Xl = pr_smem + L.X;
+  const int xs_staged = L.x_doubles;
+  int* flag = (int*)(pr_smem + L.flag);
   const double* __restrict__ Xs = xs_staged ? Xl : a.Xs;
   const int xld = xs_staged ? DP + 1 : DP;
 
-  if (WLDS)
-    for (int e = tid; e < NP * NP; e += NP) {         // (blockDim.x == NP) coalesced rows of the matrix in memory, zeros above the diagonal included
-      const int i = e / NP, k = e - i * NP;
-      Wl[i * WLD + k] = a.W[e];
-    }
+  if (WLDS) pr_load_w(Wl, a.W, NP, tid);
   al_s[tid] = a.alpha[tid];
   if (tid < 64) ls_s[tid] = (tid < d) ? a.ls[tid] : 1.0;
   if (xs_staged)
@@ -463,87 +425,46 @@ int ensure_w_transposed(gpbo_ctx* ctx, Model& m) {
   return GPBO_OK;
 }
 
-// Largest padded size the one launch serves with W in memory (debug build: GPBO_POLISH_FUSED_MAX_NP read per call — the crossover
-// against the lockstep rounds, scripts/r06_polish_fused_ab.py: at N = 512 a run of ~50 evaluations already loses to them, 2.46
-// against 2.13 ms — and 0 = never, the lockstep path alone: the checker's switch, with GPBO_POLISH_FUSED=0)
-int polish_fused_max_np() {
-  int v = POLISH_FUSED_NP_DEFAULT;
-  if (const char* e = dbg_env("GPBO_POLISH_FUSED_MAX_NP")) v = atoi(e);
-  return v > PR_MAX_NP ? PR_MAX_NP : v;
-}
-
-// W in LDS for NP <= 128 (whenever the image fits: 1), streamed from memory above (2), 0 = not served
-static int polish_rows_mode(const Model& m) {
-  const int cap = polish_fused_max_np();
-  if (m.NP > cap) return 0;
-  if (m.NP <= PR_LDS_NP && (size_t)pr_lds_doubles((int)m.NP, m.d, m.DP, true) * sizeof(double) + 16 <= (size_t)160 * 1024) return 1;
-  if (m.NP <= PR_MAX_NP && (size_t)pr_lds_doubles((int)m.NP, m.d, m.DP, false) * sizeof(double) + 16 <= (size_t)160 * 1024) return 2;
-  return 0;
-}
-
-size_t polish_fused_lds_bytes(const Model& m) {
-  return (size_t)pr_lds_doubles((int)m.NP, m.d, m.DP, polish_rows_mode(m) == 1) * sizeof(double) + 16;
-}
-
-bool polish_fused_serves(const Model& m) { return polish_rows_mode(m) != 0; }
-
-// pinned block (device-visible): doubles [seeds (S, d) | lo (d) | hi (d) | x (S, d) | f (S) | dbg (S, 4 + 3 d)] then ints
-// [status (S) | iter (S) | evals (S)]
-size_t polish_fused_pinned_bytes(int n_seeds, int d) {
-  return ((size_t)2 * n_seeds * d + 2 * (size_t)d + (size_t)n_seeds + (size_t)n_seeds * (4 + 3 * (size_t)d)) * sizeof(double) +
-         (size_t)3 * n_seeds * sizeof(int);
-}
-
-int launch_polish_fused(gpbo_ctx* ctx, Model& m, int acq, double acq_param, double y_max, double y_mean, double y_std, const double* seeds,
-                        int n_seeds, const double* box_lo, const double* box_hi, int max_iter, int eval_repeat, double* host_block,
-                        double* dev_block) {
+int launch_polish_fused(gpbo_ctx* ctx, Model& m, const PolishPlan& plan, const PolishBlock& block, int acq, double acq_param,
+                        double y_max, double y_mean, double y_std, const double* seeds, int n_seeds, const double* box_lo,
+                        const double* box_hi, int max_iter, int eval_repeat) {
+  if (plan.mode == SearchMode::NotServed) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "launch_polish_fused: the model is outside the one-launch path's range");
   const int d = m.d;
   if (!(ctx->func_attrs & ATTR_POLISH_FUSED)) {
-    GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(polish_rows_kernel<GPBO_KERNEL_MATERN25, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-    GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(polish_rows_kernel<GPBO_KERNEL_RBF, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-    GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(polish_rows_kernel<GPBO_KERNEL_MATERN25, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-    GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(polish_rows_kernel<GPBO_KERNEL_RBF, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
+    const int rc = for_each_kernel_wlds([&](auto k, auto wlds) -> int {
+      GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(polish_rows_kernel<decltype(k)::value, decltype(wlds)::value>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, SEARCH_LDS_BYTES));
+      return GPBO_OK;
+    });
+    if (rc) return rc;
     ctx->func_attrs |= ATTR_POLISH_FUSED;
   }
-  const size_t S = (size_t)n_seeds;
-  double* h = host_block;
-  std::copy(seeds, seeds + S * d, h);
-  std::copy(box_lo, box_lo + d, h + S * d);
-  std::copy(box_hi, box_hi + d, h + S * d + d);
+  double* h = (double*)ctx->polish_pinned;
+  std::copy(seeds, seeds + (size_t)n_seeds * d, h + block.seeds);
+  std::copy(box_lo, box_lo + d, h + block.lo);
+  std::copy(box_hi, box_hi + d, h + block.hi);
   PolishFusedArgs a{};
   a.W = m.W; a.Xs = m.Xs; a.alpha = m.alpha; a.ls = m.ls;
   a.NP = (int)m.NP; a.N = (int)m.N; a.d = d; a.DP = m.DP;
   a.y_mean = y_mean; a.y_std = y_std;
   a.acq = acq; a.acq_param = acq_param; a.y_max = y_max;
   a.max_iter = max_iter; a.eval_only = eval_repeat;
-  double* dv = dev_block;
-  a.seeds = dv; a.lo = dv + S * d; a.hi = dv + S * d + d;
-  a.x_out = dv + S * d + 2 * d;
-  a.f_out = a.x_out + S * d;
-  a.dbg = a.f_out + S;
-  int* iv = (int*)(a.dbg + S * (4 + 3 * (size_t)d));
-  a.status_out = iv; a.iter_out = iv + S; a.eval_out = iv + 2 * S;
+  double* dv = (double*)ctx->polish_pinned_dev;
+  int* iv = (int*)dv;
+  a.seeds = dv + block.seeds; a.lo = dv + block.lo; a.hi = dv + block.hi;
+  a.x_out = dv + block.x; a.f_out = dv + block.f; a.dbg = dv + block.dbg;
+  a.status_out = iv + block.status; a.iter_out = iv + block.iter; a.eval_out = iv + block.evals;
   a.negvar = ctx->negvar;
-  const size_t lds = polish_fused_lds_bytes(m);
-  const int rows_mode = polish_rows_mode(m);
-  const dim3 grid((unsigned)n_seeds), rows_block((unsigned)m.NP);
-  if (rows_mode == 2) {
+  if (plan.mode == SearchMode::WInMemory) {
     // the transposed copy for the row walk lives in the slot's K buffer (a fit assembles K straight into L; gpbo_get_K and the LML
     // path, which write K, invalidate it): made once per fit
     if (const int rc = ensure_w_transposed(ctx, m)) return rc;
     a.Wt = m.K;
-    if (m.kernel == GPBO_KERNEL_MATERN25) polish_rows_kernel<GPBO_KERNEL_MATERN25, false><<<grid, rows_block, lds, ctx->stream>>>(a);
-    else polish_rows_kernel<GPBO_KERNEL_RBF, false><<<grid, rows_block, lds, ctx->stream>>>(a);
-  } else if (rows_mode == 1) {
-    if (m.kernel == GPBO_KERNEL_MATERN25) polish_rows_kernel<GPBO_KERNEL_MATERN25, true><<<grid, rows_block, lds, ctx->stream>>>(a);
-    else polish_rows_kernel<GPBO_KERNEL_RBF, true><<<grid, rows_block, lds, ctx->stream>>>(a);
-  } else {
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "launch_polish_fused: the model is outside the one-launch path's range");
   }
+  with_kernel_wlds(m.kernel, plan.mode == SearchMode::WInLds, [&](auto k, auto wlds) -> int {
+    polish_rows_kernel<decltype(k)::value, decltype(wlds)::value><<<dim3((unsigned)n_seeds), dim3((unsigned)m.NP), (size_t)plan.lds_bytes, ctx->stream>>>(a);
+    return GPBO_OK;
+  });
   GPBO_HIP(ctx, hipGetLastError());
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return GPBO_OK;

@@ -1,5 +1,6 @@
 // The posterior at ONE point with THREAD = TRAINING POINT, one workgroup of NP threads: the pieces polish_fused.hip (value and
 // gradient, one local search per workgroup) and evolve.hip (value only, one differential evolution per workgroup) share.
+//   * pr_lane: a lane's double in every lane; pr_load_w: W from memory into its padded LDS square;
 //   * pr_kstar: k*_i = k(|x / l - X_i / l|^2) of thread i's point (the squared distance as one fma chain over the DP padded columns);
 //   * pr_row_lds: v_i = (W k*)_i over row i of W in LDS (a padded square [NP][NP + 1]), four accumulators;
 //   * pr_rows_mem: the same with W in memory: threads tid < NP / 2 walk rows 2 tid, 2 tid + 1 of W through its transposed copy
@@ -16,6 +17,21 @@ namespace gpbo {
 #define GPBO_PR_INFLIGHT 16
 #endif
 constexpr int PR_INFLIGHT = GPBO_PR_INFLIGHT;      // 16-byte loads in flight per lane in the walks over W in memory (128 is a multiple)
+
+__device__ __forceinline__ double pr_lane(double v, int i) {      // v of lane i (i uniform), in every lane
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), i);
+  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), i);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+}
+
+// Wl [NP][NP + 1] = W [NP][NP] (blockDim.x == NP): coalesced rows of the matrix in memory, zeros above the diagonal included
+__device__ __forceinline__ void pr_load_w(double* Wl, const double* W, int NP, int tid) {
+  for (int e = tid; e < NP * NP; e += NP) {
+    const int i = e / NP, k = e - i * NP;
+    Wl[i * (NP + 1) + k] = W[e];
+  }
+}
 
 template <int KERNEL>
 __device__ __forceinline__ double pr_kstar(const double* xs, const double* xr, int DP, double& d2_out) {
@@ -67,7 +83,7 @@ __device__ __forceinline__ void pr_rows_mem(const double* __restrict__ Wt, const
 }
 
 // Wt = W^T made once per fit into the slot's K buffer (a fit assembles K straight into L; gpbo_get_K and the LML path, which write
-// K, clear m.wt_valid): polish_fused.hip
+// K, clear m.wt_valid).  Defined in polish_fused.hip with its kernel: a __global__ function needs one translation unit.
 int ensure_w_transposed(gpbo_ctx* ctx, Model& m);
 
 }  // namespace gpbo

@@ -381,7 +381,7 @@ POLISH_CASES = [(N, d) for d in (33, 48, 64) for N in (64, 128, 192, 384, 512)]
 
 @pytest.mark.parametrize("N,d", POLISH_CASES)
 def test_one_fused_local_search_evaluation_at_wide_widths(debug_engine, polish_any_size, N, d):
-    """test_gpu_polish_fused's single-evaluation comparison on both sides of polish_rows_mode's LDS decisions (W in LDS at NP = 64
+    """test_gpu_polish_fused's single-evaluation comparison on both sides of plan_polish's LDS decisions (csrc/search_plan.h) (W in LDS at NP = 64
     / 128 if its image fits, W in memory from 192 on; X staged or not)."""
     from test_gpu_polish_fused import _polish_eval
 
