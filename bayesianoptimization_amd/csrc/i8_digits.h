@@ -64,6 +64,23 @@ GPBO_HD inline int i8_row_exponent(double maxabs) {
   return maxabs > 0.0 ? e : 0;
 }
 
+// ---- operand layout of v_mfma_i32_16x16x64_i8 (posterior_i8.hip) ----------------------------------------------------------
+// Both operands lie in fragment order, [block of 16 items][64-step][plane][lane] 16 bytes: an item is a row of W or a candidate,
+// a 64-step is 64 consecutive train points, lane 16 g + r holds item r's bytes for train points 16 g ... 16 g + 15 of the step.
+// Index of the 16-byte fragment that holds (item of the block, train point k, plane), given the block's first 64-step in its buffer:
+template <int S>
+GPBO_HD constexpr int64_t i8_frag_index(int64_t first_step, int64_t k, int plane, int item) {
+  return ((first_step + (k >> 6)) * S + plane) * 64 + ((k >> 4) & 3) * 16 + item;
+}
+// k* digits: every block of 16 candidates holds all NP / 64 steps
+GPBO_HD constexpr int64_t i8_kd_block(int64_t cb, int64_t NP) { return cb * (NP / 64); }
+// W digits, lower triangle: the block of rows 16 b ... 16 b + 15 holds the steps 0 ... b / 4 (the last one zero where it lies past
+// the diagonal), so it starts at sum_{b' < b} (b' / 4 + 1); no padding steps
+GPBO_HD constexpr int64_t i8_wd_block(int64_t b) {
+  const int64_t q = b >> 2, r = b & 3;
+  return b + 2 * q * (q - 1) + r * q;
+}
+
 // The S level sums of one output (acc[l], l = s + t, weight 256^(2S-2-l) in units of 2^-(16S-4)) -> their sum in fp64, in
 // units of the lowest level (times 2^i8_scale_exp(e) that is v_i).  Every level converts exactly; the levels are taken in
 // three groups whose sums are exact (each spans fewer than 53 bits: the top S - 4 levels, the next two, the last two), the

@@ -2,19 +2,21 @@
 // accuracy (fixed-point Ozaki scheme: i8_digits.h).
 //
 // Why: the fp64 slab GEMM (posterior_kernel_v2.hip, GEN = 2) runs at 0.93 of the fp64 matrix peak and is 92 % of a C3
-// step.  v_mfma_i32_32x32x32_i8 does 32 768 MACs in the cycles v_mfma_f64_16x16x4_f64 takes for 512: with both operands
+// step.  v_mfma_i32_16x16x64_i8 does 16 384 MACs in half the cycles v_mfma_f64_16x16x4_f64 takes for 512: with both operands
 // split into I8_S = 7 int8 digit planes, the 28 products (s, t), s + t <= S - 1, cost less than half the fp64 GEMM's
 // matrix-pipe time, and integer sums are exact.
 //
 //   workgroup = 4 waves (one per SIMD), 128 rows of W x 64 candidates; heaviest row chunks first, as in v2;
-//   wave w    = one 32-row block x two 32-candidate blocks = 2 x S int32 accumulator tiles (224 registers);
-//   k step    = 32 train points: S A fragments (the wave's rows) + 2 S B fragments (k* digits), 16 B per lane each,
-//               loaded from memory in fragment order one step ahead; each fragment feeds up to S products.
-//   triangle  = a wave walks the k steps 0 ... its own row block only (the digit planes of W are packed as the lower
-//               triangle of 32 x 32 blocks, upper parts of the diagonal block zero).
-// The operand lane maps of the int8 MFMA need not be known: A and B use the same (lane half, byte) -> k assignment, and the
-// sum over k does not care which k sits where.  The C/D map (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5),
-// the same for every non-f64 MFMA on gfx950) places each row's scale and each candidate's sum.
+//   wave w    = two 16-row blocks x four 16-candidate blocks = 8 x S int32 accumulator tiles (224 registers);
+//   k step    = 64 train points: 2 S A fragments (the wave's rows) + 4 S B fragments (k* digits), 16 B per lane each, in
+//               fragment order (i8_frag_index); each fragment feeds up to 4 S products, 224 per step;
+//   triangle  = a wave walks the k steps 0 ... the one that holds its own diagonal only (the digit planes of W are packed as
+//               the lower triangle, zero past the diagonal inside the last step).
+// The MFMA shape: 16x16x64 and 32x32x32 do the same MACs per cycle; the tile per wave, the bytes per k and the summation order
+// of the epilogue are those of the 32x32x32 kernel this one replaced, so the results are the same bits.
+// The operand lane maps of the int8 MFMA need not be known: A and B use the same (lane group, byte) -> k assignment, and the
+// sum over k does not care which k sits where.  The C/D map (col = lane & 15, row = 4 (lane >> 4) + reg, the same for every
+// non-f64 16 x 16 MFMA on gfx950) places each row's scale and each candidate's sum.
 //
 // The level sums are exact, so v_i is the correctly rounded value of the truncated digit product whatever the tiling; the
 // sum of squares is then taken in a fixed order per 128-row chunk, as the fp64 kernels do per 256-row chunk.  mu (k* . alpha)
@@ -27,13 +29,9 @@
 namespace gpbo {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
-constexpr int I8_CANDS = 64;   // candidates per workgroup (2 blocks of 32)
+constexpr int I8_CANDS = 64;   // candidates per workgroup (4 blocks of 16)
 constexpr int I8_BUF_FLAGS = 0x00020000;   // gfx9 buffer descriptor word 3: raw buffer, 32-bit data format
-
-// first 32 x 32 step of row block rb in the packed W: row blocks 0 ... rb - 1 hold q + 2 steps each
-__host__ __device__ inline int64_t wd_block(int64_t rb) { return rb * (rb + 3) / 2; }
 
 // ---- W -> digit planes, once per fit ----------------------------------------------------------------------------------
 // Row exponents: one wave per row, max |W_ij| over the row's N x N lower-triangle part (order-free, so deterministic).
@@ -54,17 +52,17 @@ __global__ __launch_bounds__(256) void wd_row_scale_kernel(const double* __restr
   }
 }
 
-// Digit planes: thread = (32 x 32 block (rb, ks <= rb + 1), lane); lane 32 h + c holds row 32 rb + c, columns 32 ks + 16 h + j.
-// Layout [wd_block(rb) + ks][plane][lane] 16 B.  Entries outside the N x N lower triangle are zero (as pack_w_elem); each row
-// block carries one zero step past its diagonal, so that a wave can always walk an even number of steps (see the GEMM).
+// Digit planes: thread = (16-row block b, 64-step ks <= b / 4, lane); lane 16 g + r holds row 16 b + r, columns 64 ks + 16 g + j.
+// Layout: i8_frag_index from the block's first step i8_wd_block(b).  Entries outside the N x N lower triangle are zero (as
+// pack_w_elem), the part of a block's last step past its diagonal included.
 __global__ __launch_bounds__(256) void wd_pack_kernel(const double* __restrict__ W, const int* __restrict__ wexp,
                                                       uint4* __restrict__ Wd, int64_t N, int64_t NP) {
-  const int rb = blockIdx.y;
+  const int b = blockIdx.y;
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int ks = t >> 6, lane = t & 63;
-  if (ks > rb + 1) return;
-  const int64_t row = (int64_t)rb * 32 + (lane & 31);
-  const int64_t c0 = (int64_t)ks * 32 + (lane >> 5) * 16;
+  if (ks > b / 4) return;
+  const int64_t row = (int64_t)b * 16 + (lane & 15);
+  const int64_t c0 = (int64_t)ks * 64 + (lane >> 4) * 16;
   const int e = wexp[row];
   uint32_t w[I8_S][4] = {};
 #pragma unroll
@@ -75,21 +73,20 @@ __global__ __launch_bounds__(256) void wd_pack_kernel(const double* __restrict__
 #pragma unroll
     for (int s = 0; s < I8_S; ++s) w[s][j >> 2] |= i8_digit_byte<I8_S>(q, s) << (8 * (j & 3));
   }
-  uint4* dst = Wd + ((wd_block(rb) + ks) * I8_S) * 64 + lane;
+  uint4* dst = Wd + i8_frag_index<I8_S>(i8_wd_block(b), c0, 0, lane & 15);
 #pragma unroll
   for (int s = 0; s < I8_S; ++s) dst[s * 64] = make_uint4(w[s][0], w[s][1], w[s][2], w[s][3]);
 }
 
 static int pack_wd(gpbo_ctx* ctx, Model& m) {
-  const int64_t nrb = m.NP / 32;
+  const int64_t nb = m.NP / 16;   // NP is a multiple of 64 (launch_posterior_slab_i8)
   int rc;
-  if ((rc = ensure(ctx, &m.Wd, &m.cap_Wd, wd_block(nrb) * I8_S * 64))) return rc;
+  if ((rc = ensure(ctx, &m.Wd, &m.cap_Wd, i8_wd_block(nb) * I8_S * 64))) return rc;
   if ((rc = ensure(ctx, &m.wscale, &m.cap_wscale, 2 * m.NP))) return rc;
   int* wexp = reinterpret_cast<int*>(m.wscale + m.NP);   // the row exponents behind the scales
   wd_row_scale_kernel<<<dim3((unsigned)((m.NP + 3) / 4)), dim3(256), 0, ctx->stream>>>(m.W, wexp, m.wscale, m.N, m.NP);
   GPBO_HIP(ctx, hipGetLastError());
-  wd_pack_kernel<<<dim3((unsigned)(((nrb + 1) * 64 + 255) / 256), (unsigned)nrb), dim3(256), 0, ctx->stream>>>(m.W, wexp, m.Wd, m.N,
-                                                                                                           m.NP);
+  wd_pack_kernel<<<dim3((unsigned)((m.NP + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream>>>(m.W, wexp, m.Wd, m.N, m.NP);
   GPBO_HIP(ctx, hipGetLastError());
   m.wd_valid = true;
   return GPBO_OK;
@@ -119,80 +116,123 @@ __global__ __launch_bounds__(256, 1) void posterior_i8_kernel(I8Args p) {
   // with 256 MB ... 4 GB slabs alike.)
   const int r = p.nchunks - 1 - bid / p.n_ctiles;
   const int ct = bid - (bid / p.n_ctiles) * p.n_ctiles;
-  const int nks = p.NP / 32;
-  const int rb = r * (I8_ROWS / 32) + wave;     // this wave's 32-row block
-  const bool active = rb < nks;                 // false only in a ragged last chunk
+  const int nks = p.NP / 64;
+  const int rb = r * (I8_ROWS / 32) + wave;     // this wave's 32 rows: the 16-row blocks 2 rb and 2 rb + 1
+  const bool active = rb < p.NP / 32;           // false only in a ragged last chunk
 
   __shared__ double red[4][I8_CANDS];
-  double ss[2] = {0.0, 0.0};   // per candidate: sum of v^2 over this lane's rows
+  double ss[4] = {0.0, 0.0, 0.0, 0.0};   // per candidate block: sum of v^2 over the wave's rows (see the epilogue)
   if (active) {
-    v16i acc[2][S];
+    v4i acc[2][4][S];
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int l = 0; l < S; ++l) acc[c][l] = v16i{};
-    // Operands through buffer descriptors (wave-uniform bases, the lane as a constant 32-bit offset, the walk along k as the
-    // scalar offset), as in posterior_kernel_v2: no 64-bit address arithmetic per load.
-    const uint4* wa = p.Wd + wd_block(rb) * S * 64;
-    const uint4* kb0 = p.Kd + ((int64_t)(2 * ct) * nks) * S * 64;
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int l = 0; l < S; ++l) acc[a][j][l] = v4i{};
+    // Operands through buffer descriptors (wave-uniform bases, the lane as a constant 32-bit offset, the block and the walk along k
+    // as the scalar offset), as in posterior_kernel_v2: no 64-bit address arithmetic per load.
+    const int n = rb / 2 + 1;                   // 64-steps up to the diagonal: both 16-row blocks hold exactly these
+    const uint4* wa = p.Wd + i8_wd_block(2 * rb) * S * 64;
+    const uint4* kb0 = p.Kd + i8_kd_block(4 * ct, p.NP) * S * 64;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wa), 0, 0x7fffffff, I8_BUF_FLAGS);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(kb0), 0, 0x7fffffff, I8_BUF_FLAGS);
-    const unsigned voff = (unsigned)lane * 16u, vofB1 = voff + (unsigned)nks * S * 1024u;
-    v4i a[S], b0[S], b1[S], na[S], nb0[S], nb1[S];
-    auto load = [&](int ks, v4i(&ra)[S], v4i(&rb0)[S], v4i(&rb1)[S]) {
-      const unsigned o = (unsigned)ks * S * 1024u;
+    const unsigned voff = (unsigned)lane * 16u;
+    const unsigned sofA = (unsigned)n * S * 1024u, sofB = (unsigned)nks * S * 1024u;   // block strides, scalar like the k walk
+    // One operand set is 6 S fragments = 168 registers, so beside 224 accumulators there is ONE set, and each part of it is
+    // re-loaded for the next step as soon as its last product of this step has issued.  A step is four phases of 2 S (S + 1)
+    // = 56 products: A0 x B01, A1 x B01, A0 x B23, A1 x B23 (A0 / A1 the upper / lower 16 rows, B01 / B23 the candidate blocks 0, 1
+    // / 2, 3).  B01 is free after the second phase, A0 after the third, A1 and B23 after the fourth: k* digits (which come from
+    // beyond L2) are in flight for two phases before their first use, W digits (L2) for one.
+    v4i a[2][S], b[4][S];
+    auto load_a = [&](int ks, int i) {
+      const unsigned o = (unsigned)ks * S * 1024u + i * sofA;
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        ra[s] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsA, voff, o + s * 1024u, 0));
-        rb0[s] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsB, voff, o + s * 1024u, 0));
-        rb1[s] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsB, vofB1, o + s * 1024u, 0));
-      }
+      for (int s = 0; s < S; ++s)
+        a[i][s] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsA, voff, o + s * 1024u, 0));
     };
-    // (s, t) with s + t <= S - 1, level l = s + t; consecutive products go to different accumulators
-    auto mma = [&](const v4i(&ra)[S], const v4i(&rb0)[S], const v4i(&rb1)[S]) {
+    auto load_b = [&](int ks, int j0) {
+      const unsigned o = (unsigned)ks * S * 1024u;
 #pragma unroll
       for (int s = 0; s < S; ++s)
 #pragma unroll
-        for (int t = 0; t + s < S; ++t) {
-          acc[0][s + t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ra[s], rb0[t], acc[0][s + t], 0, 0, 0);
-          acc[1][s + t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ra[s], rb1[t], acc[1][s + t], 0, 0, 0);
-        }
+        for (int j = j0; j < j0 + 2; ++j)
+          b[j][s] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsB, voff, o + j * sofB + s * 1024u, 0));
     };
-    // Two register sets, one step of look-ahead each and no copies (a copy waits for its load at once).  The wave walks an
-    // even number of steps, rb + 1 or rb + 2: the extra one is the zero step packed past the diagonal (k* exists there:
-    // rb even < nks - 1).  The last look-ahead reloads the last step (in bounds, unused): the body has no branch.
-    const int n = (rb | 1) + 1;
-    load(0, a, b0, b1);
+    // (s, t) with s + t <= S - 1, level l = s + t; consecutive products go to different accumulators
+    auto mma = [&](int i, int j0) {
+#pragma unroll
+      for (int s = 0; s < S; ++s)
+#pragma unroll
+        for (int t = 0; t + s < S; ++t)
+#pragma unroll
+          for (int j = j0; j < j0 + 2; ++j)
+            acc[i][j][s + t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i][s], b[j][t], acc[i][j][s + t], 0, 0, 0);
+    };
+    // (the first step's loads in the order of their use, as every later step's: the wait counts of the loop body are those of
+    // the worse of its two entries)
+    load_a(0, 0);
+    load_b(0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    load_a(0, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    load_b(0, 2);
 #pragma unroll 1
-    for (int ks = 0; ks < n; ks += 2) {
-      load(ks + 1, na, nb0, nb1);
-      __builtin_amdgcn_sched_barrier(0);   // keep the loads here: hipcc otherwise sinks them next to their first use
-      mma(a, b0, b1);
-      load(min(ks + 2, n - 1), a, b0, b1);
+    for (int ks = 0; ks < n; ++ks) {
+      // the look-ahead past the last step reloads the last step (in bounds, unused): the body has no branch.
+      // sched_barrier: hipcc otherwise sinks the loads next to their first use
+      const int nx = min(ks + 1, n - 1);
       __builtin_amdgcn_sched_barrier(0);
-      mma(na, nb0, nb1);
+      mma(0, 0);
+      __builtin_amdgcn_sched_barrier(0);   // (A1 and B23, loaded last, are still in flight here)
+      mma(1, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      load_b(nx, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      mma(0, 2);
+      __builtin_amdgcn_sched_barrier(0);
+      load_a(nx, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      mma(1, 2);
+      __builtin_amdgcn_sched_barrier(0);
+      load_a(nx, 1);
+      load_b(nx, 2);
     }
 
-    // epilogue: v = (exact level sum, rounded once) x 2^(row scale); sum of v^2 over the wave's rows in register order
+    // epilogue: v = (exact level sum, rounded once) x 2^(row scale); sum of v^2 over the wave's rows.  The order is the one of the
+    // 32 x 32 C layout, whose lane half h held rows 4 h + {0-3, 8-11, 16-19, 24-27} as ONE fma chain: here lane group g = lane >> 4
+    // holds rows 4 g + reg of the upper (a = 0) and lower (a = 1) 16-row tile, so the chain of half h runs through group h (rows
+    // 4 h + 0-3), group h + 2 (+ 8), group h (+ 16), group h + 2 (+ 24), handed over by three cross-lane moves.  Every lane runs
+    // both legs of a tile; the leg that does not belong to its group computes a value nobody reads.
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = rb * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-      const double sc = p.wscale[row];
+    for (int j = 0; j < 4; ++j) {
+      double s = 0.0;
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        int32_t lv[S];
+      for (int a = 0; a < 2; ++a) {
+        double v[4];
 #pragma unroll
-        for (int l = 0; l < S; ++l) lv[l] = acc[c][l][i];
-        const double v = i8_combine<S>(lv) * sc;
-        ss[c] = fma(v, v, ss[c]);
-        __builtin_amdgcn_sched_barrier(0);   // one output at a time: hoisting all 224 accumulator reads spills
+        for (int i = 0; i < 4; ++i) {
+          const int row = rb * 32 + 16 * a + 4 * (lane >> 4) + i;
+          int32_t lv[S];
+#pragma unroll
+          for (int l = 0; l < S; ++l) lv[l] = acc[a][j][l][i];
+          v[i] = i8_combine<S>(lv) * p.wscale[row];
+          __builtin_amdgcn_sched_barrier(0);   // one output at a time: hoisting all 224 accumulator reads spills
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s = fma(v[i], v[i], s);   // groups 0, 1: their rows of this tile
+        s = __shfl_xor(s, 32);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s = fma(v[i], v[i], s);   // groups 2, 3: theirs, on top
+        if (a == 0) s = __shfl_xor(s, 32);
       }
+      ss[j] = s;   // groups 2, 3: the chain of half 0, of half 1
     }
   }
 #pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const double o = __shfl_xor(ss[c], 32);
-    if (lane < 32) red[wave][c * 32 + lane] = ss[c] + o;   // rows 4 h + ...: lane half 0's sum + half 1's
+  for (int j = 0; j < 4; ++j) {
+    const double o = __shfl_xor(ss[j], 16);
+    if ((lane >> 4) == 2) red[wave][j * 16 + (lane & 15)] = ss[j] + o;   // half 0's sum + half 1's
   }
   __syncthreads();
   if (tid < I8_CANDS) {

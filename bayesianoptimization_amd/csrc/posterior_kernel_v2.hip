@@ -316,9 +316,9 @@ __global__ __launch_bounds__(WAVES * 64, 4) void posterior_kernel_v2(PostArgs2 p
 // memory each pair of points cost the wave four s_load_dwordx16 + s_waitcnt round trips per iteration, which left the
 // fp64 VALU — the unit this kernel is bound by — idle about 40 % of the time (14.2 ms per C3 pass).
 // DIG = S > 0 (posterior_i8.hip): the same k* values and partial means, but the slab holds the S int8 digit planes of
-// k* (i8_digits.h) in the B-operand order of v_mfma_i32_32x32x32_i8 — [candidate block of 32][32 train points][plane]
-// [lane] 16 bytes, lane 32 h + c = candidate c, train points 16 h ... 16 h + 15 — written as one 16-byte store per plane
-// and 16 train points.
+// k* (i8_digits.h) in the operand order of v_mfma_i32_16x16x64_i8 (i8_frag_index) — [candidate block of 16][64 train points]
+// [plane][lane] 16 bytes, lane 16 g + c = candidate c, train points 16 g ... 16 g + 15 — written as one 16-byte store per plane
+// and 16 train points: a wave's store instruction is 1 KiB, four candidate blocks of 256 contiguous bytes (two whole lines) each.
 constexpr int GEN_CH = 64;
 template <int DP, int KERNEL, int DIG = 0>
 __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict__ Xs, const double* __restrict__ alpha,
@@ -352,7 +352,8 @@ __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict
     __syncthreads();
     if (DIG > 0 && live) {
       // 16 train points at a time: the digit planes of 16 k* values are one 16-byte operand chunk per plane
-      uint4* Kd = reinterpret_cast<uint4*>(Kst) + ((ml >> 5) * (int64_t)(NP / 32) * DIG) * 64 + (ml & 31);
+      uint4* Kd = reinterpret_cast<uint4*>(Kst);
+      const int64_t cb = i8_kd_block(ml >> 4, NP);
 #pragma unroll 1
       for (int kg = 0; kg < GEN_CH; kg += 16) {
         constexpr int DS = DIG > 0 ? DIG : 5;   // (the fp64 instantiations compile this branch too)
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict
           }
         }
         const int k = kc + kg;   // multiple of 16
-        uint4* dst = Kd + ((int64_t)(k >> 5) * DIG) * 64 + ((k >> 4) & 1) * 32;
+        uint4* dst = Kd + i8_frag_index<DS>(cb, k, 0, (int)(ml & 15));
 #pragma unroll
         for (int t = 0; t < DIG; ++t) {
           const uint32_t x = t ? 0x80808080u : 0u;   // planes below the leading one: byte - 128 (i8_digit_byte)
