@@ -247,6 +247,19 @@ __global__ __launch_bounds__(256, 1) void posterior_i8_kernel(I8Args p) {
 // the generation's grid ends with the device's compute units full (GPBO_KSTAR_GB still caps it).  The byte bound I8_SLAB_BYTES is
 // a constant of the rule: the debug build's slab-size switch (GPBO_I8_SLAB_MB, which produced the table quoted there) went with
 // the plain byte rule, so another bound is probed by rebuilding.
+// One slab's launch: a workgroup per (128-row chunk, 64-candidate tile of the slab), the chunk outermost (heaviest first).  `part`
+// is [nchunks][Mp]; the slab holds the candidates m0 ... m0 + ldk (ldk a multiple of 64).
+static int launch_i8_gemm(gpbo_ctx* ctx, const uint4* Wd, const double* wscale, const uint4* Kd, double* part, int64_t NP, int64_t Mp,
+                          int nchunks, int64_t ldk, int64_t m0) {
+  I8Args a;
+  a.Wd = Wd; a.wscale = wscale; a.Kd = Kd; a.part = part;
+  a.NP = (int)NP; a.Mp = Mp; a.nchunks = nchunks; a.n_ctiles = (int)(ldk / I8_CANDS); a.m0 = m0;
+  const int64_t nblocks = (int64_t)a.n_ctiles * a.nchunks;
+  posterior_i8_kernel<I8_S><<<dim3((unsigned)nblocks), dim3(256), 0, ctx->stream>>>(a);
+  GPBO_HIP(ctx, hipGetLastError());
+  return GPBO_OK;
+}
+
 int launch_posterior_slab_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
   if (m.NP > I8_NP_MAX || m.NP % 64) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: the int8 GEMM serves NP <= 16384");
   int rc;
@@ -259,14 +272,74 @@ int launch_posterior_slab_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan
   for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
     const int64_t ldk = (Mp - m0 < ms) ? (Mp - m0) : ms;
     if ((rc = launch_kstar_digits(ctx, m, ctx->kst, ldk, Mp, m0, plan.mu_chunks))) return rc;
-    I8Args a;
-    a.Wd = m.Wd; a.wscale = m.wscale; a.Kd = reinterpret_cast<const uint4*>(ctx->kst); a.part = ctx->part;
-    a.NP = (int)m.NP; a.Mp = Mp; a.nchunks = plan.part_chunks; a.n_ctiles = (int)(ldk / I8_CANDS); a.m0 = m0;
-    const int64_t nblocks = (int64_t)a.n_ctiles * a.nchunks;
-    posterior_i8_kernel<I8_S><<<dim3((unsigned)nblocks), dim3(256), 0, ctx->stream>>>(a);
-    GPBO_HIP(ctx, hipGetLastError());
+    if ((rc = launch_i8_gemm(ctx, m.Wd, m.wscale, reinterpret_cast<const uint4*>(ctx->kst), ctx->part, m.NP, Mp, plan.part_chunks, ldk, m0)))
+      return rc;
   }
   return GPBO_OK;
 }
 
 }  // namespace gpbo
+
+#ifdef GPBO_DEBUG   // the stages of the int8 pass alone (include/gpbo.h, "debug build"): tests/test_gpu_int8_exact.py
+using namespace gpbo;
+
+static bool i8_debug_np_ok(int64_t NP) { return NP >= 64 && NP <= I8_NP_MAX && NP % 64 == 0; }
+
+int gpbo_debug_i8_pack_w(gpbo_ctx* ctx, const double* W, int64_t N, int64_t NP, void* Wd_out, int* wexp_out, double* wscale_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!W || !Wd_out || !wexp_out || !wscale_out || !i8_debug_np_ok(NP) || N < 1 || N > NP)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_i8_pack_w: bad arguments (NP a multiple of 64 in [64, 16384], 1 <= N <= NP)");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  Model m;   // a scratch model that owns W, Wd and wscale only: no slot of the context is touched
+  m.N = N; m.NP = NP;
+  auto done = [&](int code) {
+    if (m.W) (void)hipFree(m.W);
+    if (m.Wd) (void)hipFree(m.Wd);
+    if (m.wscale) (void)hipFree(m.wscale);
+    return code;
+  };
+  const size_t sq = (size_t)NP * NP * sizeof(double);
+  if (hipMalloc((void**)&m.W, sq) != hipSuccess) return done(GPBO_ERR_HIP);
+  if (hipMemcpy(m.W, W, sq, hipMemcpyHostToDevice) != hipSuccess) return done(GPBO_ERR_HIP);
+  int rc = pack_wd(ctx, m);
+  if (rc) return done(rc);
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return done(GPBO_ERR_HIP);
+  const size_t wd_bytes = (size_t)i8_wd_block(NP / 16) * I8_S * 64 * sizeof(uint4);
+  if (hipMemcpy(Wd_out, m.Wd, wd_bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(GPBO_ERR_HIP);
+  if (hipMemcpy(wscale_out, m.wscale, (size_t)NP * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(GPBO_ERR_HIP);
+  if (hipMemcpy(wexp_out, m.wscale + NP, (size_t)NP * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return done(GPBO_ERR_HIP);
+  return done(GPBO_OK);
+}
+
+int gpbo_debug_i8_gemm(gpbo_ctx* ctx, const void* Wd, const double* wscale, const void* Kd, int64_t NP, int64_t M, double* part_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!Wd || !wscale || !Kd || !part_out || !i8_debug_np_ok(NP) || M < I8_CANDS || M % I8_CANDS || M > (1 << 20))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_i8_gemm: bad arguments (NP a multiple of 64 in [64, 16384], M a multiple of 64)");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  const int nchunks = (int)((NP + I8_ROWS - 1) / I8_ROWS);
+  const size_t wd_bytes = (size_t)i8_wd_block(NP / 16) * I8_S * 64 * sizeof(uint4);
+  const size_t kd_bytes = (size_t)M * NP * I8_S;
+  const size_t part_bytes = (size_t)nchunks * M * sizeof(double);
+  uint4 *dW = nullptr, *dK = nullptr;
+  double *dS = nullptr, *dP = nullptr;
+  auto done = [&](int code) {
+    if (dW) (void)hipFree(dW);
+    if (dK) (void)hipFree(dK);
+    if (dS) (void)hipFree(dS);
+    if (dP) (void)hipFree(dP);
+    return code;
+  };
+  if (hipMalloc((void**)&dW, wd_bytes) != hipSuccess || hipMalloc((void**)&dK, kd_bytes) != hipSuccess ||
+      hipMalloc((void**)&dS, (size_t)NP * sizeof(double)) != hipSuccess || hipMalloc((void**)&dP, part_bytes) != hipSuccess)
+    return done(GPBO_ERR_HIP);
+  if (hipMemcpy(dW, Wd, wd_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dK, Kd, kd_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(dS, wscale, (size_t)NP * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(dP, 0xff, part_bytes) != hipSuccess)   // NaN where the kernel writes nothing
+    return done(GPBO_ERR_HIP);
+  const int rc = launch_i8_gemm(ctx, dW, dS, dK, dP, NP, M, nchunks, M, 0);
+  if (rc) return done(rc);
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return done(GPBO_ERR_HIP);
+  if (hipMemcpy(part_out, dP, part_bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(GPBO_ERR_HIP);
+  return done(GPBO_OK);
+}
+#endif  // GPBO_DEBUG

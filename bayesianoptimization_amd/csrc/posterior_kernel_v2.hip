@@ -492,3 +492,48 @@ int launch_posterior_fused(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& 
 }
 
 }  // namespace gpbo
+
+#ifdef GPBO_DEBUG   // the k* generation alone, both branches side by side (include/gpbo.h, "debug build"): tests/test_gpu_int8_exact.py
+using namespace gpbo;
+
+int gpbo_debug_i8_kstar_digits(gpbo_ctx* ctx, int64_t NP, int64_t m0, int64_t ldk, void* Kd_out, double* kst_out, double* mu_part_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  Model& m = ctx->models[0];
+  if (!m.fitted || ctx->pending_info[0]) GPBO_FAIL(ctx, GPBO_ERR_STATE, "debug_i8_kstar_digits: model slot 0 has not been fitted");
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "debug_i8_kstar_digits: no candidates resident (call gpbo_set_candidates)");
+  if (ctx->d_c != m.d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_i8_kstar_digits: candidate dimension differs from the fitted model");
+  const int64_t Mp = round_up(ctx->M, POST_CANDS);
+  if (!Kd_out || !kst_out || !mu_part_out || m0 < 0 || ldk < 64 || m0 % 64 || ldk % 64 || m0 + ldk > Mp)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_i8_kstar_digits: bad arguments (m0, ldk multiples of 64 inside the padded candidate set)");
+  if (m.NP > I8_NP_MAX || m.NP % 64) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "debug_i8_kstar_digits: the int8 GEMM serves NP <= 16384");
+  if (NP != m.NP)   // the caller sized its buffers from NP: refuse before anything is written
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_i8_kstar_digits: NP is not the padded size of the model in slot 0");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  const int nchunks = (int)((m.NP + POST_ROWS - 1) / POST_ROWS);
+  int rc;
+  if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * m.DP))) return rc;
+  if ((rc = ensure(ctx, &ctx->mu_part, &ctx->cap_mu_part, (int64_t)nchunks * Mp))) return rc;
+  if ((rc = launch_prescale(ctx, ctx->Xc, ctx->M, m.d, m.DP, m.ls, ctx->Xcs, Mp))) return rc;
+  const size_t kd_bytes = (size_t)ldk * m.NP * I8_S, kst_bytes = (size_t)ldk * m.NP * sizeof(double);
+  void* dKd = nullptr;     // slabs of their own: the context's slab workspace keeps its size
+  double* dKst = nullptr;
+  auto done = [&](int code) {
+    if (dKd) (void)hipFree(dKd);
+    if (dKst) (void)hipFree(dKst);
+    return code;
+  };
+  if (hipMalloc(&dKd, kd_bytes) != hipSuccess || hipMalloc((void**)&dKst, kst_bytes) != hipSuccess) return done(GPBO_ERR_HIP);
+  for (int which = 0; which < 2; ++which) {   // 0: the digit branch, 1: the fp64 branch; the partial means of each
+    rc = which ? launch_kstar_slab(ctx, m, dKst, ldk, Mp, m0, nchunks) : launch_kstar_digits(ctx, m, dKd, ldk, Mp, m0, nchunks);
+    if (rc) return done(rc);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return done(GPBO_ERR_HIP);
+    for (int q = 0; q < nchunks; ++q)
+      if (hipMemcpy(mu_part_out + ((int64_t)which * nchunks + q) * ldk, ctx->mu_part + (int64_t)q * Mp + m0, (size_t)ldk * sizeof(double),
+                    hipMemcpyDeviceToHost) != hipSuccess)
+        return done(GPBO_ERR_HIP);
+  }
+  if (hipMemcpy(Kd_out, dKd, kd_bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(GPBO_ERR_HIP);
+  if (hipMemcpy(kst_out, dKst, kst_bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(GPBO_ERR_HIP);
+  return done(GPBO_OK);
+}
+#endif  // GPBO_DEBUG

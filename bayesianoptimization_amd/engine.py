@@ -664,6 +664,58 @@ class GpEngine:
                                               float(beta), dptr(Cm)))
         return Cm
 
+    # the stages of the int8 posterior pass alone (posterior_i8.hip; S = 7 digit planes, operands as raw int8 in fragment order).
+    # I8_S and _i8_wd_bytes restate i8_digits.h's I8_S and i8_wd_block: tests/test_i8_reference_host.py holds them to the header.
+    I8_S = 7
+
+    @staticmethod
+    def _i8_wd_bytes(NP: int) -> int:
+        q = NP // 64
+        return (NP // 16 + 2 * q * (q - 1)) * GpEngine.I8_S * 64 * 16
+
+    def debug_i8_pack_w(self, W, N: int):
+        """wd_row_scale_kernel + wd_pack_kernel on W (NP x NP): (digit buffer int8, row exponents int32, row scales)."""
+        self._need_debug("gpbo_debug_i8_pack_w")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        NP = W.shape[0]
+        if W.ndim != 2 or W.shape[1] != NP or NP % 64 or not 64 <= NP <= 16384:
+            raise ValueError("debug_i8_pack_w: W must be NP x NP, NP a multiple of 64 in [64, 16384]")
+        Wd = np.empty(self._i8_wd_bytes(NP), dtype=np.int8)
+        wexp = np.empty(NP, dtype=np.int32)
+        wscale = np.empty(NP)
+        self._check(self._lib.gpbo_debug_i8_pack_w(self._h, dptr(W), int(N), NP, Wd.ctypes.data_as(C.c_void_p),
+                                                   wexp.ctypes.data_as(C.POINTER(C.c_int)), dptr(wscale)))
+        return Wd, wexp, wscale
+
+    def debug_i8_kstar_digits(self, NP: int, m0: int, ldk: int):
+        """The k* generation of slot 0's model (padded size NP) for the resident candidates [m0, m0 + ldk): (digit slab int8,
+        fp64 slab [NP][ldk], partial means [2][ceil(NP / 256)][ldk]: digit branch, fp64 branch).  The library refuses an NP that is
+        not the fitted model's before it writes."""
+        self._need_debug("gpbo_debug_i8_kstar_digits")
+        if NP % 64 or not 64 <= NP <= 16384 or ldk < 64:
+            raise ValueError("debug_i8_kstar_digits: NP a multiple of 64 in [64, 16384], ldk >= 64")
+        Kd = np.empty(int(ldk) * NP * self.I8_S, dtype=np.int8)
+        kst = np.empty((NP, int(ldk)))
+        mu_part = np.empty((2, (NP + 255) // 256, int(ldk)))
+        self._check(self._lib.gpbo_debug_i8_kstar_digits(self._h, int(NP), int(m0), int(ldk), Kd.ctypes.data_as(C.c_void_p), dptr(kst),
+                                                         dptr(mu_part)))
+        return Kd, kst, mu_part
+
+    def debug_i8_gemm(self, Wd, wscale, Kd, NP: int, M: int):
+        """posterior_i8_kernel on raw operands: part [ceil(NP / 128)][M]."""
+        self._need_debug("gpbo_debug_i8_gemm")
+        Wd = np.ascontiguousarray(Wd, dtype=np.int8)
+        Kd = np.ascontiguousarray(Kd, dtype=np.int8)
+        wscale = np.ascontiguousarray(wscale, dtype=np.float64)
+        if NP % 64 or not 64 <= NP <= 16384 or M % 64 or M < 64:
+            raise ValueError("debug_i8_gemm: NP a multiple of 64 in [64, 16384], M a multiple of 64")
+        if Wd.size != self._i8_wd_bytes(NP) or Kd.size != M * NP * self.I8_S or wscale.size != NP:
+            raise ValueError("debug_i8_gemm: operand sizes do not match NP and M")
+        part = np.empty(((NP + 127) // 128, M))
+        self._check(self._lib.gpbo_debug_i8_gemm(self._h, Wd.ctypes.data_as(C.c_void_p), dptr(wscale), Kd.ctypes.data_as(C.c_void_p),
+                                                 NP, M, dptr(part)))
+        return part
+
     def gemm_bench(self, m, n, k, b_trans=True, a_trans=False, lower_only=False, iters=10) -> dict:
         self._need_debug("gpbo_debug_gemm_bench")
         out = np.zeros(2)

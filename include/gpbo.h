@@ -455,6 +455,22 @@ int gpbo_debug_latency_probe(gpbo_ctx* ctx, long long* out, int n);
  * v_fma_f64 (scalar-operand) only, 2: 16 MFMA + 256 VALU, 3: 16 + 128, 4: 8 + 256.
  * out[3] = { kernel ms, MFMA TFLOP/s, VALU TFLOP/s }. */
 int gpbo_hybrid_probe(gpbo_ctx* ctx, int iters, int cfg, double* out);
+/* The stages of the int8 posterior pass (posterior_i8.hip) alone, each through the production kernels and launch rule, so that
+ * a test can compare them with exact integer arithmetic on the host (tests/i8_reference.py).  S = 7 digit planes; operands in
+ * fragment order, [block of 16 items][64-step][plane][lane 16 g + item] 16 bytes.  None of them touches a model slot.
+ * gpbo_debug_i8_pack_w: wd_row_scale_kernel + wd_pack_kernel on a host matrix W (NP x NP row-major, NP a multiple of 64, 1 <= N
+ * <= NP): Wd_out = the raw digit buffer of the lower triangle (block b of 16 rows holds the steps 0 ... b / 4: (NP / 16 + 2 q (q - 1))
+ * S 64 fragments, q = NP / 64), wexp_out / wscale_out (NP,) = the rows' exponents and the epilogue's powers of two. */
+int gpbo_debug_i8_pack_w(gpbo_ctx* ctx, const double* W, int64_t N, int64_t NP, void* Wd_out, int* wexp_out, double* wscale_out);
+/* The k* generation for the model of slot 0 and the resident candidates [m0, m0 + ldk) (multiples of 64 inside the candidate set
+ * padded to 128), by its digit branch and by its fp64 branch.  NP = the model's padded size, by which the caller sized the
+ * buffers (GPBO_ERR_INVALID if it is not): Kd_out = the digit slab (ldk NP S bytes), kst_out = the fp64 slab
+ * [NP][ldk], mu_part_out [2][ceil(NP / 256)][ldk] = the partial means of the digit branch, then of the fp64 branch. */
+int gpbo_debug_i8_kstar_digits(gpbo_ctx* ctx, int64_t NP, int64_t m0, int64_t ldk, void* Kd_out, double* kst_out, double* mu_part_out);
+/* posterior_i8_kernel on caller-supplied operands (raw bytes: digits the packers never produce are allowed): Wd as
+ * gpbo_debug_i8_pack_w returns it, wscale (NP,), Kd (M NP S bytes), M a multiple of 64; part_out [ceil(NP / 128)][M] = the
+ * sums of v^2 per 128-row chunk. */
+int gpbo_debug_i8_gemm(gpbo_ctx* ctx, const void* Wd, const double* wscale, const void* Kd, int64_t NP, int64_t M, double* part_out);
 #endif /* GPBO_DEBUG */
 
 #ifdef __cplusplus
