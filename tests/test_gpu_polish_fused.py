@@ -149,6 +149,41 @@ def test_ei_and_poi_evaluations_agree_with_the_host_formula_to_rounding(debug_en
         scale_g = norm.cdf(z)[:, None] * np.abs(dmu) + norm.pdf(z)[:, None] * np.abs(dsd) if acq == O.EI else \
             (norm.pdf(z) / sd)[:, None] * (np.abs(dmu) + np.abs(z)[:, None] * np.abs(dsd))
         assert np.all(np.abs(got["g"] - g) <= 1e-10 * (1.0 + z * z)[:, None] * scale_g + 1e-300)
+    # The same evaluations over the whole z range (both tails, |z| = 1, the underflow edge), against the 50-digit truth of
+    # tests/acq_truth.py on the mu, sd, dmu, dsd the evaluation ITSELF returns: only the formula — 0.5 erfc(-z / sqrt2), exp, the
+    # coefficients ca, cs — is under test, at 8 c_ref (c_ref: SciPy's arithmetic on the same inputs; acq_truth's error model).
+    # Measured on an MI355X, worst c over the sweep (SciPy's on the same inputs): f EI 0.44 (0.51), f POI 0.99 (1.11), gradient — the
+    # coefficients ca, cs — EI 0.95 (1.07), POI 0.86 (1.23).
+    import acq_truth as T
+
+    wide = np.vstack([np.random.RandomState(6).uniform(size=(52, 4)), X[:12] + 10.0 ** np.linspace(-5, -2, 12)[:, None]])
+    first = _polish_eval(eng, O.UCB, 1.0, 0.0, ym, ys, wide)
+    s50, lo, hi = float(np.median(first["sd"])), float(first["mu"].min()), float(first["mu"].max())
+    z_seen, worst = [], {}
+    for y_max in (lo - 20 * s50, float(np.quantile(first["mu"], 0.25)), float(np.median(first["mu"])), float(np.quantile(first["mu"], 0.75)),
+                  hi + 2 * s50, hi + 10 * s50):
+        for acq, name in ((O.EI, "ei"), (O.POI, "poi")):
+            got = _polish_eval(eng, acq, xi, y_max, ym, ys, wide)
+            assert np.array_equal(got["mu"], first["mu"]) and np.array_equal(got["sd"], first["sd"])
+            tr = T.acq_truth(got["mu"], got["sd"], y_max, xi, got["dmu"], got["dsd"])
+            assert tr["ok"].all()
+            ref_f = T.reference_values(got["mu"], got["sd"], y_max, xi)[0 if acq == O.EI else 1]
+            ref_g = T.reference_gradients(got["mu"], got["sd"], got["dmu"], got["dsd"], y_max, xi)[0 if acq == O.EI else 1]
+            c_ref_f = T.worst(T.constants(ref_f, tr[name], tr["w_" + name]))
+            c_ref_g = T.worst(T.constants(ref_g, tr["g_" + name], tr["w_g_" + name]))
+            c_f = T.worst(T.constants(-got["f"], tr[name], tr["w_" + name]))
+            c_g = T.worst(T.constants(got["g"], tr["g_" + name], tr["w_g_" + name]))
+            print(f"polish eval {name} y_max={y_max:+.3f}: f c_dev {c_f:.3f} c_ref {c_ref_f:.3f}; g c_dev {c_g:.3f} c_ref {c_ref_g:.3f}; "
+                  f"z [{tr['z'].min():.1f}, {tr['z'].max():.1f}]")
+            for k, v in (("f_" + name, (c_f, c_ref_f)), ("g_" + name, (c_g, c_ref_g))):
+                worst[k] = tuple(max(a, b) for a, b in zip(worst.get(k, (0.0, 0.0)), v))
+            assert c_f <= 8.0 * c_ref_f and c_g <= 8.0 * c_ref_g
+            z_seen.append(tr["z"])
+            assert np.mean(tr["t_" + name] >= T.DBL_MIN) >= 0.5 or y_max > hi + 8 * s50
+    print("polish eval worst (device, reference):", {k: (round(a, 3), round(b, 3)) for k, (a, b) in worst.items()})
+    z_seen = np.concatenate(z_seen)
+    assert z_seen.min() < -38.5 and z_seen.max() > 38.5
+    assert all(np.sum((z_seen >= a) & (z_seen < b)) >= 8 for a, b in ((-38.5, -8), (-8, -1), (-1, 1), (1, 8), (8, 38.5)))
 
 
 def _both(eng, switch, acq, param, y_max, ym, ys, seeds, box, max_iter=0):

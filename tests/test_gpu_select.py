@@ -40,6 +40,13 @@ def _cases():
     out.append(("short_last_block", np.concatenate([np.full(4096, 5.0), rng.randn(100)])))
     a = rng.randn(M); a[a > 0] = np.inf; a[:10] = -np.inf
     out.append(("infinities", a))
+    # the default form's size edges: one workgroup of 4 x 256 items is its own merge / two workgroups and the merge launch (1024 / 1025);
+    # ITEMS 4 -> 16 (2^18 / 2^18 + 1)
+    rng = np.random.RandomState(1)
+    out += [(f"random_{M}", rng.randn(M)) for M in (1023, 1024, 1025, (1 << 18) - 1, 1 << 18, (1 << 18) + 1)]
+    out.append(("all_equal_1025", np.zeros(1025)))          # a plateau across the one-workgroup edge: the last item alone in block 2
+    a = rng.randn(1025); a[[7, 1023, 1024]] = np.nan
+    out.append(("nans_1025", a))
     return out
 
 
