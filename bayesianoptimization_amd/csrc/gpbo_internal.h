@@ -99,7 +99,7 @@ struct LookAhead {
 
 struct gpbo_ctx {
   int device = 0;
-  int compute_units = 0;   // of the device, asked once (launch_posterior_slab_i8: the slab width that fills them)
+  int compute_units = 0;   // of the device, asked once (prepare_posterior_i8: the slab width that fills them)
   hipStream_t stream = nullptr;
   std::string err;
   gpbo::Model models[GPBO_MAX_MODELS];
@@ -406,12 +406,6 @@ int ensure(gpbo_ctx* ctx, T** p, int64_t* cap, int64_t need) {
   return GPBO_OK;
 }
 
-// Candidates per k* slab of a slab walk (posterior_kernel.hip): what the workspace budget holds at bytes_per_cand — GPBO_KSTAR_GB
-// (default 4 GB), clipped to 80 % of what the device could give the slab; hipMemGetInfo is asked only when the slab buffer would
-// have to grow (it costs tens of microseconds per call) — and at most `cap` and `preferred`, rounded down to 128, at most Mp.
-// Below 128 the caller decides: the fp64 / fp32 walks fail, the int8 walk takes 128.
-int64_t kstar_slab_width(gpbo_ctx* ctx, int64_t Mp, int64_t bytes_per_cand, int64_t cap, int64_t preferred = INT64_MAX);
-
 // ---- launchers implemented in the kernel translation units ---------------------------------
 // fit_kernels.hip
 int launch_prescale(gpbo_ctx* ctx, const double* X, int64_t n, int d, int DP, const double* ls,
@@ -482,15 +476,20 @@ struct PostEnds {
 };
 // The launchers of the paths (PostPath: posterior_plan.h); plan_posterior sizes their grids and ctx->part / ctx->mu_part.
 int launch_posterior_fused(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan, const PostEnds& ends);   // Fused256, Fused512
-int launch_posterior_slab(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan);                          // SlabF64
+// The slab paths (the walk: posterior_kernel.hip): the k* slab of candidates [m0, m0 + ldk) as fp64 values, fp32 values or int8
+// digit planes (+ the partial means) ...
 int launch_kstar_slab(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks);
-int launch_kstar_digits(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks);  // posterior_kernel_v2.hip
-int launch_posterior_slab_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan);                       // posterior_i8.hip
+int launch_kstar_slab_f32(gpbo_ctx* ctx, Model& m, float* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks);
+int launch_kstar_digits(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks);
+// ... and each path's GEMM over that slab: the partial sums of squares of candidates [m0, m0 + ldk) into ctx->part [part_chunks][Mp]
+int launch_slab_gemm_f64(gpbo_ctx* ctx, Model& m, const double* slab, int64_t ldk, int64_t m0, int64_t Mp, int part_chunks);
+int launch_slab_gemm_f32(gpbo_ctx* ctx, Model& m, const float* slab, int64_t ldk, int64_t m0, int64_t Mp, int part_chunks);   // posterior_kernel_f32.hip
+int launch_slab_gemm_i8(gpbo_ctx* ctx, Model& m, const void* slab, int64_t ldk, int64_t m0, int64_t Mp, int part_chunks);      // posterior_i8.hip
+int prepare_posterior_i8(gpbo_ctx* ctx, Model& m);   // before the first int8 slab: W's digit planes (once per fit), the device's compute units
 // posterior_cov.hip
 int launch_posterior_cov(gpbo_ctx* ctx, Model& m, int64_t M, double y_std, double** cov_dev, int64_t* ld_cov);
 // posterior_kernel_f32.hip
 int launch_pack_w32(gpbo_ctx* ctx, Model& m);
-int launch_posterior_slab_f32(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan);
 // acq_kernels.hip
 struct AcqArgs {
   int acq; double param; double y_max; int n_constraints;

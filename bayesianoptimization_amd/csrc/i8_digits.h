@@ -15,7 +15,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "posterior_plan.h"   // I8_NP_MAX: the largest NP the int8 GEMM serves
+#include "posterior_plan.h"   // I8_S, the digits per operand; I8_NP_MAX, the largest NP the int8 GEMM serves
 
 #if defined(__HIPCC__)
 #define GPBO_HD __host__ __device__
@@ -25,7 +25,7 @@
 
 namespace gpbo {
 
-constexpr int I8_S = 7;            // digits per operand: 28 int8 products, truncation ~2^-54 of max_j|W_ij| sum_j k*_j
+// I8_S = 7 digits per operand: 28 int8 products, truncation ~2^-54 of max_j|W_ij| sum_j k*_j
 // the int32 level sums: a level holds <= S products of |digit| <= 128 per train point
 static_assert((int64_t)I8_S * 128 * 128 * I8_NP_MAX < ((int64_t)1 << 31), "int32 level sums overflow at I8_NP_MAX");
 

@@ -25,13 +25,13 @@
 
 #include "gpbo_internal.h"
 #include "i8_digits.h"
+#include "posterior_tile.h"
 
 namespace gpbo {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int I8_CANDS = 64;   // candidates per workgroup (4 blocks of 16)
-constexpr int I8_BUF_FLAGS = 0x00020000;   // gfx9 buffer descriptor word 3: raw buffer, 32-bit data format
 
 // ---- W -> digit planes, once per fit ----------------------------------------------------------------------------------
 // Row exponents: one wave per row, max |W_ij| over the row's N x N lower-triangle part (order-free, so deterministic).
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void wd_pack_kernel(const double* __restrict__
 }
 
 static int pack_wd(gpbo_ctx* ctx, Model& m) {
-  const int64_t nb = m.NP / 16;   // NP is a multiple of 64 (launch_posterior_slab_i8)
+  const int64_t nb = m.NP / 16;   // NP is a multiple of 64 (prepare_posterior_i8)
   int rc;
   if ((rc = ensure(ctx, &m.Wd, &m.cap_Wd, i8_wd_block(nb) * I8_S * 64))) return rc;
   if ((rc = ensure(ctx, &m.wscale, &m.cap_wscale, 2 * m.NP))) return rc;
@@ -96,12 +96,9 @@ static int pack_wd(gpbo_ctx* ctx, Model& m) {
 struct I8Args {
   const uint4* Wd;
   const double* wscale;
-  const uint4* Kd;     // the slab's digit planes (kstar_gen_kernel<.., DIG = I8_S>)
+  const uint4* Kd;     // the slab's digit planes (kstar_gen_kernel<.., SlabI8>)
   double* part;        // [chunk of 128 rows][Mp] sums of squares
-  int NP;
-  int64_t Mp;
-  int nchunks;         // 128-row chunks
-  int n_ctiles;        // 64-candidate tiles of the slab
+  PostGrid g;          // 128-row chunks x 64-candidate tiles of the slab
   int64_t m0;          // first candidate of the slab
 };
 
@@ -110,15 +107,11 @@ __global__ __launch_bounds__(256, 1) void posterior_i8_kernel(I8Args p) {
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
-  const int bid = blockIdx.x;
-  // Heaviest row chunks first; the workgroups resident at any time share a chunk, so its digit planes of W come out of L2.
-  // (Candidate tile outermost instead, so that the row chunks of a tile share its k* digits in L2: 283 ms per C3 pass against 196,
-  // with 256 MB ... 4 GB slabs alike.)
-  const int r = p.nchunks - 1 - bid / p.n_ctiles;
-  const int ct = bid - (bid / p.n_ctiles) * p.n_ctiles;
-  const int nks = p.NP / 64;
+  int r, ct;
+  p.g.map(blockIdx.x, r, ct);
+  const int nks = p.g.NP / 64;
   const int rb = r * (I8_ROWS / 32) + wave;     // this wave's 32 rows: the 16-row blocks 2 rb and 2 rb + 1
-  const bool active = rb < p.NP / 32;           // false only in a ragged last chunk
+  const bool active = rb < p.g.NP / 32;           // false only in a ragged last chunk
 
   __shared__ double red[4][I8_CANDS];
   double ss[4] = {0.0, 0.0, 0.0, 0.0};   // per candidate block: sum of v^2 over the wave's rows (see the epilogue)
@@ -134,9 +127,9 @@ __global__ __launch_bounds__(256, 1) void posterior_i8_kernel(I8Args p) {
     // as the scalar offset), as in posterior_kernel_v2: no 64-bit address arithmetic per load.
     const int n = rb / 2 + 1;                   // 64-steps up to the diagonal: both 16-row blocks hold exactly these
     const uint4* wa = p.Wd + i8_wd_block(2 * rb) * S * 64;
-    const uint4* kb0 = p.Kd + i8_kd_block(4 * ct, p.NP) * S * 64;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wa), 0, 0x7fffffff, I8_BUF_FLAGS);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(kb0), 0, 0x7fffffff, I8_BUF_FLAGS);
+    const uint4* kb0 = p.Kd + i8_kd_block(4 * ct, p.g.NP) * S * 64;
+    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wa), 0, 0x7fffffff, BUF_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(kb0), 0, 0x7fffffff, BUF_FLAGS);
     const unsigned voff = (unsigned)lane * 16u;
     const unsigned sofA = (unsigned)n * S * 1024u, sofB = (unsigned)nks * S * 1024u;   // block strides, scalar like the k walk
     // One operand set is 6 S fragments = 168 registers, so beside 224 accumulators there is ONE set, and each part of it is
@@ -237,12 +230,12 @@ __global__ __launch_bounds__(256, 1) void posterior_i8_kernel(I8Args p) {
   __syncthreads();
   if (tid < I8_CANDS) {
     const double v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-    p.part[(int64_t)r * p.Mp + p.m0 + (int64_t)ct * I8_CANDS + tid] = v;
+    p.part[(int64_t)r * p.g.Mp + p.m0 + (int64_t)ct * I8_CANDS + tid] = v;
   }
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------------
-// SlabI8 (posterior_plan.h): the slab walk of launch_posterior_slab, but the slab is S bytes per element and its width comes from
+// SlabI8 (posterior_plan.h) in the slab walk (launch_posterior_slabs): the slab is I8_S bytes per element and its width comes from
 // i8_slab_width: small enough that the 32 row chunks re-read it from the 256 MB Infinity Cache rather than from HBM, and such that
 // the generation's grid ends with the device's compute units full (GPBO_KSTAR_GB still caps it).  The byte bound I8_SLAB_BYTES is
 // a constant of the rule: the debug build's slab-size switch (GPBO_I8_SLAB_MB, which produced the table quoted there) went with
@@ -253,28 +246,25 @@ static int launch_i8_gemm(gpbo_ctx* ctx, const uint4* Wd, const double* wscale, 
                           int nchunks, int64_t ldk, int64_t m0) {
   I8Args a;
   a.Wd = Wd; a.wscale = wscale; a.Kd = Kd; a.part = part;
-  a.NP = (int)NP; a.Mp = Mp; a.nchunks = nchunks; a.n_ctiles = (int)(ldk / I8_CANDS); a.m0 = m0;
-  const int64_t nblocks = (int64_t)a.n_ctiles * a.nchunks;
-  posterior_i8_kernel<I8_S><<<dim3((unsigned)nblocks), dim3(256), 0, ctx->stream>>>(a);
+  a.g = {(int)NP, Mp, nchunks, (int)(ldk / I8_CANDS)};
+  a.m0 = m0;
+  posterior_i8_kernel<I8_S><<<dim3((unsigned)a.g.blocks()), dim3(256), 0, ctx->stream>>>(a);
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }
 
-int launch_posterior_slab_i8(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
+// ... with the model's own digit planes of W, for one slab of the walk
+int launch_slab_gemm_i8(gpbo_ctx* ctx, Model& m, const void* slab, int64_t ldk, int64_t m0, int64_t Mp, int part_chunks) {
+  return launch_i8_gemm(ctx, m.Wd, m.wscale, static_cast<const uint4*>(slab), ctx->part, m.NP, Mp, part_chunks, ldk, m0);
+}
+
+// What the walk needs before its first int8 slab: the size check, W's digit planes (once per fit) and the device's compute units
+// (once per context: i8_slab_width fills them).
+int prepare_posterior_i8(gpbo_ctx* ctx, Model& m) {
   if (m.NP > I8_NP_MAX || m.NP % 64) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: the int8 GEMM serves NP <= 16384");
   int rc;
   if (!m.wd_valid && (rc = pack_wd(ctx, m))) return rc;
-  const int64_t per_cand = m.NP * I8_S;          // bytes of one candidate's digit planes
   if (!ctx->compute_units) GPBO_HIP(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  // no cap: the kernel's buffer offsets start at its own candidate tile
-  const int64_t ms = i8_slab_width(m.NP, per_cand, kstar_slab_width(ctx, Mp, per_cand, INT64_MAX), ctx->compute_units);
-  if ((rc = ensure(ctx, &ctx->kst, &ctx->cap_kst, (ms * per_cand + 7) / 8))) return rc;
-  for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
-    const int64_t ldk = (Mp - m0 < ms) ? (Mp - m0) : ms;
-    if ((rc = launch_kstar_digits(ctx, m, ctx->kst, ldk, Mp, m0, plan.mu_chunks))) return rc;
-    if ((rc = launch_i8_gemm(ctx, m.Wd, m.wscale, reinterpret_cast<const uint4*>(ctx->kst), ctx->part, m.NP, Mp, plan.part_chunks, ldk, m0)))
-      return rc;
-  }
   return GPBO_OK;
 }
 

@@ -9,6 +9,8 @@
 //   Small      posterior_small.hip      batched GEMV (latency path: predicts of the host optimisers)
 //   Fused256   posterior_kernel_v2.hip  GEN = 1: k* generated inside the MFMA kernel, 8 waves, 256-row chunks
 //   Fused512   posterior_kernel_v2.hip  GEN = 1, 16 waves, 512-row chunks
+// and the three slab paths, which share one walk (launch_posterior_slabs below; the slab's size and caps: slab_spec,
+// posterior_plan.h) and one k* generator (kstar_gen_kernel<.., the path>, posterior_kernel_v2.hip) and differ in their GEMM:
 //   SlabF64    posterior_kernel_v2.hip  GEN = 2: k* slab generated once + fp64 MFMA GEMM
 //   SlabI8     posterior_i8.hip         the same slab as int8 digit planes + int8 MFMA GEMM
 //   SlabF32    posterior_kernel_f32.hip fp32 k* slab + fp32 MFMA GEMM (precision F32)
@@ -49,7 +51,10 @@ __global__ __launch_bounds__(256) void posterior_finalize_kernel(const double* _
   posterior_finalize_elem(ss, mun, y_mean, y_std, mu + m, sd + m, negvar);
 }
 
-int64_t kstar_slab_width(gpbo_ctx* ctx, int64_t Mp, int64_t bytes_per_cand, int64_t cap, int64_t preferred) {
+// Candidates per k* slab: what the workspace budget holds at bytes_per_cand — GPBO_KSTAR_GB (default 4 GB), clipped to 80 % of
+// what the device could give the slab; hipMemGetInfo is asked only when the slab buffer would have to grow (it costs tens of
+// microseconds per call) — and at most `cap`, rounded down to 128, at most Mp.  Below 128 the walk decides.
+static int64_t kstar_slab_width(gpbo_ctx* ctx, int64_t Mp, int64_t bytes_per_cand, int64_t cap) {
   const char* e = getenv("GPBO_KSTAR_GB");      // read per call: the slab-loop test changes it between passes
   const double budget_gb = (e && atof(e) > 0.0) ? atof(e) : 4.0;
   int64_t budget = (int64_t)(budget_gb * 1e9);
@@ -61,8 +66,44 @@ int64_t kstar_slab_width(gpbo_ctx* ctx, int64_t Mp, int64_t bytes_per_cand, int6
       if (avail < budget) budget = avail;
     }
   }
-  const int64_t ms = std::min({budget / bytes_per_cand, cap, preferred}) / 128 * 128;
+  const int64_t ms = std::min(budget / bytes_per_cand, cap) / 128 * 128;
   return std::min(ms, Mp);
+}
+
+// The slab paths: the candidates in slabs of ms, per slab the k* generation into ctx->kst (+ the partial means) and the path's GEMM
+// over it (the partial sums of squares).  The int8 path first makes sure of W's digit planes (prepare_posterior_i8).
+static int launch_posterior_slabs(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
+  int rc;
+  if (plan.path == PostPath::SlabI8 && (rc = prepare_posterior_i8(ctx, m))) return rc;
+  const SlabSpec spec = slab_spec(plan.path, m.NP);
+  int64_t ms = kstar_slab_width(ctx, Mp, spec.bytes_per_cand, spec.offset_cap);
+  if (plan.path == PostPath::SlabI8) ms = i8_slab_width(m.NP, spec.bytes_per_cand, ms, ctx->compute_units);
+  if (ms < 128) {
+    if (!spec.narrow_ok) GPBO_FAIL(ctx, GPBO_ERR_HIP, "posterior: not enough device memory for one k* slab");
+    ms = 128;
+  }
+  if ((rc = ensure(ctx, &ctx->kst, &ctx->cap_kst, slab_doubles(ms, spec.bytes_per_cand)))) return rc;
+  if (ms / 64 * plan.part_chunks > 0x7fffffffLL)   // the GEMM's grid for a full slab: 64-candidate tiles x row chunks
+    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
+  for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
+    const int64_t ldk = std::min(ms, Mp - m0);
+    switch (plan.path) {
+      case PostPath::SlabF64:
+        if ((rc = launch_kstar_slab(ctx, m, ctx->kst, ldk, Mp, m0, plan.mu_chunks))) return rc;
+        if ((rc = launch_slab_gemm_f64(ctx, m, ctx->kst, ldk, m0, Mp, plan.part_chunks))) return rc;
+        break;
+      case PostPath::SlabF32:
+        if ((rc = launch_kstar_slab_f32(ctx, m, reinterpret_cast<float*>(ctx->kst), ldk, Mp, m0, plan.mu_chunks))) return rc;
+        if ((rc = launch_slab_gemm_f32(ctx, m, reinterpret_cast<const float*>(ctx->kst), ldk, m0, Mp, plan.part_chunks))) return rc;
+        break;
+      case PostPath::SlabI8:
+        if ((rc = launch_kstar_digits(ctx, m, ctx->kst, ldk, Mp, m0, plan.mu_chunks))) return rc;
+        if ((rc = launch_slab_gemm_i8(ctx, m, ctx->kst, ldk, m0, Mp, plan.part_chunks))) return rc;
+        break;
+      default: GPBO_FAIL(ctx, GPBO_ERR_STATE, "posterior: not a slab path");
+    }
+  }
+  return GPBO_OK;
 }
 
 static int ensure_posterior_outputs(gpbo_ctx* ctx, Model& m, int64_t Mp) {
@@ -127,9 +168,9 @@ int launch_posterior(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y
     case PostPath::Small: rc = launch_posterior_small(ctx, m, (int)M, y_mean, y_std); break;
     case PostPath::Fused256:
     case PostPath::Fused512: rc = launch_posterior_fused(ctx, m, Mp, plan, ends); break;
-    case PostPath::SlabF64: rc = launch_posterior_slab(ctx, m, Mp, plan); break;
-    case PostPath::SlabI8: rc = launch_posterior_slab_i8(ctx, m, Mp, plan); break;
-    case PostPath::SlabF32: rc = launch_posterior_slab_f32(ctx, m, Mp, plan); break;
+    case PostPath::SlabF64:
+    case PostPath::SlabI8:
+    case PostPath::SlabF32: rc = launch_posterior_slabs(ctx, m, Mp, plan); break;
   }
   ev_end(ctx, T_POST_MAIN);
   if (rc) return rc;

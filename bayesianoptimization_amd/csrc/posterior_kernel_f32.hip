@@ -2,9 +2,9 @@
 //
 // The factorisation (K, L, W = L^-1, alpha) stays in fp64 — it is O(N^3) once per fit and its accuracy
 // decides everything downstream.  What runs in fp32 is the M-scaled part:
-//   kstar_gen_f32_kernel : k* evaluated in fp64 (distance, sqrt, exp) and ROUNDED to fp32 into the slab
-//                          [NP][slab] (half the HBM traffic of the fp64 slab); the means k*.alpha are
-//                          accumulated in fp64 before rounding, so mu keeps fp64 accuracy;
+//   kstar_gen_kernel<.., SlabF32> (posterior_kernel_v2.hip): k* evaluated in fp64 (distance, sqrt, exp) and
+//                          ROUNDED to fp32 into the slab [NP][slab] (half the HBM traffic of the fp64 slab); the
+//                          means k*.alpha are accumulated in fp64 before rounding, so mu keeps fp64 accuracy;
 //   posterior_kernel_f32 : V = W K*^T on v_mfma_f32_16x16x4_f32 (exact f32, 2x the fp64 matrix rate) with W
 //                          rounded to fp32 in fragment order; sum of squares in fp32 inside a 256-row chunk,
 //                          fp64 across lanes / waves / chunks.
@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "gpbo_internal.h"
+#include "posterior_tile.h"
 
 namespace gpbo {
 
@@ -29,10 +30,7 @@ struct PostArgsF32 {
   const float* Wp;      // packed (pack_w32_kernel)
   const float* Kst;     // [NP][ldk]
   double* part;         // [nchunks][Mp]
-  int NP;
-  int64_t Mp;
-  int nchunks;
-  int n_ctiles;
+  PostGrid g;           // (nchunks: chunks of 256 or 512 rows, by the kernel)
   int64_t ldk;
   int64_t m0;
 };
@@ -88,61 +86,6 @@ int launch_pack_w32(gpbo_ctx* ctx, Model& m) {
   return GPBO_OK;
 }
 
-// (train points staged through LDS and read back as broadcasts: see kstar_gen_kernel in posterior_kernel_v2.hip)
-constexpr int GEN32_CH = 64;
-template <int DP, int KERNEL>
-__global__ __launch_bounds__(256) void kstar_gen_f32_kernel(const double* __restrict__ Xs, const double* __restrict__ alpha,
-                                                            const double* __restrict__ Xcs, float* __restrict__ Kst,
-                                                            int64_t ldk, int NP, double* __restrict__ mu_part,
-                                                            int64_t Mp, int64_t m0) {
-  __shared__ __attribute__((aligned(16))) double xs[GEN32_CH * DP];
-  __shared__ double al[GEN32_CH];
-  const int64_t ml = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = ml < ldk;
-  const int k0 = blockIdx.y * POST_ROWS, k1 = min(NP, k0 + POST_ROWS);
-  double xc[DP];
-  {
-    const double* xcp = Xcs + (m0 + (live ? ml : 0)) * DP;
-#pragma unroll
-    for (int t = 0; t < DP; t += 2) {
-      const double2 v = *reinterpret_cast<const double2*>(xcp + t);
-      xc[t] = v.x;
-      xc[t + 1] = v.y;
-    }
-  }
-  double mu = 0.0;
-  for (int kc = k0; kc < k1; kc += GEN32_CH) {
-    __syncthreads();
-    {
-      const double2* src = reinterpret_cast<const double2*>(Xs + (int64_t)kc * DP);
-      double2* dst = reinterpret_cast<double2*>(xs);
-      for (int e = threadIdx.x; e < GEN32_CH * DP / 2; e += 256) dst[e] = src[e];
-      if (threadIdx.x < GEN32_CH) al[threadIdx.x] = alpha[kc + threadIdx.x];
-    }
-    __syncthreads();
-    if (live) {
-#pragma unroll 2
-      for (int kk = 0; kk < GEN32_CH; kk += 2) {
-        const double* xr = xs + kk * DP;
-        double d2a = 0.0, d2b = 0.0;
-#pragma unroll
-        for (int t = 0; t < DP; ++t) {
-          const double da = xc[t] - xr[t], db = xc[t] - xr[DP + t];
-          d2a = fma(da, da, d2a);
-          d2b = fma(db, db, d2b);
-        }
-        const double ka = gpbo_kernel_value<KERNEL>(d2a), kb = gpbo_kernel_value<KERNEL>(d2b);
-        const int k = kc + kk;
-        Kst[(int64_t)k * ldk + ml] = (float)ka;
-        Kst[(int64_t)(k + 1) * ldk + ml] = (float)kb;
-        mu = fma(ka, al[kk], mu);
-        mu = fma(kb, al[kk + 1], mu);
-      }
-    }
-  }
-  if (live) mu_part[(int64_t)blockIdx.y * Mp + m0 + ml] = mu;
-}
-
 // Wave = 32 rows = two 16-row MFMA tiles, workgroup chunk = 256 rows; p.nchunks counts chunks of 256 rows.
 __global__ __launch_bounds__(512, 4) void posterior_kernel_f32(PostArgsF32 p) {
   __shared__ __attribute__((aligned(16))) float Ks[2 * F32_BK * F32_STRIDE];   // 20 KiB
@@ -153,10 +96,9 @@ __global__ __launch_bounds__(512, 4) void posterior_kernel_f32(PostArgsF32 p) {
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
-  const int bid = blockIdx.x;
-  const int r = p.nchunks - 1 - bid / p.n_ctiles;
-  const int ct = bid - (bid / p.n_ctiles) * p.n_ctiles;
-  const int NP = p.NP;
+  int r, ct;
+  p.g.map(blockIdx.x, r, ct);
+  const int NP = p.g.NP;
   const int k_end = min(NP, (r + 1) * CROWS);
   const int n_stages = (k_end + F32_BK - 1) / F32_BK;   // NP is a multiple of 64, so k_end is a multiple of 32
 
@@ -259,7 +201,7 @@ __global__ __launch_bounds__(512, 4) void posterior_kernel_f32(PostArgsF32 p) {
     double v = 0.0;
 #pragma unroll
     for (int w = 0; w < 8; ++w) v += red[w * F32_CANDS + tid];
-    p.part[(int64_t)r * p.Mp + p.m0 + (int64_t)ct * F32_CANDS + tid] = v;
+    p.part[(int64_t)r * p.g.Mp + p.m0 + (int64_t)ct * F32_CANDS + tid] = v;
   }
 }
 
@@ -286,10 +228,9 @@ __global__ __launch_bounds__(512, 4) void posterior_kernel_f32x(PostArgsF32 p) {
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
-  const int bid = blockIdx.x;
-  const int r = p.nchunks - 1 - bid / p.n_ctiles;
-  const int ct = bid - (bid / p.n_ctiles) * p.n_ctiles;
-  const int NP = p.NP;
+  int r, ct;
+  p.g.map(blockIdx.x, r, ct);
+  const int NP = p.g.NP;
   const int k_end = min(NP, (r + 1) * CROWS);
   const int n_stages = k_end / BKX;                       // NP is a multiple of 64
   const int tileA = r * CT + wave, tileB = r * CT + CT - 1 - wave;    // global 32-row tiles (earlier / later)
@@ -302,7 +243,6 @@ __global__ __launch_bounds__(512, 4) void posterior_kernel_f32x(PostArgsF32 p) {
   // offsets (no per-lane 64-bit address arithmetic between the MFMAs; see posterior_kernel_v2.hip)
   const f4* wpA = reinterpret_cast<const f4*>(p.Wp) + ((int64_t)(tA >> 1) * quads * 4 + (tA & 1) * 2) * 64;
   const f4* wpB = reinterpret_cast<const f4*>(p.Wp) + ((int64_t)(tB >> 1) * quads * 4 + (tB & 1) * 2) * 64;
-  constexpr int BUF_FLAGS = 0x00020000;
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4*>(wpA), 0, 0x7fffffff, BUF_FLAGS);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4*>(wpB), 0, 0x7fffffff, BUF_FLAGS);
   const unsigned voff16 = (unsigned)lane * 16u, voff4 = (unsigned)lane * 4u;
@@ -419,39 +359,20 @@ __global__ __launch_bounds__(512, 4) void posterior_kernel_f32x(PostArgsF32 p) {
     double v = 0.0;
 #pragma unroll
     for (int w = 0; w < 8; ++w) v += red[w * F32_CANDS + tid];
-    p.part[(int64_t)r * p.Mp + p.m0 + (int64_t)ct * F32_CANDS + tid] = v;
+    p.part[(int64_t)r * p.g.Mp + p.m0 + (int64_t)ct * F32_CANDS + tid] = v;
   }
 }
 
-// SlabF32 per candidate slab (the walk of launch_posterior_slab); the slab buffer (ctx->kst, sized in doubles) is shared with the
-// fp64 path.  The GEMM runs on the MFMA form f32_use_mfma32 picks (posterior_plan.h), in plan.part_chunks row chunks.
-int launch_posterior_slab_f32(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
-  // 32-bit buffer offsets of a stage's rows (f32x kernel)
-  const int64_t ms = kstar_slab_width(ctx, Mp, m.NP * 4, (int64_t)160 * 1000 * 1000);
-  if (ms < 128) GPBO_FAIL(ctx, GPBO_ERR_HIP, "posterior: not enough device memory for one k* slab");
-  int rc;
-  if ((rc = ensure(ctx, &ctx->kst, &ctx->cap_kst, (ms * m.NP + 1) / 2))) return rc;
-  float* kst = reinterpret_cast<float*>(ctx->kst);
-  for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
-    const int64_t ldk = (Mp - m0 < ms) ? (Mp - m0) : ms;
-    rc = with_dp_kernel(ctx, m.DP, m.kernel, [&](auto dp, auto k) {
-      kstar_gen_f32_kernel<decltype(dp)::value, decltype(k)::value><<<dim3((unsigned)((ldk + 255) / 256), (unsigned)plan.mu_chunks),
-                                                                      dim3(256), 0, ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, kst, ldk,
-                                                                                                   (int)m.NP, ctx->mu_part, Mp, m0);
-      GPBO_HIP(ctx, hipGetLastError());
-      return GPBO_OK;
-    });
-    if (rc) return rc;
-    PostArgsF32 a;
-    a.Wp = m.Wp32; a.Kst = kst; a.part = ctx->part; a.NP = (int)m.NP; a.Mp = Mp;
-    a.n_ctiles = (int)(ldk / F32_CANDS); a.ldk = ldk; a.m0 = m0;
-    a.nchunks = plan.part_chunks;
-    const int64_t nblocks = (int64_t)a.n_ctiles * a.nchunks;
-    if (nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
-    if (f32_use_mfma32(m.NP)) posterior_kernel_f32x<32><<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);   // (W packed for it)
-    else posterior_kernel_f32<<<dim3((unsigned)nblocks), dim3(512), 0, ctx->stream>>>(a);
-    GPBO_HIP(ctx, hipGetLastError());
-  }
+// SlabF32's GEMM for one slab of the walk (launch_posterior_slabs), on the MFMA form f32_use_mfma32 picks (posterior_plan.h; W is
+// packed for it), in part_chunks row chunks.
+int launch_slab_gemm_f32(gpbo_ctx* ctx, Model& m, const float* slab, int64_t ldk, int64_t m0, int64_t Mp, int part_chunks) {
+  PostArgsF32 a;
+  a.Wp = m.Wp32; a.Kst = slab; a.part = ctx->part;
+  a.g = {(int)m.NP, Mp, part_chunks, (int)(ldk / F32_CANDS)};
+  a.ldk = ldk; a.m0 = m0;
+  if (f32_use_mfma32(m.NP)) posterior_kernel_f32x<32><<<dim3((unsigned)a.g.blocks()), dim3(512), 0, ctx->stream>>>(a);
+  else posterior_kernel_f32<<<dim3((unsigned)a.g.blocks()), dim3(512), 0, ctx->stream>>>(a);
+  GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }
 

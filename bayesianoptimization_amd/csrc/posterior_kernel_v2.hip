@@ -1,6 +1,6 @@
 // posterior_kernel_v2 — the posterior MFMA kernel tiled for FOUR waves per SIMD (v1, 2 waves/SIMD, is in the git
 // history), with the k* operand either generated in-kernel (GEN = 1: the Fused256 / Fused512 paths of posterior_plan.h) or
-// read from a slab (GEN = 2: SlabF64).
+// read from a slab (GEN = 2: SlabF64) — and kstar_gen_kernel, which writes the slab of every slab path.
 //
 // Why: the in-tree probe (gpbo_mfma_f64_probe) shows that on gfx950 a SIMD only reaches the
 // 64-cycle issue cadence of v_mfma_f64_16x16x4_f64 when >= 4 waves feed it (1 wave: 140 cycles per
@@ -20,6 +20,7 @@
 #include "gpbo_internal.h"
 #include "fit_bodies.h"
 #include "i8_digits.h"
+#include "posterior_tile.h"
 
 namespace gpbo {
 
@@ -40,18 +41,13 @@ struct PostArgs2 {
   const double* Xcs;
   double* part;
   double* mu_part;
-  int NP;
-  int64_t Mp;
-  int nchunks;
-  int n_ctiles;
+  PostGrid g;
   const double* Kst;   // GEN == 2: materialised k* slab [NP][ldk], candidate-contiguous
   int64_t ldk;
   int64_t m0;          // first candidate of the slab (outputs are indexed m0 + local)
   int fuse_ends = 0;   // GEN == 1, one row chunk: raw candidates in, mu / sd out (PostEnds, gpbo_internal.h)
   PostEnds ends = {};
 };
-
-constexpr int BUF_FLAGS = 0x00020000;   // gfx9 buffer descriptor word 3: raw buffer, 32-bit data format
 
 // GEN = 1: k* generated in the kernel (fused).  GEN = 2: k* read from a slab materialised by
 // kstar_gen_kernel (the fp64 VALU work of the generation shares the FP64 datapath with the MFMAs — measured:
@@ -80,15 +76,10 @@ __global__ __launch_bounds__(WAVES * 64, 4) void posterior_kernel_v2(PostArgs2 p
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
-  // Heaviest row chunks first; the workgroups resident at any time share a chunk, so its rows of W come out of L2.
-  // (Round-2 A/B: mappings that put the two chunks of a candidate tile 1 ... 64 block ids apart, hoping the second
-  // chunk's k* reads would hit the first one's in L2, never lowered FETCH_SIZE — 3.5e11 ... 6.6e11 B against 3.3e11 —
-  // and cost up to 6 % of the time; removed.)
-  const int bid = blockIdx.x;
-  const int r = p.nchunks - 1 - bid / p.n_ctiles;
-  const int ct = bid - (bid / p.n_ctiles) * p.n_ctiles;
-  const bool last = (r == p.nchunks - 1);
-  const int NP = p.NP;
+  int r, ct;
+  p.g.map(blockIdx.x, r, ct);
+  const bool last = (r == p.g.nchunks - 1);
+  const int NP = p.g.NP;
   const int k_end = min(NP, (r + 1) * ROWS);
   const int n_stages = k_end / BK;
 
@@ -300,7 +291,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void posterior_kernel_v2(PostArgs2 p
         posterior_finalize_elem(0.0 + v, 0.0 + u, p.ends.y_mean, p.ends.y_std, p.ends.mu + m, p.ends.sd + m, p.ends.negvar);
       return;
     }
-    p.part[(int64_t)r * p.Mp + m] = v;
+    p.part[(int64_t)r * p.g.Mp + m] = v;
     if (GEN != 2 && last) {
       double u = 0.0;
 #pragma unroll
@@ -310,21 +301,27 @@ __global__ __launch_bounds__(WAVES * 64, 4) void posterior_kernel_v2(PostArgs2 p
   }
 }
 
-// k* slab generation: thread = candidate (coordinates in registers), loop over a chunk of 256 train points, coalesced
-// stores to Kst[k][m]; also the partial means sum_k k*[k] alpha[k] per chunk.  The train points of the chunk are staged
-// through LDS 64 at a time and read back as broadcasts (every lane the same address): as scalar loads straight from
-// memory each pair of points cost the wave four s_load_dwordx16 + s_waitcnt round trips per iteration, which left the
-// fp64 VALU — the unit this kernel is bound by — idle about 40 % of the time (14.2 ms per C3 pass).
-// DIG = S > 0 (posterior_i8.hip): the same k* values and partial means, but the slab holds the S int8 digit planes of
-// k* (i8_digits.h) in the operand order of v_mfma_i32_16x16x64_i8 (i8_frag_index) — [candidate block of 16][64 train points]
-// [plane][lane] 16 bytes, lane 16 g + c = candidate c, train points 16 g ... 16 g + 15 — written as one 16-byte store per plane
-// and 16 train points: a wave's store instruction is 1 KiB, four candidate blocks of 256 contiguous bytes (two whole lines) each.
+// k* slab generation: thread = candidate (coordinates in registers), loop over a chunk of 256 train points; also the partial
+// means sum_k k*[k] alpha[k] per chunk.  The train points of the chunk are staged through LDS 64 at a time and read back as
+// broadcasts (every lane the same address): as scalar loads straight from memory each pair of points cost the wave four
+// s_load_dwordx16 + s_waitcnt round trips per iteration, which left the fp64 VALU — the unit this kernel is bound by — idle about
+// 40 % of the time (14.2 ms per C3 pass).
+// SLAB = the slab path (posterior_plan.h) names what the slab holds; the k* values and the partial means are the same for all:
+//   SlabF64  the values, Kst[k][m] (candidate-contiguous: coalesced stores);
+//   SlabF32  the values ROUNDED to fp32 (half the HBM traffic; the means are accumulated in fp64 before the rounding);
+//   SlabI8   their I8_S int8 digit planes (i8_digits.h) in the operand order of v_mfma_i32_16x16x64_i8 (i8_frag_index) — [candidate
+//            block of 16][64 train points][plane][lane] 16 bytes, lane 16 g + c = candidate c, train points 16 g ... 16 g + 15 —
+//            written as one 16-byte store per plane and 16 train points: a wave's store instruction is 1 KiB, four candidate
+//            blocks of 256 contiguous bytes (two whole lines) each.
 constexpr int GEN_CH = 64;
-template <int DP, int KERNEL, int DIG = 0>
+template <PostPath SLAB> struct slab_value { using type = double; };
+template <> struct slab_value<PostPath::SlabF32> { using type = float; };
+template <int DP, int KERNEL, PostPath SLAB>
 __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict__ Xs, const double* __restrict__ alpha,
-                                                        const double* __restrict__ Xcs, double* __restrict__ Kst,
+                                                        const double* __restrict__ Xcs, void* __restrict__ slab,
                                                         int64_t ldk, int NP, double* __restrict__ mu_part,
                                                         int64_t Mp, int64_t m0) {
+  static_assert(SLAB == PostPath::SlabF64 || SLAB == PostPath::SlabF32 || SLAB == PostPath::SlabI8, "a slab path");
   __shared__ __attribute__((aligned(16))) double xs[GEN_CH * DP];
   __shared__ double al[GEN_CH];
   const int64_t ml = (int64_t)blockIdx.x * 256 + threadIdx.x;   // slab-local candidate
@@ -341,6 +338,24 @@ __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict
     }
   }
   double mu = 0.0;
+  // k* of the staged train points kk, kk + 1, and their share of the mean (ka then kb, ascending k).  Two steps, so that each
+  // form keeps the mean's fmas where its schedule had them: behind the value forms' stores, in front of the digit form's split.
+  auto pair = [&](int kk, double& ka, double& kb) {
+    const double* xr = xs + kk * DP;           // the same address in every lane: LDS broadcast
+    double d2a = 0.0, d2b = 0.0;
+#pragma unroll
+    for (int t = 0; t < DP; ++t) {
+      const double da = xc[t] - xr[t], db = xc[t] - xr[DP + t];
+      d2a = fma(da, da, d2a);
+      d2b = fma(db, db, d2b);
+    }
+    ka = gpbo_kernel_value<KERNEL>(d2a);
+    kb = gpbo_kernel_value<KERNEL>(d2b);
+  };
+  auto mean = [&](int kk, double ka, double kb) {
+    mu = fma(ka, al[kk], mu);
+    mu = fma(kb, al[kk + 1], mu);
+  };
   for (int kc = k0; kc < k1; kc += GEN_CH) {      // NP is a multiple of 64: every refill is full
     __syncthreads();
     {
@@ -350,120 +365,95 @@ __global__ __launch_bounds__(256) void kstar_gen_kernel(const double* __restrict
       if (threadIdx.x < GEN_CH) al[threadIdx.x] = alpha[kc + threadIdx.x];
     }
     __syncthreads();
-    if (DIG > 0 && live) {
+    if (!live) continue;
+    if constexpr (SLAB == PostPath::SlabI8) {
       // 16 train points at a time: the digit planes of 16 k* values are one 16-byte operand chunk per plane
-      uint4* Kd = reinterpret_cast<uint4*>(Kst);
+      constexpr int S = I8_S;
+      uint4* Kd = static_cast<uint4*>(slab);
       const int64_t cb = i8_kd_block(ml >> 4, NP);
 #pragma unroll 1
       for (int kg = 0; kg < GEN_CH; kg += 16) {
-        constexpr int DS = DIG > 0 ? DIG : 5;   // (the fp64 instantiations compile this branch too)
-        uint32_t w[DS][4] = {};
+        uint32_t w[S][4] = {};
 #pragma unroll
         for (int kk = kg; kk < kg + 16; kk += 2) {
-          const double* xr = xs + kk * DP;
-          double d2a = 0.0, d2b = 0.0;
-#pragma unroll
-          for (int t = 0; t < DP; ++t) {
-            const double da = xc[t] - xr[t], db = xc[t] - xr[DP + t];
-            d2a = fma(da, da, d2a);
-            d2b = fma(db, db, d2b);
-          }
-          const double ka = gpbo_kernel_value<KERNEL>(d2a), kb = gpbo_kernel_value<KERNEL>(d2b);
-          mu = fma(ka, al[kk], mu);
-          mu = fma(kb, al[kk + 1], mu);
-          const int64_t qa = i8_quantize<DS>(ka), qb = i8_quantize<DS>(kb);
+          double ka, kb;
+          pair(kk, ka, kb);
+          mean(kk, ka, kb);
+          const int64_t qa = i8_quantize<S>(ka), qb = i8_quantize<S>(kb);
           const int j = kk - kg;
 #pragma unroll
-          for (int t = 0; t < DIG; ++t) {
-            w[t][j >> 2] |= (uint32_t)((qa >> (8 * (DIG - 1 - t))) & 255) << (8 * (j & 3));
-            w[t][j >> 2] |= (uint32_t)((qb >> (8 * (DIG - 1 - t))) & 255) << (8 * ((j + 1) & 3));
+          for (int t = 0; t < S; ++t) {
+            w[t][j >> 2] |= (uint32_t)((qa >> (8 * (S - 1 - t))) & 255) << (8 * (j & 3));
+            w[t][j >> 2] |= (uint32_t)((qb >> (8 * (S - 1 - t))) & 255) << (8 * ((j + 1) & 3));
           }
         }
         const int k = kc + kg;   // multiple of 16
-        uint4* dst = Kd + i8_frag_index<DS>(cb, k, 0, (int)(ml & 15));
+        uint4* dst = Kd + i8_frag_index<S>(cb, k, 0, (int)(ml & 15));
 #pragma unroll
-        for (int t = 0; t < DIG; ++t) {
+        for (int t = 0; t < S; ++t) {
           const uint32_t x = t ? 0x80808080u : 0u;   // planes below the leading one: byte - 128 (i8_digit_byte)
           dst[t * 64] = make_uint4(w[t][0] ^ x, w[t][1] ^ x, w[t][2] ^ x, w[t][3] ^ x);
         }
       }
-    } else if (live) {
+    } else {
+      using T = typename slab_value<SLAB>::type;
+      T* Kst = static_cast<T*>(slab);
 #pragma unroll 2
       for (int kk = 0; kk < GEN_CH; kk += 2) {
-        const double* xr = xs + kk * DP;           // the same address in every lane: LDS broadcast
-        double d2a = 0.0, d2b = 0.0;
-#pragma unroll
-        for (int t = 0; t < DP; ++t) {
-          const double da = xc[t] - xr[t], db = xc[t] - xr[DP + t];
-          d2a = fma(da, da, d2a);
-          d2b = fma(db, db, d2b);
-        }
-        const double ka = gpbo_kernel_value<KERNEL>(d2a), kb = gpbo_kernel_value<KERNEL>(d2b);
+        double ka, kb;
+        pair(kk, ka, kb);
         const int k = kc + kk;
-        Kst[(int64_t)k * ldk + ml] = ka;
-        Kst[(int64_t)(k + 1) * ldk + ml] = kb;
-        mu = fma(ka, al[kk], mu);
-        mu = fma(kb, al[kk + 1], mu);
+        Kst[(int64_t)k * ldk + ml] = (T)ka;
+        Kst[(int64_t)(k + 1) * ldk + ml] = (T)kb;
+        mean(kk, ka, kb);
       }
     }
   }
   if (live) mu_part[(int64_t)blockIdx.y * Mp + m0 + ml] = mu;
 }
 
-template <int DIG>
-static int launch_gen(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
+template <PostPath SLAB>
+static int launch_gen(gpbo_ctx* ctx, Model& m, void* slab, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
   return with_dp_kernel(ctx, m.DP, m.kernel, [&](auto dp, auto k) {
-    kstar_gen_kernel<decltype(dp)::value, decltype(k)::value, DIG><<<dim3((unsigned)((ldk + 255) / 256), (unsigned)nchunks), dim3(256), 0,
-                                                                     ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, Kst, ldk, (int)m.NP,
-                                                                                    ctx->mu_part, Mp, m0);
+    kstar_gen_kernel<decltype(dp)::value, decltype(k)::value, SLAB><<<dim3((unsigned)((ldk + 255) / 256), (unsigned)nchunks), dim3(256), 0,
+                                                                      ctx->stream>>>(m.Xs, m.alpha, ctx->Xcs, slab, ldk, (int)m.NP,
+                                                                                     ctx->mu_part, Mp, m0);
     GPBO_HIP(ctx, hipGetLastError());
     return GPBO_OK;
   });
 }
 
-// the I8_S int8 digit planes of the k* slab (ldk a multiple of 32) + the same partial means as launch_kstar_slab
-int launch_kstar_digits(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  return launch_gen<I8_S>(ctx, m, static_cast<double*>(Kd), ldk, Mp, m0, nchunks);
-}
-
-// k* slab [NP][ldk] (+ partial means) for candidates [m0, m0 + ldk) of the scaled set ctx->Xcs — also used by the
-// covariance path (posterior_cov.hip)
+// The slab for candidates [m0, m0 + ldk) of the scaled set ctx->Xcs + their partial means in ctx->mu_part [nchunks][Mp]:
+// k* [NP][ldk] — also used by the covariance path (posterior_cov.hip) —
 int launch_kstar_slab(gpbo_ctx* ctx, Model& m, double* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
-  return launch_gen<0>(ctx, m, Kst, ldk, Mp, m0, nchunks);
+  return launch_gen<PostPath::SlabF64>(ctx, m, Kst, ldk, Mp, m0, nchunks);
+}
+// ... the same rounded to fp32,
+int launch_kstar_slab_f32(gpbo_ctx* ctx, Model& m, float* Kst, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
+  return launch_gen<PostPath::SlabF32>(ctx, m, Kst, ldk, Mp, m0, nchunks);
+}
+// ... its I8_S int8 digit planes (ldk a multiple of 32)
+int launch_kstar_digits(gpbo_ctx* ctx, Model& m, void* Kd, int64_t ldk, int64_t Mp, int64_t m0, int nchunks) {
+  return launch_gen<PostPath::SlabI8>(ctx, m, Kd, ldk, Mp, m0, nchunks);
 }
 
-// The kernel's arguments for ncands candidates in nchunks row chunks (no slab, no fused ends) and its grid size.
-static int post_args(gpbo_ctx* ctx, const Model& m, int64_t Mp, int nchunks, int64_t ncands, PostArgs2* a, int64_t* nblocks) {
-  a->Wp = m.Wp; a->Xs = m.Xs; a->alpha = m.alpha; a->Xcs = ctx->Xcs; a->part = ctx->part;
-  a->mu_part = ctx->mu_part; a->NP = (int)m.NP; a->Mp = Mp; a->nchunks = nchunks;
-  a->n_ctiles = (int)(ncands / V2_CANDS);
-  a->Kst = nullptr; a->ldk = 0; a->m0 = 0;
-  *nblocks = (int64_t)a->n_ctiles * nchunks;
-  if (*nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
-  return GPBO_OK;
+// The kernel's arguments for ncands candidates in nchunks row chunks (no slab, no fused ends).
+static PostArgs2 post_args(gpbo_ctx* ctx, const Model& m, int64_t Mp, int nchunks, int64_t ncands) {
+  PostArgs2 a;
+  a.Wp = m.Wp; a.Xs = m.Xs; a.alpha = m.alpha; a.Xcs = ctx->Xcs; a.part = ctx->part; a.mu_part = ctx->mu_part;
+  a.g = {(int)m.NP, Mp, nchunks, (int)(ncands / V2_CANDS)};
+  a.Kst = nullptr; a.ldk = 0; a.m0 = 0;
+  return a;
 }
 
-// SlabF64: kstar_gen_kernel -> posterior_kernel_v2<.., GEN = 2> per candidate slab.  The slab width is bounded by the workspace
-// budget (kstar_slab_width); a slab only has to be wide enough to fill the chip (4e9 B = 121 984 candidates at N = 4096 = 1906
-// candidate tiles x 16 row chunks per launch); measured at C3: one 34 GB slab 263.7 ms, eight 4 GB slabs 264.4 ms (round 1
-// A/B) — the big workspace bought nothing.  32 train points per stage: 262.9 vs 264.0 ms per C3 launch (round-2 A/B).
-int launch_posterior_slab(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan) {
-  // the slab kernel addresses a stage's rows as 32-bit buffer offsets: 3 rows of ldk doubles must stay below 2^31 bytes
-  const int64_t ms = kstar_slab_width(ctx, Mp, m.NP * 8, (int64_t)80 * 1000 * 1000);
-  if (ms < 128) GPBO_FAIL(ctx, GPBO_ERR_HIP, "posterior: not enough device memory for one k* slab");
-  int rc;
-  if ((rc = ensure(ctx, &ctx->kst, &ctx->cap_kst, ms * m.NP))) return rc;
-  for (int64_t m0 = 0; m0 < Mp; m0 += ms) {
-    const int64_t ldk = (Mp - m0 < ms) ? (Mp - m0) : ms;
-    if ((rc = launch_kstar_slab(ctx, m, ctx->kst, ldk, Mp, m0, plan.mu_chunks))) return rc;
-    PostArgs2 a;
-    int64_t nblocks;
-    if ((rc = post_args(ctx, m, Mp, plan.part_chunks, ldk, &a, &nblocks))) return rc;
-    a.Kst = ctx->kst; a.ldk = ldk; a.m0 = m0;
-    const size_t lds = (size_t)(2 * 32 * V2_STRIDE) * sizeof(double);
-    posterior_kernel_v2<4, 0, 2, 32><<<dim3((unsigned)nblocks), dim3(512), lds, ctx->stream>>>(a);
-    GPBO_HIP(ctx, hipGetLastError());
-  }
+// SlabF64's GEMM for one slab of the walk (launch_posterior_slabs): posterior_kernel_v2<.., GEN = 2>.  32 train points per stage:
+// 262.9 vs 264.0 ms per C3 launch (round-2 A/B).
+int launch_slab_gemm_f64(gpbo_ctx* ctx, Model& m, const double* slab, int64_t ldk, int64_t m0, int64_t Mp, int part_chunks) {
+  PostArgs2 a = post_args(ctx, m, Mp, part_chunks, ldk);
+  a.Kst = slab; a.ldk = ldk; a.m0 = m0;
+  const size_t lds = (size_t)(2 * 32 * V2_STRIDE) * sizeof(double);
+  posterior_kernel_v2<4, 0, 2, 32><<<dim3((unsigned)a.g.blocks()), dim3(512), lds, ctx->stream>>>(a);
+  GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }
 
@@ -471,10 +461,9 @@ int launch_posterior_slab(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& p
 // the plan says so (one row chunk).  Mp must be a multiple of 64.
 int launch_posterior_fused(gpbo_ctx* ctx, Model& m, int64_t Mp, const PostPlan& plan, const PostEnds& ends) {
   if (plan.fuse_ends && plan.part_chunks != 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "posterior: fused ends need one row chunk");
-  PostArgs2 a;
-  int64_t nblocks;
-  int rc;
-  if ((rc = post_args(ctx, m, Mp, plan.part_chunks, Mp, &a, &nblocks))) return rc;
+  PostArgs2 a = post_args(ctx, m, Mp, plan.part_chunks, Mp);
+  const int64_t nblocks = a.g.blocks();
+  if (nblocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "posterior: grid too large; shard the candidates");
   if (plan.fuse_ends) { a.fuse_ends = 1; a.ends = ends; }
   const bool wide = plan.path == PostPath::Fused512;
   return with_dp_kernel(ctx, m.DP, m.kernel, [&](auto dp, auto k) {

@@ -14,11 +14,14 @@ constexpr int POST_CANDS = 128;      // candidate padding granule (Mp = round_up
 constexpr int I8_ROWS = 128;         // rows of W per workgroup of the int8 GEMM (4 waves x 32)
 constexpr int64_t I8_NP_MIN = 2048;  // fp64 models take the int8 GEMM from this NP on ...
 constexpr int I8_NP_MAX = 16384;     // ... up to this one: i8_digits.h's int32 level sums bound it
+constexpr int I8_S = 7;              // int8 digit planes per operand (i8_digits.h): bytes per k* value of SlabI8's slab
 
 enum class PostPath {
   Small,     // batched GEMV                                       posterior_small.hip
   Fused256,  // k* generated inside the MFMA kernel, 8 waves       posterior_kernel_v2.hip (GEN = 1)
   Fused512,  // ... 16 waves, 512-row chunks                       posterior_kernel_v2.hip (GEN = 1, WAVES = 16)
+  // The slab paths: one walk (posterior_kernel.hip, launch_posterior_slabs) over slabs of slab_spec's size, per slab one launch
+  // of kstar_gen_kernel<.., the path> (posterior_kernel_v2.hip) and one of the path's GEMM:
   SlabF64,   // k* slab + fp64 MFMA GEMM                           posterior_kernel_v2.hip (GEN = 2)
   SlabI8,    // k* slab as int8 digit planes + int8 MFMA GEMM      posterior_i8.hip
   SlabF32,   // fp32 k* slab + fp32 MFMA GEMM                      posterior_kernel_f32.hip
@@ -41,7 +44,33 @@ inline bool f32_use_mfma32(int64_t NP) { return NP >= POST_ROWS_WIDE; }
 // batch it comes in; the int32 level sums bound NP from above.
 inline bool posterior_i8_serves(int64_t NP) { return NP >= I8_NP_MIN && NP <= I8_NP_MAX; }
 
-// SlabI8's slab width in candidates (one launch of kstar_gen_kernel<.., DIG> + one of the int8 GEMM per slab), from NP, the bytes of
+// What the slab walk needs to know about a slab path's slab.  The workspace budget (kstar_slab_width) divided by bytes_per_cand
+// gives the slab's width in candidates, at most offset_cap; a budget that holds fewer than 128 candidates fails the pass unless
+// narrow_ok, which takes 128.
+//   SlabF64, SlabF32: both value GEMMs address the rows of a stage as 32-bit buffer offsets from the stage's first row (ldk x 8
+//   resp. 4 bytes apart: posterior_kernel_v2<.., GEN = 2>, posterior_kernel_f32x), so three rows of ldk values must stay below 2^31
+//   bytes: 80e6 doubles, 160e6 floats.  A slab only has to be wide enough to fill the chip anyway (4e9 B = 121 984 candidates at
+//   N = 4096 = 1906 candidate tiles x 16 row chunks per launch); measured at C3: one 34 GB slab 263.7 ms, eight 4 GB slabs 264.4 ms
+//   (round 1 A/B) — the big workspace bought nothing.
+//   SlabI8: no cap — the int8 GEMM's buffer offsets start at its own candidate tile; its width comes from i8_slab_width below.
+struct SlabSpec {
+  int64_t bytes_per_cand;   // of one candidate's NP k* values in the slab
+  int64_t offset_cap;       // candidates
+  bool narrow_ok;
+};
+inline SlabSpec slab_spec(PostPath path, int64_t NP) {
+  switch (path) {
+    case PostPath::SlabF64: return {8 * NP, (int64_t)80 * 1000 * 1000, false};
+    case PostPath::SlabF32: return {4 * NP, (int64_t)160 * 1000 * 1000, false};
+    case PostPath::SlabI8: return {I8_S * NP, INT64_MAX, true};
+    default: return {0, 0, false};   // not a slab path
+  }
+}
+// The slab buffer is counted in doubles: ms candidates take (ms * bytes_per_cand + 7) / 8 of them.  (8 NP bytes: ms * NP exactly;
+// 4 NP bytes: x = ms * NP floats, (4 x + 7) / 8 = (x + 1) / 2 only because the division floors: x even gives x / 2, x odd (x + 1) / 2.)
+inline int64_t slab_doubles(int64_t ms, int64_t bytes_per_cand) { return (ms * bytes_per_cand + 7) / 8; }
+
+// SlabI8's slab width in candidates (one launch of kstar_gen_kernel<.., SlabI8> + one of the int8 GEMM per slab), from NP, the bytes of
 // one candidate's digit planes (NP x S), the width the workspace budget grants (kstar_slab_width: a multiple of 128, <= Mp) and the
 // device's compute units.
 // Two things bound it.  The GEMM's 32 row chunks re-read the slab, so it has to stay in the 256 MB Infinity Cache (C3 pass per slab

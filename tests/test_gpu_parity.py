@@ -541,33 +541,79 @@ def test_small_batch_rows_do_not_depend_on_the_batch(debug_engine):
         os.environ.pop("GPBO_SMALL_MAX")
 
 
-def test_kstar_slab_loop_equals_single_slab(engine):
-    """The k* slab is bounded by a workspace budget; a candidate set larger than one slab is walked slab by slab.
-    Force ~7 slabs (GPBO_KSTAR_GB) and compare bitwise with the single-slab pass, in fp64 and fp32 modes."""
+# The slab paths (posterior_plan.h): how each is reached, its padded size NP (each with a ragged last row chunk for its own GEMM)
+# and the bytes of one k* value in its slab.
+_SLAB_PATHS = {
+    "f64": dict(NP=640, elem=8, f32=False, debug=False),       # SlabF64, 256-row chunks
+    "f32_16": dict(NP=320, elem=4, f32=True, debug=False),     # SlabF32 on 16x16 MFMAs, 256-row chunks
+    "f32_32": dict(NP=576, elem=4, f32=True, debug=False),     # SlabF32 on 32x32 MFMAs, 512-row chunks
+    "i8": dict(NP=576, elem=7, f32=False, debug=True),         # SlabI8 (GPBO_POST_KERNEL=8: debug build), 128-row chunks
+}
+_slab_oracles = {}
+
+
+def _slab_case(N, d, kernel):
+    """Inputs and the oracle's posterior for one (N, d, kernel), computed once and shared by the paths that use it."""
+    key = (N, d, kernel)
+    if key not in _slab_oracles:
+        X, y = _data(N, d, seed=41)
+        Xc = np.random.RandomState(42).uniform(size=(1000, d))      # Mp = 1024
+        Xc[7] = X[3]                                                 # a training point: variance ~ noise, the cancellation case
+        mu_o, sd_o = O.predict(O.fit_fixed_theta(kernel, X, y, 0.9, 1e-6), Xc)
+        for a in (X, y, Xc, mu_o, sd_o):
+            a.setflags(write=False)
+        _slab_oracles[key] = (X, y, Xc, mu_o, sd_o)
+    return _slab_oracles[key]
+
+
+@pytest.mark.parametrize("d,kernel", [(5, O.MATERN25), (17, O.MATERN25), (17, O.RBF)])       # DP = 8, 32
+@pytest.mark.parametrize("path", list(_SLAB_PATHS))
+def test_kstar_slab_loop_equals_single_slab(request, path, d, kernel):
+    """The k* slab is bounded by a workspace budget; a candidate set larger than one slab is walked slab by slab (one walk and
+    one k* generator for the three slab paths: launch_posterior_slabs, kstar_gen_kernel).  Per path, with padded train rows
+    (N = NP - 2) and 1000 candidates (Mp = 1024): the pass over ONE slab, over slabs of 384 candidates (384 + 384 + 256: a
+    narrower last slab) and over eight slabs of 128 (half of every generator workgroup idle) — widths forced through
+    GPBO_KSTAR_GB from the path's bytes per candidate — give bitwise the same mu and sd, and the single-slab pass agrees with
+    the oracle at its path's bar: TOL in fp64, test_gpu_f32.py's in fp32, test_gpu_int8_posterior.py's elementwise 1e-5 on the
+    int8 GEMM."""
     import os
 
     from bayesianoptimization_amd.engine import F32, F64
 
-    N, d, M = 640, 6, 3000          # NP = 640 > 512 -> slab + GEMM path; Mp = 3072
-    X, y = _data(N, d, seed=41)
+    row = _SLAB_PATHS[path]
+    engine = request.getfixturevalue("debug_engine" if row["debug"] else "engine")
+    NP = row["NP"]
+    X, y, Xc, mu_o, sd_o = _slab_case(NP - 2, d, kernel)
     yn, ym, ys = O.normalize_targets(y)
-    Xc = np.random.RandomState(42).uniform(size=(M, d))
-    for prec in (F64, F32):
-        engine.fit(X, yn, O.MATERN25, 0.9, 1e-6, precision=prec)
-        engine.set_candidates(Xc)
-        mu1, sd1 = engine.posterior(0, ym, ys)
-        per_cand = 640 * (8 if prec == F64 else 4)
-        os.environ["GPBO_KSTAR_GB"] = repr(512 * per_cand / 1e9 * 1.01)    # room for 512 candidates per slab
-        try:
-            mu2, sd2 = engine.posterior(0, ym, ys)
-        finally:
-            os.environ.pop("GPBO_KSTAR_GB")
-        assert np.array_equal(mu1, mu2) and np.array_equal(sd1, sd2)
-    gp = O.fit_fixed_theta(O.MATERN25, X, y, 0.9, 1e-6)
-    mu_o, sd_o = O.predict(gp, Xc)
-    engine.fit(X, yn, O.MATERN25, 0.9, 1e-6)
-    mu, sd = engine.posterior(0, ym, ys)
-    assert rel_err(mu, mu_o) < TOL and rel_err(sd, sd_o) < TOL
+    engine.fit(X, yn, kernel, 0.9, 1e-6, precision=F32 if row["f32"] else F64)
+    engine.set_candidates(Xc)
+    if row["debug"]:
+        os.environ["GPBO_POST_KERNEL"] = "8"
+    out = {}
+    try:
+        for width in (None, 384, 128):
+            if width is not None:
+                os.environ["GPBO_KSTAR_GB"] = repr(width * NP * row["elem"] / 1e9 * 1.01)    # room for `width` candidates per slab
+            out[width] = engine.posterior(0, ym, ys)
+    finally:
+        os.environ.pop("GPBO_KSTAR_GB", None)
+        os.environ.pop("GPBO_POST_KERNEL", None)
+    mu, sd = out[None]
+    for width in (384, 128):
+        assert np.array_equal(mu, out[width][0]) and np.array_equal(sd, out[width][1]), width
+    if path == "f64":
+        errs = (rel_err(mu, mu_o), rel_err(sd, sd_o))
+        print(path, d, kernel, "rel_err mu, sd:", errs)
+        assert errs[0] < TOL and errs[1] < TOL
+    elif row["f32"]:
+        errs = (rel_err(mu, mu_o), float(np.max(np.abs(sd**2 - sd_o**2)) / ys**2))
+        print(path, d, kernel, "rel_err mu, max |sd^2 - sd_o^2| / ys^2:", errs)
+        assert errs[0] < 1e-7 and errs[1] < 2e-5
+    else:
+        pos = sd_o > 0
+        errs = (float(np.max(np.abs(mu - mu_o) / np.maximum(np.abs(mu_o), ys))), float(np.max(np.abs(sd - sd_o)[pos] / sd_o[pos])))
+        print(path, d, kernel, "elementwise mu, sd:", errs)
+        assert errs[0] <= 1e-5 and errs[1] <= 1e-5
 
 
 # ---- gpbo_fit_append (SURVEY.md §8 f4) ---------------------------------------------------------------------

@@ -5,7 +5,9 @@ the system C++ compiler and checked against the rule written out below as a tabl
     reached from M = Mp and from M = Mp - 127 (the same padded batch);
   * M at the GEMV limit and one above it, with GPBO_POST_SMALL=0 and without, fp32 and fp64;
   * every GPBO_POST_KERNEL digit over the whole grid (2, 3 always; 4 up to NP = 1024; 8 for 512 < NP <= 16384; fp64 only);
-  * the partial-row counts the finalize kernel sums and whether a fused kernel writes mu / sd itself.
+  * the partial-row counts the finalize kernel sums and whether a fused kernel writes mu / sd itself;
+  * the slab paths' slab (slab_spec): bytes per candidate, offset cap and whether a slab below 128 candidates is allowed, and
+    the size of the slab buffer (slab_doubles) against the three expressions it replaced.
 
 A threshold of the header moved by one step (64 in NP, 128 in Mp) changes at least one row of the grid."""
 import ctypes
@@ -26,6 +28,12 @@ extern "C" void plan(int64_t NP, int64_t M, int f32, int64_t lim, int force, int
   const gpbo::PostPlan p = gpbo::plan_posterior(NP, M, f32 != 0, lim, force, no_small != 0, no_fuse != 0);
   out[0] = (int)p.path; out[1] = p.fuse_ends; out[2] = p.part_chunks; out[3] = p.mu_chunks;
 }
+extern "C" void spec(int path, int64_t NP, int64_t* out) {
+  const gpbo::SlabSpec s = gpbo::slab_spec((gpbo::PostPath)path, NP);
+  out[0] = s.bytes_per_cand; out[1] = s.offset_cap; out[2] = s.narrow_ok;
+}
+extern "C" int64_t slab_doubles(int64_t ms, int64_t bytes_per_cand) { return gpbo::slab_doubles(ms, bytes_per_cand); }
+extern "C" int i8_s() { return gpbo::I8_S; }
 """
 
 PATHS = ["Small", "Fused256", "Fused512", "SlabF64", "SlabI8", "SlabF32"]   # enum class PostPath, in order
@@ -46,11 +54,21 @@ def build_plan(tmp_dir, include_dir=CSRC):
     L.plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                        ctypes.POINTER(ctypes.c_int)]
 
+    L.spec.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.slab_doubles.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    L.slab_doubles.restype = ctypes.c_int64
+
     def plan(NP, M, f32, lim, force=0, no_small=False, no_fuse=False):
         out = (ctypes.c_int * 4)()
         L.plan(NP, M, int(f32), lim, force, int(no_small), int(no_fuse), out)
         return PATHS[out[0]], bool(out[1]), out[2], out[3]
 
+    def spec(path, NP):
+        out = (ctypes.c_int64 * 3)()
+        L.spec(PATHS.index(path), NP, out)
+        return out[0], out[1], bool(out[2])
+
+    plan.spec, plan.slab_doubles, plan.i8_s = spec, L.slab_doubles, L.i8_s()
     return plan
 
 
@@ -127,3 +145,25 @@ def test_headline_configs(plan):
     assert plan(512, 65536, False, 48, no_fuse=True) == ("Fused512", False, 1, 1)
     assert plan(1024, 1 << 20, True, 512) == ("SlabF32", False, 2, 4)
     assert plan(448, 1 << 20, True, 48) == ("SlabF32", False, 2, 2)
+
+
+def test_slab_spec_of_the_three_slab_paths(plan):
+    """bytes per candidate 8 NP / 4 NP / I8_S NP; three rows of a stage as 32-bit buffer offsets cap the value slabs at 80e6 / 160e6
+    candidates, the int8 slab has no cap; only the int8 walk may run a slab below 128 candidates."""
+    assert plan.i8_s == 7
+    for NP in (64, 640, 2048, 16384):
+        assert plan.spec("SlabF64", NP) == (8 * NP, 80 * 1000 * 1000, False)
+        assert plan.spec("SlabF32", NP) == (4 * NP, 160 * 1000 * 1000, False)
+        assert plan.spec("SlabI8", NP) == (7 * NP, 2**63 - 1, True)
+        assert 3 * 8 * plan.spec("SlabF64", NP)[1] < 2**31 and 3 * 4 * plan.spec("SlabF32", NP)[1] < 2**31
+
+
+def test_slab_buffer_size_equals_the_three_former_expressions(plan):
+    """The slab buffer is counted in doubles.  (ms * bytes_per_cand + 7) / 8 is ms * NP for fp64, (ms * NP + 1) / 2 for fp32 — odd
+    products included: NP is a multiple of 64 on the device, the rule itself does not need it — and (ms * 7 NP + 7) / 8 for int8."""
+    for ms, NP in itertools.product((1, 3, 127, 128, 129, 384, 8191, 8192, 121984, 80 * 1000 * 1000), (1, 63, 64, 65, 320, 577, 640, 2048, 16384)):
+        assert plan.slab_doubles(ms, 8 * NP) == ms * NP
+        assert plan.slab_doubles(ms, 4 * NP) == (ms * NP + 1) // 2
+        assert plan.slab_doubles(ms, 7 * NP) == (ms * NP * 7 + 7) // 8
+        for bpc in (8 * NP, 4 * NP, 7 * NP):
+            assert 8 * plan.slab_doubles(ms, bpc) >= ms * bpc > 8 * (plan.slab_doubles(ms, bpc) - 1)
