@@ -590,7 +590,7 @@ int run_evolve(gpbo_ctx* ctx, const EvolveObjective& o, const EvolveRun& r) {
     }
   }
   if (!(ctx->func_attrs & ATTR_EVOLVE)) {
-    const int rc = for_each_kernel_wlds([&](auto k, auto wlds) -> int {
+    const int rc = for_each_kernel_wlds(ctx, [&](auto k, auto wlds) -> int {
       GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(evolve_kernel<decltype(k)::value, decltype(wlds)::value>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, SEARCH_LDS_BYTES));
       return GPBO_OK;
@@ -601,10 +601,10 @@ int run_evolve(gpbo_ctx* ctx, const EvolveObjective& o, const EvolveRun& r) {
   int launches = 0;
   int st[I_COUNT];
   for (;;) {
-    with_kernel_wlds(model ? model->kernel : 0, plan.mode == SearchMode::WInLds, [&](auto k, auto wlds) -> int {
+    if (const int rc = with_kernel_wlds(ctx, model ? model->kernel : 0, plan.mode == SearchMode::WInLds, [&](auto k, auto wlds) -> int {
       evolve_kernel<decltype(k)::value, decltype(wlds)::value><<<dim3(1), block, (size_t)plan.lds_bytes, ctx->stream>>>(a);
       return GPBO_OK;
-    });
+    })) return rc;
     ++launches;
     GPBO_HIP(ctx, hipGetLastError());
     GPBO_HIP(ctx, hipMemcpyAsync(st, a.ist, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));

@@ -68,10 +68,11 @@ int launch_kmat(gpbo_ctx* ctx, Model& m, double noise, double* out) {
   const int64_t nt = m.NP / 64;
   dim3 grid((unsigned)(nt * (nt + 1) / 2), 1, (unsigned)ctx->lanes);
   const size_t lds = (size_t)2 * m.DP * 64 * sizeof(double);
-  if (m.kernel == GPBO_KERNEL_MATERN25)
-    kmat_kernel<GPBO_KERNEL_MATERN25><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride);
-  else
-    kmat_kernel<GPBO_KERNEL_RBF><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride);
+  const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
+    kmat_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride);
+    return GPBO_OK;
+  });
+  if (rc) return rc;
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }
@@ -585,10 +586,11 @@ int launch_append_row(gpbo_ctx* ctx, Model& m, int64_t j) {
   double* lv = kv + m.NP;
   double* uv = lv + m.NP;
   const unsigned vb = (unsigned)((m.NP + 255) / 256);
-  if (m.kernel == GPBO_KERNEL_MATERN25)
-    append_kvec_kernel<GPBO_KERNEL_MATERN25><<<dim3(vb), dim3(256), 0, ctx->stream>>>(m.Xs, m.DP, j, m.NP, m.noise, kv, m.K);
-  else
-    append_kvec_kernel<GPBO_KERNEL_RBF><<<dim3(vb), dim3(256), 0, ctx->stream>>>(m.Xs, m.DP, j, m.NP, m.noise, kv, m.K);
+  const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
+    append_kvec_kernel<decltype(k)::value><<<dim3(vb), dim3(256), 0, ctx->stream>>>(m.Xs, m.DP, j, m.NP, m.noise, kv, m.K);
+    return GPBO_OK;
+  });
+  if (rc) return rc;
   GPBO_HIP(ctx, hipGetLastError());
   trmv_lower_kernel<<<dim3((unsigned)((m.NP + 3) / 4)), dim3(256), 0, ctx->stream>>>(m.W, kv, lv, m.NP, 0);
   GPBO_HIP(ctx, hipGetLastError());

@@ -278,10 +278,12 @@ int fused_max_np() { return fused_max_from(env_override(dbg_env("GPBO_FUSED_MAX_
 int launch_fused_small(gpbo_ctx* ctx, Model& m, int mode, int src, int n_ls, const double* X, const double* y, const double* ls_in,
                        double* scal, int* info_out, int64_t info_pitch, double* out, int64_t out_pitch) {
   if (!(ctx->func_attrs & ATTR_FUSED)) {
-    GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fused_small_kernel<GPBO_KERNEL_MATERN25>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)C128_LDS_BYTES));
-    GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fused_small_kernel<GPBO_KERNEL_RBF>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)C128_LDS_BYTES));
+    const int rc = for_each_kernel(ctx, [&](auto k) -> int {
+      GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fused_small_kernel<decltype(k)::value>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)C128_LDS_BYTES));
+      return GPBO_OK;
+    });
+    if (rc) return rc;
     ctx->func_attrs |= ATTR_FUSED;
   }
   FusedArgs a{};
@@ -293,10 +295,11 @@ int launch_fused_small(gpbo_ctx* ctx, Model& m, int mode, int src, int n_ls, con
   a.lane_stride = ctx->lane_stride;
   a.info_out = info_out; a.info_pitch = info_pitch; a.out = out; a.out_pitch = out_pitch;
   const dim3 grid((unsigned)ctx->lanes), block(512);
-  if (m.kernel == GPBO_KERNEL_MATERN25)
-    fused_small_kernel<GPBO_KERNEL_MATERN25><<<grid, block, C128_LDS_BYTES, ctx->stream>>>(a);
-  else
-    fused_small_kernel<GPBO_KERNEL_RBF><<<grid, block, C128_LDS_BYTES, ctx->stream>>>(a);
+  const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
+    fused_small_kernel<decltype(k)::value><<<grid, block, C128_LDS_BYTES, ctx->stream>>>(a);
+    return GPBO_OK;
+  });
+  if (rc) return rc;
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }

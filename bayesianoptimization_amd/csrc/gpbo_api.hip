@@ -398,8 +398,8 @@ static int check_gp_args(gpbo_ctx* ctx, const char* who, int64_t N, int d, int k
   const auto w = [who] { return std::string(who); };     // (built on a failure only)
   if (N < 1 || N > (1 << 16)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w() + ": N out of range [1, 65536]");
   if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, w() + ": d out of range [1, 64]");
-  if (kernel != GPBO_KERNEL_RBF && kernel != GPBO_KERNEL_MATERN25)
-    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, w() + ": kernel must be RBF or Matern(nu=2.5)");
+  if (kernel != GPBO_KERNEL_RBF && kernel != GPBO_KERNEL_MATERN25 && kernel != GPBO_KERNEL_MATERN15 && kernel != GPBO_KERNEL_MATERN05)
+    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, w() + ": kernel must be RBF or Matern(nu=2.5, 1.5 or 0.5)");
   if (n_ls != 1 && n_ls != d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w() + ": length_scale must have 1 or d entries");
   for (int64_t t = 0; t < (int64_t)n_theta * n_ls; ++t)
     if (!(length_scales[t] > 0.0) || !std::isfinite(length_scales[t]))

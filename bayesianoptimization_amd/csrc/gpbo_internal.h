@@ -302,9 +302,12 @@ inline int search_np_override() { return env_override(dbg_env("GPBO_POLISH_FUSED
 // subnormal rescaling (d2 is a sum of squares of O(1) numbers; exact 0 handled), and K^2/3 as K^2 * (1/3).
 // The fit-side kernel matrix (kmat_kernel) uses the same function, so K and k* share one arithmetic.
 #ifdef __HIPCC__
-__device__ __forceinline__ double gpbo_sqrt_pos(double x) {
+// The refinement both roots share: from y = v_rsq_f64(x), g -> sqrt(x) and h -> 1 / (2 sqrt(x)) side by side (Goldschmidt), g closed
+// by one Newton step.
+__device__ __forceinline__ void gpbo_sqrt_refine(double x, double& g, double& h) {
   const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y, h = 0.5 * y;
+  g = x * y;
+  h = 0.5 * y;
   double r = fma(-h, g, 0.5);
   g = fma(g, r, g);
   h = fma(h, r, h);
@@ -312,6 +315,10 @@ __device__ __forceinline__ double gpbo_sqrt_pos(double x) {
   g = fma(g, r, g);
   h = fma(h, r, h);
   g = fma(fma(-g, g, x), h, g);
+}
+__device__ __forceinline__ double gpbo_sqrt_pos(double x) {
+  double g, h;
+  gpbo_sqrt_refine(x, g, h);
   return x > 0.0 ? g : x;   // 0 -> 0 (rsq(0) = inf would give NaN), NaN -> NaN
 }
 // exp(x) for x <= 0 (the only arguments a stationary kernel has): n = rint(x / ln 2), r = x - n ln 2 in two pieces (the high one
@@ -344,13 +351,58 @@ __device__ __forceinline__ double gpbo_exp_nonpos(double x) {
   // n is an integer-valued double or NaN; beyond int range the conversion saturates, which is still "result 0"
   return __builtin_amdgcn_ldexp(p, (int)fmax(n, -2147483000.0));
 }
+// 1 / sqrt(x) for x > 0 from the same refinement: 2 h closed by one Newton step against the refined root — ~1 ulp, where a raw
+// v_rsq_f64 has about 26 good bits.  The Matern nu = 0.5 slope divides by r with it.
+__device__ __forceinline__ double gpbo_rsqrt_pos(double x) {
+  double g, h;
+  gpbo_sqrt_refine(x, g, h);
+  const double inv = h + h;
+  return fma(inv, fma(-g, inv, 1.0), inv);
+}
+static_assert(GPBO_KERNEL_RBF == 0 && GPBO_KERNEL_MATERN25 == 1 && GPBO_KERNEL_MATERN15 == 2 && GPBO_KERNEL_MATERN05 == 3,
+              "the kernel kinds of gpbo.h");
+// Matern nu = 1.5 (kernels.py Matern.__call__): s = sqrt(3) r, k = (1 + s) exp(-s); nu = 0.5: k = exp(-r).  d2 = 0 gives exactly 1.
 template <int KERNEL>
 __device__ __forceinline__ double gpbo_kernel_value(double d2) {
+  static_assert(KERNEL >= GPBO_KERNEL_RBF && KERNEL <= GPBO_KERNEL_MATERN05, "unknown kernel kind");
   if (KERNEL == GPBO_KERNEL_MATERN25) {
     const double k = gpbo_sqrt_pos(d2) * 2.23606797749978969641;
     return (1.0 + k + (k * k) * 0.33333333333333333333) * gpbo_exp_nonpos(-k);
+  } else if (KERNEL == GPBO_KERNEL_MATERN15) {
+    const double s = gpbo_sqrt_pos(d2) * 1.73205080756887729353;
+    return (1.0 + s) * gpbo_exp_nonpos(-s);
+  } else if (KERNEL == GPBO_KERNEL_MATERN05) {
+    return gpbo_exp_nonpos(-gpbo_sqrt_pos(d2));
   } else {
     return gpbo_exp_nonpos(-0.5 * d2);
+  }
+}
+// The slope f(d2) of a kernel, given its value kv = gpbo_kernel_value<KERNEL>(d2) — the one factor both gradients are made of:
+//   dk / dxs_t      =  f * (xs_t - Xs_t)      the gradient in the (scaled) inputs: posterior_small.hip, polish_fused.hip
+//   dK / dlog l_t   = -f * (xs_t - Xs_t)^2    what the LML gradient accumulates: lml_bodies.h (kernels.py:1764-1766, 1567-1582)
+//   RBF        f = -k
+//   nu = 2.5   f = -(5/3) (1 + s) exp(-s), s = sqrt(5) r        (no 1 / r singularity)
+//   nu = 1.5   f = -3 exp(-sqrt(3) r)                           (none either)
+//   nu = 0.5   f = -exp(-r) / r for r > 0 and 0 at r = 0: sklearn zeroes the non-finite gradient entries of coincident points
+//              (kernels.py: K_gradient[~np.isfinite(K_gradient)] = 0), so a candidate ON a training point gets no gradient from it.
+// LIBM_ROOT: the nu = 2.5 root as sqrt(5 d2) through the library's square root, the arithmetic the LML gradient has had from its
+// first version (its values are part of what a theta search returns); everywhere else the root is gpbo_sqrt_pos, as in the value.
+template <int KERNEL, bool LIBM_ROOT = false>
+__device__ __forceinline__ double gpbo_kernel_slope(double d2, double kv) {
+  static_assert(KERNEL >= GPBO_KERNEL_RBF && KERNEL <= GPBO_KERNEL_MATERN05, "unknown kernel kind");
+  if (KERNEL == GPBO_KERNEL_MATERN25) {
+    if (LIBM_ROOT) {
+      const double tmp = sqrt(5.0 * d2);
+      return -(5.0 / 3.0 * (tmp + 1.0) * gpbo_exp_nonpos(-tmp));
+    }
+    const double s = gpbo_sqrt_pos(d2) * 2.23606797749978969641;      // sqrt(5) r
+    return -1.66666666666666666667 * (1.0 + s) * gpbo_exp_nonpos(-s);
+  } else if (KERNEL == GPBO_KERNEL_MATERN15) {
+    return -3.0 * gpbo_exp_nonpos(-(gpbo_sqrt_pos(d2) * 1.73205080756887729353));
+  } else if (KERNEL == GPBO_KERNEL_MATERN05) {
+    return d2 > 0.0 ? -kv * gpbo_rsqrt_pos(d2) : 0.0;
+  } else {
+    return -kv;
   }
 }
 #endif
@@ -359,27 +411,40 @@ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 inline int pad_dim(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : 64; }
 
 // Template instance dispatch of the posterior launchers: f(kernel) / f(dp, kernel) with std::integral_constant arguments for the
-// model's kernel type (GPBO_KERNEL_MATERN25, anything else RBF) and padded dimension (pad_dim's values).
+// model's kernel type (the four kinds of gpbo.h) and padded dimension (pad_dim's values).  A kind outside the four runs nothing:
+// check_gp_args (gpbo_api.hip) lets none into a model, and one that got here anyway is an error, never a silent RBF.
 template <typename F>
-int with_kernel(int kernel, F&& f) {
-  if (kernel == GPBO_KERNEL_MATERN25) return f(std::integral_constant<int, GPBO_KERNEL_MATERN25>{});
-  return f(std::integral_constant<int, GPBO_KERNEL_RBF>{});
+int with_kernel(gpbo_ctx* ctx, int kernel, F&& f) {
+  switch (kernel) {
+    case GPBO_KERNEL_RBF: return f(std::integral_constant<int, GPBO_KERNEL_RBF>{});
+    case GPBO_KERNEL_MATERN25: return f(std::integral_constant<int, GPBO_KERNEL_MATERN25>{});
+    case GPBO_KERNEL_MATERN15: return f(std::integral_constant<int, GPBO_KERNEL_MATERN15>{});
+    case GPBO_KERNEL_MATERN05: return f(std::integral_constant<int, GPBO_KERNEL_MATERN05>{});
+  }
+  GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "unknown kernel kind " + std::to_string(kernel));
 }
-// ... and the four <KERNEL, WLDS> instances of the one-launch search kernels (search_plan.h: W in LDS or streamed from memory)
+// every kind's instance in turn (the per-device function attributes of a kernel template)
 template <typename F>
-int with_kernel_wlds(int kernel, bool wlds, F&& f) {
-  return with_kernel(kernel, [&](auto k) -> int { return wlds ? f(k, std::true_type{}) : f(k, std::false_type{}); });
-}
-template <typename F>
-int for_each_kernel_wlds(F&& f) {
-  for (const int kernel : {GPBO_KERNEL_MATERN25, GPBO_KERNEL_RBF})
-    for (const bool wlds : {true, false})
-      if (const int rc = with_kernel_wlds(kernel, wlds, f)) return rc;
+int for_each_kernel(gpbo_ctx* ctx, F&& f) {
+  for (const int kernel : {GPBO_KERNEL_MATERN25, GPBO_KERNEL_RBF, GPBO_KERNEL_MATERN15, GPBO_KERNEL_MATERN05})
+    if (const int rc = with_kernel(ctx, kernel, f)) return rc;
   return GPBO_OK;
+}
+// ... and the <KERNEL, WLDS> instances of the one-launch search kernels (search_plan.h: W in LDS or streamed from memory)
+template <typename F>
+int with_kernel_wlds(gpbo_ctx* ctx, int kernel, bool wlds, F&& f) {
+  return with_kernel(ctx, kernel, [&](auto k) -> int { return wlds ? f(k, std::true_type{}) : f(k, std::false_type{}); });
+}
+template <typename F>
+int for_each_kernel_wlds(gpbo_ctx* ctx, F&& f) {
+  return for_each_kernel(ctx, [&](auto k) -> int {
+    if (const int rc = f(k, std::true_type{})) return rc;
+    return f(k, std::false_type{});
+  });
 }
 template <typename F>
 int with_dp_kernel(gpbo_ctx* ctx, int DP, int kernel, F&& f) {
-  return with_kernel(kernel, [&](auto k) -> int {
+  return with_kernel(ctx, kernel, [&](auto k) -> int {
     switch (DP) {
       case 4: return f(std::integral_constant<int, 4>{}, k);
       case 8: return f(std::integral_constant<int, 8>{}, k);

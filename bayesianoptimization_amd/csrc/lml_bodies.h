@@ -82,13 +82,8 @@ __device__ __forceinline__ void lml_grad_tile_body(const double* Xs, const int D
         double kin;
         if constexpr (KT) kin = ktile[(ty * 4 + a) * 64 + tx * 4 + b];
         else kin = Kinv[i * NP + j];
-        double g;
-        if (KERNEL == GPBO_KERNEL_MATERN25) {
-          const double tmp = sqrt(5.0 * d2[a][b]);
-          g = 5.0 / 3.0 * (tmp + 1.0) * gpbo_exp_nonpos(-tmp);
-        } else {
-          g = gpbo_exp_nonpos(-0.5 * d2[a][b]);
-        }
+        // dK_ij / dlog l_t = g * (Xs_it - Xs_jt)^2 with g = -slope (gpbo_internal.h)
+        const double g = -gpbo_kernel_slope<KERNEL, true>(d2[a][b], gpbo_kernel_value<KERNEL>(d2[a][b]));
         c = wgt * (ai * aj - kin) * g;
       }
       coef[a][b] = c;

@@ -98,21 +98,26 @@ int launch_lml_grad(gpbo_ctx* ctx, Model& m, int n_ls, const double* Kinv, doubl
     const size_t lds2 = (size_t)(4096 + std::max(GT_LDS_DOUBLES, 2 * m.DP * 64 + 8)) * sizeof(double);
     if (!(ctx->func_attrs & ATTR_KINV_GRAD)) {
       const int cap = (int)((4096 + 2 * GPBO_MAX_DIM * 64 + 8) * sizeof(double));
-      GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kinv_grad_kernel<GPBO_KERNEL_MATERN25>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-      GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kinv_grad_kernel<GPBO_KERNEL_RBF>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+      const int rc = for_each_kernel(ctx, [&](auto k) -> int {
+        GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kinv_grad_kernel<decltype(k)::value>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+        return GPBO_OK;
+      });
+      if (rc) return rc;
       ctx->func_attrs |= ATTR_KINV_GRAD;
     }
-    if (m.kernel == GPBO_KERNEL_MATERN25)
-      kinv_grad_kernel<GPBO_KERNEL_MATERN25><<<grid, dim3(256), lds2, ctx->stream>>>(g, m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, partial, ls);
-    else
-      kinv_grad_kernel<GPBO_KERNEL_RBF><<<grid, dim3(256), lds2, ctx->stream>>>(g, m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, partial, ls);
-    GPBO_HIP(ctx, hipGetLastError());
-  } else if (m.kernel == GPBO_KERNEL_MATERN25)
-    lml_grad_kernel<GPBO_KERNEL_MATERN25><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, Kinv, partial, ls);
-  else
-    lml_grad_kernel<GPBO_KERNEL_RBF><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, Kinv, partial, ls);
+    const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
+      kinv_grad_kernel<decltype(k)::value><<<grid, dim3(256), lds2, ctx->stream>>>(g, m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, partial, ls);
+      return GPBO_OK;
+    });
+    if (rc) return rc;
+  } else {
+    const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
+      lml_grad_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, Kinv, partial, ls);
+      return GPBO_OK;
+    });
+    if (rc) return rc;
+  }
   GPBO_HIP(ctx, hipGetLastError());
   lml_grad_final_kernel<<<dim3((unsigned)(n_ls + (with_terms ? 1 : 0)), (unsigned)ctx->lanes), dim3(256), 0, ctx->stream>>>(
       partial, ntiles, n_ls, out, ls, out_pitch, m.yn, m.alpha, m.L, m.N, m.NP);

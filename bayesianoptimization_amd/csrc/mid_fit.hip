@@ -113,10 +113,11 @@ int launch_kmat_q(gpbo_ctx* ctx, Model& m, double noise, double* out) {
   const int64_t nt = m.NP / 64;
   dim3 grid((unsigned)(4 * (nt * (nt + 1) / 2)), 1, (unsigned)ctx->lanes);
   const size_t lds = (size_t)m.DP * 80 * sizeof(double);
-  if (m.kernel == GPBO_KERNEL_MATERN25)
-    kmat_q_kernel<GPBO_KERNEL_MATERN25><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride);
-  else
-    kmat_q_kernel<GPBO_KERNEL_RBF><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride);
+  const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
+    kmat_q_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride);
+    return GPBO_OK;
+  });
+  if (rc) return rc;
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }

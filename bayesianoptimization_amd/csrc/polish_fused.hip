@@ -279,12 +279,7 @@ __global__ __launch_bounds__(WLDS ? SEARCH_LDS_NP : SEARCH_MAX_NP) void polish_r
     {
       double d2;
       const double kv = pr_kstar<KERNEL>(xs, Xs + (int64_t)tid * xld, DP, d2);
-      if (KERNEL == GPBO_KERNEL_MATERN25) {
-        const double sq = gpbo_sqrt_pos(d2) * 2.23606797749978969641;      // sqrt(5) r
-        fi = -1.66666666666666666667 * (1.0 + sq) * gpbo_exp_nonpos(-sq);
-      } else {
-        fi = -kv;
-      }
+      fi = gpbo_kernel_slope<KERNEL>(d2, kv);
       if (tid >= N) fi = 0.0;          // padding rows carry no gradient
       ks[tid] = kv;
     }
@@ -431,7 +426,7 @@ int launch_polish_fused(gpbo_ctx* ctx, Model& m, const PolishPlan& plan, const P
   if (plan.mode == SearchMode::NotServed) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "launch_polish_fused: the model is outside the one-launch path's range");
   const int d = m.d;
   if (!(ctx->func_attrs & ATTR_POLISH_FUSED)) {
-    const int rc = for_each_kernel_wlds([&](auto k, auto wlds) -> int {
+    const int rc = for_each_kernel_wlds(ctx, [&](auto k, auto wlds) -> int {
       GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(polish_rows_kernel<decltype(k)::value, decltype(wlds)::value>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, SEARCH_LDS_BYTES));
       return GPBO_OK;
@@ -461,10 +456,10 @@ int launch_polish_fused(gpbo_ctx* ctx, Model& m, const PolishPlan& plan, const P
     if (const int rc = ensure_w_transposed(ctx, m)) return rc;
     a.Wt = m.K;
   }
-  with_kernel_wlds(m.kernel, plan.mode == SearchMode::WInLds, [&](auto k, auto wlds) -> int {
+  if (const int rc = with_kernel_wlds(ctx, m.kernel, plan.mode == SearchMode::WInLds, [&](auto k, auto wlds) -> int {
     polish_rows_kernel<decltype(k)::value, decltype(wlds)::value><<<dim3((unsigned)n_seeds), dim3((unsigned)m.NP), (size_t)plan.lds_bytes, ctx->stream>>>(a);
     return GPBO_OK;
-  });
+  })) return rc;
   GPBO_HIP(ctx, hipGetLastError());
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return GPBO_OK;

@@ -60,10 +60,10 @@ int launch_posterior_cov(gpbo_ctx* ctx, Model& m, int64_t M, double y_std, doubl
   if ((rc = launch_gemm(ctx, h))) return rc;
   const dim3 grid((unsigned)((M + 255) / 256), (unsigned)M);
   const double scale = y_std * y_std;
-  with_kernel(m.kernel, [&](auto k) {
+  if (const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
     cov_finalize_kernel<decltype(k)::value><<<grid, dim3(256), 0, ctx->stream>>>(ctx->Xcs, m.DP, M, Mp, scale, C);
     return GPBO_OK;
-  });
+  })) return rc;
   GPBO_HIP(ctx, hipGetLastError());
   *cov_dev = C;
   *ld_cov = Mp;

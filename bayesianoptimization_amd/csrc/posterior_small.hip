@@ -138,10 +138,10 @@ int launch_posterior_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, double
   double* ks = ctx->part;
   double* vsq = ctx->part + rows * m.NP;
   const dim3 kgrid((unsigned)((m.NP + 255) / 256), (unsigned)((M + 15) / 16));
-  with_kernel(m.kernel, [&](auto k) {
+  if (const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
     kstar_small_kernel<decltype(k)::value><<<kgrid, dim3(256), 0, ctx->stream>>>(m.Xs, ctx->Xcs, m.DP, m.NP, M, ks);
     return GPBO_OK;
-  });
+  })) return rc;
   GPBO_HIP(ctx, hipGetLastError());
   // passes of up to 16 candidates (the row order of the dot products does not depend on the pass width, so a
   // candidate's result is bitwise the same whether it is evaluated alone or inside a batch)
@@ -171,8 +171,8 @@ int launch_posterior_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, double
 //   mu      = y_std * sum_k alpha_k k_k + y_mean          d mu    / d x_t = y_std * sum_k alpha_k dk_k/dxs_t / l_t
 //   var_n   = 1 - v.v                                     d var_n / d x_t = -2 * sum_k u_k dk_k/dxs_t / l_t
 //   sd      = y_std * sqrt(max(var_n, 0))                 d sd    / d x_t = y_std * (d var_n / d x_t) / (2 sqrt(var_n))
-//   dk_k/dxs_t = f_k * (xs_t - Xs_kt),  f_k = -(5/3) (1 + sqrt5 r) exp(-sqrt5 r)  (Matern-2.5, no 1/r singularity)
-//                                       f_k = -k_k                                 (RBF)
+//   dk_k/dxs_t = f_k * (xs_t - Xs_kt),  f_k = gpbo_kernel_slope (gpbo_internal.h: every kind's formula; Matern nu = 0.5 has a 1/r
+//                                       singularity and takes f = 0 at r = 0, the others have none)
 // (sklearn has no analytic input gradient; the formulas are the derivatives of kernels.py:1722-1724 / 1559-1560 and of
 // _gpr.py:443-494.)  Kernels: kstar_grad_small (k and f), gemv_small<STORE_V> (v), gemvt_small + reduce (u = W^T v in
 // two deterministic passes), grad_small (the two k-sums per dimension, fixed reduction order), finalize_small.
@@ -192,13 +192,7 @@ __global__ __launch_bounds__(256) void kstar_grad_small_kernel(const double* __r
       d2 = fma(df, df, d2);
     }
     const double kv = gpbo_kernel_value<KERNEL>(d2);
-    double f;
-    if (KERNEL == GPBO_KERNEL_MATERN25) {
-      const double s = gpbo_sqrt_pos(d2) * 2.23606797749978969641;      // sqrt(5) r
-      f = -1.66666666666666666667 * (1.0 + s) * gpbo_exp_nonpos(-s);
-    } else {
-      f = -kv;
-    }
+    const double f = gpbo_kernel_slope<KERNEL>(d2, kv);
     ks[(int64_t)c * NP + k] = kv;
     fs[(int64_t)c * NP + k] = (k < N) ? f : 0.0;      // padding rows carry no gradient
   }
@@ -441,10 +435,10 @@ int launch_posterior_grad_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, d
   double* partial = vb + rows * m.NP;
   double* gpart = partial + (int64_t)n_splits * M * m.NP;
   const dim3 kgrid((unsigned)((m.NP + 255) / 256), (unsigned)((M + 15) / 16));
-  with_kernel(m.kernel, [&](auto k) {
+  if (const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
     kstar_grad_small_kernel<decltype(k)::value><<<kgrid, dim3(256), 0, ctx->stream>>>(m.Xs, ctx->Xcs, m.DP, m.NP, m.N, M, ks, fs);
     return GPBO_OK;
-  });
+  })) return rc;
   GPBO_HIP(ctx, hipGetLastError());
   // v = W k*: passes of 8 candidates (a padded last pass reads/writes scratch rows that exist: rows = M + 16)
   {

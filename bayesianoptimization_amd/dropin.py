@@ -15,14 +15,16 @@ import numpy as np
 
 from . import fused_acquisition as A
 from ._lib import MAX_DIM
+from .engine import MATERN25
+from .engine import RBF as K_RBF
 from .gpr import HipGPR, describe_kernel, shared_engine
 
 
-def _note_unsupported(kernel, what: str) -> str | None:
+def _note_unsupported(kernel, what: str, matern_family: bool = False) -> str | None:
     """One UserWarning when a model's kernel is outside the device path: the model is swapped all the same (so that a later
     `set_gp_params(kernel=...)` with a supported kernel puts it on the GPU) and runs scikit-learn's code until then."""
     try:
-        describe_kernel(kernel)
+        describe_kernel(kernel, matern_family)
     except NotImplementedError as exc:
         warnings.warn(f"accelerate(): {what}: {exc}; it keeps running scikit-learn's GaussianProcessRegressor on the host "
                       "(the reference's path) until its kernel is one the HIP engine evaluates", UserWarning, stacklevel=3)
@@ -73,7 +75,7 @@ WARM_SIZES = (12, 70, 200, 270, 330)
 
 
 def warm_up(engine, bounds, acquisition=None, kernel=None, n_restarts_optimizer: int = 5, n_constraints: int = 0,
-            n_random: int = 10_000, lml_on_device="auto", sizes=WARM_SIZES) -> float:
+            n_random: int = 10_000, lml_on_device="auto", sizes=WARM_SIZES, matern_family: bool = False) -> float:
     """Pay the first-use costs of a small-N suggest() now instead of inside the user's maximize() loop: every code object is
     loaded, every buffer family allocated for this dimension, every dispatch band's launch sequence (and its captured graph)
     run once.  Five synthetic default-configuration suggest() calls (theta search with restarts, candidates on the device,
@@ -100,7 +102,7 @@ def warm_up(engine, bounds, acquisition=None, kernel=None, n_restarts_optimizer:
     if kernel is None:
         kernel = Matern(nu=2.5)
     try:
-        describe_kernel(kernel)
+        describe_kernel(kernel, matern_family)
     except NotImplementedError:
         return 0.0
     with warnings.catch_warnings():
@@ -121,7 +123,7 @@ def warm_up(engine, bounds, acquisition=None, kernel=None, n_restarts_optimizer:
             cv = None if cm is None else np.cos(2.0 * U.sum(1))[:, None].repeat(n_constraints, 1).squeeze()
             sp.register_bulk(X, y, cv)
             gp = HipGPR(kernel=clone(kernel), alpha=1e-6, normalize_y=True, n_restarts_optimizer=n_restarts_optimizer,
-                        random_state=np.random.RandomState(1), engine=engine)
+                        random_state=np.random.RandomState(1), engine=engine, matern_family=matern_family)
             gp.lml_on_device = lml_on_device
             fn = copy.deepcopy(fn0)
             try:
@@ -133,16 +135,16 @@ def warm_up(engine, bounds, acquisition=None, kernel=None, n_restarts_optimizer:
 
 def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=None, precision: str = "f64",
                devices=None, local_search: str = "auto", lml_on_device="auto", warm: bool = True,
-               mixed_search: str = "reference"):
+               mixed_search: str = "reference", matern_family: bool = False):
     """Swap the GP(s) and the acquisition function of `optimizer` in place; returns `optimizer`.
 
     `devices=[0, 1, ...]`: shard the random stage of every suggest() over these GPUs from this ONE process (GroupEngine:
     replicated fit, contiguous candidate blocks, one RCCL all-gather of the per-device arg-best records); the suggestion
     is bit for bit the single-GPU one.
 
-    A model whose kernel is outside the HIP path (anything but Matern(nu=2.5) / RBF, see gpr.describe_kernel) — now, or after
-    a later `optimizer.set_gp_params(kernel=...)` (bayes_opt/bayesian_optimization.py:403-407) — degrades instead of raising:
-    that model runs scikit-learn's own fit / predict (the reference's trajectory, bit for bit) with one UserWarning, the
+    A model whose kernel is outside the HIP path (anything but Matern(nu=2.5) / RBF, or with `matern_family` the Matern family of
+    gpr.describe_kernel) — now, or after a later `optimizer.set_gp_params(kernel=...)`
+    (bayes_opt/bayesian_optimization.py:403-407) — degrades instead of raising: that model runs scikit-learn's own fit / predict (the reference's trajectory, bit for bit) with one UserWarning, the
     fused acquisition classes run over its `predict`.  Supported models have NO CPU fallback: RuntimeError / ImportError
     when no GPU or no built library is available.
     `n_random` overrides the number of random candidates per suggest() (reference default 10_000).
@@ -163,6 +165,11 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
     trip per trial.  "device": the same walk, draw for draw on the optimizer's RandomState, with the trials evaluated on the
     device (gpbo_evolve_mixed) wherever it applies — one model without constraint GPs, stock UCB / EI / POI (also under GPHedge
     and ConstantLiar), at most 512 observations, SciPy 1.15.x; the energies agree with the host's to rounding.
+    `matern_family` (default False): opt in to the other closed-form Matern kernels on the device — Matern(nu=1.5),
+    Matern(nu=0.5) and Matern(nu=inf) (evaluated as RBF, as scikit-learn does) — for the target GP and every constraint GP, now or
+    after a later `set_gp_params(kernel=...)`.  Off, such a kernel degrades to the host like any other.  A nu = 0.5 posterior has
+    kinks at the training points; the device local search uses the analytic gradient with a coincident training point contributing
+    0 (scikit-learn's convention for the kernel's non-finite gradient entries).
     `warm` (default True): run `warm_up` once per engine and dimension — five synthetic suggest() calls (~0.3 s) that load the
     code objects, allocate and launch every small-N path, so that no suggest() of the user's loop carries a first-use spike.
     The optimizer's RandomState is not touched.
@@ -175,7 +182,8 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
         engine = shared_engine(tuple(devices)) if devices is not None else shared_engine(device)
     space = optimizer._space
     transform = None if _identity_transform(space) else space.kernel_transform
-    noted = _note_unsupported(optimizer._gp.kernel, "the target GP")
+    matern_family = bool(matern_family)
+    noted = _note_unsupported(optimizer._gp.kernel, "the target GP", matern_family)
     width = int(getattr(space, "bounds", np.zeros((0, 2))).shape[0])      # columns in kernel space (categoricals are one-hot there)
     too_wide = None
     if width > MAX_DIM:
@@ -185,7 +193,8 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
                           f"one-hot), the HIP engine takes {MAX_DIM}; the models keep running scikit-learn's "
                           "GaussianProcessRegressor on the host (the reference's path)", UserWarning, stacklevel=2)
         noted = noted or too_wide
-    optimizer._gp = HipGPR.from_sklearn(optimizer._gp, transform=transform, engine=engine, slot=0, precision=precision)
+    optimizer._gp = HipGPR.from_sklearn(optimizer._gp, transform=transform, engine=engine, slot=0, precision=precision,
+                                        matern_family=matern_family)
     optimizer._gp.lml_on_device = lml_on_device
     if noted:
         optimizer._gp._host_warned = noted          # said once, here
@@ -194,8 +203,9 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
         if len(constraint._model) > 7:
             raise NotImplementedError("at most 7 constraint GPs fit the engine's model slots")
         for j, m in enumerate(constraint._model):
-            noted = _note_unsupported(m.kernel, f"constraint GP {j}") or too_wide
-            constraint._model[j] = HipGPR.from_sklearn(m, transform=transform, engine=engine, slot=j + 1, precision=precision)
+            noted = _note_unsupported(m.kernel, f"constraint GP {j}", matern_family) or too_wide
+            constraint._model[j] = HipGPR.from_sklearn(m, transform=transform, engine=engine, slot=j + 1, precision=precision,
+                                                       matern_family=matern_family)
             constraint._model[j].lml_on_device = lml_on_device
             if noted:
                 constraint._model[j]._host_warned = noted
@@ -214,13 +224,23 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
                 f.device_evolve = True
     from .engine import GpEngine
 
-    if warm and isinstance(engine, GpEngine) and transform is None and not too_wide and not engine.__dict__.get("_warmed", {}).get(width):
+    # once per engine and dimension — and once more when the TARGET GP's kernel at this moment is one of the opt-in kinds, whose
+    # instances Matern(nu=2.5) / RBF never load (a constraint GP's other kind, or a kernel set later, warms as it goes)
+    warm_key = width
+    if matern_family:
+        try:
+            kind = describe_kernel(optimizer._gp.kernel, True)[0]
+            warm_key = width if kind in (K_RBF, MATERN25) else (width, kind)
+        except NotImplementedError:
+            pass
+    if warm and isinstance(engine, GpEngine) and transform is None and not too_wide and not engine.__dict__.get("_warmed", {}).get(warm_key):
         # (a real engine only: test doubles have nothing to warm; mixed spaces run their local searches on the host and warm
-        # as they go; once per engine and dimension)
+        # as they go)
         fn = optimizer._acquisition_function
         warm_up(engine, space.bounds, acquisition=fn if isinstance(fn, A.AcquisitionFunction) else None,
                 kernel=optimizer._gp.kernel, n_restarts_optimizer=int(optimizer._gp.n_restarts_optimizer or 0),
                 n_constraints=0 if constraint is None else len(constraint._model),
-                n_random=int(getattr(fn, "default_n_random", 10_000)), lml_on_device=lml_on_device)
-        engine.__dict__.setdefault("_warmed", {})[width] = True
+                n_random=int(getattr(fn, "default_n_random", 10_000)), lml_on_device=lml_on_device,
+                matern_family=matern_family)
+        engine.__dict__.setdefault("_warmed", {})[warm_key] = True
     return optimizer

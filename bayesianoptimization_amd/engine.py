@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import dptr, iptr
 
-RBF, MATERN25 = 0, 1
+RBF, MATERN25, MATERN15, MATERN05 = 0, 1, 2, 3
 UCB, EI, POI = 0, 1, 2
 F64, F32 = 0, 1
 

@@ -15,6 +15,8 @@ estimator so all of that keeps its meaning, and replaces the two numeric stages:
 
 Supported on the HIP path: Matern(nu=2.5) and RBF (optionally wrapped by bayes_opt's `wrap_kernel`,
 optionally scaled by a fixed-at-1 ConstantKernel as in sklearn's default), scalar `alpha`, 1-D targets.
+With `matern_family=True` (opt-in) also the other closed-form members of the Matern family: nu = 1.5, nu = 0.5 and nu = inf
+(which scikit-learn evaluates with RBF's formulas).
 Anything else — `set_gp_params(kernel=Matern(nu=1.5))` on an accelerated optimizer
 (bayes_opt/bayesian_optimization.py:403-407), a per-sample `alpha`, several targets — is outside the device path: the
 estimator then IS its base class for that fit (scikit-learn's own `fit` / `predict`, the reference's arithmetic and
@@ -36,7 +38,7 @@ from sklearn.utils import check_random_state
 from sklearn.utils.validation import validate_data
 
 from ._lib import MAX_DIM
-from .engine import MATERN25, GpEngine
+from .engine import MATERN05, MATERN15, MATERN25, GpEngine
 from .engine import RBF as K_RBF
 
 _shared_engines: dict = {}
@@ -60,12 +62,16 @@ def shared_engine(device=0) -> GpEngine:
     return _shared_engines[key]
 
 
-def describe_kernel(kernel):
+def describe_kernel(kernel, matern_family=False):
     """(kind, length_scale array) for a supported kernel, else raise NotImplementedError.
 
     Accepts Matern(nu=2.5) / RBF, dynamic subclasses made by bayes_opt.parameter.wrap_kernel
     (parameter.py:457-495; MRO WrappedKernel -> Matern -> RBF), and `ConstantKernel(1, "fixed") * k`
     (sklearn's default kernel, _gpr.py:241-246).
+
+    `matern_family=True` (opt-in: HipGPR / accelerate pass their own flag) also accepts Matern(nu=1.5), Matern(nu=0.5) and
+    Matern(nu=inf) — the last as the RBF kind: kernels.py evaluates it with RBF's value and gradient.  Any other nu (Bessel
+    functions, kernels.py:1725-1733) stays outside the device path.
     """
     k = kernel
     if isinstance(k, Product):
@@ -76,14 +82,22 @@ def describe_kernel(kernel):
             raise NotImplementedError(f"HIP path supports only a fixed unit ConstantKernel factor, got {kernel!r}")
         k = inner
     if isinstance(k, Matern):
-        if k.nu != 2.5:
+        if matern_family:
+            kind = _MATERN_KINDS.get(float(k.nu))
+            if kind is None:
+                raise NotImplementedError(f"HIP path supports Matern with nu = 0.5, 1.5, 2.5 or inf, got nu={k.nu}")
+        elif k.nu != 2.5:
             raise NotImplementedError(f"HIP path supports Matern(nu=2.5) only, got nu={k.nu}")
-        kind = MATERN25
+        else:
+            kind = MATERN25
     elif isinstance(k, RBF):
         kind = K_RBF
     else:
         raise NotImplementedError(f"HIP path supports Matern(nu=2.5) and RBF kernels, got {type(kernel).__name__}")
     return kind, np.atleast_1d(np.asarray(k.length_scale, dtype=np.float64))
+
+
+_MATERN_KINDS = {0.5: MATERN05, 1.5: MATERN15, 2.5: MATERN25, float("inf"): K_RBF}
 
 
 def _bare_length_scale_kernel(kernel) -> bool:
@@ -122,7 +136,7 @@ class HipGPR(GaussianProcessRegressor):
     def __init__(self, kernel=None, *, alpha=1e-10, optimizer="fmin_l_bfgs_b", n_restarts_optimizer=0,
                  normalize_y=False, copy_X_train=True, n_targets=None, random_state=None,
                  transform=None, engine=None, slot=0, lml_on_device="auto", precision="f64", incremental=True,
-                 theta_lockstep=True):
+                 theta_lockstep=True, matern_family=False):
         super().__init__(kernel=kernel, alpha=alpha, optimizer=optimizer,
                          n_restarts_optimizer=n_restarts_optimizer, normalize_y=normalize_y,
                          copy_X_train=copy_X_train, n_targets=n_targets, random_state=random_state)
@@ -145,6 +159,9 @@ class HipGPR(GaussianProcessRegressor):
         # theta search with restarts: advance the independent L-BFGS-B runs together, their LML evaluations side by
         # side on the device (gpbo_lml_batch); same iterates and same RandomState draws as one run after another
         self.theta_lockstep = theta_lockstep
+        # opt-in: Matern(nu=1.5), Matern(nu=0.5) and Matern(nu=inf) run on the device too (describe_kernel); off, they are
+        # outside the device path like every kernel but Matern(nu=2.5) / RBF
+        self.matern_family = matern_family
 
     # -- outside the device path ------------------------------------------------------------------
     #: True after a fit that the device path does not cover: every numeric method is then the base class's
@@ -155,7 +172,7 @@ class HipGPR(GaussianProcessRegressor):
     def _unsupported_reason(self, kernel, y=None, X=None):
         """Why this configuration is outside the device path (None when it is inside)."""
         try:
-            describe_kernel(kernel)
+            describe_kernel(kernel, self.matern_family)
         except NotImplementedError as exc:
             return str(exc)
         if np.iterable(self.alpha):
@@ -237,13 +254,14 @@ class HipGPR(GaussianProcessRegressor):
         return np.ascontiguousarray(X)
 
     @classmethod
-    def from_sklearn(cls, gp: GaussianProcessRegressor, transform=None, engine=None, slot=0, precision="f64"):
+    def from_sklearn(cls, gp: GaussianProcessRegressor, transform=None, engine=None, slot=0, precision="f64", matern_family=False):
         """Same hyper-parameters (and the same RandomState object) as an existing estimator."""
         p = gp.get_params(deep=False)
         return cls(kernel=p["kernel"], alpha=p["alpha"], optimizer=p["optimizer"],
                    n_restarts_optimizer=p["n_restarts_optimizer"], normalize_y=p["normalize_y"],
                    copy_X_train=p["copy_X_train"], n_targets=p.get("n_targets"),
-                   random_state=p["random_state"], transform=transform, engine=engine, slot=slot, precision=precision)
+                   random_state=p["random_state"], transform=transform, engine=engine, slot=slot, precision=precision,
+                   matern_family=matern_family)
 
     # -- log marginal likelihood ---------------------------------------------------------------------
     def _device_lml_ok(self, kernel) -> bool:
@@ -254,7 +272,7 @@ class HipGPR(GaussianProcessRegressor):
         if np.iterable(self.alpha):
             return False
         try:
-            _, ls = describe_kernel(kernel)
+            _, ls = describe_kernel(kernel, self.matern_family)
         except NotImplementedError:
             return False
         if _bare_length_scale_kernel(kernel):
@@ -272,7 +290,7 @@ class HipGPR(GaussianProcessRegressor):
         else:
             kernel = self.kernel_
             kernel.theta = theta
-        kind, ls = describe_kernel(kernel)
+        kind, ls = describe_kernel(kernel, self.matern_family)
         out = self._engine().lml(self._tx(self.X_train_), self.y_train_, kind, ls, float(self.alpha),
                                  eval_gradient=eval_gradient, slot=self.slot)
         self.__dict__.pop("_L_cache", None)      # the slot's factorisation now belongs to this theta
@@ -417,7 +435,7 @@ class HipGPR(GaussianProcessRegressor):
             self._lml_lazy = True
 
         self._in_fit = False
-        kind, ls = describe_kernel(self.kernel_)
+        kind, ls = describe_kernel(self.kernel_, self.matern_family)
         if ls.shape[0] not in (1, self.n_features_in_):
             raise ValueError("Anisotropic kernel must have the same number of dimensions as data")
         self._kind, self._ls = kind, ls
@@ -439,7 +457,7 @@ class HipGPR(GaussianProcessRegressor):
         # theta = log(length scale(s)) for the kernels _device_lml_ok admits (one free length-scale hyper-parameter,
         # kernels.py:Hyperparameter/theta); checked once here — starts[0] IS kernel_.theta — instead of cloning the kernel
         # for every evaluation (a clone costs ~0.1 ms of sklearn's get_params / signature machinery)
-        kind, ls0 = describe_kernel(self.kernel_)
+        kind, ls0 = describe_kernel(self.kernel_, self.matern_family)
         if not np.all(np.abs(ls0 - np.exp(starts[0])) <= 1e-12 * np.abs(np.exp(starts[0]))):
             raise RuntimeError("theta does not map to the length scale as expected")    # pragma: no cover
         uploaded = [False]

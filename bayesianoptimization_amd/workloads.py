@@ -12,11 +12,13 @@ import numpy as np
 
 RBF = 0
 MATERN25 = 1
+MATERN15 = 2
+MATERN05 = 3
 UCB = 0
 EI = 1
 POI = 2
 
-KERNEL_NAMES = {RBF: "rbf", MATERN25: "matern25"}
+KERNEL_NAMES = {RBF: "rbf", MATERN25: "matern25", MATERN15: "matern15", MATERN05: "matern05"}
 ACQ_NAMES = {UCB: "ucb", EI: "ei", POI: "poi"}
 
 

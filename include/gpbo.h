@@ -49,7 +49,9 @@ enum gpbo_status {
                                  communicators are intact — this step has no result, the next one may  -> RuntimeError */
 };
 
-enum gpbo_kernel { GPBO_KERNEL_RBF = 0, GPBO_KERNEL_MATERN25 = 1 };
+/* The stationary kernels every entry point with an `int kernel` takes: RBF and the closed-form members of the Matern family
+ * (nu = 2.5, 1.5, 0.5; kernels.py Matern.__call__).  Any other value is GPBO_ERR_UNSUPPORTED. */
+enum gpbo_kernel { GPBO_KERNEL_RBF = 0, GPBO_KERNEL_MATERN25 = 1, GPBO_KERNEL_MATERN15 = 2, GPBO_KERNEL_MATERN05 = 3 };
 enum gpbo_acq { GPBO_ACQ_UCB = 0, GPBO_ACQ_EI = 1, GPBO_ACQ_POI = 2 };
 enum gpbo_precision { GPBO_F64 = 0, GPBO_F32 = 1 };
 
@@ -73,7 +75,7 @@ int gpbo_device_info(gpbo_ctx* ctx, char* buf, int buflen);
 /* ---- fit at fixed theta ----------------------------------------------------------------- */
 /* Replaces the tail of GaussianProcessRegressor.fit (sklearn/gaussian_process/_gpr.py:346-364,
  * called from bayes_opt/acquisition.py:84 and bayes_opt/constraint.py:148,151):
- *   K = k(X/ls, X/ls) + noise*I   (Matern-2.5: kernels.py:1711-1738; RBF: kernels.py:1556-1565)
+ *   K = k(X/ls, X/ls) + noise*I   (Matern nu = 2.5 / 1.5 / 0.5: kernels.py:1711-1738; RBF: kernels.py:1556-1565)
  *   L = cholesky(K, lower)        (_gpr.py:349)
  *   alpha = cho_solve(L, y_norm)  (_gpr.py:360-364)
  * and additionally forms W = L^-1, the operator the posterior kernel applies to k*.
