@@ -36,6 +36,8 @@ SIGNATURES = {
     "gpbo_device_info": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "gpbo_fit": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int,
                            _c_double_p, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int)]),
+    "gpbo_fit_scaled": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, C.c_int,
+                                  C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int)]),
     "gpbo_fit_begin": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int,
                                  _c_double_p, C.c_int, C.c_double, C.c_int]),
     "gpbo_fit_wait": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
@@ -43,6 +45,8 @@ SIGNATURES = {
                                   C.POINTER(C.c_int)]),
     "gpbo_lml": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p,
                            C.c_int, C.c_double, C.c_int, _c_double_p, _c_double_p, C.POINTER(C.c_int)]),
+    "gpbo_lml_scaled": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, C.c_int,
+                                  C.c_double, C.c_double, C.c_double, C.c_int, _c_double_p, _c_double_p, C.POINTER(C.c_int)]),
     "gpbo_lml_batch": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p,
                                  C.c_int, C.c_double, C.c_int, _c_double_p, _c_double_p, C.POINTER(C.c_int)]),
     "gpbo_get_K": (C.c_int, [C.c_void_p, C.c_int, _c_double_p]),

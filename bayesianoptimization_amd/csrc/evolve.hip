@@ -44,6 +44,7 @@ struct EvolveArgs {
   const double *W, *Wt, *Xs, *alpha, *ls;
   int NP, N, DP;
   double y_mean, y_std;
+  double amplitude, white;             // of slot 0's model: normalised variance = amplitude * (1 - |W k*|^2) + white
   int acq;
   double acq_param, y_max;
   int analytic;
@@ -442,7 +443,7 @@ __global__ __launch_bounds__(SEARCH_MAX_NP) void evolve_kernel(const EvolveArgs 
       }
       s2 = pr_lane(s2, 0);
       mm = pr_lane(mm, 0);
-      double var = 1.0 - s2;
+      double var = fma(a.amplitude, 1.0 - s2, a.white);
       if (var < 0.0) var = 0.0;
       const double sd = sqrt(var * (a.y_std * a.y_std));
       const double mu = a.y_std * mm + a.y_mean;
@@ -569,6 +570,7 @@ int run_evolve(gpbo_ctx* ctx, const EvolveObjective& o, const EvolveRun& r) {
   int* dw = (int*)dblock.p;
   EvolveArgs a{};
   a.analytic = model ? 0 : 1;
+  a.amplitude = 1.0; a.white = 0.0;
   a.D = D; a.S = S; a.maxiter = r.maxiter; a.budget = model ? plan.evals_per_launch : r.budget;
   a.pop = dd + b.pop; a.energies = dd + b.E; a.arg1 = dd + b.arg1; a.arg2 = dd + b.arg2; a.aw = dd + b.aw; a.aa = dd + b.aa;
   a.eval_x = dd + b.eval_x; a.eval_out = dd + b.eval_out; a.scale = dd + b.scale;
@@ -582,6 +584,7 @@ int run_evolve(gpbo_ctx* ctx, const EvolveObjective& o, const EvolveRun& r) {
   if (model) {
     Model& m = *model;
     a.W = m.W; a.Xs = m.Xs; a.alpha = m.alpha; a.ls = m.ls;
+    a.amplitude = m.amplitude; a.white = m.white;
     a.NP = NP; a.N = (int)m.N; a.DP = m.DP;
     block = dim3((unsigned)m.NP);
     if (plan.mode == SearchMode::WInMemory) {

@@ -18,11 +18,19 @@ __device__ __forceinline__ void prescale_elem(const double* X, const int64_t n, 
   out[idx] = v;
 }
 
-// mu = y_std * (k* . alpha) + y_mean ; sd = sqrt(max(1 - |W k*|^2, 0) * y_std^2) for one candidate (sklearn _gpr.py:444-447, 474-494):
-// posterior_finalize_kernel's element, also the epilogue of a fused posterior launch that owns all rows of its candidates.
+// The normalised variance of a model c * k + white * I from q = |W k*|^2 of its unit-amplitude fit: c (1 - q) + white, one fma —
+// at c = 1, white = 0 the bits of 1 - q.
+__device__ __forceinline__ double scaled_variance(const double amplitude, const double white, const double ss) {
+  return fma(amplitude, 1.0 - ss, white);
+}
+
+// mu = y_std * (k* . alpha) + y_mean ; sd = sqrt(max(c (1 - |W k*|^2) + white, 0) * y_std^2) for one candidate (sklearn
+// _gpr.py:444-447, 474-494): posterior_finalize_kernel's element, also the epilogue of a fused posterior launch that owns all rows
+// of its candidates.
 __device__ __forceinline__ void posterior_finalize_elem(const double ss, const double mun, const double y_mean, const double y_std,
-                                                        double* mu, double* sd, int* negvar) {
-  double var = 1.0 - ss;
+                                                        const double amplitude, const double white, double* mu, double* sd,
+                                                        int* negvar) {
+  double var = scaled_variance(amplitude, white, ss);
   if (var < 0.0) {                   // _gpr.py:479-485 (NaN stays NaN, as in numpy); the host warns as sklearn does
     *negvar = 1;
     var = 0.0;

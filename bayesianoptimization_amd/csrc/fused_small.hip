@@ -61,6 +61,7 @@ __device__ __forceinline__ void fs_run_tiles(const GemmArgs& g, const int tiles_
 struct FusedArgs {
   int64_t N, NP;
   int d, DP, n_ls, mode;          // mode 0: fit (W packed for the posterior kernels), 1: LML value, 2: LML value + gradient
+  int noise_grad;                 // mode 2: the noise component g_eta behind the n_ls gradient entries (lml_bodies.h)
   int src;                        // 0: raw X / y / length scales given; 1: Xs, yn, ls already resident in the model (refit at the same theta)
   double noise;
   const double* X;                // raw (N, d): device memory, or pinned host memory (device-visible)
@@ -227,20 +228,22 @@ __device__ __forceinline__ void fs_lml(const FusedArgs& a, const int64_t lo, con
     g.C = Km; g.ldc = NP; g.batch = 1; g.lower_only = 1; g.k_from_tile = 1; g.lanes = 1;
     fs_run_tiles<false, true>(g, nblk, nblk, 1, lds_half, half, t256);
     const int ntile = nblk * (nblk + 1) / 2;
+    const int n_out = a.n_ls + a.noise_grad;
     for (int r = 0; r < ntile; r += 2) {
       const int b = r + half;
       int bi = 0, bj = 0;
       if (b < ntile) lower_tile_of(b, bi, bj);
-      lml_grad_tile_body<KERNEL>(a.Xs + lo, a.DP, a.n_ls, a.N, NP, a.alpha + lo, Km, tmp, bi, bj, lds_half, t256, b < ntile);
+      lml_grad_tile_body<KERNEL>(a.Xs + lo, a.DP, a.n_ls, a.N, NP, a.alpha + lo, Km, tmp, bi, bj, lds_half, t256, b < ntile, nullptr,
+                                 a.noise_grad != 0);
     }
     __syncthreads();
-    for (int r = 0; r < a.n_ls; r += 2) {
+    for (int r = 0; r < n_out; r += 2) {
       const int t = r + half;
-      lml_grad_final_body(tmp, ntile, a.n_ls, scal + 2, t < a.n_ls ? t : 0, lds_half, t256, t < a.n_ls);
+      lml_grad_final_body(tmp, ntile, n_out, scal + 2, t < n_out ? t : 0, lds_half, t256, t < n_out);
     }
   }
   __syncthreads();
-  const int nout = 2 + (a.mode == 2 ? a.n_ls : 0);
+  const int nout = 2 + (a.mode == 2 ? a.n_ls + a.noise_grad : 0);
   if (tid < nout) a.out[(int64_t)zl * a.out_pitch + tid] = scal[tid];
 }
 
@@ -276,7 +279,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 int fused_max_np() { return fused_max_from(env_override(dbg_env("GPBO_FUSED_MAX_NP"))); }
 
 int launch_fused_small(gpbo_ctx* ctx, Model& m, int mode, int src, int n_ls, const double* X, const double* y, const double* ls_in,
-                       double* scal, int* info_out, int64_t info_pitch, double* out, int64_t out_pitch) {
+                       double* scal, int* info_out, int64_t info_pitch, double* out, int64_t out_pitch, bool noise_grad) {
   if (!(ctx->func_attrs & ATTR_FUSED)) {
     const int rc = for_each_kernel(ctx, [&](auto k) -> int {
       GPBO_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fused_small_kernel<decltype(k)::value>),
@@ -288,6 +291,7 @@ int launch_fused_small(gpbo_ctx* ctx, Model& m, int mode, int src, int n_ls, con
   }
   FusedArgs a{};
   a.N = m.N; a.NP = m.NP; a.d = m.d; a.DP = m.DP; a.n_ls = n_ls; a.mode = mode; a.src = src; a.noise = m.noise;
+  a.noise_grad = (mode == 2 && noise_grad) ? 1 : 0;
   a.X = X; a.y = y; a.ls_in = ls_in;
   a.ls = m.ls; a.Xs = m.Xs; a.K = m.K; a.L = m.L; a.W = m.W; a.Wp = m.Wp; a.dinv = m.dinv; a.tmp = m.tmp; a.yn = m.yn;
   a.tvec = m.tvec; a.alpha = m.alpha; a.scal = scal;

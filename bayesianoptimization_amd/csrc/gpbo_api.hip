@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "gpbo_internal.h"
+#include "scaled_kernel.h"    // a scaled model c * k + white * I as the unit model at noise (white + alpha) / c
 
 namespace gpbo {
 
@@ -321,7 +322,7 @@ static int stage_small_inputs(gpbo_ctx* ctx, const Model& m, const double* X, co
 // length scales of the pinned window; src 1: the model's resident Xs / yn / ls.  The pivot word and the LML scalars land in the
 // pinned words *info_host / *out_host (valid after the stream has drained) without copy nodes.
 static int enqueue_fused(gpbo_ctx* ctx, Model& m, const double* X, const double* y_norm, const double* X_dev, const double* y_dev,
-                         double noise, int mode, int n_ls, int src, int** info_host, double** out_host) {
+                         double noise, int mode, int n_ls, int src, int** info_host, double** out_host, bool noise_grad = false) {
   int rc;
   m.noise = noise;
   const double *Xd = X_dev, *yd = y_dev;
@@ -342,7 +343,7 @@ static int enqueue_fused(gpbo_ctx* ctx, Model& m, const double* X, const double*
   if (!ctx->no_timing) ctx->ev[T_KMAT].used = ctx->ev[T_CHOL].used = ctx->ev[T_TRTRI].used = false;   // one kernel: no phase events
   if ((rc = launch_fused_small(ctx, m, mode, src, n_ls, Xd, yd, pinned_dev(ctx, h.ls), scal, pinned_dev(ctx, h.info),
                                (int64_t)(PIN_INFO_PITCH / sizeof(int)), mode ? pinned_dev(ctx, h.out) : nullptr,
-                               (int64_t)(PIN_OUT_PITCH / sizeof(double)))))
+                               (int64_t)(PIN_OUT_PITCH / sizeof(double)), noise_grad)))
     return rc;
   if (mode == 0) m.wp_packed = true;
   else ev_end(ctx, T_FIT);
@@ -430,6 +431,8 @@ static int prepare_model(gpbo_ctx* ctx, Model& m, const char* who, bool have_inp
   m.wd_valid = false;      // W is about to change: the int8 digit planes of the old one must not be used
   m.wt_valid = false;      // (K no longer holds the transpose of this slot's W)
   m.M_post = -1;
+  m.amplitude = 1.0;       // a unit model until gpbo_fit_scaled says otherwise
+  m.white = 0.0;
   const int64_t NP = round_up(N, NB);
   const int DP = pad_dim(d);
   if ((rc = alloc_model(ctx, m, NP, DP))) return rc;
@@ -517,18 +520,43 @@ static int wait_all_pending_fits(gpbo_ctx* ctx) {
   return GPBO_OK;
 }
 
+// gpbo_fit (amplitude 1, white 0) and gpbo_fit_scaled: the fit at `noise`; the slot keeps amplitude and white for its posteriors
+static int fit_slot(gpbo_ctx* ctx, const char* who, int slot, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                    const double* length_scale, int n_ls, double noise, double amplitude, double white, int precision, int* info) {
+  int* info_h = nullptr;
+  int rc = check_slot(ctx, slot);
+  if (rc) return rc;
+  if ((rc = no_pending_fit(ctx, slot, who))) return rc;
+  Model& m = ctx->models[slot];
+  if ((rc = prepare_model(ctx, m, who, X && y_norm, N, d, kernel, length_scale, n_ls, noise, precision))) return rc;
+  m.amplitude = amplitude;
+  m.white = white;
+  if ((rc = enqueue_factor(ctx, m, X, y_norm, nullptr, nullptr, noise, &info_h))) return rc;
+  return finish_fit(ctx, m, info_h, info);
+}
+
+// amplitude > 0, white >= 0, alpha >= 0, all finite: what both scaled entry points require
+static int check_scaled_args(gpbo_ctx* ctx, const char* who, double amplitude, double white, double alpha) {
+  if (!scaled_args_ok(amplitude, white))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, std::string(who) + ": amplitude must be > 0 and white >= 0, both finite");
+  if (!(alpha >= 0.0) || !std::isfinite(alpha)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, std::string(who) + ": alpha must be >= 0 and finite");
+  return GPBO_OK;
+}
+
 int gpbo_fit(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int64_t N, int d,
              int kernel, const double* length_scale, int n_ls, double noise, int precision,
              int* info) {
   if (info) *info = 0;
-  int* info_h = nullptr;
-  int rc = check_slot(ctx, slot);
-  if (rc) return rc;
-  if ((rc = no_pending_fit(ctx, slot, "gpbo_fit"))) return rc;
-  Model& m = ctx->models[slot];
-  if ((rc = prepare_model(ctx, m, "gpbo_fit", X && y_norm, N, d, kernel, length_scale, n_ls, noise, precision))) return rc;
-  if ((rc = enqueue_factor(ctx, m, X, y_norm, nullptr, nullptr, noise, &info_h))) return rc;
-  return finish_fit(ctx, m, info_h, info);
+  return fit_slot(ctx, "gpbo_fit", slot, X, y_norm, N, d, kernel, length_scale, n_ls, noise, 1.0, 0.0, precision, info);
+}
+
+int gpbo_fit_scaled(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                    const double* length_scale, int n_ls, double amplitude, double white, double alpha, int precision, int* info) {
+  if (info) *info = 0;
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (const int rc = check_scaled_args(ctx, "gpbo_fit_scaled", amplitude, white, alpha)) return rc;
+  return fit_slot(ctx, "gpbo_fit_scaled", slot, X, y_norm, N, d, kernel, length_scale, n_ls, scaled_eta(amplitude, white, alpha),
+                  amplitude, white, precision, info);
 }
 
 int gpbo_fit_begin(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int64_t N, int d, int kernel,
@@ -604,7 +632,7 @@ int gpbo_fit_append(gpbo_ctx* ctx, int slot, const double* x_new, int64_t n_new,
     const Model old = m;   // alloc_model resets the descriptor along with the buffers
     if ((rc = alloc_model(ctx, m, round_up(NP_new + NP_new / 4, NB), DP))) { (void)hipFree(keep); return rc; }
     m.N = old.N; m.NP = old.NP; m.d = old.d; m.DP = old.DP; m.kernel = old.kernel; m.precision = old.precision;
-    m.noise = old.noise;
+    m.noise = old.noise; m.amplitude = old.amplitude; m.white = old.white;
     GPBO_HIP(ctx, hipMemcpyAsync(m.ls, ls_h, GPBO_MAX_DIM * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     GPBO_HIP(ctx, hipMemcpyAsync(m.Xs, keep, (size_t)N0 * DP * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -637,7 +665,7 @@ int gpbo_fit_append(gpbo_ctx* ctx, int slot, const double* x_new, int64_t n_new,
 
 // The part of a log-marginal-likelihood evaluation that follows the factorisation, enqueued on ctx->stream: the scalar
 // terms, K^-1 = W^T W and the gradient reduction, and the copy of the results to the pinned words *out_host.
-static int lml_tail(gpbo_ctx* ctx, Model& m, int n_ls, int eval_gradient, double** out_host) {
+static int lml_tail(gpbo_ctx* ctx, Model& m, int n_ls, int eval_gradient, double** out_host, bool noise_grad) {
   int rc;
   // the kernels write the scalars into the pinned words themselves (PIN_OUT_PITCH bytes per lane): no copy node
   double* out_h = pin_lane(ctx->pinned).out;
@@ -646,7 +674,7 @@ static int lml_tail(gpbo_ctx* ctx, Model& m, int n_ls, int eval_gradient, double
   if (!eval_gradient && (rc = launch_lml_terms(ctx, m, out_d, pitch))) return rc;
   if (eval_gradient) {
     if (kinv_in_grad_launch(tier_of(m))) {      // kinv_grad_kernel; the two LML terms in its final launch
-      if ((rc = launch_lml_grad(ctx, m, n_ls, nullptr, m.tmp, out_d, pitch, true))) return rc;
+      if ((rc = launch_lml_grad(ctx, m, n_ls, nullptr, m.tmp, out_d, pitch, true, noise_grad))) return rc;
     } else {                                    // the W^T W GEMM into the K buffer, then the trace reduction; partials go to m.tmp
       GemmArgs g{};
       g.m = (int)m.NP; g.n = (int)m.NP; g.k = (int)m.NP; g.alpha = 1.0; g.beta = 0.0;
@@ -654,7 +682,7 @@ static int lml_tail(gpbo_ctx* ctx, Model& m, int n_ls, int eval_gradient, double
       g.B = m.W; g.ldb = m.NP;
       g.C = m.K; g.ldc = m.NP; g.batch = 1; g.lower_only = 1; g.k_from_tile = 1;
       if ((rc = launch_gemm(ctx, g))) return rc;
-      if ((rc = launch_lml_grad(ctx, m, n_ls, m.K, m.tmp, out_d, pitch, true))) return rc;     // ... and the two LML terms
+      if ((rc = launch_lml_grad(ctx, m, n_ls, m.K, m.tmp, out_d, pitch, true, noise_grad))) return rc;     // ... and the two LML terms
     }
   }
   ev_end(ctx, T_FIT);
@@ -665,13 +693,15 @@ static int lml_tail(gpbo_ctx* ctx, Model& m, int n_ls, int eval_gradient, double
 // One log-marginal-likelihood evaluation of the prepared model m (and, in lane mode, of ctx->lanes models) enqueued on ctx->stream,
 // inputs from the host (X, y_norm) or resident on the device (X_dev, y_dev): the one fused launch, or factorisation + tail.  Results
 // land in the pinned words *out_host (yT alpha, sum log L_ii, gradient...) and *info_host once the stream has drained.
+// noise_grad (with eval_gradient): the gradient's noise component g_eta as word 2 + n_ls (gpbo_lml_scaled).
 static int enqueue_lml(gpbo_ctx* ctx, Model& m, const double* X, const double* y_norm, const double* X_dev, const double* y_dev,
-                       double noise, int n_ls, int eval_gradient, double** out_host, int** info_host) {
+                       double noise, int n_ls, int eval_gradient, double** out_host, int** info_host, bool noise_grad = false) {
+  noise_grad = noise_grad && eval_gradient;
   if (tier_of(m) == FitTier::Fused)
-    return enqueue_fused(ctx, m, X, y_norm, X_dev, y_dev, noise, eval_gradient ? 2 : 1, n_ls, 0, info_host, out_host);
+    return enqueue_fused(ctx, m, X, y_norm, X_dev, y_dev, noise, eval_gradient ? 2 : 1, n_ls, 0, info_host, out_host, noise_grad);
   int rc = enqueue_factor(ctx, m, X, y_norm, X_dev, y_dev, noise, info_host, false);
   if (rc) return rc;
-  return lml_tail(ctx, m, n_ls, eval_gradient, out_host);
+  return lml_tail(ctx, m, n_ls, eval_gradient, out_host, noise_grad);
 }
 
 static void lml_finish(const double* out_h, const int* info_h, int64_t N, int n_ls, int eval_gradient, double* lml,
@@ -702,6 +732,40 @@ int gpbo_lml(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int
   if ((rc = enqueue_lml(ctx, m, X, y_norm, nullptr, nullptr, noise, n_ls, eval_gradient, &out_h, &info_h))) return rc;
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   lml_finish(out_h, info_h, N, n_ls, eval_gradient, lml, grad, info);
+  return GPBO_OK;
+}
+
+int gpbo_lml_scaled(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                    const double* length_scale, int n_ls, double amplitude, double white, double alpha, int eval_gradient,
+                    double* lml, double* grad, int* info) {
+  if (info) *info = 0;
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!lml || (eval_gradient && !grad)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_scaled: NULL output");
+  int rc = check_slot(ctx, slot);
+  if (rc) return rc;
+  if ((rc = check_scaled_args(ctx, "gpbo_lml_scaled", amplitude, white, alpha))) return rc;
+  if ((rc = no_pending_fit(ctx, slot, "gpbo_lml_scaled"))) return rc;
+  const double eta = scaled_eta(amplitude, white, alpha);
+  int* info_h = nullptr;
+  double* out_h = nullptr;
+  // the unit model's evaluation U of the targets y / sqrt(c) at noise eta; the slot is left unfitted (and a unit model), as by gpbo_lml
+  Model& m = ctx->models[slot];
+  if ((rc = prepare_model(ctx, m, "gpbo_lml_scaled", X && y_norm, N, d, kernel, length_scale, n_ls, eta, GPBO_F64))) return rc;
+  const double ts = scaled_target_scale(amplitude);
+  std::vector<double> ys((size_t)N);       // (alive until the stream has drained below)
+  for (int64_t i = 0; i < N; ++i) ys[(size_t)i] = y_norm[i] * ts;
+  if ((rc = enqueue_lml(ctx, m, X, ys.data(), nullptr, nullptr, eta, n_ls, eval_gradient, &out_h, &info_h, true))) return rc;
+  GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (*info_h != 0) {      // as gpbo_lml: -inf and a zero gradient
+    if (info) *info = *info_h;
+    *lml = -INFINITY;
+    if (eval_gradient) for (int t = 0; t < n_ls + 2; ++t) grad[t] = 0.0;
+    return GPBO_OK;
+  }
+  double unit = 0.0;
+  lml_finish(out_h, info_h, N, n_ls, 0, &unit, nullptr, nullptr);
+  *lml = scaled_lml(unit, N, amplitude);
+  if (eval_gradient) scaled_lml_gradient(amplitude, white, alpha, N, out_h[0], out_h + 2, n_ls, out_h[2 + n_ls], grad);
   return GPBO_OK;
 }
 
@@ -950,12 +1014,19 @@ int gpbo_get_K(gpbo_ctx* ctx, int slot, double* out) {
   Model& m = ctx->models[slot];
   m.wt_valid = false;
   if ((rc = tier_of(m) == FitTier::Strip ? launch_kmat_q(ctx, m, m.noise, m.K) : launch_kmat(ctx, m, m.noise, m.K))) return rc;   // the fit's own kernel
-  return copy_square(ctx, m, m.K, out, 0);
+  if ((rc = copy_square(ctx, m, m.K, out, 0))) return rc;
+  if (m.amplitude != 1.0)      // a scaled slot holds the unit model K' = K / c
+    for (int64_t i = 0; i < m.N * m.N; ++i) out[i] = scaled_K_entry(m.amplitude, out[i]);
+  return GPBO_OK;
 }
 int gpbo_get_L(gpbo_ctx* ctx, int slot, double* out) {
   int rc = need_fitted(ctx, slot);
   if (rc) return rc;
-  return copy_square(ctx, ctx->models[slot], ctx->models[slot].L, out, 1);
+  const Model& m = ctx->models[slot];
+  if ((rc = copy_square(ctx, m, m.L, out, 1))) return rc;
+  if (m.amplitude != 1.0)      // L_ = sqrt(c) L'
+    for (int64_t i = 0; i < m.N * m.N; ++i) out[i] = scaled_L_entry(m.amplitude, out[i]);
+  return GPBO_OK;
 }
 int gpbo_get_Linv(gpbo_ctx* ctx, int slot, double* out) {
   int rc = need_fitted(ctx, slot);
@@ -968,6 +1039,8 @@ int gpbo_get_alpha(gpbo_ctx* ctx, int slot, double* out) {
   Model& m = ctx->models[slot];
   GPBO_HIP(ctx, hipMemcpyAsync(out, m.alpha, (size_t)m.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (m.amplitude != 1.0)      // alpha_ = alpha' / c
+    for (int64_t i = 0; i < m.N; ++i) out[i] = scaled_alpha_entry(m.amplitude, out[i]);
   return GPBO_OK;
 }
 

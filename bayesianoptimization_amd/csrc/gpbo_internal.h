@@ -34,6 +34,8 @@ struct Model {
   int kernel = 0;
   int precision = 0;
   double noise = 0.0;      // value added to the diagonal of K at the last fit
+  double amplitude = 1.0;  // c of a scaled model c * k + white * I (gpbo_fit_scaled): the fit itself is the unit-amplitude one at
+  double white = 0.0;      // noise (white + alpha) / c; every place that turns |W k*|^2 into a variance applies c and white
   int64_t cap_NP = 0;      // allocated capacity (NP) of the square buffers
   int cap_DP = 0;
   double* ls = nullptr;    // [GPBO_MAX_DIM] length scale per dimension (device)
@@ -206,10 +208,10 @@ constexpr size_t FUSED_STAGE_BYTES = ((size_t)STAGE_NP_CAP * GPBO_MAX_DIM + STAG
 constexpr size_t PIN_WINDOW = 16384;
 constexpr int PIN_WINDOWS = 2 + GPBO_LML_BATCH_MAX;
 // every window but the last, one layout: per lane the length scales at +0, the potrf info words at PIN_LANE_INFO, the LML
-// scalars (yT alpha, sum log L_ii, gradient[GPBO_MAX_DIM]) at PIN_LANE_OUT.  A single fit or evaluation is lane 0.
+// scalars (yT alpha, sum log L_ii, gradient[GPBO_MAX_DIM], the noise component) at PIN_LANE_OUT.  A single fit or evaluation is lane 0.
 constexpr size_t PIN_LS_PITCH = GPBO_MAX_DIM * sizeof(double);
 constexpr size_t PIN_INFO_PITCH = 8;
-constexpr size_t PIN_OUT_PITCH = (2 + GPBO_MAX_DIM) * sizeof(double);
+constexpr size_t PIN_OUT_PITCH = (3 + GPBO_MAX_DIM) * sizeof(double);
 constexpr size_t PIN_LANE_INFO = 4096, PIN_LANE_OUT = 8192;
 static_assert(GPBO_LML_BATCH_MAX * PIN_LS_PITCH <= PIN_LANE_INFO, "lane length scales overlap the lane info words");
 static_assert(PIN_LANE_INFO + GPBO_LML_BATCH_MAX * PIN_INFO_PITCH <= PIN_LANE_OUT, "lane info words overlap the lane LML scalars");
@@ -507,12 +509,13 @@ bool gemm_fat_rule(const GemmArgs& g);
 // chol_kernels.hip: blocked Cholesky of m.L in place + inverted 64x64 diagonal blocks (128-column steps, `outer`-column panels);
 // stamps (device, >= 8 words, may be null): in-kernel clocks of the first diagonal workgroup
 int launch_cholesky128(gpbo_ctx* ctx, Model& m, int outer, long long* stamps);
-// fused_small.hip: the fit (mode 0: ... + packed W) or an LML evaluation (1: value, 2: value + gradient) of m (and, in lane mode, of
+// fused_small.hip: the fit (mode 0: ... + packed W) or an LML evaluation (1: value, 2: value + gradient; noise_grad: + the noise
+// component g_eta behind the length scales' — scaled_kernel.h) of m (and, in lane mode, of
 // ctx->lanes models) as ONE launch; src 0: raw X / y / ls_in given (device-visible), 1: m.Xs / m.yn / m.ls resident.  The pivot word
 // and the LML scalars land in the device-visible host words info_out / out (pitches per lane, in ints / doubles).
 int fused_max_np();
 int launch_fused_small(gpbo_ctx* ctx, Model& m, int mode, int src, int n_ls, const double* X, const double* y, const double* ls_in,
-                       double* scal, int* info_out, int64_t info_pitch, double* out, int64_t out_pitch);
+                       double* scal, int* info_out, int64_t info_pitch, double* out, int64_t out_pitch, bool noise_grad = false);
 // mid_fit.hip: the strip path's launches (lane-aware through ctx->lanes / lane_stride)
 int mid_max_np();
 int launch_mid_inputs(gpbo_ctx* ctx, Model& m, const double* X, const double* y, const double* ls_in);
@@ -535,6 +538,7 @@ struct PostEnds {
   int d;
   int64_t M;
   double y_mean, y_std;
+  double amplitude, white;   // of the model (1, 0 unless it is a scaled one)
   double* mu;
   double* sd;
   int* negvar;
@@ -596,7 +600,8 @@ int launch_posterior_grad_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, d
 // (out / grad: lane l's words l * out_pitch doubles behind lane 0's — device memory or device-visible pinned host words)
 int launch_lml_terms(gpbo_ctx* ctx, Model& m, double* out2, int64_t out_pitch);
 int launch_lml_grad(gpbo_ctx* ctx, Model& m, int n_ls, const double* Kinv, double* partial, double* out, int64_t out_pitch,
-                    bool with_terms);   // out[2..] = gradient; with_terms: out[0], out[1] too (launch_lml_terms' job, same arithmetic)
+                    bool with_terms,    // out[2..] = gradient; with_terms: out[0], out[1] too (launch_lml_terms' job, same arithmetic)
+                    bool noise_grad = false);   // out[2 + n_ls] = g_eta = 0.5 (|alpha|^2 - tr K^-1), the component for dK / dtheta = I
 // comm.hip: ncclCommCount of the context's communicator (0: none, -1: not answered)
 int comm_nranks(gpbo_ctx* ctx);
 // mt_jump.hip: states_dev[w] = block 1 + poly_idx[w] * stride_blocks of the MT19937 sequence whose block 0 is key_dev

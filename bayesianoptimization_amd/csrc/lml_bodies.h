@@ -38,10 +38,15 @@ __device__ __forceinline__ void lml_terms_body(const double* y, const double* al
 // Lower 64x64 tile (bi, bj <= bi) by a 256-thread group: sum over the tile of (alpha_i alpha_j - Kinv_ij) * dK_ij/dtheta_t.
 // `smem`: 2 * DP * 64 + 4 doubles; 1 + 2 * (n_ls == 1 ? 1 : n_ls) barriers.  KT: the tile of K^-1 comes as the 64x64 row-major image
 // `ktile` (the fused K^-1 + gradient kernel keeps it in LDS) instead of from Kinv.
+// noise_grad: one more component behind the n_ls of the length scales, the same reduction with dK/dtheta = I — the tile's share of
+// sum_i (alpha_i^2 - Kinv_ii), which only the diagonal entries of a diagonal tile have (2 more barriers; a tile's partials are then
+// n_ls + 1 apart).  Not asked for, the body computes and stores exactly what it does without the argument.
 template <int KERNEL, bool KT = false>
 __device__ __forceinline__ void lml_grad_tile_body(const double* Xs, const int DP, const int n_ls, const int64_t N, const int64_t NP,
                                                    const double* alpha, const double* Kinv, double* partial, const int bi, const int bj,
-                                                   double* smem, const int tid, const bool write, const double* ktile = nullptr) {
+                                                   double* smem, const int tid, const bool write, const double* ktile = nullptr,
+                                                   const bool noise_grad = false) {
+  const int n_out = n_ls + (noise_grad ? 1 : 0);
   double* XiT = smem;             // [DP][64]
   double* XjT = smem + DP * 64;   // [DP][64]
   double* sh = XjT + DP * 64;     // [4]
@@ -93,7 +98,7 @@ __device__ __forceinline__ void lml_grad_tile_body(const double* Xs, const int D
   const int64_t tile = (int64_t)bi * (bi + 1) / 2 + bj;
   if (n_ls == 1) {
     const double tot = block_sum_256(s_iso, sh, tid);
-    if (tid == 0 && write) partial[tile] = tot;
+    if (tid == 0 && write) partial[tile * n_out] = tot;
   } else {
     for (int t = 0; t < n_ls; ++t) {
       double s = 0.0;
@@ -105,12 +110,30 @@ __device__ __forceinline__ void lml_grad_tile_body(const double* Xs, const int D
           s = fma(coef[a][b], df * df, s);
         }
       const double tot = block_sum_256(s, sh, tid);
-      if (tid == 0 && write) partial[tile * n_ls + t] = tot;
+      if (tid == 0 && write) partial[tile * n_out + t] = tot;
     }
+  }
+  if (noise_grad) {
+    double s = 0.0;
+    if (bi == bj && ty == tx) {      // the thread's 4x4 block sits on the diagonal
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const int64_t i = (int64_t)bi * 64 + ty * 4 + a;
+        if (i < N) {
+          double kin;
+          if constexpr (KT) kin = ktile[(ty * 4 + a) * 64 + ty * 4 + a];
+          else kin = Kinv[i * NP + i];
+          s += fma(alpha[i], alpha[i], -kin);
+        }
+      }
+    }
+    const double tot = block_sum_256(s, sh, tid);
+    if (tid == 0 && write) partial[tile * n_out + n_ls] = tot;
   }
 }
 
-// out[t] = 0.5 * sum over tiles (fixed order) of partial[tile][t]   (one 256-thread group per t; two barriers)
+// out[t] = 0.5 * sum over tiles (fixed order) of partial[tile][t]   (one 256-thread group per t; two barriers); n_ls: the partials
+// per tile (the noise component included where the tiles computed it)
 __device__ __forceinline__ void lml_grad_final_body(const double* partial, const int64_t ntiles, const int n_ls, double* out, const int t,
                                                     double* sh, const int tid, const bool write) {
   double s = 0.0;

@@ -27,12 +27,13 @@ template <int KERNEL>
 __global__ __launch_bounds__(256) void lml_grad_kernel(const double* __restrict__ Xs, int DP, int n_ls, int64_t N,
                                                        int64_t NP, const double* __restrict__ alpha,
                                                        const double* __restrict__ Kinv, double* __restrict__ partial,
-                                                       int64_t lane_stride) {
+                                                       int64_t lane_stride, int noise_grad) {
   const int bj = blockIdx.x, bi = blockIdx.y;
   if (bj > bi) return;
   const int64_t lo = (int64_t)blockIdx.z * lane_stride;
   extern __shared__ __attribute__((aligned(16))) double lg_smem[];
-  lml_grad_tile_body<KERNEL>(Xs + lo, DP, n_ls, N, NP, alpha + lo, Kinv + lo, partial + lo, bi, bj, lg_smem, (int)threadIdx.x, true);
+  lml_grad_tile_body<KERNEL>(Xs + lo, DP, n_ls, N, NP, alpha + lo, Kinv + lo, partial + lo, bi, bj, lg_smem, (int)threadIdx.x, true,
+                            nullptr, noise_grad != 0);
 }
 
 // K^-1 = W^T W and the gradient tile sums in ONE launch (the strip path's evaluations, NP <= mid_max_np()): a workgroup computes its
@@ -41,7 +42,8 @@ __global__ __launch_bounds__(256) void lml_grad_kernel(const double* __restrict_
 // Dynamic LDS: 4096 (the tile) + max(GT_LDS_DOUBLES, 2 * DP * 64 + 8) doubles.
 template <int KERNEL>
 __global__ __launch_bounds__(256) void kinv_grad_kernel(GemmArgs g, const double* __restrict__ Xs, int DP, int n_ls, int64_t N, int64_t NP,
-                                                        const double* __restrict__ alpha, double* __restrict__ partial, int64_t lane_stride) {
+                                                        const double* __restrict__ alpha, double* __restrict__ partial, int64_t lane_stride,
+                                                        int noise_grad) {
   const int bj = blockIdx.x, bi = blockIdx.y;
   if (bj > bi) return;
   extern __shared__ __attribute__((aligned(16))) double kg_smem[];
@@ -51,11 +53,13 @@ __global__ __launch_bounds__(256) void kinv_grad_kernel(GemmArgs g, const double
   const int64_t lo = (int64_t)zl * lane_stride;
   gemm_tile_body<false, true, true>(g, bi, bj, zl, 0, work, (int)threadIdx.x, true, ctile);
   __syncthreads();
-  lml_grad_tile_body<KERNEL, true>(Xs + lo, DP, n_ls, N, NP, alpha + lo, nullptr, partial + lo, bi, bj, work, (int)threadIdx.x, true, ctile);
+  lml_grad_tile_body<KERNEL, true>(Xs + lo, DP, n_ls, N, NP, alpha + lo, nullptr, partial + lo, bi, bj, work, (int)threadIdx.x, true, ctile,
+                                  noise_grad != 0);
 }
 
 // out[2 + t] = 0.5 * sum over tiles (fixed order) of partial[tile][t] for workgroup t < n_ls; workgroup n_ls (launched only when
-// the caller asks for it) computes the two LML terms out[0], out[1] — the evaluation's scalars leave in ONE launch.
+// the caller asks for it) computes the two LML terms out[0], out[1] — the evaluation's scalars leave in ONE launch.  n_ls counts
+// the partials per tile: with the noise component, the length scales' + 1 (out[2 + n_ls of the length scales] = g_eta).
 __global__ __launch_bounds__(256) void lml_grad_final_kernel(const double* __restrict__ partial, int64_t ntiles,
                                                              int n_ls, double* __restrict__ out, int64_t lane_stride,
                                                              int64_t out_pitch, const double* __restrict__ y,
@@ -78,11 +82,12 @@ int launch_lml_terms(gpbo_ctx* ctx, Model& m, double* out2, int64_t out_pitch) {
   return GPBO_OK;
 }
 
-// Kinv must hold K^-1 (lower 64x64 tiles incl. full diagonal tiles); partial needs ntiles*n_ls doubles.
+// Kinv must hold K^-1 (lower 64x64 tiles incl. full diagonal tiles); partial needs ntiles * (n_ls + noise_grad) doubles.
 // out: the evaluation's scalars [y.alpha, sum log L_ii, gradient...]; with_terms: the first two are computed here as well.
 // Kinv null: K^-1 = W^T W is formed tile by tile inside the gradient launch (kinv_grad_kernel).
 int launch_lml_grad(gpbo_ctx* ctx, Model& m, int n_ls, const double* Kinv, double* partial, double* out, int64_t out_pitch,
-                    bool with_terms) {
+                    bool with_terms, bool noise_grad) {
+  const int ng = noise_grad ? 1 : 0;
   const unsigned nb = (unsigned)(m.NP / 64);
   const int64_t ntiles = (int64_t)nb * (nb + 1) / 2;
   const size_t lds = (size_t)(2 * m.DP * 64 + 8) * sizeof(double);
@@ -107,20 +112,20 @@ int launch_lml_grad(gpbo_ctx* ctx, Model& m, int n_ls, const double* Kinv, doubl
       ctx->func_attrs |= ATTR_KINV_GRAD;
     }
     const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
-      kinv_grad_kernel<decltype(k)::value><<<grid, dim3(256), lds2, ctx->stream>>>(g, m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, partial, ls);
+      kinv_grad_kernel<decltype(k)::value><<<grid, dim3(256), lds2, ctx->stream>>>(g, m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, partial, ls, ng);
       return GPBO_OK;
     });
     if (rc) return rc;
   } else {
     const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
-      lml_grad_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, Kinv, partial, ls);
+      lml_grad_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, n_ls, m.N, m.NP, m.alpha, Kinv, partial, ls, ng);
       return GPBO_OK;
     });
     if (rc) return rc;
   }
   GPBO_HIP(ctx, hipGetLastError());
-  lml_grad_final_kernel<<<dim3((unsigned)(n_ls + (with_terms ? 1 : 0)), (unsigned)ctx->lanes), dim3(256), 0, ctx->stream>>>(
-      partial, ntiles, n_ls, out, ls, out_pitch, m.yn, m.alpha, m.L, m.N, m.NP);
+  lml_grad_final_kernel<<<dim3((unsigned)(n_ls + ng + (with_terms ? 1 : 0)), (unsigned)ctx->lanes), dim3(256), 0, ctx->stream>>>(
+      partial, ntiles, n_ls + ng, out, ls, out_pitch, m.yn, m.alpha, m.L, m.N, m.NP);
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }

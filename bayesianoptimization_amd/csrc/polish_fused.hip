@@ -35,6 +35,7 @@ struct PolishFusedArgs {
   const double *W, *Wt, *Xs, *alpha, *ls;      // Wt: W transposed, row-major (polish_rows_kernel with W in memory), else null
   int NP, N, d, DP;
   double y_mean, y_std;
+  double amplitude, white;             // of the model: normalised variance = amplitude * (1 - |W k*|^2) + white
   int acq;
   double acq_param, y_max;
   int max_iter, eval_only;             // eval_only = R > 0: R evaluations at the seed, no search (debug entry)
@@ -363,7 +364,7 @@ __global__ __launch_bounds__(WLDS ? SEARCH_LDS_NP : SEARCH_MAX_NP) void polish_r
         tot0 += r[2 * DP];
         tot1 += r[2 * DP + 1];
       }
-      double var = 1.0 - tot0;
+      double var = fma(a.amplitude, 1.0 - tot0, a.white);
       if (var < 0.0) {
         if (lane == 0) *a.negvar = 1;
         var = 0.0;
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(WLDS ? SEARCH_LDS_NP : SEARCH_MAX_NP) void polish_r
       if (lane < d) {
         const double inv_l = 1.0 / ls_s[lane];
         dmu = a.y_std * sa * inv_l;
-        dsd = (sdn > 0.0) ? -(a.y_std * sb * inv_l) / sdn : 0.0;       // a clipped (zero) variance has no slope
+        dsd = (sdn > 0.0) ? -((a.y_std * sb * inv_l) * a.amplitude) / sdn : 0.0;       // a clipped (zero) variance has no slope
         g = polish_acq_grad(ca, cs, dmu, dsd);
         if (!__builtin_isfinite(g)) g = 0.0;
       }
@@ -442,6 +443,7 @@ int launch_polish_fused(gpbo_ctx* ctx, Model& m, const PolishPlan& plan, const P
   a.W = m.W; a.Xs = m.Xs; a.alpha = m.alpha; a.ls = m.ls;
   a.NP = (int)m.NP; a.N = (int)m.N; a.d = d; a.DP = m.DP;
   a.y_mean = y_mean; a.y_std = y_std;
+  a.amplitude = m.amplitude; a.white = m.white;
   a.acq = acq; a.acq_param = acq_param; a.y_max = y_max;
   a.max_iter = max_iter; a.eval_only = eval_repeat;
   double* dv = (double*)ctx->polish_pinned_dev;

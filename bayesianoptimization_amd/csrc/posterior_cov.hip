@@ -3,6 +3,7 @@
 //     V     = solve_triangular(L_, K_trans.T)       -> V = W K*^T   (W = L^-1, one MFMA GEMM, W lower triangular)
 //     y_cov = kernel_(X) - V.T @ V                  -> second MFMA GEMM (A given transposed) + the kernel of the batch
 //     y_cov * y_train_std^2                         (_gpr.py:461-466; no clipping on this branch)
+// A scaled model c * k + white * I (gpbo_fit_scaled) holds the unit-amplitude W: y_cov = c (k(X) - V^T V) + white * I.
 // called by bayes_opt through BayesianOptimization.predict(..., return_cov=True) (bayes_opt/bayesian_optimization.py:238).
 // The reference path drags L_ (N x N) through LAPACK on the host; here K*^T, V and V^T V never leave HBM and only the
 // M x M result crosses the boundary.  kernel_(X) follows kernels.py:1735-1738 / 1556-1565: exact unit diagonal.
@@ -12,7 +13,8 @@ namespace gpbo {
 
 template <int KERNEL>
 __global__ __launch_bounds__(256) void cov_finalize_kernel(const double* __restrict__ Xcs, int DP, int64_t M, int64_t ldc,
-                                                           double scale, double* __restrict__ C) {
+                                                           double scale, double amplitude, double white,
+                                                           double* __restrict__ C) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t i = blockIdx.y;
   if (j >= M) return;
@@ -27,7 +29,7 @@ __global__ __launch_bounds__(256) void cov_finalize_kernel(const double* __restr
     }
     kv = gpbo_kernel_value<KERNEL>(d2);
   }
-  C[i * ldc + j] = (kv - C[i * ldc + j]) * scale;
+  C[i * ldc + j] = fma(amplitude, kv - C[i * ldc + j], i == j ? white : 0.0) * scale;
 }
 
 // Requires ctx->Xc to hold the M raw candidates.  Scratch: ctx->kst = [K*^T (NP x Mp) | V (NP x Mp) | V^T V (Mp x Mp)].
@@ -61,7 +63,7 @@ int launch_posterior_cov(gpbo_ctx* ctx, Model& m, int64_t M, double y_std, doubl
   const dim3 grid((unsigned)((M + 255) / 256), (unsigned)M);
   const double scale = y_std * y_std;
   if (const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
-    cov_finalize_kernel<decltype(k)::value><<<grid, dim3(256), 0, ctx->stream>>>(ctx->Xcs, m.DP, M, Mp, scale, C);
+    cov_finalize_kernel<decltype(k)::value><<<grid, dim3(256), 0, ctx->stream>>>(ctx->Xcs, m.DP, M, Mp, scale, m.amplitude, m.white, C);
     return GPBO_OK;
   })) return rc;
   GPBO_HIP(ctx, hipGetLastError());

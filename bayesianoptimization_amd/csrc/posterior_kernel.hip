@@ -29,7 +29,7 @@ namespace gpbo {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-// mu = y_std * (k* . alpha) + y_mean ; sd = sqrt(max(1 - sum_chunks part, 0) * y_std^2)
+// mu = y_std * (k* . alpha) + y_mean ; sd = sqrt(max(c (1 - sum_chunks part) + white, 0) * y_std^2)
 // NAN_FROM_MU (the int8 GEMM's partials): its sum of squares comes from the integer digits of k*, and an integer cannot carry a NaN
 // (a NaN k* quantises to some integer): sd would come out finite where the fp64 paths and sklearn give NaN.  The partial means are
 // fp64 sums over the same k*, NaN exactly when one of them is, so sd takes mu's NaN.  Finite candidates keep the bits of the plain
@@ -38,7 +38,7 @@ template <bool NAN_FROM_MU>
 __global__ __launch_bounds__(256) void posterior_finalize_kernel(const double* __restrict__ part,
                                                                  const double* __restrict__ mu_part,
                                                                  int nchunks, int n_mu, int64_t Mp, int64_t M,
-                                                                 double y_mean, double y_std,
+                                                                 double y_mean, double y_std, double amplitude, double white,
                                                                  double* __restrict__ mu,
                                                                  double* __restrict__ sd, int* __restrict__ negvar) {
   const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void posterior_finalize_kernel(const double* _
   double mun = 0.0;
   for (int q = 0; q < n_mu; ++q) mun += mu_part[(int64_t)q * Mp + m];
   if (NAN_FROM_MU && mun != mun) ss = mun;
-  posterior_finalize_elem(ss, mun, y_mean, y_std, mu + m, sd + m, negvar);
+  posterior_finalize_elem(ss, mun, y_mean, y_std, amplitude, white, mu + m, sd + m, negvar);
 }
 
 // Candidates per k* slab: what the workspace budget holds at bytes_per_cand — GPBO_KSTAR_GB (default 4 GB), clipped to 80 % of
@@ -162,7 +162,7 @@ int launch_posterior(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y
   }
   if ((rc = ensure_posterior_outputs(ctx, m, Mp))) return rc;
   if (!plan.fuse_ends && (rc = launch_prescale(ctx, ctx->Xc, M, m.d, m.DP, m.ls, ctx->Xcs, Mp))) return rc;
-  const PostEnds ends{ctx->Xc, m.ls, m.d, M, y_mean, y_std, m.mu, m.sd, ctx->negvar};
+  const PostEnds ends{ctx->Xc, m.ls, m.d, M, y_mean, y_std, m.amplitude, m.white, m.mu, m.sd, ctx->negvar};
   ev_begin(ctx, T_POST_MAIN);
   switch (plan.path) {
     case PostPath::Small: rc = launch_posterior_small(ctx, m, (int)M, y_mean, y_std); break;
@@ -177,10 +177,10 @@ int launch_posterior(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y
   ev_begin(ctx, T_POST_FINAL);   // recorded on every path, so that last_timings() always has the key
   if (plan.path == PostPath::SlabI8)
     posterior_finalize_kernel<true><<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream>>>(
-        ctx->part, ctx->mu_part, plan.part_chunks, plan.mu_chunks, Mp, M, y_mean, y_std, m.mu, m.sd, ctx->negvar);
+        ctx->part, ctx->mu_part, plan.part_chunks, plan.mu_chunks, Mp, M, y_mean, y_std, m.amplitude, m.white, m.mu, m.sd, ctx->negvar);
   else if (!plan.fuse_ends && plan.path != PostPath::Small)
     posterior_finalize_kernel<false><<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream>>>(
-        ctx->part, ctx->mu_part, plan.part_chunks, plan.mu_chunks, Mp, M, y_mean, y_std, m.mu, m.sd, ctx->negvar);
+        ctx->part, ctx->mu_part, plan.part_chunks, plan.mu_chunks, Mp, M, y_mean, y_std, m.amplitude, m.white, m.mu, m.sd, ctx->negvar);
   ev_end(ctx, T_POST_FINAL);
   GPBO_HIP(ctx, hipGetLastError());
   m.M_post = M;

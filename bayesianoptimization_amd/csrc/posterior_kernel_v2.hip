@@ -288,7 +288,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void posterior_kernel_v2(PostArgs2 p
 #pragma unroll
       for (int w = 0; w < WAVES; ++w) u += mured[w * V2_CANDS + tid];
       if (m < p.ends.M)
-        posterior_finalize_elem(0.0 + v, 0.0 + u, p.ends.y_mean, p.ends.y_std, p.ends.mu + m, p.ends.sd + m, p.ends.negvar);
+        posterior_finalize_elem(0.0 + v, 0.0 + u, p.ends.y_mean, p.ends.y_std, p.ends.amplitude, p.ends.white, p.ends.mu + m, p.ends.sd + m, p.ends.negvar);
       return;
     }
     p.part[(int64_t)r * p.g.Mp + m] = v;

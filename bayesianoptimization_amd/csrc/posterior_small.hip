@@ -96,8 +96,9 @@ static void launch_gemv(gpbo_ctx* ctx, Model& m, const double* ks, double* vsq, 
 
 __global__ __launch_bounds__(256) void finalize_small_kernel(const double* __restrict__ vsq, const double* __restrict__ ks,
                                                              const double* __restrict__ alpha, int64_t NP,
-                                                             double y_mean, double y_std, double* __restrict__ mu,
-                                                             double* __restrict__ sd, int* __restrict__ negvar) {
+                                                             double y_mean, double y_std, double amplitude, double white,
+                                                             double* __restrict__ mu, double* __restrict__ sd,
+                                                             int* __restrict__ negvar) {
   __shared__ double sh[4];
   const int c = blockIdx.x;
   double s = 0.0, m = 0.0;
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void finalize_small_kernel(const double* __res
     tot[q] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
   }
   if (threadIdx.x == 0) {
-    double var = 1.0 - tot[0];
+    double var = fma(amplitude, 1.0 - tot[0], white);
     if (var < 0.0) {
       *negvar = 1;
       var = 0.0;
@@ -158,7 +159,8 @@ int launch_posterior_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, double
     else launch_gemv<16, 2>(ctx, m, ksp, vp);
   }
   GPBO_HIP(ctx, hipGetLastError());
-  finalize_small_kernel<<<dim3((unsigned)M), dim3(256), 0, ctx->stream>>>(vsq, ks, m.alpha, m.NP, y_mean, y_std, m.mu, m.sd, ctx->negvar);
+  finalize_small_kernel<<<dim3((unsigned)M), dim3(256), 0, ctx->stream>>>(vsq, ks, m.alpha, m.NP, y_mean, y_std, m.amplitude, m.white, m.mu,
+                                                                          m.sd, ctx->negvar);
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }
@@ -370,8 +372,8 @@ __global__ __launch_bounds__(256) void grad_small_kernel(const double* __restric
 __global__ __launch_bounds__(256) void grad_final_kernel(const double* __restrict__ vbuf, const double* __restrict__ ks,
                                                          const double* __restrict__ alpha, const double* __restrict__ ls,
                                                          const double* __restrict__ gpart, int DP, int d, int64_t NP,
-                                                         double y_mean, double y_std, double* __restrict__ mu,
-                                                         double* __restrict__ sd, double* __restrict__ dmu,
+                                                         double y_mean, double y_std, double amplitude, double white,
+                                                         double* __restrict__ mu, double* __restrict__ sd, double* __restrict__ dmu,
                                                          double* __restrict__ dsd, int* __restrict__ negvar) {
   __shared__ double sh[8];
   const int c = blockIdx.x;
@@ -392,7 +394,7 @@ __global__ __launch_bounds__(256) void grad_final_kernel(const double* __restric
     __syncthreads();
     tot[q] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
   }
-  double var = 1.0 - tot[0];
+  double var = fma(amplitude, 1.0 - tot[0], white);
   if (var < 0.0) {
     if (threadIdx.x == 0) *negvar = 1;
     var = 0.0;
@@ -411,8 +413,8 @@ __global__ __launch_bounds__(256) void grad_final_kernel(const double* __restric
     }
     const double inv_l = 1.0 / ls[threadIdx.x];
     dmu[(int64_t)c * d + threadIdx.x] = y_std * a * inv_l;
-    // d sd / d x = y_std * (-2 b / l) / (2 sqrt(var_n)); a clipped (zero) variance has no slope
-    dsd[(int64_t)c * d + threadIdx.x] = (sdn > 0.0) ? -(y_std * b * inv_l) / sdn : 0.0;
+    // d sd / d x = y_std * c * (-2 b / l) / (2 sqrt(var_n)), var_n = c (1 - q) + white; a clipped (zero) variance has no slope
+    dsd[(int64_t)c * d + threadIdx.x] = (sdn > 0.0) ? -((y_std * b * inv_l) * amplitude) / sdn : 0.0;
   }
 }
 
@@ -457,7 +459,7 @@ int launch_posterior_grad_small(gpbo_ctx* ctx, Model& m, int M, double y_mean, d
                                                                                 gpart);
   GPBO_HIP(ctx, hipGetLastError());
   grad_final_kernel<<<dim3((unsigned)M), dim3(256), 0, ctx->stream>>>(vb, ks, m.alpha, m.ls, gpart, m.DP, m.d, m.NP, y_mean, y_std,
-                                                                      mu_out, sd_out, dmu_dev, dsd_dev, ctx->negvar);
+                                                                      m.amplitude, m.white, mu_out, sd_out, dmu_dev, dsd_dev, ctx->negvar);
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }

@@ -17,14 +17,19 @@ from . import fused_acquisition as A
 from ._lib import MAX_DIM
 from .engine import MATERN25
 from .engine import RBF as K_RBF
-from .gpr import HipGPR, describe_kernel, shared_engine
+from .gpr import HipGPR, describe_kernel, describe_scaled_kernel, shared_engine
 
 
-def _note_unsupported(kernel, what: str, matern_family: bool = False) -> str | None:
+def _note_unsupported(kernel, what: str, matern_family: bool = False, scaled_kernels: bool = False) -> str | None:
     """One UserWarning when a model's kernel is outside the device path: the model is swapped all the same (so that a later
     `set_gp_params(kernel=...)` with a supported kernel puts it on the GPU) and runs scikit-learn's code until then."""
     try:
-        describe_kernel(kernel, matern_family)
+        try:
+            describe_kernel(kernel, matern_family)
+        except NotImplementedError:
+            if not scaled_kernels:
+                raise
+            describe_scaled_kernel(kernel, matern_family)
     except NotImplementedError as exc:
         warnings.warn(f"accelerate(): {what}: {exc}; it keeps running scikit-learn's GaussianProcessRegressor on the host "
                       "(the reference's path) until its kernel is one the HIP engine evaluates", UserWarning, stacklevel=3)
@@ -135,7 +140,7 @@ def warm_up(engine, bounds, acquisition=None, kernel=None, n_restarts_optimizer:
 
 def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=None, precision: str = "f64",
                devices=None, local_search: str = "auto", lml_on_device="auto", warm: bool = True,
-               mixed_search: str = "reference", matern_family: bool = False):
+               mixed_search: str = "reference", matern_family: bool = False, scaled_kernels: bool = False):
     """Swap the GP(s) and the acquisition function of `optimizer` in place; returns `optimizer`.
 
     `devices=[0, 1, ...]`: shard the random stage of every suggest() over these GPUs from this ONE process (GroupEngine:
@@ -170,6 +175,13 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
     after a later `set_gp_params(kernel=...)`.  Off, such a kernel degrades to the host like any other.  A nu = 0.5 posterior has
     kinks at the training points; the device local search uses the analytic gradient with a coincident training point contributing
     0 (scikit-learn's convention for the kernel's non-finite gradient entries).
+    `scaled_kernels` (default False): opt in to a signal variance and a noise level on the device — `ConstantKernel * k`,
+    `k * ConstantKernel` and either `+ WhiteKernel` around a kernel k the device evaluates, every hyper-parameter free or fixed
+    (gpr.describe_scaled_kernel) — for the target GP and every constraint GP, now or after a later `set_gp_params(kernel=...)`.
+    The theta search of such a model evaluates its restarts one after another (gpbo_lml_scaled; the same RandomState draws).  Off,
+    such a kernel degrades to the host like any other; so it does on a device group (`devices=[...]`), which has no scaled path.
+    Such a model is not warmed up, and the engine is not marked warm for its width: a later accelerate() with a kernel that is
+    warmed still runs its warm-up.
     `warm` (default True): run `warm_up` once per engine and dimension — five synthetic suggest() calls (~0.3 s) that load the
     code objects, allocate and launch every small-N path, so that no suggest() of the user's loop carries a first-use spike.
     The optimizer's RandomState is not touched.
@@ -183,7 +195,8 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
     space = optimizer._space
     transform = None if _identity_transform(space) else space.kernel_transform
     matern_family = bool(matern_family)
-    noted = _note_unsupported(optimizer._gp.kernel, "the target GP", matern_family)
+    scaled_kernels = bool(scaled_kernels)
+    noted = _note_unsupported(optimizer._gp.kernel, "the target GP", matern_family, scaled_kernels)
     width = int(getattr(space, "bounds", np.zeros((0, 2))).shape[0])      # columns in kernel space (categoricals are one-hot there)
     too_wide = None
     if width > MAX_DIM:
@@ -194,7 +207,7 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
                           "GaussianProcessRegressor on the host (the reference's path)", UserWarning, stacklevel=2)
         noted = noted or too_wide
     optimizer._gp = HipGPR.from_sklearn(optimizer._gp, transform=transform, engine=engine, slot=0, precision=precision,
-                                        matern_family=matern_family)
+                                        matern_family=matern_family, scaled_kernels=scaled_kernels)
     optimizer._gp.lml_on_device = lml_on_device
     if noted:
         optimizer._gp._host_warned = noted          # said once, here
@@ -203,9 +216,9 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
         if len(constraint._model) > 7:
             raise NotImplementedError("at most 7 constraint GPs fit the engine's model slots")
         for j, m in enumerate(constraint._model):
-            noted = _note_unsupported(m.kernel, f"constraint GP {j}", matern_family) or too_wide
+            noted = _note_unsupported(m.kernel, f"constraint GP {j}", matern_family, scaled_kernels) or too_wide
             constraint._model[j] = HipGPR.from_sklearn(m, transform=transform, engine=engine, slot=j + 1, precision=precision,
-                                                       matern_family=matern_family)
+                                                       matern_family=matern_family, scaled_kernels=scaled_kernels)
             constraint._model[j].lml_on_device = lml_on_device
             if noted:
                 constraint._model[j]._host_warned = noted
@@ -237,10 +250,12 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
         # (a real engine only: test doubles have nothing to warm; mixed spaces run their local searches on the host and warm
         # as they go)
         fn = optimizer._acquisition_function
-        warm_up(engine, space.bounds, acquisition=fn if isinstance(fn, A.AcquisitionFunction) else None,
-                kernel=optimizer._gp.kernel, n_restarts_optimizer=int(optimizer._gp.n_restarts_optimizer or 0),
-                n_constraints=0 if constraint is None else len(constraint._model),
-                n_random=int(getattr(fn, "default_n_random", 10_000)), lml_on_device=lml_on_device,
-                matern_family=matern_family)
-        engine.__dict__.setdefault("_warmed", {})[warm_key] = True
+        took = warm_up(engine, space.bounds, acquisition=fn if isinstance(fn, A.AcquisitionFunction) else None,
+                       kernel=optimizer._gp.kernel, n_restarts_optimizer=int(optimizer._gp.n_restarts_optimizer or 0),
+                       n_constraints=0 if constraint is None else len(constraint._model),
+                       n_random=int(getattr(fn, "default_n_random", 10_000)), lml_on_device=lml_on_device,
+                       matern_family=matern_family)
+        if took > 0.0:      # (0: warm_up had nothing to run — a kernel it does not warm, a scaled one among them — and the next
+            # accelerate() on this engine and width still owes its warm-up)
+            engine.__dict__.setdefault("_warmed", {})[warm_key] = True
     return optimizer

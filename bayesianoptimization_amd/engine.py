@@ -49,6 +49,11 @@ def advance_mt19937(random_state, n_words: int, lib=None):
 _INT_ARRAYS: dict = {}      # ctypes array types by length (creating one costs ~2 us per call)
 
 
+def _is_scaled(amplitude, white) -> bool:
+    """Does (amplitude, white) ask for a scaled model (gpbo_fit_scaled / gpbo_lml_scaled)?  1 and 0 are the unit model's calls."""
+    return float(amplitude) != 1.0 or float(white) != 0.0
+
+
 class GpEngine:
     """One engine context = one GPU, one HIP stream, 8 model slots (0 = target GP, 1.. = constraint GPs) and one resident
     candidate matrix.  Calls are synchronous from the host's point of view unless noted (`posterior(fetch=False)` only
@@ -71,6 +76,7 @@ class GpEngine:
         self._serial: dict[int, int] = {}    # slot -> number of times its factorisation was rewritten
         self._overlap_depth = 0              # > 0 inside overlapped_fits()
         self._pending_fits: set[int] = set()  # slots with a gpbo_fit_begin not yet waited for
+        self._scaled: dict[int, tuple[float, float]] = {}   # slot -> (amplitude, white) of its scaled fit (absent: 1, 0)
         self.timing = True                   # the calls record their HIP event pairs (set_timing)
 
     # -- lifecycle ---------------------------------------------------------------------------
@@ -115,8 +121,12 @@ class GpEngine:
         return json.loads(buf.value.decode())
 
     # -- fit ---------------------------------------------------------------------------------
-    def fit(self, X, y_norm, kernel: int, length_scale, noise: float, slot: int = 0, precision: int = F64):
-        """K + noise*I -> L, W = L^-1, alpha, at fixed theta (sklearn _gpr.py:346-364)."""
+    def fit(self, X, y_norm, kernel: int, length_scale, noise: float, slot: int = 0, precision: int = F64,
+            amplitude: float = 1.0, white: float = 0.0):
+        """K + noise*I -> L, W = L^-1, alpha, at fixed theta (sklearn _gpr.py:346-364).
+        amplitude / white other than 1 / 0: the scaled model amplitude * k + (white + noise) * I (ConstantKernel * k + WhiteKernel
+        under an estimator whose alpha is `noise`; gpbo_fit_scaled) — the slot's posteriors then carry amplitude and white."""
+        scaled = _is_scaled(amplitude, white)
         X = np.ascontiguousarray(X, dtype=np.float64)
         if X.ndim != 2:
             raise ValueError("X must be 2-D (n_samples, n_features)")
@@ -127,6 +137,17 @@ class GpEngine:
         info = C.c_int(0)
         self._settle(slot)
         self._touch(slot)
+        if scaled:
+            # gpbo_fit_begin has no scaled twin: inside overlapped_fits() a scaled fit runs here and now, on the context's own stream
+            # (its slot is settled above; the fits pending on OTHER slots keep running on their streams and are waited for as usual)
+            self._scaled.pop(int(slot), None)
+            rc = self._lib.gpbo_fit_scaled(self._h, int(slot), dptr(X), dptr(y_norm), X.shape[0], X.shape[1], int(kernel), dptr(ls),
+                                           int(ls.shape[0]), float(amplitude), float(white), float(noise), int(precision),
+                                           C.byref(info))
+            self._check(rc, info.value)
+            self._scaled[int(slot)] = (float(amplitude), float(white))
+            return self._touch(slot)
+        self._scaled.pop(int(slot), None)
         if self._overlap_depth > 0:
             # inside overlapped_fits(): enqueue on the slot's own stream and return; waited for (and checked) at the end
             # of the block or by the first call that reads the slot
@@ -148,7 +169,8 @@ class GpEngine:
         """`fit()` calls inside the block are enqueued on their slots' own streams (gpbo_fit_begin) and overlap on the
         device — the target GP and the constraint GPs of one suggest() (bayes_opt/acquisition.py:84-86).  Leaving the
         block waits for all of them; a kernel matrix that is not positive definite raises there (np.linalg.LinAlgError
-        with sklearn's hint, as fit() does).  Any call that reads a slot in between waits for that slot first."""
+        with sklearn's hint, as fit() does).  Any call that reads a slot in between waits for that slot first.  A scaled fit
+        (amplitude / white given) is not enqueued: it completes inside its fit() call and raises there."""
         self._overlap_depth += 1
         try:
             yield self
@@ -193,10 +215,14 @@ class GpEngine:
         elif int(slot) in self._pending_fits:
             self._wait_fit(int(slot))
 
-    def fit_append(self, x_new, y_norm, slot: int = 0):
+    def fit_append(self, x_new, y_norm, slot: int = 0, amplitude: float = 1.0, white: float = 0.0):
         """Grow the slot's fitted model by the rows `x_new` at unchanged kernel/length scale/noise (gpbo_fit_append);
-        `y_norm` = ALL normalised targets, old and new.  `x_new` may be empty (new targets for the same inputs)."""
+        `y_norm` = ALL normalised targets, old and new.  `x_new` may be empty (new targets for the same inputs).
+        The slot keeps the amplitude and white of its fit: the two arguments say which model the caller believes it is growing,
+        and anything else than the slot's own is refused."""
         self._settle(slot)
+        if (float(amplitude), float(white)) != self._scaled.get(int(slot), (1.0, 0.0)):
+            raise ValueError("fit_append: amplitude / white differ from the slot's fitted model")
         y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
         x_new = np.ascontiguousarray(x_new, dtype=np.float64)
         if x_new.ndim != 2:
@@ -276,13 +302,27 @@ class GpEngine:
     def fit_serial(self, slot: int = 0) -> int:
         return self._serial.get(int(slot), 0)
 
-    def lml(self, X, y_norm, kernel: int, length_scale, noise: float, eval_gradient=True, slot: int = 0):
-        """(log marginal likelihood, d/dlog(length_scale)) at theta (sklearn _gpr.py:575-652). Clobbers the slot's fit."""
+    def lml(self, X, y_norm, kernel: int, length_scale, noise: float, eval_gradient=True, slot: int = 0,
+            amplitude: float = 1.0, white: float = 0.0, scaled=None):
+        """(log marginal likelihood, d/dlog(length_scale)) at theta (sklearn _gpr.py:575-652). Clobbers the slot's fit.
+        amplitude / white other than 1 / 0: of the scaled model amplitude * k + (white + noise) * I (gpbo_lml_scaled), the gradient
+        in [log amplitude, log length_scale ..., log white].  scaled=True asks for that form whatever the two values are (a search
+        over amplitude passes through 1)."""
         self._settle(slot)
         X = np.ascontiguousarray(X, dtype=np.float64)
         y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
         ls = np.ascontiguousarray(np.atleast_1d(np.asarray(length_scale, dtype=np.float64)))
         val = C.c_double(0.0)
+        self._scaled.pop(int(slot), None)
+        if scaled or (scaled is None and _is_scaled(amplitude, white)):
+            grad = np.zeros(ls.shape[0] + 2)
+            info = C.c_int(0)
+            self._touch(slot)
+            rc = self._lib.gpbo_lml_scaled(self._h, int(slot), dptr(X), dptr(y_norm), X.shape[0], X.shape[1], int(kernel), dptr(ls),
+                                           int(ls.shape[0]), float(amplitude), float(white), float(noise), int(bool(eval_gradient)),
+                                           C.byref(val), dptr(grad), C.byref(info))
+            self._check(rc, info.value)
+            return (val.value, grad) if eval_gradient else val.value
         grad = np.zeros(ls.shape[0])
         info = C.c_int(0)
         self._touch(slot)
@@ -830,6 +870,7 @@ class GroupEngine(GpEngine):
         self._serial = {}
         self._overlap_depth = 0     # group fits are synchronous on every device: overlapped_fits() is a plain block
         self._pending_fits = set()  # (never filled: the inherited accessors only look at it)
+        self._scaled = {}           # (never filled: a device group refuses scaled kernels)
         self.timing = True
         self._resident = False      # the group's candidate shards are in place (a small predict on device 0 clobbers them)
         self.collective = self._lib.gpbo_group_collective(g).decode()
@@ -909,7 +950,20 @@ class GroupEngine(GpEngine):
         return int(a[0]), int(b[0])
 
     # -- replicated model ----------------------------------------------------------------------
-    def fit(self, X, y_norm, kernel: int, length_scale, noise: float, slot: int = 0, precision: int = F64):
+    def _refuse_scaled(self, amplitude, white):
+        if _is_scaled(amplitude, white):
+            raise NotImplementedError("a device group has no scaled-kernel (ConstantKernel / WhiteKernel) path")
+
+    def lml(self, X, y_norm, kernel: int, length_scale, noise: float, eval_gradient=True, slot: int = 0,
+            amplitude: float = 1.0, white: float = 0.0, scaled=None):
+        if scaled:
+            self._refuse_scaled(0.0, 0.0)
+        self._refuse_scaled(amplitude, white)
+        return super().lml(X, y_norm, kernel, length_scale, noise, eval_gradient, slot)
+
+    def fit(self, X, y_norm, kernel: int, length_scale, noise: float, slot: int = 0, precision: int = F64,
+            amplitude: float = 1.0, white: float = 0.0):
+        self._refuse_scaled(amplitude, white)
         X = np.ascontiguousarray(X, dtype=np.float64)
         if X.ndim != 2:
             raise ValueError("X must be 2-D (n_samples, n_features)")
@@ -924,7 +978,8 @@ class GroupEngine(GpEngine):
         self._gcheck(rc, info.value, borrowed=(X, y_norm, ls, info))
         return self._touch(slot)
 
-    def fit_append(self, x_new, y_norm, slot: int = 0):
+    def fit_append(self, x_new, y_norm, slot: int = 0, amplitude: float = 1.0, white: float = 0.0):
+        self._refuse_scaled(amplitude, white)
         y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
         x_new = np.ascontiguousarray(x_new, dtype=np.float64)
         if x_new.ndim != 2:

@@ -17,6 +17,10 @@ Supported on the HIP path: Matern(nu=2.5) and RBF (optionally wrapped by bayes_o
 optionally scaled by a fixed-at-1 ConstantKernel as in sklearn's default), scalar `alpha`, 1-D targets.
 With `matern_family=True` (opt-in) also the other closed-form members of the Matern family: nu = 1.5, nu = 0.5 and nu = inf
 (which scikit-learn evaluates with RBF's formulas).
+With `scaled_kernels=True` (opt-in) also a signal variance and a noise level around any of those: `C * k`, `k * C` and either
+`+ WhiteKernel`, every hyper-parameter free or fixed (describe_scaled_kernel) — the device fits the unit-amplitude model at noise
+(noise_level + alpha) / constant_value and applies the two values wherever a variance is formed; the theta search evaluates its
+restarts one after another (gpbo_lml_scaled).
 Anything else — `set_gp_params(kernel=Matern(nu=1.5))` on an accelerated optimizer
 (bayes_opt/bayesian_optimization.py:403-407), a per-sample `alpha`, several targets — is outside the device path: the
 estimator then IS its base class for that fit (scikit-learn's own `fit` / `predict`, the reference's arithmetic and
@@ -33,12 +37,12 @@ from operator import itemgetter
 import numpy as np
 from sklearn.base import clone
 from sklearn.gaussian_process import GaussianProcessRegressor
-from sklearn.gaussian_process.kernels import RBF, ConstantKernel, Matern, Product
+from sklearn.gaussian_process.kernels import RBF, ConstantKernel, Matern, Product, Sum, WhiteKernel
 from sklearn.utils import check_random_state
 from sklearn.utils.validation import validate_data
 
 from ._lib import MAX_DIM
-from .engine import MATERN05, MATERN15, MATERN25, GpEngine
+from .engine import MATERN05, MATERN15, MATERN25, GpEngine, GroupEngine
 from .engine import RBF as K_RBF
 
 _shared_engines: dict = {}
@@ -100,6 +104,72 @@ def describe_kernel(kernel, matern_family=False):
 _MATERN_KINDS = {0.5: MATERN05, 1.5: MATERN15, 2.5: MATERN25, float("inf"): K_RBF}
 
 
+class ScaledKernel(tuple):
+    """What describe_scaled_kernel returns: (kind, length_scale, amplitude, white, theta_index), also by name."""
+    __slots__ = ()
+    kind = property(itemgetter(0))
+    length_scale = property(itemgetter(1))
+    amplitude = property(itemgetter(2))
+    white = property(itemgetter(3))
+    theta_index = property(itemgetter(4))
+
+
+def describe_scaled_kernel(kernel, matern_family=False):
+    """ScaledKernel(kind, length_scale, amplitude c, white w, theta_index) of `c * k + w`, else raise NotImplementedError.
+
+    Accepted: a unit kernel k that describe_kernel knows (Matern / RBF, bare), `ConstantKernel * k`, `k * ConstantKernel`, and any
+    of those `+ WhiteKernel` in either operand order; every hyper-parameter free or fixed.  Missing parts are c = 1 and w = 0.
+    The device orders the model's parameters [c, length_scale (n_ls of them), w]; `theta_index[i]` is the place in that list of
+    the i-th entry of `kernel.theta` — the free hyper-parameters in scikit-learn's operand order (kernels.py: a Sum's / Product's
+    theta is k1's followed by k2's) — so theta = log(device[theta_index]) and d/dtheta = device_gradient[theta_index].
+    Rejected: more than one constant factor, a constant times a sum (`C * (k + W)`), a sum of sums, anything else."""
+    def refuse(why):
+        raise NotImplementedError(f"HIP path supports k, C * k, k * C and any of them + WhiteKernel (k: Matern / RBF); {why}, got {kernel!r}")
+
+    white_k, body = None, kernel
+    if isinstance(kernel, Sum):
+        a, b = kernel.k1, kernel.k2
+        if isinstance(a, WhiteKernel) and not isinstance(b, WhiteKernel):
+            white_k, body = a, b
+        elif isinstance(b, WhiteKernel) and not isinstance(a, WhiteKernel):
+            white_k, body = b, a
+        else:
+            refuse("a sum needs exactly one WhiteKernel operand")
+        if isinstance(body, Sum):
+            refuse("a nested sum is not")
+    const_k, base = None, body
+    if isinstance(body, Product):
+        a, b = body.k1, body.k2
+        if isinstance(a, ConstantKernel) and not isinstance(b, ConstantKernel):
+            const_k, base = a, b
+        elif isinstance(b, ConstantKernel) and not isinstance(a, ConstantKernel):
+            const_k, base = b, a
+        else:
+            refuse("a product needs exactly one ConstantKernel factor")
+    if not isinstance(base, RBF):      # (Matern and wrap_kernel's classes derive from RBF; a Product / Sum here is a second factor or C * (k + W))
+        refuse(f"the unit kernel is a {type(base).__name__}")
+    kind, ls = describe_kernel(base, matern_family)
+    n_ls = ls.shape[0]
+    c = float(const_k.constant_value) if const_k is not None else 1.0
+    w = float(white_k.noise_level) if white_k is not None else 0.0
+    if not (np.isfinite(c) and c > 0.0 and np.isfinite(w) and w >= 0.0):
+        refuse("constant_value must be > 0 and noise_level >= 0")
+
+    def places(k):      # device places of k's free hyper-parameters, in k.theta's order
+        if k is const_k:
+            return [] if k.hyperparameter_constant_value.fixed else [0]
+        if k is white_k:
+            return [] if k.hyperparameter_noise_level.fixed else [1 + n_ls]
+        if k is base:
+            return [] if k.hyperparameter_length_scale.fixed else list(range(1, 1 + n_ls))
+        return places(k.k1) + places(k.k2)
+
+    index = np.asarray(places(kernel), dtype=np.intp)
+    if index.shape[0] != kernel.n_dims:      # a hyper-parameter this description does not know (a subclass with more of them)
+        refuse("the kernel has hyper-parameters beyond constant_value, length_scale and noise_level")
+    return ScaledKernel((kind, ls, c, w, index))
+
+
 def _bare_length_scale_kernel(kernel) -> bool:
     """True for a bare Matern / RBF (or a wrap_kernel subclass of one) whose length scale is free: its theta IS log(length_scale)
     and its bounds ARE log(length_scale_bounds) (kernels.py: Hyperparameter("length_scale", "numeric", bounds, n_elements)), so the
@@ -136,7 +206,7 @@ class HipGPR(GaussianProcessRegressor):
     def __init__(self, kernel=None, *, alpha=1e-10, optimizer="fmin_l_bfgs_b", n_restarts_optimizer=0,
                  normalize_y=False, copy_X_train=True, n_targets=None, random_state=None,
                  transform=None, engine=None, slot=0, lml_on_device="auto", precision="f64", incremental=True,
-                 theta_lockstep=True, matern_family=False):
+                 theta_lockstep=True, matern_family=False, scaled_kernels=False):
         super().__init__(kernel=kernel, alpha=alpha, optimizer=optimizer,
                          n_restarts_optimizer=n_restarts_optimizer, normalize_y=normalize_y,
                          copy_X_train=copy_X_train, n_targets=n_targets, random_state=random_state)
@@ -162,6 +232,20 @@ class HipGPR(GaussianProcessRegressor):
         # opt-in: Matern(nu=1.5), Matern(nu=0.5) and Matern(nu=inf) run on the device too (describe_kernel); off, they are
         # outside the device path like every kernel but Matern(nu=2.5) / RBF
         self.matern_family = matern_family
+        # opt-in: C * k, k * C and either + WhiteKernel run on the device too (describe_scaled_kernel); off, a ConstantKernel other
+        # than a fixed 1 and every WhiteKernel are outside the device path
+        self.scaled_kernels = scaled_kernels
+
+    def _describe(self, kernel):
+        """ScaledKernel of a kernel on the device path; theta_index None = a unit kernel describe_kernel itself accepts (today's
+        calls and today's theta handling), NotImplementedError = outside the device path."""
+        try:
+            kind, ls = describe_kernel(kernel, self.matern_family)
+            return ScaledKernel((kind, ls, 1.0, 0.0, None))
+        except NotImplementedError:
+            if not self.scaled_kernels:
+                raise
+        return describe_scaled_kernel(kernel, self.matern_family)
 
     # -- outside the device path ------------------------------------------------------------------
     #: True after a fit that the device path does not cover: every numeric method is then the base class's
@@ -172,9 +256,11 @@ class HipGPR(GaussianProcessRegressor):
     def _unsupported_reason(self, kernel, y=None, X=None):
         """Why this configuration is outside the device path (None when it is inside)."""
         try:
-            describe_kernel(kernel, self.matern_family)
+            sk = self._describe(kernel)
         except NotImplementedError as exc:
             return str(exc)
+        if sk.theta_index is not None and isinstance(self.engine, GroupEngine):
+            return "a device group has no scaled-kernel (ConstantKernel / WhiteKernel) path"
         if np.iterable(self.alpha):
             return "HIP path supports a scalar alpha only"
         if y is not None and np.ndim(y) == 2 and np.shape(y)[1] != 1:
@@ -225,7 +311,7 @@ class HipGPR(GaussianProcessRegressor):
         # `_host_fitting` keeps the base fit's theta search (its own log_marginal_likelihood calls, after it has set X_train_)
         # off the device for the whole fit: this model is outside the device path (width > GPBO_MAX_DIM, several targets).
         self._held = None
-        for k in ("_kind", "_ls", "_L_cache", "_alpha_cache", "log_marginal_likelihood_value_", "_lml_lazy", "X_train_", "y_train_"):
+        for k in ("_kind", "_ls", "_scale", "_L_cache", "_alpha_cache", "log_marginal_likelihood_value_", "_lml_lazy", "X_train_", "y_train_"):
             self.__dict__.pop(k, None)
         self._host_mode = False
         self._host_fitting = True
@@ -254,14 +340,15 @@ class HipGPR(GaussianProcessRegressor):
         return np.ascontiguousarray(X)
 
     @classmethod
-    def from_sklearn(cls, gp: GaussianProcessRegressor, transform=None, engine=None, slot=0, precision="f64", matern_family=False):
+    def from_sklearn(cls, gp: GaussianProcessRegressor, transform=None, engine=None, slot=0, precision="f64", matern_family=False,
+                     scaled_kernels=False):
         """Same hyper-parameters (and the same RandomState object) as an existing estimator."""
         p = gp.get_params(deep=False)
         return cls(kernel=p["kernel"], alpha=p["alpha"], optimizer=p["optimizer"],
                    n_restarts_optimizer=p["n_restarts_optimizer"], normalize_y=p["normalize_y"],
                    copy_X_train=p["copy_X_train"], n_targets=p.get("n_targets"),
                    random_state=p["random_state"], transform=transform, engine=engine, slot=slot, precision=precision,
-                   matern_family=matern_family)
+                   matern_family=matern_family, scaled_kernels=scaled_kernels)
 
     # -- log marginal likelihood ---------------------------------------------------------------------
     def _device_lml_ok(self, kernel) -> bool:
@@ -272,9 +359,12 @@ class HipGPR(GaussianProcessRegressor):
         if np.iterable(self.alpha):
             return False
         try:
-            _, ls = describe_kernel(kernel, self.matern_family)
+            sk = self._describe(kernel)
         except NotImplementedError:
             return False
+        if sk.theta_index is not None:       # a scaled model: every free hyper-parameter has its place in the device's gradient
+            return not isinstance(self.engine, GroupEngine)
+        ls = sk.length_scale
         if _bare_length_scale_kernel(kernel):
             return True
         free = [h for h in kernel.hyperparameters if not h.fixed]
@@ -290,9 +380,17 @@ class HipGPR(GaussianProcessRegressor):
         else:
             kernel = self.kernel_
             kernel.theta = theta
-        kind, ls = describe_kernel(kernel, self.matern_family)
-        out = self._engine().lml(self._tx(self.X_train_), self.y_train_, kind, ls, float(self.alpha),
-                                 eval_gradient=eval_gradient, slot=self.slot)
+        sk = self._describe(kernel)
+        kind, ls = sk.kind, sk.length_scale
+        if sk.theta_index is not None:
+            # gpbo_lml_scaled: the gradient in the device's order [log c, log l ..., log w], picked into theta's
+            out = self._engine().lml(self._tx(self.X_train_), self.y_train_, kind, ls, float(self.alpha),
+                                     eval_gradient=eval_gradient, slot=self.slot, amplitude=sk.amplitude, white=sk.white, scaled=True)
+            if eval_gradient:
+                out = (out[0], np.asarray(out[1])[sk.theta_index])
+        else:
+            out = self._engine().lml(self._tx(self.X_train_), self.y_train_, kind, ls, float(self.alpha),
+                                     eval_gradient=eval_gradient, slot=self.slot)
         self.__dict__.pop("_L_cache", None)      # the slot's factorisation now belongs to this theta
         self.__dict__.pop("_alpha_cache", None)
         if not getattr(self, "_in_fit", False) and hasattr(self, "_kind"):
@@ -415,7 +513,8 @@ class HipGPR(GaussianProcessRegressor):
                     starts.append(self._rng.uniform(bounds[:, 0], bounds[:, 1]))
             # (each lockstep lane holds its own K, L, W: ~40 N^2 bytes per lane -> sequential beyond N = 16384)
             if (self.theta_lockstep and len(starts) > 1 and self.optimizer == "fmin_l_bfgs_b"
-                    and self.X_train_.shape[0] <= 16384 and self._device_lml_ok(self.kernel_)):
+                    and self.X_train_.shape[0] <= 16384 and self._device_lml_ok(self.kernel_)
+                    and self._describe(self.kernel_).theta_index is None):      # (gpbo_lml_batch's lanes share one noise and one target vector)
                 optima = self._theta_search_lockstep(starts, bounds)
             else:
                 optima = [self._constrained_optimization(obj_func, start, bounds) for start in starts]
@@ -435,10 +534,12 @@ class HipGPR(GaussianProcessRegressor):
             self._lml_lazy = True
 
         self._in_fit = False
-        kind, ls = describe_kernel(self.kernel_, self.matern_family)
+        sk = self._describe(self.kernel_)
+        kind, ls = sk.kind, sk.length_scale
         if ls.shape[0] not in (1, self.n_features_in_):
             raise ValueError("Anisotropic kernel must have the same number of dimensions as data")
         self._kind, self._ls = kind, ls
+        self._scale = (sk.amplitude, sk.white) if sk.theta_index is not None else None      # None: a unit model (gpbo_fit)
         # _gpr.py:346-364 on the device (LinAlgError with sklearn's hint when K is not PD)
         self._device_fit_tail()
         return self
@@ -550,7 +651,9 @@ class HipGPR(GaussianProcessRegressor):
         same factorisation plus one row, which is what the append computes."""
         eng = self._engine()
         X, y = self.X_train_, self.y_train_
-        key = (self._kind, self._ls.tobytes(), float(self.alpha), self._precision_code())
+        scale = self.__dict__.get("_scale")
+        key = (self._kind, self._ls.tobytes(), float(self.alpha), self._precision_code(), scale)
+        extra = {} if scale is None else {"amplitude": scale[0], "white": scale[1]}      # (a unit model makes today's calls)
         held = self.__dict__.get("_held")
         self._held = None
         # (copy_X_train=False keeps the caller's array: an in-place edit would go unnoticed, so no appends then)
@@ -560,11 +663,11 @@ class HipGPR(GaussianProcessRegressor):
             n0 = X0.shape[0]
             if n0 <= X.shape[0] and X0.shape[1] == X.shape[1] and np.array_equal(X0, X[:n0]):
                 serial = eng.fit_append(self._tx(X[n0:]) if X.shape[0] > n0 else np.empty((0, X.shape[1])), y,
-                                        slot=self.slot)
+                                        slot=self.slot, **extra)
                 self._held = {"key": key, "engine": eng, "serial": serial, "X": X}
                 return
         serial = eng.fit(self._tx(X), y, self._kind, self._ls, float(self.alpha), slot=self.slot,
-                         precision=self._precision_code())
+                         precision=self._precision_code(), **extra)
         self._held = {"key": key, "engine": eng, "serial": serial, "X": X}
 
     # -- predict -----------------------------------------------------------------------------------

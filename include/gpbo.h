@@ -88,6 +88,16 @@ int gpbo_fit(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int
              int kernel, const double* length_scale, int n_ls, double noise, int precision,
              int* info);
 
+/* gpbo_fit for a scaled model  K = amplitude * k + (white + alpha) * I  — scikit-learn's ConstantKernel(amplitude) * k +
+ * WhiteKernel(white) under an estimator with `alpha`.  The device fits the unit-amplitude model at noise (white + alpha) / amplitude
+ * and the slot keeps amplitude and white: every later posterior of the slot (gpbo_posterior, gpbo_predict*, gpbo_polish_seeds,
+ * gpbo_evolve_mixed) gives  sigma = y_std sqrt(max(amplitude (1 - |W k*|^2) + white, 0)), the mean is unchanged.  amplitude > 0,
+ * white >= 0, alpha >= 0, all finite, else GPBO_ERR_INVALID.  amplitude = 1, white = 0 is gpbo_fit at noise = alpha, bit for bit.
+ * gpbo_fit, gpbo_fit_begin and gpbo_lml make the slot a unit model again; gpbo_fit_append keeps the slot's amplitude and white.
+ * There is no gpbo_fit_begin twin: a scaled fit is synchronous, on the context's own stream (fits pending on other slots go on). */
+int gpbo_fit_scaled(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                    const double* length_scale, int n_ls, double amplitude, double white, double alpha, int precision, int* info);
+
 /* Append n_new observations to a fitted slot at UNCHANGED kernel, length scale and noise.
  * Replaces re-running the whole fixed-theta fit (_gpr.py:346-364) on X u x_new, which is what the reference's
  * maximize() loop does every iteration (bayes_opt/bayesian_optimization.py:377-388 -> acquisition.py:79-86) and what
@@ -125,6 +135,14 @@ int gpbo_lml(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int
              int kernel, const double* length_scale, int n_ls, double noise, int eval_gradient,
              double* lml, double* grad, int* info);
 
+/* gpbo_lml for the scaled model of gpbo_fit_scaled: the log marginal likelihood of y_norm under amplitude * k + (white + alpha) * I
+ * and, with eval_gradient, its gradient in [log amplitude, log length_scale ..., log white]: grad has n_ls + 2 entries.  A non-PD
+ * kernel matrix gives -inf and a zero gradient, as gpbo_lml does; the slot is left unfitted, as by gpbo_lml.  There is no batched
+ * twin: the lanes of gpbo_lml_batch share one noise and one target vector. */
+int gpbo_lml_scaled(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                    const double* length_scale, int n_ls, double amplitude, double white, double alpha, int eval_gradient,
+                    double* lml, double* grad, int* info);
+
 /* n_theta evaluations of gpbo_lml on the SAME (X, y_norm) at different length scales (length_scales: n_theta x n_ls,
  * row-major), in scratch models of their own ("lanes") so that the latency-bound factorisations share the device.
  * This is what the theta search's independent L-BFGS-B runs (the initial theta + n_restarts_optimizer restarts,
@@ -137,10 +155,11 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
                    const double* length_scales, int n_ls, double noise, int eval_gradient, double* lml, double* grad,
                    int* info);
 
-/* Parity accessors (tests): copy device state back as (N,N) row-major / (N,) float64. */
+/* Parity accessors (tests): copy device state back as (N,N) row-major / (N,) float64.  For a slot of gpbo_fit_scaled K, L and
+ * alpha are scikit-learn's quantities of the scaled model (c K', sqrt(c) L', alpha' / c of the unit model the device holds). */
 int gpbo_get_K(gpbo_ctx* ctx, int slot, double* out);      /* kernel matrix incl. noise, full symmetric */
 int gpbo_get_L(gpbo_ctx* ctx, int slot, double* out);      /* lower Cholesky factor, upper zeroed (gp.L_) */
-int gpbo_get_Linv(gpbo_ctx* ctx, int slot, double* out);   /* W = L^-1, lower */
+int gpbo_get_Linv(gpbo_ctx* ctx, int slot, double* out);   /* W = L^-1, lower; of a scaled slot the UNIT model's W' = sqrt(c) L_^-1 */
 int gpbo_get_alpha(gpbo_ctx* ctx, int slot, double* out);  /* gp.alpha_ */
 
 /* ---- candidates ------------------------------------------------------------------------- */
