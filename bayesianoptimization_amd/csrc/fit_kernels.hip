@@ -54,12 +54,13 @@ int launch_prescale(gpbo_ctx* ctx, const double* X, int64_t n, int d, int DP, co
 template <int KERNEL>
 __global__ __launch_bounds__(256) void kmat_kernel(const double* __restrict__ Xs, int DP, int64_t N,
                                                    int64_t NP, double noise, double* __restrict__ K,
-                                                   int64_t lane_stride) {
+                                                   int64_t lane_stride, const double* __restrict__ pair) {
   // blockIdx.x = bi (bi + 1) / 2 + bj, bj <= bi
   int bi, bj;
   lower_tile_of((int)blockIdx.x, bi, bj);
   Xs += (int64_t)blockIdx.z * lane_stride;
   K += (int64_t)blockIdx.z * lane_stride;
+  if (pair) noise = pair[(int64_t)blockIdx.z * lane_stride];      // scaled lanes: the lane's own eta (ctx->lane_pair)
   extern __shared__ __attribute__((aligned(16))) double kmat_smem[];
   kmat_tile_body<KERNEL>(Xs, DP, N, NP, noise, K, bi, bj, kmat_smem, (int)threadIdx.x);
 }
@@ -69,10 +70,28 @@ int launch_kmat(gpbo_ctx* ctx, Model& m, double noise, double* out) {
   dim3 grid((unsigned)(nt * (nt + 1) / 2), 1, (unsigned)ctx->lanes);
   const size_t lds = (size_t)2 * m.DP * 64 * sizeof(double);
   const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
-    kmat_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride);
+    kmat_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride,
+                                                                           ctx->lane_pair);
     return GPBO_OK;
   });
   if (rc) return rc;
+  GPBO_HIP(ctx, hipGetLastError());
+  return GPBO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Scaled lanes (ctx->lane_pair): lane l's targets yn = y * ts_l, one multiply per element as gpbo_lml_scaled forms it on the host;
+// the padding beyond n stays as the caller's fill left it.
+__global__ __launch_bounds__(256) void lane_targets_kernel(const double* __restrict__ y, int64_t n, const double* __restrict__ pair,
+                                                           double* __restrict__ yn, int64_t lane_stride) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t lo = (int64_t)blockIdx.y * lane_stride;
+  if (i < n) yn[lo + i] = y[i] * pair[lo + 1];
+}
+
+int launch_lane_targets(gpbo_ctx* ctx, const double* y, int64_t n, double* yn) {
+  lane_targets_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)ctx->lanes), dim3(256), 0, ctx->stream>>>(y, n, ctx->lane_pair, yn,
+                                                                                                           ctx->lane_stride);
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }

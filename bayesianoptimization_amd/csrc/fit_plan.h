@@ -100,6 +100,9 @@ enum FitBuf { FB_LS, FB_XS, FB_K, FB_L, FB_W, FB_DINV, FB_TMP, FB_YN, FB_TVEC, F
               FB_INFO,                    // lanes only: its pivot words (ctx->info_dev)
               FB_COUNT };
 constexpr int64_t FIT_SCAL_DOUBLES = 8 + GPBO_MAX_DIM;   // what an evaluation needs of ctx->red
+constexpr int64_t FIT_INFO_DOUBLES = 32;                  // FB_INFO: the pivot word first ...
+constexpr int64_t FIT_INFO_PAIR = 2;                      // ... and a scaled lane's [eta, target scale] this many doubles behind it
+static_assert(FIT_INFO_PAIR + 2 <= FIT_INFO_DOUBLES, "the lane's noise / target-scale pair leaves its info region");
 struct FitBuffers { int64_t size[FB_COUNT]; };
 inline FitBuffers fit_buffers(int64_t NP, int DP) {
   FitBuffers b{};
@@ -110,7 +113,7 @@ inline FitBuffers fit_buffers(int64_t NP, int DP) {
   b.size[FB_TMP] = std::max<int64_t>(NP * NP / 2, NP * (int64_t)GPBO_MAX_DIM);         // trtri's workspace | raw inputs (N, d)
   b.size[FB_YN] = b.size[FB_TVEC] = b.size[FB_ALPHA] = NP;
   b.size[FB_SCAL] = FIT_SCAL_DOUBLES;
-  b.size[FB_INFO] = 32;
+  b.size[FB_INFO] = FIT_INFO_DOUBLES;
   return b;
 }
 // One lane of the slab: the buffers one behind the other, each rounded up to 32 doubles.

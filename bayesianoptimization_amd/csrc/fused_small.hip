@@ -67,6 +67,8 @@ struct FusedArgs {
   const double* X;                // raw (N, d): device memory, or pinned host memory (device-visible)
   const double* y;                // (N)
   const double* ls_in;            // [lanes][GPBO_MAX_DIM] length scales (pinned host, device-visible)
+  const double* pair_in;          // scaled lanes (else null): [lanes][eta, ts] (pinned host, device-visible) — lane l runs at noise
+                                  // eta_l on the targets y * ts_l
   double *ls, *Xs, *K, *L, *W, *Wp, *dinv, *tmp, *yn, *tvec, *alpha, *scal;   // lane 0's buffers
   int* info;                      // lane 0's pivot word (device)
   int64_t lane_stride;            // doubles between the lanes' buffers
@@ -98,15 +100,21 @@ __device__ __forceinline__ void fs_inputs(const FusedArgs& a, const int64_t lo, 
     if (tid < GPBO_MAX_DIM) ls[tid] = a.ls_in[(int64_t)zl * GPBO_MAX_DIM + tid];
     __syncthreads();
     for (int64_t idx = tid; idx < a.NP * a.DP; idx += 512) prescale_elem(a.X, a.N, a.d, a.DP, ls, a.Xs + lo, idx);
-    for (int64_t i = tid; i < a.NP; i += 512) a.yn[lo + i] = (i < a.N) ? a.y[i] : 0.0;
+    if (a.pair_in) {
+      const double ts = a.pair_in[zl * 2 + 1];
+      for (int64_t i = tid; i < a.NP; i += 512) a.yn[lo + i] = (i < a.N) ? a.y[i] * ts : 0.0;
+    } else {
+      for (int64_t i = tid; i < a.NP; i += 512) a.yn[lo + i] = (i < a.N) ? a.y[i] : 0.0;
+    }
   }
   __syncthreads();
 }
 
 // ---- K (lower 64x64 tiles) straight into the buffer the Cholesky factorises in place
 template <int KERNEL>
-__device__ __forceinline__ void fs_kmat(const FusedArgs& a, const int64_t lo, double* smem) {
+__device__ __forceinline__ void fs_kmat(const FusedArgs& a, const int64_t lo, const int zl, double* smem) {
   FS_THREAD();
+  const double noise = a.pair_in ? a.pair_in[zl * 2] : a.noise;
   const int nblk = (int)(a.NP / NB);
   const int ntile = nblk * (nblk + 1) / 2;
   for (int r = 0; r < ntile; r += 2) {
@@ -114,7 +122,7 @@ __device__ __forceinline__ void fs_kmat(const FusedArgs& a, const int64_t lo, do
     if (b < ntile) {
       int bi, bj;
       lower_tile_of(b, bi, bj);
-      kmat_tile_body<KERNEL>(a.Xs + lo, a.DP, a.N, a.NP, a.noise, a.L + lo, bi, bj, lds_half, t256);
+      kmat_tile_body<KERNEL>(a.Xs + lo, a.DP, a.N, a.NP, noise, a.L + lo, bi, bj, lds_half, t256);
     } else {
       __syncthreads();
     }
@@ -254,7 +262,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int64_t lo = (int64_t)zl * a.lane_stride;
   const int nblk = (int)(a.NP / NB);
   fs_inputs(a, lo, zl);
-  fs_kmat<KERNEL>(a, lo, fs_smem);
+  fs_kmat<KERNEL>(a, lo, zl, fs_smem);
   // Cholesky: launch_cholesky128's schedule with ONE outer panel (what chol_outer gives up to NP = 2048), every launch of it a
   // phase of this workgroup
   for (int kb = 0; kb < nblk; kb += 2) {
@@ -293,6 +301,8 @@ int launch_fused_small(gpbo_ctx* ctx, Model& m, int mode, int src, int n_ls, con
   a.N = m.N; a.NP = m.NP; a.d = m.d; a.DP = m.DP; a.n_ls = n_ls; a.mode = mode; a.src = src; a.noise = m.noise;
   a.noise_grad = (mode == 2 && noise_grad) ? 1 : 0;
   a.X = X; a.y = y; a.ls_in = ls_in;
+  if (ctx->lane_pair && (src != 0 || mode == 0)) GPBO_FAIL(ctx, GPBO_ERR_STATE, "scaled lanes are LML evaluations of raw inputs");
+  a.pair_in = ctx->lane_pair ? pinned_dev(ctx, pin_lane(ctx->pinned).pair) : nullptr;
   a.ls = m.ls; a.Xs = m.Xs; a.K = m.K; a.L = m.L; a.W = m.W; a.Wp = m.Wp; a.dinv = m.dinv; a.tmp = m.tmp; a.yn = m.yn;
   a.tvec = m.tvec; a.alpha = m.alpha; a.scal = scal;
   a.info = ctx->info_dev;

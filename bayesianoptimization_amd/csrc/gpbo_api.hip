@@ -448,6 +448,8 @@ static int enqueue_factor(gpbo_ctx* ctx, Model& m, const double* X, const double
   int rc;
   const int64_t N = m.N, NP = m.NP;
   const FitTier tier = tier_of(m);
+  // scaled lanes read the resident inputs (lml_batch_run): a host-input sequence would run them at `noise` on unscaled targets
+  if (ctx->lane_pair && !X_dev) GPBO_FAIL(ctx, GPBO_ERR_STATE, "scaled lanes need device-resident inputs");
   if (tier == FitTier::Fused) return enqueue_fused(ctx, m, X, y_norm, X_dev, y_dev, noise, 0, 0, 0, info_host, nullptr);
   if (tier == FitTier::Strip) {      // inputs straight from pinned host memory (or the resident device copies): no copy / fill nodes
     const double *Xd = X_dev, *yd = y_dev;
@@ -460,9 +462,14 @@ static int enqueue_factor(gpbo_ctx* ctx, Model& m, const double* X, const double
   GPBO_HIP(ctx, lane_h2d(ctx, m.ls, pin_lane(ctx->pinned).ls, PIN_LS_PITCH, GPBO_MAX_DIM * sizeof(double)));
   GPBO_HIP(ctx, lane_memset(ctx, m.yn, (size_t)NP * sizeof(double)));
   if (X_dev) {
-    for (int l = 0; l < ctx->lanes; ++l)     // every lane gets the same targets
-      GPBO_HIP(ctx, hipMemcpyAsync(m.yn + (int64_t)l * ctx->lane_stride, y_dev, (size_t)N * sizeof(double),
-                                   hipMemcpyDeviceToDevice, ctx->stream));
+    if (ctx->lane_pair) {                    // scaled lanes: the window's [eta, ts] words to the lanes, targets y * ts_l
+      GPBO_HIP(ctx, lane_h2d(ctx, ctx->lane_pair, pin_lane(ctx->pinned).pair, PIN_PAIR_PITCH, 2 * sizeof(double)));
+      if ((rc = launch_lane_targets(ctx, y_dev, N, m.yn))) return rc;
+    } else {
+      for (int l = 0; l < ctx->lanes; ++l)     // every lane gets the same targets
+        GPBO_HIP(ctx, hipMemcpyAsync(m.yn + (int64_t)l * ctx->lane_stride, y_dev, (size_t)N * sizeof(double),
+                                     hipMemcpyDeviceToDevice, ctx->stream));
+    }
     if ((rc = launch_prescale(ctx, X_dev, N, m.d, m.DP, m.ls, m.Xs, NP))) return rc;
   } else {
     GPBO_HIP(ctx, hipMemcpyAsync(m.tmp, X, (size_t)N * m.d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -875,7 +882,9 @@ static LmlLane& lml_lane_find(gpbo_ctx* ctx, const LmlKey& key) {
 
 static LmlKey lml_lane_key(const gpbo_ctx* ctx, const Model& m, int n_ls, int eval_gradient, int group, const double* gbase) {
   LmlKey k;
-  k.N = m.N; k.d = m.d; k.kernel = m.kernel; k.n_ls = n_ls; k.eval_gradient = eval_gradient; k.noise = m.noise;
+  k.N = m.N; k.d = m.d; k.kernel = m.kernel; k.n_ls = n_ls; k.eval_gradient = eval_gradient;
+  k.scaled = ctx->lane_pair ? 1 : 0;
+  k.noise = k.scaled ? 0.0 : m.noise;       // (a scaled group's noise is a word of its pinned window, not part of the sequence)
   k.lanes = ctx->lanes; k.group = group; k.X = ctx->lml_X; k.y = ctx->lml_y; k.K = gbase;
   return k;
 }
@@ -894,7 +903,7 @@ static void lml_lane_capture(gpbo_ctx* ctx, LmlLane& e, int g, Model& m, int n_l
     int crc = GPBO_ERR_HIP;
     hipError_t err = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
     if (err == hipSuccess) {
-      crc = enqueue_lml(ctx, m, nullptr, nullptr, ctx->lml_X, ctx->lml_y, m.noise, n_ls, eval_gradient, &oh, &ih);
+      crc = enqueue_lml(ctx, m, nullptr, nullptr, ctx->lml_X, ctx->lml_y, m.noise, n_ls, eval_gradient, &oh, &ih, ctx->lane_pair != nullptr);
       err = hipStreamEndCapture(ctx->stream, &graph);
     }
     instantiated = err == hipSuccess && crc == GPBO_OK && graph &&
@@ -921,21 +930,22 @@ static void lml_lane_capture(gpbo_ctx* ctx, LmlLane& e, int g, Model& m, int n_l
 }
 }  // namespace gpbo
 
-extern "C" {
-
-int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_norm, int64_t N, int d, int kernel,
-                   const double* length_scales, int n_ls, double noise, int eval_gradient, double* lml, double* grad,
-                   int* info) {
-  if (!ctx) return GPBO_ERR_INVALID;
-  if (n_theta < 1 || n_theta > GPBO_LML_BATCH_MAX) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch: n_theta out of range [1, 8]");
-  if (!lml || !length_scales || (eval_gradient && !grad) || (!X) != (!y_norm))
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch: NULL argument");
+// What gpbo_lml_batch and gpbo_lml_batch_scaled share: the argument checks, the resident inputs, the lanes' evaluations enqueued
+// group by group (direct launches or the group's graph) and the wait for the groups' streams.  The callers have checked n_theta's
+// range and their pointers (lane_args_ok).  `pair` (scaled: [n_theta][eta, ts],
+// else null): lane i runs at noise pair[2 i] on the targets y * pair[2 i + 1] and also reduces the gradient's noise component — the
+// two words enter through the group's pinned window like the length scales, so a replayed graph reads each call's own.  On success
+// lane i's words are in *groups_out's window 1 + i / per_group, lane i % per_group.
+static int lml_batch_run(gpbo_ctx* ctx, const char* who, int n_theta, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                         const double* length_scales, int n_ls, double noise, const double* pair, int eval_gradient,
+                         LaneGroups* groups_out) {
+  const auto w = [who] { return std::string(who); };
   int rc = wait_all_pending_fits(ctx);   // their pinned windows are the ones the lane groups are about to use
   if (rc) return rc;
   const bool reuse_inputs = !X;     // X == y_norm == NULL: the inputs of the previous call are still on the device
   if (reuse_inputs && (ctx->lml_N != N || ctx->lml_d != d))
-    GPBO_FAIL(ctx, GPBO_ERR_STATE, "gpbo_lml_batch: no resident inputs of this shape (pass X and y_norm)");
-  if ((rc = check_gp_args(ctx, "gpbo_lml_batch", N, d, kernel, length_scales, n_theta, n_ls, noise))) return rc;
+    GPBO_FAIL(ctx, GPBO_ERR_STATE, w() + ": no resident inputs of this shape (pass X and y_norm)");
+  if ((rc = check_gp_args(ctx, who, N, d, kernel, length_scales, n_theta, n_ls, noise))) return rc;
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
 
   // One slab, one layout per lane: every kernel of the evaluation runs ONCE for all lanes (lane = a grid dimension,
@@ -962,6 +972,7 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
     ctx->red = gbase + slab.off[FB_SCAL]; ctx->cap_red = sizes.size[FB_SCAL] * (int64_t)sizeof(double);
     ctx->info_dev = (int*)(gbase + slab.off[FB_INFO]);
     ctx->lanes = std::min(groups.per_group, n_theta - l0); ctx->lane_stride = slab.stride;
+    ctx->lane_pair = pair ? gbase + slab.off[FB_INFO] + FIT_INFO_PAIR : nullptr;
     ctx->no_timing = true;
     ctx->no_lookahead = groups.n_groups > 1;
     Model m;     // a view of the group's first lane (not owning)
@@ -970,6 +981,10 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
     for (int i = 0; i < FB_MODEL_COUNT; ++i) *buf[i] = gbase + slab.off[i];
     // theta enters through the pinned length-scale words ([lane][64]) that the sequence's first copy reads
     for (int l = 0; l < ctx->lanes; ++l) stage_length_scales(ctx->pinned, l, length_scales + (int64_t)(l0 + l) * n_ls, n_ls, d);
+    for (int l = 0; pair && l < ctx->lanes; ++l) {      // ... and so do a scaled lane's noise and target scale
+      double* ph = pin_lane(ctx->pinned, l).pair;
+      ph[0] = pair[2 * (l0 + l)]; ph[1] = pair[2 * (l0 + l) + 1];
+    }
     const LmlKey key = lml_lane_key(ctx, m, n_ls, eval_gradient, g, gbase);
     LmlLane& e = lml_lane_find(ctx, key);
     const bool graph = e.seen && graph_eligible(tier_of(m));      // from the second sighting on
@@ -980,7 +995,7 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
       continue;
     }
     double* oh = nullptr; int* ih = nullptr;
-    rc = enqueue_lml(ctx, m, nullptr, nullptr, ctx->lml_X, ctx->lml_y, noise, n_ls, eval_gradient, &oh, &ih);
+    rc = enqueue_lml(ctx, m, nullptr, nullptr, ctx->lml_X, ctx->lml_y, noise, n_ls, eval_gradient, &oh, &ih, pair != nullptr);
     e.key = key;
     e.seen = (rc == GPBO_OK);
   }
@@ -988,12 +1003,78 @@ int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_
     hipError_t err = hipStreamSynchronize(ctx->lml_stream[g]);
     if (err != hipSuccess && rc == GPBO_OK) GPBO_HIP(ctx, err);
   }
+  *groups_out = groups;
+  return rc;
+}
+
+// 1 ... GPBO_LML_BATCH_MAX lanes, outputs and length scales given, X and y_norm both given or both NULL
+static int lane_args_ok(gpbo_ctx* ctx, const char* who, int n_theta, const double* X, const double* y_norm, const double* length_scales,
+                        int eval_gradient, const double* lml, const double* grad) {
+  if (n_theta < 1 || n_theta > GPBO_LML_BATCH_MAX) GPBO_FAIL(ctx, GPBO_ERR_INVALID, std::string(who) + ": n_theta out of range [1, 8]");
+  if (!lml || !length_scales || (eval_gradient && !grad) || (!X) != (!y_norm))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, std::string(who) + ": NULL argument");
+  return GPBO_OK;
+}
+
+// lane i's words of a finished batch
+static PinLane batch_lane(const gpbo_ctx* ctx, const LaneGroups& groups, int i) {
+  const int g = i / groups.per_group;
+  return pin_lane(pin_window(ctx, 1 + g), i - g * groups.per_group);
+}
+
+extern "C" {
+
+int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                   const double* length_scales, int n_ls, double noise, int eval_gradient, double* lml, double* grad,
+                   int* info) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  int rc = lane_args_ok(ctx, "gpbo_lml_batch", n_theta, X, y_norm, length_scales, eval_gradient, lml, grad);
   if (rc) return rc;
+  LaneGroups groups{};
+  if ((rc = lml_batch_run(ctx, "gpbo_lml_batch", n_theta, X, y_norm, N, d, kernel, length_scales, n_ls, noise, nullptr, eval_gradient,
+                          &groups)))
+    return rc;
   for (int i = 0; i < n_theta; ++i) {
-    const int g = i / groups.per_group;
-    const PinLane h = pin_lane(pin_window(ctx, 1 + g), i - g * groups.per_group);
+    const PinLane h = batch_lane(ctx, groups, i);
     if (info) info[i] = 0;
     lml_finish(h.out, h.info, N, n_ls, eval_gradient, lml + i, eval_gradient ? grad + (size_t)i * n_ls : nullptr, info ? info + i : nullptr);
+  }
+  return GPBO_OK;
+}
+
+int gpbo_lml_batch_scaled(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                          const double* length_scales, int n_ls, const double* amplitudes, const double* whites, double alpha,
+                          int eval_gradient, double* lml, double* grad, int* info) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  int rc = lane_args_ok(ctx, "gpbo_lml_batch_scaled", n_theta, X, y_norm, length_scales, eval_gradient, lml, grad);
+  if (rc) return rc;
+  if (!amplitudes || !whites) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpbo_lml_batch_scaled: NULL argument");
+  // lane i is the unit model's evaluation of the targets y / sqrt(c_i) at noise eta_i (scaled_kernel.h), as gpbo_lml_scaled runs it
+  double pair[2 * GPBO_LML_BATCH_MAX];
+  for (int i = 0; i < n_theta; ++i) {
+    if ((rc = check_scaled_args(ctx, "gpbo_lml_batch_scaled", amplitudes[i], whites[i], alpha))) return rc;
+    pair[2 * i] = scaled_eta(amplitudes[i], whites[i], alpha);
+    pair[2 * i + 1] = scaled_target_scale(amplitudes[i]);
+  }
+  LaneGroups groups{};
+  if ((rc = lml_batch_run(ctx, "gpbo_lml_batch_scaled", n_theta, X, y_norm, N, d, kernel, length_scales, n_ls, 0.0, pair, eval_gradient,
+                          &groups)))
+    return rc;
+  const int n_g = n_ls + 2;
+  for (int i = 0; i < n_theta; ++i) {
+    const PinLane h = batch_lane(ctx, groups, i);
+    if (info) info[i] = 0;
+    double* g = eval_gradient ? grad + (size_t)i * n_g : nullptr;
+    if (*h.info != 0) {      // as gpbo_lml_scaled: -inf and a zero gradient, this lane only
+      if (info) info[i] = *h.info;
+      lml[i] = -INFINITY;
+      for (int t = 0; g && t < n_g; ++t) g[t] = 0.0;
+      continue;
+    }
+    double unit = 0.0;
+    lml_finish(h.out, h.info, N, n_ls, 0, &unit, nullptr, nullptr);
+    lml[i] = scaled_lml(unit, N, amplitudes[i]);
+    if (g) scaled_lml_gradient(amplitudes[i], whites[i], alpha, N, h.out[0], h.out + 2, n_ls, h.out[2 + n_ls], g);
   }
   return GPBO_OK;
 }

@@ -69,11 +69,12 @@ struct Model {
 struct LmlKey {
   int64_t N = 0;
   int d = 0, kernel = 0, n_ls = 0, eval_gradient = 0, lanes = 0, group = 0;
+  int scaled = 0;          // gpbo_lml_batch_scaled: noise and target scale per lane through the pinned window, `noise` stays 0
   double noise = 0.0;
   const void* X = nullptr; const void* y = nullptr; const void* K = nullptr;   // the resident inputs and the group's slab
   bool operator==(const LmlKey& o) const {
-    return N == o.N && d == o.d && kernel == o.kernel && n_ls == o.n_ls && eval_gradient == o.eval_gradient && noise == o.noise &&
-           lanes == o.lanes && group == o.group && X == o.X && y == o.y && K == o.K;
+    return N == o.N && d == o.d && kernel == o.kernel && n_ls == o.n_ls && eval_gradient == o.eval_gradient && scaled == o.scaled &&
+           noise == o.noise && lanes == o.lanes && group == o.group && X == o.X && y == o.y && K == o.K;
   }
 };
 struct LmlLane {
@@ -120,6 +121,9 @@ struct gpbo_ctx {
   // sit l * lane_stride doubles behind the ones of the Model passed in (one slab, same layout per lane)
   int lanes = 1;
   int64_t lane_stride = 0;
+  // gpbo_lml_batch_scaled: lane 0's [eta, target scale] on the device (lane l's l * lane_stride doubles behind), staged in the
+  // pinned window's PIN_LANE_PAIR words; null: every lane runs at the launchers' `noise` with the targets as they are
+  double* lane_pair = nullptr;
   double* lml_slab = nullptr; int64_t cap_lml_slab = 0;
   gpbo::LmlLane lml_lane[gpbo::LML_GRAPH_POOL];
   uint64_t lml_lane_clock = 0;
@@ -207,25 +211,28 @@ constexpr size_t FUSED_STAGE_BYTES = ((size_t)STAGE_NP_CAP * GPBO_MAX_DIM + STAG
 // and candidate entry points, so that no two subsystems share a byte whatever stays in flight.
 constexpr size_t PIN_WINDOW = 16384;
 constexpr int PIN_WINDOWS = 2 + GPBO_LML_BATCH_MAX;
-// every window but the last, one layout: per lane the length scales at +0, the potrf info words at PIN_LANE_INFO, the LML
-// scalars (yT alpha, sum log L_ii, gradient[GPBO_MAX_DIM], the noise component) at PIN_LANE_OUT.  A single fit or evaluation is lane 0.
+// every window but the last, one layout: per lane the length scales at +0, the potrf info words at PIN_LANE_INFO, the
+// [eta, target scale] pair of a scaled lane at PIN_LANE_PAIR, the LML scalars (yT alpha, sum log L_ii, gradient[GPBO_MAX_DIM], the
+// noise component) at PIN_LANE_OUT.  A single fit or evaluation is lane 0.
 constexpr size_t PIN_LS_PITCH = GPBO_MAX_DIM * sizeof(double);
 constexpr size_t PIN_INFO_PITCH = 8;
 constexpr size_t PIN_OUT_PITCH = (3 + GPBO_MAX_DIM) * sizeof(double);
-constexpr size_t PIN_LANE_INFO = 4096, PIN_LANE_OUT = 8192;
+constexpr size_t PIN_PAIR_PITCH = 2 * sizeof(double);
+constexpr size_t PIN_LANE_INFO = 4096, PIN_LANE_PAIR = 4096 + 256, PIN_LANE_OUT = 8192;
 static_assert(GPBO_LML_BATCH_MAX * PIN_LS_PITCH <= PIN_LANE_INFO, "lane length scales overlap the lane info words");
-static_assert(PIN_LANE_INFO + GPBO_LML_BATCH_MAX * PIN_INFO_PITCH <= PIN_LANE_OUT, "lane info words overlap the lane LML scalars");
+static_assert(PIN_LANE_INFO + GPBO_LML_BATCH_MAX * PIN_INFO_PITCH <= PIN_LANE_PAIR, "lane info words overlap the lane noise / target-scale pairs");
+static_assert(PIN_LANE_PAIR + GPBO_LML_BATCH_MAX * PIN_PAIR_PITCH <= PIN_LANE_OUT, "lane noise / target-scale pairs overlap the lane LML scalars");
 static_assert(PIN_LANE_OUT + GPBO_LML_BATCH_MAX * PIN_OUT_PITCH <= PIN_WINDOW, "lane LML scalars leave the window");
 // the address the device sees a word of the pinned window allocation at
 template <typename T>
 T* pinned_dev(const gpbo_ctx* ctx, T* host) { return (T*)(ctx->pinned_base_dev + ((const char*)host - (const char*)ctx->pinned_base)); }
 inline void* pin_window(const gpbo_ctx* ctx, int w) { return (char*)ctx->pinned_base + PIN_WINDOW * (size_t)w; }
 // lane l's words in a window (host addresses; the kernels take pinned_dev() of lane 0's and the pitches)
-struct PinLane { double* ls; int* info; double* out; };
+struct PinLane { double* ls; int* info; double* out; double* pair; };
 inline PinLane pin_lane(void* window, int l = 0) {
   char* w = (char*)window;
   return {(double*)(w + (size_t)l * PIN_LS_PITCH), (int*)(w + PIN_LANE_INFO + (size_t)l * PIN_INFO_PITCH),
-          (double*)(w + PIN_LANE_OUT + (size_t)l * PIN_OUT_PITCH)};
+          (double*)(w + PIN_LANE_OUT + (size_t)l * PIN_OUT_PITCH), (double*)(w + PIN_LANE_PAIR + (size_t)l * PIN_PAIR_PITCH)};
 }
 // aux window
 constexpr size_t PIN_AUX_SEL_OUT = 256;                              // SelState + picks[GPBO_MAX_SEEDS + 1] coming back
@@ -249,15 +256,16 @@ struct LaunchScope {
   const int64_t cap_red;
   const int lanes;
   const int64_t lane_stride;
+  double* const lane_pair;
   const bool no_timing, no_lookahead;
   explicit LaunchScope(gpbo_ctx* c)
       : ctx(c), stream(c->stream), pinned(c->pinned), info_dev(c->info_dev), red(c->red), cap_red(c->cap_red), lanes(c->lanes),
-        lane_stride(c->lane_stride), no_timing(c->no_timing), no_lookahead(c->no_lookahead) {}
+        lane_stride(c->lane_stride), lane_pair(c->lane_pair), no_timing(c->no_timing), no_lookahead(c->no_lookahead) {}
   LaunchScope(const LaunchScope&) = delete;
   LaunchScope& operator=(const LaunchScope&) = delete;
   ~LaunchScope() {
     ctx->stream = stream; ctx->pinned = pinned; ctx->info_dev = info_dev; ctx->red = red; ctx->cap_red = cap_red;
-    ctx->lanes = lanes; ctx->lane_stride = lane_stride; ctx->no_timing = no_timing; ctx->no_lookahead = no_lookahead;
+    ctx->lanes = lanes; ctx->lane_stride = lane_stride; ctx->lane_pair = lane_pair; ctx->no_timing = no_timing; ctx->no_lookahead = no_lookahead;
   }
 };
 
@@ -478,6 +486,7 @@ int ensure(gpbo_ctx* ctx, T** p, int64_t* cap, int64_t need) {
 int launch_prescale(gpbo_ctx* ctx, const double* X, int64_t n, int d, int DP, const double* ls,
                     double* out, int64_t n_pad);
 int launch_kmat(gpbo_ctx* ctx, Model& m, double noise, double* out);   // out: m.K, or m.L (factorised in place)
+int launch_lane_targets(gpbo_ctx* ctx, const double* y, int64_t n, double* yn);   // scaled lanes: yn = y * ts_l per lane (ctx->lane_pair)
 int launch_fill_w_diag(gpbo_ctx* ctx, Model& m, bool zero_fill = true);
 int launch_trmv(gpbo_ctx* ctx, Model& m);
 int launch_append_row(gpbo_ctx* ctx, Model& m, int64_t j);   // row j (== current m.N) from the prescaled m.Xs[j]

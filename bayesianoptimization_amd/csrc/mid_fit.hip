@@ -38,15 +38,22 @@ namespace gpbo {
 // ---- inputs ---------------------------------------------------------------------------------------------------------------
 // X (N, d) and y (N) are device-visible (pinned host staging or device memory, shared by all lanes); ls_in = [lanes][64] length
 // scales in the pinned window.  Element idx of the zero-padded [NP][DP] image per thread: prescale_elem's arithmetic.
+// pair_in (scaled lanes, else null) = [lanes][eta, ts] in the pinned window: lane l's targets are y * ts_l and the pair goes to the
+// lane's device words `pair` for kmat_q_kernel.
 __global__ __launch_bounds__(256) void mid_inputs_kernel(const double* __restrict__ X, const double* __restrict__ y,
                                                          const double* __restrict__ ls_in, int64_t N, int64_t NP, int d, int DP,
                                                          double* __restrict__ ls, double* __restrict__ Xs, double* __restrict__ yn,
-                                                         int* __restrict__ info, int64_t lane_stride) {
+                                                         int* __restrict__ info, int64_t lane_stride,
+                                                         const double* __restrict__ pair_in, double* __restrict__ pair) {
   const int64_t lo = (int64_t)blockIdx.y * lane_stride;
   const double* lsi = ls_in + (int64_t)blockIdx.y * GPBO_MAX_DIM;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx < NP * DP) prescale_elem(X, N, d, DP, lsi, Xs + lo, idx);
-  if (idx < NP) yn[lo + idx] = (idx < N) ? y[idx] : 0.0;
+  if (pair_in) {
+    const double* pi = pair_in + (int64_t)blockIdx.y * 2;
+    if (idx < NP) yn[lo + idx] = (idx < N) ? y[idx] * pi[1] : 0.0;
+    if (idx < 2) pair[lo + idx] = pi[idx];
+  } else if (idx < NP) yn[lo + idx] = (idx < N) ? y[idx] : 0.0;
   if (idx < GPBO_MAX_DIM) ls[lo + idx] = lsi[idx];
   if (idx == 0) info[lo * 2] = 0;
 }
@@ -54,7 +61,8 @@ __global__ __launch_bounds__(256) void mid_inputs_kernel(const double* __restric
 int launch_mid_inputs(gpbo_ctx* ctx, Model& m, const double* X, const double* y, const double* ls_in) {
   const int64_t total = std::max<int64_t>(m.NP * m.DP, GPBO_MAX_DIM);
   mid_inputs_kernel<<<dim3((unsigned)((total + 255) / 256), (unsigned)ctx->lanes), dim3(256), 0, ctx->stream>>>(
-      X, y, ls_in, m.N, m.NP, m.d, m.DP, m.ls, m.Xs, m.yn, ctx->info_dev, ctx->lane_stride);
+      X, y, ls_in, m.N, m.NP, m.d, m.DP, m.ls, m.Xs, m.yn, ctx->info_dev, ctx->lane_stride,
+      ctx->lane_pair ? pinned_dev(ctx, pin_lane(ctx->pinned).pair) : nullptr, ctx->lane_pair);
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }
@@ -64,13 +72,14 @@ int launch_mid_inputs(gpbo_ctx* ctx, Model& m, const double* X, const double* y,
 // row x four columns.  Element for element the arithmetic of kmat_tile_body (fit_bodies.h).
 template <int KERNEL>
 __global__ __launch_bounds__(256) void kmat_q_kernel(const double* __restrict__ Xs, int DP, int64_t N, int64_t NP, double noise,
-                                                     double* __restrict__ K, int64_t lane_stride) {
+                                                     double* __restrict__ K, int64_t lane_stride, const double* __restrict__ pair) {
   extern __shared__ __attribute__((aligned(16))) double kq_smem[];
   int bi, bj;
   lower_tile_of((int)(blockIdx.x >> 2), bi, bj);
   const int q = (int)(blockIdx.x & 3);
   Xs += (int64_t)blockIdx.z * lane_stride;
   K += (int64_t)blockIdx.z * lane_stride;
+  if (pair) noise = pair[(int64_t)blockIdx.z * lane_stride];      // scaled lanes: the lane's own eta (ctx->lane_pair)
   const int tid = (int)threadIdx.x;
   double* XiT = kq_smem;             // [DP][64]
   double* XjT = kq_smem + DP * 64;   // [DP][16]
@@ -114,7 +123,8 @@ int launch_kmat_q(gpbo_ctx* ctx, Model& m, double noise, double* out) {
   dim3 grid((unsigned)(4 * (nt * (nt + 1) / 2)), 1, (unsigned)ctx->lanes);
   const size_t lds = (size_t)m.DP * 80 * sizeof(double);
   const int rc = with_kernel(ctx, m.kernel, [&](auto k) {
-    kmat_q_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride);
+    kmat_q_kernel<decltype(k)::value><<<grid, dim3(256), lds, ctx->stream>>>(m.Xs, m.DP, m.N, m.NP, noise, out, ctx->lane_stride,
+                                                                             ctx->lane_pair);
     return GPBO_OK;
   });
   if (rc) return rc;

@@ -140,7 +140,7 @@ def warm_up(engine, bounds, acquisition=None, kernel=None, n_restarts_optimizer:
 
 def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=None, precision: str = "f64",
                devices=None, local_search: str = "auto", lml_on_device="auto", warm: bool = True,
-               mixed_search: str = "reference", matern_family: bool = False, scaled_kernels: bool = False):
+               mixed_search: str = "reference", matern_family: bool = False, scaled_kernels: bool = False, scaled_lanes: bool = False):
     """Swap the GP(s) and the acquisition function of `optimizer` in place; returns `optimizer`.
 
     `devices=[0, 1, ...]`: shard the random stage of every suggest() over these GPUs from this ONE process (GroupEngine:
@@ -182,6 +182,12 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
     such a kernel degrades to the host like any other; so it does on a device group (`devices=[...]`), which has no scaled path.
     Such a model is not warmed up, and the engine is not marked warm for its width: a later accelerate() with a kernel that is
     warmed still runs its warm-up.
+    `scaled_lanes` (default False; needs `scaled_kernels=True`, ValueError otherwise): opt in to the lockstep theta search for
+    such a model too — the 1 + n_restarts_optimizer L-BFGS-B runs of the target GP and of every constraint GP advance together,
+    up to 8 evaluations side by side per call (gpbo_lml_batch_scaled), every one bitwise the single evaluation: the same theta, the
+    same RandomState draws (DESIGN.md §8.2 has the measured search times).  Still refused or unchanged: a device group
+    (`devices=[...]`) keeps such a model on the host, a custom optimizer, a single start and N > 16384 keep the sequential
+    search, scaled fits are not overlapped and not warmed up.
     `warm` (default True): run `warm_up` once per engine and dimension — five synthetic suggest() calls (~0.3 s) that load the
     code objects, allocate and launch every small-N path, so that no suggest() of the user's loop carries a first-use spike.
     The optimizer's RandomState is not touched.
@@ -190,12 +196,15 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
         raise ValueError("local_search must be 'auto', 'reference' or 'device'")
     if mixed_search not in ("reference", "device"):
         raise ValueError("mixed_search must be 'reference' or 'device'")
+    if scaled_lanes and not scaled_kernels:
+        raise ValueError("scaled_lanes=True needs scaled_kernels=True (it is the lockstep theta search of those models)")
     if engine is None:
         engine = shared_engine(tuple(devices)) if devices is not None else shared_engine(device)
     space = optimizer._space
     transform = None if _identity_transform(space) else space.kernel_transform
     matern_family = bool(matern_family)
     scaled_kernels = bool(scaled_kernels)
+    scaled_lanes = bool(scaled_lanes)
     noted = _note_unsupported(optimizer._gp.kernel, "the target GP", matern_family, scaled_kernels)
     width = int(getattr(space, "bounds", np.zeros((0, 2))).shape[0])      # columns in kernel space (categoricals are one-hot there)
     too_wide = None
@@ -207,7 +216,7 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
                           "GaussianProcessRegressor on the host (the reference's path)", UserWarning, stacklevel=2)
         noted = noted or too_wide
     optimizer._gp = HipGPR.from_sklearn(optimizer._gp, transform=transform, engine=engine, slot=0, precision=precision,
-                                        matern_family=matern_family, scaled_kernels=scaled_kernels)
+                                        matern_family=matern_family, scaled_kernels=scaled_kernels, scaled_lanes=scaled_lanes)
     optimizer._gp.lml_on_device = lml_on_device
     if noted:
         optimizer._gp._host_warned = noted          # said once, here
@@ -218,7 +227,8 @@ def accelerate(optimizer, device: int = 0, n_random: int | None = None, engine=N
         for j, m in enumerate(constraint._model):
             noted = _note_unsupported(m.kernel, f"constraint GP {j}", matern_family, scaled_kernels) or too_wide
             constraint._model[j] = HipGPR.from_sklearn(m, transform=transform, engine=engine, slot=j + 1, precision=precision,
-                                                       matern_family=matern_family, scaled_kernels=scaled_kernels)
+                                                       matern_family=matern_family, scaled_kernels=scaled_kernels,
+                                                       scaled_lanes=scaled_lanes)
             constraint._model[j].lml_on_device = lml_on_device
             if noted:
                 constraint._model[j]._host_warned = noted

@@ -293,6 +293,65 @@ class GpEngine:
 
         return one_round
 
+    def lml_batch_scaled_arrays(self, X, y_norm, kernel: int, length_scales, amplitudes, whites, noise: float, eval_gradient=True,
+                                reuse_inputs=False):
+        """`lml_batch_arrays` for scaled models (gpbo_lml_batch_scaled): row i is amplitudes[i] * k(length_scales[i]) + (whites[i] +
+        noise) * I.  Values (n_theta,) and gradients (n_theta, n_ls + 2) in [log amplitude, log length_scale ..., log white], each
+        lane bitwise what `lml(..., scaled=True)` returns for that row.  Model slots are not touched."""
+        self._settle()
+        ls = np.ascontiguousarray(np.atleast_2d(np.asarray(length_scales, dtype=np.float64)))
+        n, n_ls = ls.shape
+        amp = np.ascontiguousarray(np.asarray(amplitudes, dtype=np.float64).ravel())
+        wh = np.ascontiguousarray(np.asarray(whites, dtype=np.float64).ravel())
+        if amp.shape[0] != n or wh.shape[0] != n:
+            raise ValueError("amplitudes and whites need one entry per row of length_scales")
+        vals = np.zeros(n)
+        grads = np.zeros((n, n_ls + 2))
+        infos = _INT_ARRAYS.get(n)
+        if infos is None:
+            infos = _INT_ARRAYS[n] = C.c_int * n
+        if reuse_inputs:
+            xp = yp = None
+        else:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+            y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
+            xp, yp = dptr(X), dptr(y_norm)
+        rc = self._lib.gpbo_lml_batch_scaled(self._h, n, xp, yp, X.shape[0], X.shape[1], int(kernel), dptr(ls), n_ls, dptr(amp),
+                                             dptr(wh), float(noise), int(bool(eval_gradient)), dptr(vals), dptr(grads), infos())
+        if rc:
+            self._check(rc)
+        return vals, grads
+
+    def lml_search_rounds_scaled(self, X, y_norm, kernel: int, n_ls: int, noise: float):
+        """`lml_search_rounds` for a scaled model: `round(params (n <= 8, n_ls + 2)) -> (values (n,), gradients (n, n_ls + 2))`, a row
+        of `params` and of the gradients in the device's order [amplitude, length_scale ..., white] (gpbo_lml_batch_scaled).  Same
+        frame: inputs resident after the first round, arrays and pointers made once, results valid until the next round."""
+        self._settle()
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
+        N, d = int(X.shape[0]), int(X.shape[1])
+        ls = np.ones((8, n_ls))
+        amp, wh = np.ones(8), np.zeros(8)
+        vals = np.zeros(8)
+        grads = np.zeros((8, n_ls + 2))
+        infos = (C.c_int * 8)()
+        p_ls, p_amp, p_wh, p_vals, p_grads = dptr(ls), dptr(amp), dptr(wh), dptr(vals), dptr(grads)
+        xp, yp = [dptr(X)], [dptr(y_norm)]
+        call, h, kind, nz, ck = self._lib.gpbo_lml_batch_scaled, self._h, int(kernel), float(noise), self._check
+
+        def one_round(params):
+            n = params.shape[0]
+            amp[:n] = params[:, 0]
+            ls[:n] = params[:, 1:1 + n_ls]
+            wh[:n] = params[:, 1 + n_ls]
+            rc = call(h, n, xp[0], yp[0], N, d, kind, p_ls, n_ls, p_amp, p_wh, nz, 1, p_vals, p_grads, infos)
+            xp[0] = yp[0] = None              # (X, y_norm stay referenced by this closure for the search's lifetime)
+            if rc:
+                ck(rc)
+            return vals[:n], grads[:n]
+
+        return one_round
+
     def _touch(self, slot: int) -> int:
         """Every call that rewrites a slot's factorisation bumps its serial; an estimator compares the serial it got
         from its last fit with `fit_serial(slot)` to know whether the slot still holds ITS model."""
@@ -990,6 +1049,13 @@ class GroupEngine(GpEngine):
                                              x_new.shape[1], dptr(y_norm), y_norm.shape[0], C.byref(info))
         self._gcheck(rc, info.value, borrowed=(x_new, y_norm, info))
         return self._touch(slot)
+
+    def lml_batch_scaled_arrays(self, X, y_norm, kernel: int, length_scales, amplitudes, whites, noise: float, eval_gradient=True,
+                                reuse_inputs=False):
+        self._refuse_scaled(0.0, 0.0)      # (gpbo_group_lml_batch takes unit models only)
+
+    def lml_search_rounds_scaled(self, X, y_norm, kernel: int, n_ls: int, noise: float):
+        self._refuse_scaled(0.0, 0.0)
 
     def lml_batch_arrays(self, X, y_norm, kernel: int, length_scales, noise: float, eval_gradient=True, reuse_inputs=False):
         """The lanes of one lockstep round of the theta search spread over the group's devices (gpbo_group_lml_batch: lane

@@ -20,7 +20,8 @@ With `matern_family=True` (opt-in) also the other closed-form members of the Mat
 With `scaled_kernels=True` (opt-in) also a signal variance and a noise level around any of those: `C * k`, `k * C` and either
 `+ WhiteKernel`, every hyper-parameter free or fixed (describe_scaled_kernel) — the device fits the unit-amplitude model at noise
 (noise_level + alpha) / constant_value and applies the two values wherever a variance is formed; the theta search evaluates its
-restarts one after another (gpbo_lml_scaled).
+restarts one after another (gpbo_lml_scaled), or, with `scaled_lanes=True` on top (opt-in), side by side in lockstep as a unit
+model's (gpbo_lml_batch_scaled: every lane bitwise the single evaluation, so the same theta).
 Anything else — `set_gp_params(kernel=Matern(nu=1.5))` on an accelerated optimizer
 (bayes_opt/bayesian_optimization.py:403-407), a per-sample `alpha`, several targets — is outside the device path: the
 estimator then IS its base class for that fit (scikit-learn's own `fit` / `predict`, the reference's arithmetic and
@@ -206,7 +207,7 @@ class HipGPR(GaussianProcessRegressor):
     def __init__(self, kernel=None, *, alpha=1e-10, optimizer="fmin_l_bfgs_b", n_restarts_optimizer=0,
                  normalize_y=False, copy_X_train=True, n_targets=None, random_state=None,
                  transform=None, engine=None, slot=0, lml_on_device="auto", precision="f64", incremental=True,
-                 theta_lockstep=True, matern_family=False, scaled_kernels=False):
+                 theta_lockstep=True, matern_family=False, scaled_kernels=False, scaled_lanes=False):
         super().__init__(kernel=kernel, alpha=alpha, optimizer=optimizer,
                          n_restarts_optimizer=n_restarts_optimizer, normalize_y=normalize_y,
                          copy_X_train=copy_X_train, n_targets=n_targets, random_state=random_state)
@@ -235,6 +236,9 @@ class HipGPR(GaussianProcessRegressor):
         # opt-in: C * k, k * C and either + WhiteKernel run on the device too (describe_scaled_kernel); off, a ConstantKernel other
         # than a fixed 1 and every WhiteKernel are outside the device path
         self.scaled_kernels = scaled_kernels
+        # opt-in, on top of scaled_kernels: the restarts of a scaled model's theta search advance in lockstep too, their evaluations
+        # side by side (gpbo_lml_batch_scaled); off, they run one after another (gpbo_lml_scaled)
+        self.scaled_lanes = scaled_lanes
 
     def _describe(self, kernel):
         """ScaledKernel of a kernel on the device path; theta_index None = a unit kernel describe_kernel itself accepts (today's
@@ -341,14 +345,14 @@ class HipGPR(GaussianProcessRegressor):
 
     @classmethod
     def from_sklearn(cls, gp: GaussianProcessRegressor, transform=None, engine=None, slot=0, precision="f64", matern_family=False,
-                     scaled_kernels=False):
+                     scaled_kernels=False, scaled_lanes=False):
         """Same hyper-parameters (and the same RandomState object) as an existing estimator."""
         p = gp.get_params(deep=False)
         return cls(kernel=p["kernel"], alpha=p["alpha"], optimizer=p["optimizer"],
                    n_restarts_optimizer=p["n_restarts_optimizer"], normalize_y=p["normalize_y"],
                    copy_X_train=p["copy_X_train"], n_targets=p.get("n_targets"),
                    random_state=p["random_state"], transform=transform, engine=engine, slot=slot, precision=precision,
-                   matern_family=matern_family, scaled_kernels=scaled_kernels)
+                   matern_family=matern_family, scaled_kernels=scaled_kernels, scaled_lanes=scaled_lanes)
 
     # -- log marginal likelihood ---------------------------------------------------------------------
     def _device_lml_ok(self, kernel) -> bool:
@@ -514,7 +518,8 @@ class HipGPR(GaussianProcessRegressor):
             # (each lockstep lane holds its own K, L, W: ~40 N^2 bytes per lane -> sequential beyond N = 16384)
             if (self.theta_lockstep and len(starts) > 1 and self.optimizer == "fmin_l_bfgs_b"
                     and self.X_train_.shape[0] <= 16384 and self._device_lml_ok(self.kernel_)
-                    and self._describe(self.kernel_).theta_index is None):      # (gpbo_lml_batch's lanes share one noise and one target vector)
+                    # (gpbo_lml_batch's lanes share one noise and one target vector: a scaled model needs gpbo_lml_batch_scaled)
+                    and (self._describe(self.kernel_).theta_index is None or (self.scaled_kernels and self.scaled_lanes))):
                 optima = self._theta_search_lockstep(starts, bounds)
             else:
                 optima = [self._constrained_optimization(obj_func, start, bounds) for start in starts]
@@ -548,9 +553,8 @@ class HipGPR(GaussianProcessRegressor):
         """[(theta_opt, -lml_opt)] of sklearn's `_constrained_optimization` from every start, the runs advanced together:
         per round ONE gpbo_lml_batch call evaluates the theta each live run is asking for (up to 8 side by side; the
         factorisations are latency-bound, so they overlap on the device).  Each run sees exactly the values it would see
-        alone (every lane of the batch is bitwise gpbo_lml)."""
-        from .lockstep import Lockstep
-
+        alone (every lane of the batch is bitwise gpbo_lml).  A scaled model (scaled_lanes): the same over gpbo_lml_batch_scaled,
+        every lane bitwise gpbo_lml_scaled."""
         eng = self._engine()
         X, y, noise = self._tx(self.X_train_), self.y_train_, float(self.alpha)
         n_dims = len(starts[0])
@@ -558,7 +562,11 @@ class HipGPR(GaussianProcessRegressor):
         # theta = log(length scale(s)) for the kernels _device_lml_ok admits (one free length-scale hyper-parameter,
         # kernels.py:Hyperparameter/theta); checked once here — starts[0] IS kernel_.theta — instead of cloning the kernel
         # for every evaluation (a clone costs ~0.1 ms of sklearn's get_params / signature machinery)
-        kind, ls0 = describe_kernel(self.kernel_, self.matern_family)
+        sk = self._describe(self.kernel_)
+        if sk.theta_index is not None:      # a scaled model (fit admits one with scaled_lanes only)
+            evaluate = self._scaled_lane_rounds(eng, sk, X, y, noise, starts)
+            return self._lockstep_runs(eng, evaluate, starts, bounds)
+        kind, ls0 = sk.kind, sk.length_scale
         if not np.all(np.abs(ls0 - np.exp(starts[0])) <= 1e-12 * np.abs(np.exp(starts[0]))):
             raise RuntimeError("theta does not map to the length scale as expected")    # pragma: no cover
         uploaded = [False]
@@ -592,6 +600,53 @@ class HipGPR(GaussianProcessRegressor):
                 uploaded[0] = True
             return rows
 
+        return self._lockstep_runs(eng, evaluate, starts, bounds)
+
+    def _scaled_lane_rounds(self, eng, sk, X, y, noise, starts):
+        """`evaluate(thetas) -> rows [lml | d lml / d theta]` of a scaled model's lockstep search.  A theta row becomes the device's
+        parameters [c, length_scale ..., w]: exp(theta) at the places `sk.theta_index` names, the kernel's own values where a
+        hyper-parameter is fixed (either operand order: the index says where each entry goes); the device's gradient is picked
+        back with the same index.  The map is checked once against scikit-learn's own reading of starts[0]."""
+        index, n_ls = sk.theta_index, sk.length_scale.shape[0]
+        base = np.concatenate(([sk.amplitude], sk.length_scale, [sk.white]))
+
+        def to_device(thetas):
+            params = np.tile(base, (len(thetas), 1))
+            params[:, index] = np.exp(np.asarray(thetas, dtype=np.float64))
+            return params
+
+        ref = describe_scaled_kernel(self.kernel_.clone_with_theta(starts[0]), self.matern_family)
+        want = np.concatenate(([ref.amplitude], ref.length_scale, [ref.white]))
+        got = to_device([starts[0]])[0]
+        if ref.kind != sk.kind or want.shape != got.shape or not np.all(np.abs(got - want) <= 1e-12 * np.abs(want)):
+            raise RuntimeError("theta does not map to (constant_value, length_scale, noise_level) as expected")    # pragma: no cover
+        uploaded = [False]
+        self.theta_search_rounds_ = 0      # lockstep rounds = gpbo_lml_batch_scaled calls on the critical path
+        self.theta_search_evals_ = 0       # LML + gradient evaluations over all restarts
+        frame = eng.lml_search_rounds_scaled(X, y, sk.kind, n_ls, noise) if type(eng).__name__ == "GpEngine" else None
+
+        def evaluate(thetas):
+            self.theta_search_rounds_ += 1
+            self.theta_search_evals_ += len(thetas)
+            rows = np.empty((len(thetas), 1 + len(index)))
+            params = to_device(thetas)
+            for lo in range(0, len(thetas), 8):
+                p = params[lo:lo + 8]
+                if frame is not None:
+                    vals, grads = frame(p)
+                else:
+                    vals, grads = eng.lml_batch_scaled_arrays(X, y, sk.kind, p[:, 1:1 + n_ls], p[:, 0], p[:, 1 + n_ls], noise, True,
+                                                              uploaded[0])
+                rows[lo:lo + len(vals), 0] = vals
+                rows[lo:lo + len(vals), 1:] = np.asarray(grads)[:, index]
+                uploaded[0] = True
+            return rows
+
+        return evaluate
+
+    def _lockstep_runs(self, eng, evaluate, starts, bounds):
+        """The L-BFGS-B runs from every start over `evaluate` (one call per lockstep round): [(theta_opt, -lml_opt)]."""
+        from .lockstep import Lockstep
         from . import lbfgsb_lockstep
 
         if lbfgsb_lockstep.driver_available() and not np.any(bounds[:, 0] == bounds[:, 1]):

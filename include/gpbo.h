@@ -137,8 +137,8 @@ int gpbo_lml(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int
 
 /* gpbo_lml for the scaled model of gpbo_fit_scaled: the log marginal likelihood of y_norm under amplitude * k + (white + alpha) * I
  * and, with eval_gradient, its gradient in [log amplitude, log length_scale ..., log white]: grad has n_ls + 2 entries.  A non-PD
- * kernel matrix gives -inf and a zero gradient, as gpbo_lml does; the slot is left unfitted, as by gpbo_lml.  There is no batched
- * twin: the lanes of gpbo_lml_batch share one noise and one target vector. */
+ * kernel matrix gives -inf and a zero gradient, as gpbo_lml does; the slot is left unfitted, as by gpbo_lml.  Its batched twin is
+ * gpbo_lml_batch_scaled below (the lanes of gpbo_lml_batch itself share one noise and one target vector). */
 int gpbo_lml_scaled(gpbo_ctx* ctx, int slot, const double* X, const double* y_norm, int64_t N, int d, int kernel,
                     const double* length_scale, int n_ls, double amplitude, double white, double alpha, int eval_gradient,
                     double* lml, double* grad, int* info);
@@ -154,6 +154,18 @@ int gpbo_lml_scaled(gpbo_ctx* ctx, int slot, const double* X, const double* y_no
 int gpbo_lml_batch(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_norm, int64_t N, int d, int kernel,
                    const double* length_scales, int n_ls, double noise, int eval_gradient, double* lml, double* grad,
                    int* info);
+
+/* gpbo_lml_batch for scaled models: n_theta evaluations of gpbo_lml_scaled on the SAME (X, y_norm, alpha), lane i at
+ * (amplitudes[i], length_scales[i * n_ls ...], whites[i]).  lml[i], grad[i * (n_ls + 2) ...] in [log amplitude, log length_scale ...,
+ * log white] and info[i] are what gpbo_lml_scaled gives for lane i's arguments, bit for bit; a lane whose kernel matrix is not
+ * positive definite gives -inf, n_ls + 2 zeros and its pivot index in info[i], the other lanes are unaffected.  Conventions of
+ * gpbo_lml_batch: X = y_norm = NULL re-uses the resident inputs, pending fits are waited for, model slots are untouched, 1 ...
+ * GPBO_LML_BATCH_MAX lanes, the same lane groups and captured graphs — each lane's noise (white + alpha) / amplitude and target
+ * scale 1 / sqrt(amplitude) reach the kernels through the group's pinned staging words, as the length scales do, so a replayed graph
+ * evaluates the call's own values.  Still refused: device groups (gpbo_group_lml_batch takes unit models only). */
+int gpbo_lml_batch_scaled(gpbo_ctx* ctx, int n_theta, const double* X, const double* y_norm, int64_t N, int d, int kernel,
+                          const double* length_scales, int n_ls, const double* amplitudes, const double* whites, double alpha,
+                          int eval_gradient, double* lml, double* grad, int* info);
 
 /* Parity accessors (tests): copy device state back as (N,N) row-major / (N,) float64.  For a slot of gpbo_fit_scaled K, L and
  * alpha are scikit-learn's quantities of the scaled model (c K', sqrt(c) L', alpha' / c of the unit model the device holds). */
