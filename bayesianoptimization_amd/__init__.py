@@ -6,7 +6,7 @@ built library and an AMD GPU.
 """
 __version__ = "0.1.0"
 
-__all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate", "UpperConfidenceBound",
+__all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate", "suggest_batch", "UpperConfidenceBound",
            "ExpectedImprovement", "ProbabilityOfImprovement"]
 
 
@@ -26,6 +26,9 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name == "accelerate":
         from .dropin import accelerate
         return accelerate
+    if name == "suggest_batch":
+        from .batch import suggest_batch
+        return suggest_batch
     if name in ("UpperConfidenceBound", "ExpectedImprovement", "ProbabilityOfImprovement", "AcquisitionFunction"):
         from . import fused_acquisition as acquisition
         return getattr(acquisition, name)

@@ -112,7 +112,7 @@ extern "C" int gpbo_set_candidate_columns(gpbo_ctx* ctx, const double* values, i
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));       // the caller's array is borrowed for the call only
   ctx->M = M;
   ctx->d_c = d_total;
-  for (auto& m : ctx->models) m.M_post = -1;
+  drop_posteriors(ctx);
   return GPBO_OK;
 }
 
@@ -166,7 +166,7 @@ extern "C" int gpbo_transform_candidates(gpbo_ctx* ctx, int n_groups, const int*
   }
   GPBO_HIP(ctx, hipGetLastError());
   ctx->raw_valid = true;
-  for (auto& m : ctx->models) m.M_post = -1;
+  drop_posteriors(ctx);
   return GPBO_OK;
 }
 
@@ -195,7 +195,7 @@ extern "C" int gpbo_generate_candidates(gpbo_ctx* ctx, int64_t M, int d, const d
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->M = M;
   ctx->d_c = d;
-  for (auto& m : ctx->models) m.M_post = -1;
+  drop_posteriors(ctx);
   return GPBO_OK;
 }
 

@@ -645,6 +645,7 @@ extern "C" int gpbo_evolve_mixed(gpbo_ctx* ctx, int acq, double acq_param, doubl
       !success_out)
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: NULL argument");
   if (acq != GPBO_ACQ_UCB && acq != GPBO_ACQ_EI && acq != GPBO_ACQ_POI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: unknown acquisition");
+  drop_refreshable(ctx);      // as gpbo_polish_seeds: nothing resident may be refreshed after a search
   EvolveObjective o;
   o.model = &ctx->models[0];
   o.acq = acq; o.acq_param = acq_param; o.y_max = y_max; o.y_mean = y_mean; o.y_std = y_std;

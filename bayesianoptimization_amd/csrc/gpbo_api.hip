@@ -431,6 +431,7 @@ static int prepare_model(gpbo_ctx* ctx, Model& m, const char* who, bool have_inp
   m.wd_valid = false;      // W is about to change: the int8 digit planes of the old one must not be used
   m.wt_valid = false;      // (K no longer holds the transpose of this slot's W)
   m.M_post = -1;
+  m.refreshable = false;   // (gpbo_posterior_refresh: a new fit has nothing to do with the resident posterior)
   m.amplitude = 1.0;       // a unit model until gpbo_fit_scaled says otherwise
   m.white = 0.0;
   const int64_t NP = round_up(N, NB);
@@ -622,10 +623,15 @@ int gpbo_fit_append(gpbo_ctx* ctx, int slot, const double* x_new, int64_t n_new,
   m.fitted = false;
   m.wp_packed = false;
   m.wt_valid = false;
-  m.M_post = -1;
   const int64_t N0 = m.N;
   const int64_t NP_new = round_up(n_total, NB);
   const bool rebuild = (NP_new != m.NP) || n_new > 16;
+  // gpbo_posterior_refresh: the resident mu / sd stay the posterior of their N_post rows over the current candidates when they
+  // were valid for them coming in (or already stale but refreshable) and this call takes the row path; M_post = -1 either way
+  const bool resident = (m.M_post == ctx->M && ctx->M >= 1) || (m.refreshable && m.M_refresh == ctx->M);
+  const bool refreshable = resident && !rebuild && n_total - m.N_post <= 16 && n_total >= m.N_post;
+  m.M_post = -1;
+  m.refreshable = false;
   ev_begin(ctx, T_FIT);
   if (NP_new > m.cap_NP) {
     // grow the slot (25% head-room so that a maximize() loop reallocates rarely); the scaled inputs survive
@@ -667,7 +673,10 @@ int gpbo_fit_append(gpbo_ctx* ctx, int slot, const double* x_new, int64_t n_new,
     GPBO_HIP(ctx, hipMemcpyAsync(info_h, ctx->info_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = launch_trmv(ctx, m))) return rc;
   }
-  return finish_fit(ctx, m, info_h, info);
+  if ((rc = finish_fit(ctx, m, info_h, info))) return rc;
+  m.refreshable = refreshable;
+  m.M_refresh = refreshable ? ctx->M : -1;
+  return GPBO_OK;
 }
 
 // The part of a log-marginal-likelihood evaluation that follows the factorisation, enqueued on ctx->stream: the scalar
@@ -1146,9 +1155,11 @@ int gpbo_set_candidates(gpbo_ctx* ctx, const double* Xc, int64_t M, int d) {
   }
   ctx->M = M;
   ctx->d_c = d;
-  for (auto& m : ctx->models) m.M_post = -1;
+  drop_posteriors(ctx);
   return GPBO_OK;
 }
+
+static int fetch_posterior(gpbo_ctx* ctx, Model& m, double* mu, double* sd);
 
 int gpbo_posterior(gpbo_ctx* ctx, int slot, double y_mean, double y_std, double* mu, double* sd) {
   int rc = need_fitted(ctx, slot);
@@ -1157,6 +1168,11 @@ int gpbo_posterior(gpbo_ctx* ctx, int slot, double y_mean, double y_std, double*
   if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "posterior: no candidates resident (call gpbo_set_candidates)");
   if (ctx->d_c != m.d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "posterior: candidate dimension differs from the fitted model");
   if ((rc = launch_posterior(ctx, m, ctx->M, y_mean, y_std))) return rc;
+  return fetch_posterior(ctx, m, mu, sd);
+}
+
+// mu / sd of the resident candidates into the caller's arrays (either may be NULL: the results stay on the device)
+static int fetch_posterior(gpbo_ctx* ctx, Model& m, double* mu, double* sd) {
   const size_t bytes = (size_t)ctx->M * sizeof(double);
   if ((mu || sd) && bytes <= SMALL_PIN_OUT) {      // small batch: results land in the pinned block, then in the caller's arrays
     double* hmu = (double*)((char*)ctx->small_pinned + SMALL_PIN_IN);
@@ -1172,6 +1188,26 @@ int gpbo_posterior(gpbo_ctx* ctx, int slot, double y_mean, double y_std, double*
   if (sd) GPBO_HIP(ctx, hipMemcpyAsync(sd, m.sd, bytes, hipMemcpyDeviceToHost, ctx->stream));
   if (mu || sd) GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return GPBO_OK;
+}
+
+int gpbo_posterior_refresh(gpbo_ctx* ctx, int slot, double y_mean, double y_std, double* mu, double* sd, int* route) {
+  if (route) *route = 0;
+  int rc = need_fitted(ctx, slot);
+  if (rc) return rc;
+  Model& m = ctx->models[slot];
+  // route 1: the resident mu / sd are the posterior of the slot's first N_post rows over the CURRENT candidates, and only row
+  // appends have touched the slot since (the flag's keepers: gpbo_fit_append, prepare_model, drop_posteriors / drop_refreshable)
+  const bool incremental = m.refreshable && m.M_refresh == ctx->M && ctx->M >= 1 && ctx->d_c == m.d && m.mu && m.sd &&
+                           ctx->M <= m.cap_M && m.N >= m.N_post && m.N - m.N_post <= 16 && std::isfinite(m.ystd_post) &&
+                           m.ystd_post != 0.0;
+  if (!incremental) return gpbo_posterior(ctx, slot, y_mean, y_std, mu, sd);
+  m.refreshable = false;
+  if ((rc = launch_posterior_refresh(ctx, m, ctx->M, y_mean, y_std))) return rc;
+  m.M_post = ctx->M;
+  m.N_post = m.N;
+  m.ystd_post = y_std;
+  if (route) *route = 1;
+  return fetch_posterior(ctx, m, mu, sd);
 }
 
 int gpbo_predict(gpbo_ctx* ctx, int slot, const double* Xc, int64_t M, int d, double y_mean,

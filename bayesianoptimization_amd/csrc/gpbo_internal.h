@@ -61,6 +61,14 @@ struct Model {
   double* sd = nullptr;
   int64_t cap_M = 0;
   int64_t M_post = -1;     // number of candidates mu/sd are valid for (-1: none)
+  // gpbo_posterior_refresh: what the resident mu / sd reflect, recorded by the pass that wrote them ...
+  int64_t N_post = 0;      // ... this many observations
+  double ystd_post = 1.0;  // ... scaled with this y_std
+  // ... and, once gpbo_fit_append's row path has made them stale (M_post = -1), whether they are still the posterior of the first
+  // N_post rows over the context's current candidate set: "stale but refreshable".  Cleared by everything else that touches the
+  // slot's fit (prepare_model, a rebuild inside append) and by every writer of the candidates (drop_refreshable below).
+  bool refreshable = false;
+  int64_t M_refresh = -1;  // the number of candidates they were valid for when they went stale
 };
 
 // gpbo_lml_batch, per lane group it has run: the problem shape and, from the second run on, the captured launch sequence.  A pool
@@ -417,6 +425,15 @@ __device__ __forceinline__ double gpbo_kernel_slope(double d2, double kv) {
 }
 #endif
 
+// Every writer of the candidate set (and every call that uses the candidate buffers for points of its own) ends the resident
+// posteriors: none is valid (M_post) and none can be refreshed.
+inline void drop_posteriors(gpbo_ctx* ctx) {
+  for (auto& m : ctx->models) { m.M_post = -1; m.refreshable = false; }
+}
+inline void drop_refreshable(gpbo_ctx* ctx) {
+  for (auto& m : ctx->models) m.refreshable = false;
+}
+
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 inline int pad_dim(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : 64; }
 
@@ -564,6 +581,8 @@ int launch_slab_gemm_f64(gpbo_ctx* ctx, Model& m, const double* slab, int64_t ld
 int launch_slab_gemm_f32(gpbo_ctx* ctx, Model& m, const float* slab, int64_t ldk, int64_t m0, int64_t Mp, int part_chunks);   // posterior_kernel_f32.hip
 int launch_slab_gemm_i8(gpbo_ctx* ctx, Model& m, const void* slab, int64_t ldk, int64_t m0, int64_t Mp, int part_chunks);      // posterior_i8.hip
 int prepare_posterior_i8(gpbo_ctx* ctx, Model& m);   // before the first int8 slab: W's digit planes (once per fit), the device's compute units
+// posterior_refresh.hip: the resident mu / sd of m brought from m.N_post to m.N rows (gpbo_posterior_refresh's incremental route)
+int launch_posterior_refresh(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y_std);
 // posterior_cov.hip
 int launch_posterior_cov(gpbo_ctx* ctx, Model& m, int64_t M, double y_std, double** cov_dev, int64_t* ld_cov);
 // posterior_kernel_f32.hip

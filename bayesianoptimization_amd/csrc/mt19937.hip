@@ -315,7 +315,7 @@ static int mt_generate_rows(gpbo_ctx* ctx, int64_t M, int d, int64_t r0, int64_t
   (void)n_blocks;
   ctx->M = Mloc;
   ctx->d_c = d_total;
-  for (auto& m : ctx->models) m.M_post = -1;
+  drop_posteriors(ctx);
   return GPBO_OK;
 }
 

@@ -166,6 +166,7 @@ extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, doubl
   }
   if (!box_ok(box_lo, box_hi, d)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: every bound needs lo < hi");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  drop_refreshable(ctx);      // the call's trial points take the candidates' place: nothing resident may be refreshed afterwards
 
   const int n_models = 1 + n_constraints;
   // pinned block, device-visible: [the round's points (n_seeds, d)] then per model [dmu | dsd | mu | sd] of a round (pitch = the

@@ -143,6 +143,9 @@ int launch_posterior_grad(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, dou
   ev_end(ctx, T_POST_MAIN);
   if (rc) return rc;
   m.M_post = packed ? -1 : M;
+  m.refreshable = false;
+  m.N_post = m.N;
+  m.ystd_post = y_std;
   return GPBO_OK;
 }
 
@@ -184,6 +187,9 @@ int launch_posterior(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y
   ev_end(ctx, T_POST_FINAL);
   GPBO_HIP(ctx, hipGetLastError());
   m.M_post = M;
+  m.refreshable = false;     // gpbo_posterior_refresh: mu / sd now reflect all m.N rows at this y_std
+  m.N_post = m.N;
+  m.ystd_post = y_std;
   return GPBO_OK;
 }
 

@@ -547,6 +547,20 @@ class GpEngine:
         self._check(self._lib.gpbo_posterior(self._h, int(slot), float(y_mean), float(y_std), dptr(mu), dptr(sd)))
         return mu, sd
 
+    def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
+        """`posterior()` after `fit_append()`: where the slot's resident posterior was valid for the current candidates and only
+        row appends (at most 16 rows, no padding crossing) have touched the slot since, it is UPDATED — one k* generation against
+        the appended rows of W, O(M N d) — instead of recomputed (gpbo_posterior_refresh); in every other case this is
+        `posterior()`.  return_route=True: (mu, sd, route), route 1 = the update ran, 0 = the full pass."""
+        self._settle(slot)
+        M = self.n_candidates
+        mu = np.empty(M) if fetch else None
+        sd = np.empty(M) if fetch else None
+        route = C.c_int(0)
+        self._check(self._lib.gpbo_posterior_refresh(self._h, int(slot), float(y_mean), float(y_std), dptr(mu), dptr(sd),
+                                                     C.byref(route)))
+        return (mu, sd, int(route.value)) if return_route else (mu, sd)
+
     def predict(self, Xc, slot=0, y_mean=0.0, y_std=1.0):
         self.set_candidates(Xc)
         return self.posterior(slot, y_mean, y_std, fetch=True)
@@ -1150,6 +1164,10 @@ class GroupEngine(GpEngine):
         sd = np.empty(M) if fetch else None
         self._gcheck(self._lib.gpbo_group_posterior(self._g, int(slot), float(y_mean), float(y_std), dptr(mu), dptr(sd)))
         return (mu[:self.n_candidates], sd[:self.n_candidates]) if fetch else (None, None)
+
+    def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
+        raise NotImplementedError("a device group has no posterior refresh path (gpbo_posterior_refresh is per context); "
+                                  "call posterior() after fit_append()")
 
     def predict(self, Xc, slot=0, y_mean=0.0, y_std=1.0, sharded=None):
         """Small batches (the host optimisers' points) run on the first device; from `world_size * 4096` rows on the

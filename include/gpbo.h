@@ -235,6 +235,28 @@ int gpbo_transform_candidates(gpbo_ctx* ctx, int n_groups, const int* kind, cons
  * mu / sd may be NULL (results stay on the device for gpbo_acq_argbest). */
 int gpbo_posterior(gpbo_ctx* ctx, int slot, double y_mean, double y_std, double* mu, double* sd);
 
+/* gpbo_posterior after gpbo_fit_append, without the pass over W where none is needed (a batch of q suggestions by constant liar,
+ * bayes_opt/acquisition.py:1130-1143, is one full pass and q - 1 of these).  Same outputs and conventions as gpbo_posterior: mu / sd
+ * may be NULL, the results stay resident for gpbo_acq_argbest, the negative-variance flag is set whenever a variance is clipped.
+ * *route (may be NULL) reports what ran: 0 = the full pass, exactly gpbo_posterior; 1 = the incremental update.
+ * Route 1 needs ALL of: the slot's resident mu / sd were valid for the context's CURRENT candidate set when the last gpbo_fit_append
+ * ran, and since then only gpbo_fit_append calls that took the row-append path have touched the slot (0 <= rows added in total <= 16,
+ * the 64-row padding unchanged).  Everything else runs the full pass and reports 0, never a stale or mixed answer: a rebuild inside
+ * append (a padding crossing, n_new > 16), gpbo_fit / gpbo_fit_scaled / gpbo_fit_begin / gpbo_lml* on the slot, any writer of the
+ * candidates (gpbo_set_candidates, gpbo_generate_*, gpbo_set_candidate_columns, gpbo_transform_candidates, gpbo_predict*,
+ * gpbo_polish_seeds, gpbo_evolve_mixed), a packed small-path posterior that left nothing resident.  An unfitted slot is
+ * GPBO_ERR_STATE, as for every reader.  gpbo_fit_append itself still ends the resident posterior: gpbo_acq_argbest after an append
+ * needs a gpbo_posterior or a gpbo_posterior_refresh first.
+ * The update, for the appended rows r = N_post ... N - 1 and v_r(x) = sum_{i <= r} W[r, i] k(x, X_i) (the rows of W = L^-1 above an
+ * appended row do not change, so the unit variance of every candidate drops by exactly v_r(x)^2):
+ *   mu = y_std (sum_i alpha_i k(x, X_i)) + y_mean over all N rows with the new alpha (recomputed, not incremented: the targets'
+ *        normalisation may have changed);
+ *   sd = y_std sqrt(max((sd_old / y_std_old)^2 - amplitude sum_r v_r(x)^2, 0)), amplitude the slot's own (1 for a unit model; white
+ *        is already inside sd_old).  An append with n_new = 0 refreshes mu and rescales sd.
+ * One launch, one k* generation per (candidate, training point) against 1 + n_rows weight vectors: O(M N d) instead of O(M N^2).
+ * fp64 whatever the slot's precision: the refreshed sigma of a GPBO_F32 slot inherits the accuracy of the fp32 pass it started from. */
+int gpbo_posterior_refresh(gpbo_ctx* ctx, int slot, double y_mean, double y_std, double* mu, double* sd, int* route);
+
 /* Convenience: set_candidates + posterior for a host batch (the HipGPR.predict path). */
 int gpbo_predict(gpbo_ctx* ctx, int slot, const double* Xc, int64_t M, int d, double y_mean,
                  double y_std, double* mu, double* sd);
