@@ -7,7 +7,7 @@ built library and an AMD GPU.
 __version__ = "0.1.0"
 
 __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate", "suggest_batch", "UpperConfidenceBound",
-           "ExpectedImprovement", "ProbabilityOfImprovement"]
+           "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement"]
 
 
 def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must not need sklearn/scipy
@@ -29,7 +29,8 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name == "suggest_batch":
         from .batch import suggest_batch
         return suggest_batch
-    if name in ("UpperConfidenceBound", "ExpectedImprovement", "ProbabilityOfImprovement", "AcquisitionFunction"):
+    if name in ("UpperConfidenceBound", "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement",
+                "AcquisitionFunction"):
         from . import fused_acquisition as acquisition
         return getattr(acquisition, name)
     raise AttributeError(name)

@@ -18,7 +18,7 @@ from . import fused_acquisition as A
 from .engine import GroupEngine
 from .gpr import HipGPR
 
-_STOCK = (A.UpperConfidenceBound, A.ExpectedImprovement, A.ProbabilityOfImprovement)
+_STOCK = (A.UpperConfidenceBound, A.ExpectedImprovement, A.ProbabilityOfImprovement, A.LogExpectedImprovement)
 
 
 def _lie(strategy, target) -> float:
@@ -43,7 +43,7 @@ def suggest_batch(optimizer, q: int, strategy="max", n_random: int | None = None
          candidates from the optimizer's RandomState on the device, the full posterior, the arg-best.  That is pick 1, bit for bit.
       2. for p = 2 .. q: the previous pick joins the slot's model with the lie as its target (`fit_append`; the lie is 'max' /
          'min' / 'mean' of the real targets or a float, normalised with the REAL data's mean and std), the resident posterior is
-         refreshed (`posterior_refresh`) and the policy's arg-best is taken again, with y_max = max(real y_max, lie) for EI / POI.
+         refreshed (`posterior_refresh`) and the policy's arg-best is taken again, with y_max = max(real y_max, lie) for EI / POI / log EI.
       3. the policy's per-suggest bookkeeping advances once per pick — iteration counter, exploration decay — so that pick p uses
          the kappa / xi the p-th of q suggest() calls would have used.
       4. before returning, the estimator's incremental cache is dropped and the slot goes back to the fixed-theta fit of the real
@@ -57,7 +57,7 @@ def suggest_batch(optimizer, q: int, strategy="max", n_random: int | None = None
     re-uses the candidate buffer the later picks still need.
 
     NotImplementedError, never a host fallback, for: a space with an input transform (int / categorical parameters), a policy
-    other than stock UCB / EI / POI, a model in host mode (a kernel outside the device path), a device group.  q = 1 is valid;
+    other than stock UCB / EI / POI / log EI, a model in host mode (a kernel outside the device path), a device group.  q = 1 is valid;
     q < 1 is a ValueError."""
     if isinstance(q, bool) or not isinstance(q, (int, np.integer)):
         raise ValueError("q must be an integer >= 1")
@@ -69,7 +69,8 @@ def suggest_batch(optimizer, q: int, strategy="max", n_random: int | None = None
     space = optimizer._space
     if type(fn) not in _STOCK:
         raise NotImplementedError(f"suggest_batch: the policy is {type(fn).__name__}; only stock UpperConfidenceBound / "
-                                  "ExpectedImprovement / ProbabilityOfImprovement of an accelerate()d optimizer are batched")
+                                  "ExpectedImprovement / ProbabilityOfImprovement / LogExpectedImprovement of an accelerate()d "
+                                  "optimizer are batched")
     if not isinstance(gp, HipGPR) or gp.slot != 0:
         raise NotImplementedError("suggest_batch: the optimizer's GP is not on the engine (call accelerate(optimizer) first)")
     if len(space) == 0:

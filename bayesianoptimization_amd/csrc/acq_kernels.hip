@@ -45,7 +45,8 @@ __device__ __forceinline__ double acq_value(const AcqDev& a, const int64_t m) {
     const double aa = mean - a.y_max - a.param;
     const double z = aa / sd;
     if (a.acq == GPBO_ACQ_EI) base = aa * ndtr_dev(z) + sd * norm_pdf_dev(z);
-    else base = ndtr_dev(z);
+    else if (a.acq == GPBO_ACQ_POI) base = ndtr_dev(z);
+    else base = log_ei_dev(aa, sd);      // GPBO_ACQ_LOG_EI (never with constraints: build_acq_args)
   }
   double v = -1.0 * base;
   if (a.n_constraints > 0) {

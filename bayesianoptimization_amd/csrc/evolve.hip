@@ -644,6 +644,7 @@ extern "C" int gpbo_evolve_mixed(gpbo_ctx* ctx, int acq, double acq_param, doubl
   if (!kind || !col0 || !ncols || !bounds_lo || !bounds_hi || !init || !key || !pos || !x_out || !f_out || !nit_out || !nfev_out ||
       !success_out)
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: NULL argument");
+  if (acq == GPBO_ACQ_LOG_EI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: GPBO_ACQ_LOG_EI is not evaluated by the device differential evolution");
   if (acq != GPBO_ACQ_UCB && acq != GPBO_ACQ_EI && acq != GPBO_ACQ_POI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: unknown acquisition");
   drop_refreshable(ctx);      // as gpbo_polish_seeds: nothing resident may be refreshed after a search
   EvolveObjective o;

@@ -35,6 +35,16 @@ namespace {
 
 inline double norm_cdf(double z) { return 0.5 * std::erfc(-z * 0.70710678118654752440); }
 inline double norm_pdf(double z) { return std::exp(-0.5 * z * z) * 0.39894228040143267794; }
+// <cmath> has no erfcx; polish_acq_coeffs asks for it at 0.7 <= t < 19.8 only, where erfc(t) >= 1e-172 and exp(t^2) <= 1e171.
+// exp turns the rounding of t * t into a relative error of t^2 eps / 2, and r = 1 - sqrt(pi) t erfcx(t) ~ 1 / (2 t^2) multiplies it by
+// 2 t^2 once more (measured at the end points of whole searches: c = 7 at z = -7, 40 at z = -17 against a bar of 8): the product's
+// low part e = t * t - s, exact from one fma, goes back in as exp(s + e) = exp(s) (1 + e).
+inline double erfcx_host(double t) {
+  const double s = t * t;
+  const double e = std::fma(t, t, -s);
+  const double v = std::exp(s) * std::erfc(t);
+  return v + v * e;
+}
 
 // All runs in lockstep: `eval(batch, live, f, g)` evaluates the objective and its gradient at the `live` trial points of the
 // round (rows of `batch`, d columns) in one go and returns a status code; the runs that are still alive get their answers
@@ -155,9 +165,11 @@ extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, doubl
   if (n_seeds < 1 || n_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: n_seeds out of range [1, 64]");
   if (!seeds || !box_lo || !box_hi || !x_out || !f_out || !status_out || !y_mean || !y_std)
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: NULL argument");
-  if (acq != GPBO_ACQ_UCB && acq != GPBO_ACQ_EI && acq != GPBO_ACQ_POI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: unknown acquisition");
+  if (acq < GPBO_ACQ_UCB || acq > GPBO_ACQ_LOG_EI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: unknown acquisition");
   if (n_constraints < 0 || n_constraints >= GPBO_MAX_MODELS || (n_constraints > 0 && (!lb || !ub)))
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: bad constraint arguments");
+  if (acq == GPBO_ACQ_LOG_EI && n_constraints > 0)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: GPBO_ACQ_LOG_EI takes no constraints (n_constraints must be 0)");
   max_iter = clamp_max_iter(max_iter);
   for (int j = 0; j <= n_constraints; ++j) {
     if (!ctx->models[j].fitted) GPBO_FAIL(ctx, GPBO_ERR_STATE, "polish_seeds: model slot has not been fitted");
@@ -225,7 +237,7 @@ extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, doubl
       const double* dsd = o0 + (size_t)live * d + (size_t)t * d;
       const double mu = o0[2 * (size_t)live * d + t], sd = o0[2 * (size_t)live * d + live + t];
       double a, ca, cs;      // acq value; d acq = ca * dmu + cs * dsd
-      polish_acq_coeffs(acq, acq_param, y_max, mu, sd, norm_cdf, norm_pdf, a, ca, cs);
+      polish_acq_coeffs(acq, acq_param, y_max, mu, sd, norm_cdf, norm_pdf, erfcx_host, a, ca, cs);
       double f = -a;
       double* g = gv + (size_t)t * d;
       for (int i = 0; i < d; ++i) g[i] = polish_acq_grad(ca, cs, dmu[i], dsd[i]);

@@ -374,7 +374,7 @@ __global__ __launch_bounds__(WLDS ? SEARCH_LDS_NP : SEARCH_MAX_NP) void polish_r
       const double mu = a.y_std * tot1 + a.y_mean;
       double dmu = 0.0, dsd = 0.0, g = 0.0;
       double av, ca, cs;
-      polish_acq_coeffs(a.acq, a.acq_param, a.y_max, mu, sd, DevCdf(), DevPdf(), av, ca, cs);
+      polish_acq_coeffs(a.acq, a.acq_param, a.y_max, mu, sd, DevCdf(), DevPdf(), DevErfcx(), av, ca, cs);
       if (lane < d) {
         const double inv_l = 1.0 / ls_s[lane];
         dmu = a.y_std * sa * inv_l;

@@ -24,6 +24,9 @@
 #pragma once
 #include <cstddef>
 
+#include <cmath>
+
+#include "acq_formulas.h"
 #include "gpbo_internal.h"
 
 namespace gpbo {
@@ -224,12 +227,31 @@ GPBO_HD void polish_advance(PolishRun& r, double ft, const double* gt, const dou
 // f = -acq(mu, sd) and its gradient from the posterior and ITS gradient, unconstrained (acquisition.py:198-217, 485, 660-661,
 // 847-849): g_i = -(ca dmu_i + cs dsd_i).  CDF / PDF are the caller's (std::erfc / std::exp on the host, the device library's on
 // the device: EI and POI values agree to rounding between the two sides, UCB bit for bit).
-template <class Cdf, class Pdf>
-GPBO_HD void polish_acq_coeffs(int acq, double acq_param, double y_max, double mu, double sd, Cdf&& cdf_of, Pdf&& pdf_of, double& a,
-                               double& ca, double& cs) {
+// GPBO_ACQ_LOG_EI (acq_formulas.h: log h = log phi + log r below z = -1): d logEI = (Phi dmu + phi dsd) / (sd h), so above -1
+// ca = Phi / (sd h), cs = phi / (sd h), and below it — divided through by phi — cs = 1 / (sd r), ca = m / (sd r) with Mills' ratio
+// m = Phi / phi = (1 - r) / (-z), which does not cancel there (r <= 0.35).  `erfcx_of` is the caller's scaled complementary error
+// function.  A clipped variance (sd == 0) has the value log(aa) (-inf for aa <= 0) and no slope.
+template <class Cdf, class Pdf, class Erfcx>
+GPBO_HD void polish_acq_coeffs(int acq, double acq_param, double y_max, double mu, double sd, Cdf&& cdf_of, Pdf&& pdf_of,
+                               Erfcx&& erfcx_of, double& a, double& ca, double& cs) {
 #pragma clang fp contract(off)
   if (acq == GPBO_ACQ_UCB) {
     a = mu + acq_param * sd; ca = 1.0; cs = acq_param;
+  } else if (acq == GPBO_ACQ_LOG_EI) {
+    const double aa = mu - y_max - acq_param;
+    const double z = aa / sd;
+    if (sd == 0.0) {
+      a = (aa != aa) ? aa : (aa > 0.0 ? log(aa) : -__builtin_inf());
+      ca = 0.0; cs = 0.0;
+    } else if (z > -1.0) {
+      const double cdf = cdf_of(z), pdf = pdf_of(z);
+      const double h = pdf + z * cdf;
+      a = log(sd) + log(h); ca = cdf / (sd * h); cs = pdf / (sd * h);
+    } else {
+      const double r = log_ei_ratio(z, erfcx_of);
+      a = log(sd) + (-(z * z) / 2.0 - LOG_EI_HALF_LOG_2PI + log(r));
+      cs = 1.0 / (sd * r); ca = ((1.0 - r) / -z) / (sd * r);
+    }
   } else {
     const double aa = mu - y_max - acq_param;
     const double z = aa / sd;

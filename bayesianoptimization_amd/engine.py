@@ -15,7 +15,7 @@ from . import _lib
 from ._lib import dptr, iptr
 
 RBF, MATERN25, MATERN15, MATERN05 = 0, 1, 2, 3
-UCB, EI, POI = 0, 1, 2
+UCB, EI, POI, LOG_EI = 0, 1, 2, 3      # enum gpbo_acq (LOG_EI: never with constraints, never in evolve_mixed)
 F64, F32 = 0, 1
 
 TIMING_NAMES = ("fit", "posterior_main", "posterior_finalize", "acq_argbest", "kmat", "cholesky", "trtri")

@@ -24,7 +24,7 @@ import warnings
 
 import numpy as np
 from scipy.optimize import minimize
-from scipy.special import ndtr
+from scipy.special import erfcx, ndtr
 
 from . import engine as E
 from . import lbfgsb_lockstep
@@ -732,6 +732,83 @@ class ExpectedImprovement(_ImprovementBased):
         return a * cdf + std * pdf, cdf[:, None] * dmean + pdf[:, None] * dstd
 
 
+_LOG_EI_SERIES_BELOW = -28.0         # acq_formulas.h: LOG_EI_SERIES_BELOW
+_LOG_EI_SERIES = (1.0, -3.0, 15.0, -105.0, 945.0, -10395.0, 135135.0, -2027025.0, 34459425.0, -654729075.0)   # (-1)^k (2k + 1)!!
+_HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
+_SQRT_PI = np.sqrt(np.pi)
+
+
+def _log_ei_ratio(z):
+    """r(z) = h(z) / phi(z) = 1 + z Phi(z) / phi(z) for z <= -1, without the cancellation of phi + z Phi (include/gpbo.h)."""
+    z = np.asarray(z, dtype=np.float64)
+    t = -z / np.sqrt(2.0)
+    near = 1.0 - _SQRT_PI * t * erfcx(t)
+    w = 1.0 / (z * z)
+    s = np.full_like(w, _LOG_EI_SERIES[-1])
+    for c in _LOG_EI_SERIES[-2::-1]:
+        s = s * w + c
+    return np.where(z > _LOG_EI_SERIES_BELOW, near, w * s)
+
+
+class LogExpectedImprovement(_ImprovementBased):
+    """log EI(x) = log sigma + log h(z), h = phi + z Phi, a = mu - y_max - xi, z = a / sigma: the ordering of EI wherever EI is
+    representable, finite with a non-zero gradient down to z ~ -1e150 — for the late-run regime in which y_max sits above nearly
+    every posterior mean and EI itself underflows to a plateau of zeros (every random stage then returns candidate 0, every local
+    search stops at its seed).  Not a class of the reference; the formula, its switch points and its conventions are those of
+    GPBO_ACQ_LOG_EI (include/gpbo.h): sigma == 0 gives log(a) for a > 0, else -inf; NaN gives NaN.
+
+    Checked refusals: a constrained space raises ConstraintNotSupportedError (the constrained quantity would be log EI + sum_j
+    log p_j, not a product); the device differential evolution does not evaluate it, so a mixed space runs SciPy's solver over
+    `base_acq`."""
+
+    _acq_kind = E.LOG_EI
+
+    def __init__(self, xi: float = 0.01, exploration_decay=None, exploration_decay_delay=None, random_state=None) -> None:
+        super().__init__(xi=xi, exploration_decay=exploration_decay, exploration_decay_delay=exploration_decay_delay,
+                         random_state=random_state)
+
+    def _parts(self, mean, std):
+        """(a, z, log EI, r or h, below) with r where z <= -1 and h above"""
+        a = np.asarray(mean, dtype=np.float64) - self.y_max - self.xi
+        std = np.asarray(std, dtype=np.float64)
+        z = a / std
+        below = z <= -1.0
+        zb = np.where(below, z, -1.0)
+        za = np.where(below, 0.0, z)
+        r = _log_ei_ratio(zb)
+        h = _norm_pdf(za) + za * ndtr(za)
+        log_h = np.where(below, -(zb * zb) / 2.0 - _HALF_LOG_2PI + np.log(r), np.log(h))
+        at_zero = np.where(np.isnan(a), np.nan, np.where(a > 0, np.log(np.where(a > 0, a, 1.0)), -np.inf))
+        value = np.where(std == 0.0, at_zero, np.log(std) + log_h)
+        return a, z, value, np.where(below, r, h), below
+
+    def base_acq(self, mean, std):
+        self._need_y_max()
+        with np.errstate(all="ignore"):
+            return self._parts(mean, std)[2]
+
+    def base_acq_grad(self, mean, std, dmean, dstd):
+        # d log EI = (Phi da + phi ds) / (sigma h); below z = -1 divided through by phi: (m da + ds) / (sigma r), m = (1 - r) / (-z)
+        self._need_y_max()
+        with np.errstate(all="ignore"):
+            a, z, value, q, below = self._parts(mean, std)
+            std = np.asarray(std, dtype=np.float64)
+            za = np.where(below, 0.0, z)
+            ca = np.where(below, ((1.0 - q) / -np.where(below, z, -1.0)), ndtr(za)) / (std * q)
+            cs = np.where(below, 1.0, _norm_pdf(za)) / (std * q)
+            clipped = std == 0.0
+            ca, cs = np.where(clipped, 0.0, ca), np.where(clipped, 0.0, cs)
+            return value, ca[:, None] * dmean + cs[:, None] * dstd
+
+    def suggest(self, gp, target_space, n_random=None, n_smart: int = 10, fit_gp: bool = True, random_state=None):
+        if target_space.constraint is not None:
+            raise ConstraintNotSupportedError(
+                f"Received constraints, but acquisition function {type(self)} "
+                "does not support constrained optimization.")
+        return super().suggest(gp=gp, target_space=target_space, n_random=n_random, n_smart=n_smart, fit_gp=fit_gp,
+                               random_state=random_state)
+
+
 class GPHedge(AcquisitionFunction):
     """Portfolio of acquisition policies (bayes_opt/acquisition.py:1181-1360; Brochu et al., arXiv:1009.5419): every
     base policy nominates a point, one nominee is drawn with probability softmax(gains), and at the next step the gains
@@ -837,7 +914,7 @@ class GPHedge(AcquisitionFunction):
         chain = _fused_models(gp, target_space.constraint) if self.share_candidates else None
         shared = (chain is not None and all(getattr(b, "_acq_kind", None) is not None for b in self.base_acquisitions)
                   and not (target_space.constraint is not None
-                           and any(isinstance(b, UpperConfidenceBound) for b in self.base_acquisitions)))
+                           and any(isinstance(b, (UpperConfidenceBound, LogExpectedImprovement)) for b in self.base_acquisitions)))
         if shared:
             x_max = self._nominate_shared(chain, gp, target_space, n_random, n_smart, rng)
         else:

@@ -52,7 +52,24 @@ enum gpbo_status {
 /* The stationary kernels every entry point with an `int kernel` takes: RBF and the closed-form members of the Matern family
  * (nu = 2.5, 1.5, 0.5; kernels.py Matern.__call__).  Any other value is GPBO_ERR_UNSUPPORTED. */
 enum gpbo_kernel { GPBO_KERNEL_RBF = 0, GPBO_KERNEL_MATERN25 = 1, GPBO_KERNEL_MATERN15 = 2, GPBO_KERNEL_MATERN05 = 3 };
-enum gpbo_acq { GPBO_ACQ_UCB = 0, GPBO_ACQ_EI = 1, GPBO_ACQ_POI = 2 };
+/* The acquisitions every entry point with an `int acq` takes (acq_param = kappa for UCB, xi for the others).
+ * GPBO_ACQ_LOG_EI is the logarithm of EI, for the late-run regime in which y_max sits above nearly every posterior mean: EI
+ * itself is then decided among values of 1e-20 ... 1e-300 and is a plateau of zeros below z ~ -38.5, while its logarithm orders
+ * the candidates as EI does wherever EI is representable and stays finite, with a non-zero gradient, down to z ~ -1e150.  With
+ * aa = mu - y_max - xi formed left to right in fp64 and z = aa / sd:
+ *   logEI = log(sd) + log h(z),  h(z) = phi(z) + z Phi(z)
+ *     z > -1        log h = log(phi(z) + z Phi(z))
+ *     -28 < z <= -1 log h = -z^2/2 - log(2 pi)/2 + log r,  r = 1 - sqrt(pi) t erfcx(t),  t = -z / sqrt2
+ *     z <= -28      the same with r = w (1 - 3 w + 15 w^2 - ...), w = 1 / z^2: ten terms, coefficients (2k + 1)!!
+ *   gradient of -logEI: -(ca dmu + cs dsd);  z > -1: ca = Phi / (sd h), cs = phi / (sd h);
+ *                                            z <= -1: cs = 1 / (sd r), ca = m / (sd r), m = Phi / phi = (1 - r) / (-z)
+ * Conventions: sd == 0 (a clipped variance) gives log(aa) for aa > 0, else -inf, with a zero slope; NaN mu or sd gives NaN.  The
+ * selection key is the one of the other kinds, ys = -logEI: +inf is an ordinary double that sorts after every finite value, NaN
+ * sorts last and the arg-best is still the first NaN.
+ * Checked refusals (GPBO_ERR_INVALID): GPBO_ACQ_LOG_EI with n_constraints > 0 (gpbo_acq_argbest, its gpbo_comm_* / gpbo_group_*
+ * forms, gpbo_polish_seeds: the constrained quantity would be logEI + sum_j log p_j, not a product, and is not implemented), and
+ * GPBO_ACQ_LOG_EI in gpbo_evolve_mixed (the device differential evolution evaluates UCB / EI / POI only). */
+enum gpbo_acq { GPBO_ACQ_UCB = 0, GPBO_ACQ_EI = 1, GPBO_ACQ_POI = 2, GPBO_ACQ_LOG_EI = 3 };
 enum gpbo_precision { GPBO_F64 = 0, GPBO_F32 = 1 };
 
 #define GPBO_MAX_MODELS 8   /* slot 0 = target GP, slots 1.. = constraint GPs */
