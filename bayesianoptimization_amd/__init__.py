@@ -7,7 +7,7 @@ built library and an AMD GPU.
 __version__ = "0.1.0"
 
 __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate", "suggest_batch", "UpperConfidenceBound",
-           "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement"]
+           "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement", "suggest_thompson"]
 
 
 def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must not need sklearn/scipy
@@ -29,6 +29,9 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name == "suggest_batch":
         from .batch import suggest_batch
         return suggest_batch
+    if name == "suggest_thompson":
+        from .thompson import suggest_thompson
+        return suggest_thompson
     if name in ("UpperConfidenceBound", "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement",
                 "AcquisitionFunction"):
         from . import fused_acquisition as acquisition

@@ -446,8 +446,11 @@ static bool select_v2_enabled() {
 
 // the two selection launches over ctx->ys[0..M): SelState and picks[npass] at the head of ctx->red
 // `acq` (v2 only): the values are made by the block stage itself from the models' mu / sd (and stored to ctx->ys)
-static int enqueue_select(gpbo_ctx* ctx, int64_t M, int npass, bool v2, SelState** st_out, Key** picks_out, const AcqDev* acq = nullptr) {
+// `ys`: the values to select over instead of ctx->ys (a row of gpbo_sample_paths' path values)
+static int enqueue_select(gpbo_ctx* ctx, int64_t M, int npass, bool v2, SelState** st_out, Key** picks_out, const AcqDev* acq = nullptr,
+                          double* ys = nullptr) {
   int rc;
+  if (!ys) ys = ctx->ys;
   const int items = v2 ? (M <= ((int64_t)1 << 18) ? 4 : 16) : SEL_ITEMS;
   const int nblocks = (int)((M + SEL_BLOCK * items - 1) / (SEL_BLOCK * items));
   // scratch layout: SelState | picks[npass] | partial[nblocks][npass] | nan_partial[nblocks]
@@ -468,14 +471,14 @@ static int enqueue_select(gpbo_ctx* ctx, int64_t M, int npass, bool v2, SelState
     const int cap = select_v2_cap();
     const AcqDev none{};
     const dim3 grid((unsigned)nblocks), block(SEL_BLOCK);
-    if (items == 4 && acq) select_block_topk_v2_kernel<4, true><<<grid, block, 0, ctx->stream>>>(ctx->ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
-    else if (items == 4) select_block_topk_v2_kernel<4, false><<<grid, block, 0, ctx->stream>>>(ctx->ys, M, npass, cap, partial, nan_partial, none, st, picks);
-    else if (acq) select_block_topk_v2_kernel<16, true><<<grid, block, 0, ctx->stream>>>(ctx->ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
-    else select_block_topk_v2_kernel<16, false><<<grid, block, 0, ctx->stream>>>(ctx->ys, M, npass, cap, partial, nan_partial, none, st, picks);
+    if (items == 4 && acq) select_block_topk_v2_kernel<4, true><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
+    else if (items == 4) select_block_topk_v2_kernel<4, false><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, none, st, picks);
+    else if (acq) select_block_topk_v2_kernel<16, true><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
+    else select_block_topk_v2_kernel<16, false><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, none, st, picks);
     if (nblocks > 1)
-      select_merge_topk_v2_kernel<<<dim3(1), dim3(SEL_BLOCK), 0, ctx->stream>>>(ctx->ys, partial, nan_partial, nblocks, npass, cap, st, picks);
+      select_merge_topk_v2_kernel<<<dim3(1), dim3(SEL_BLOCK), 0, ctx->stream>>>(ys, partial, nan_partial, nblocks, npass, cap, st, picks);
   } else {
-    select_block_topk_kernel<<<dim3((unsigned)nblocks), dim3(SEL_BLOCK), 0, ctx->stream>>>(ctx->ys, M, npass, partial, nan_partial);
+    select_block_topk_kernel<<<dim3((unsigned)nblocks), dim3(SEL_BLOCK), 0, ctx->stream>>>(ys, M, npass, partial, nan_partial);
     select_merge_topk_kernel<<<dim3(1), dim3(SEL_BLOCK), 0, ctx->stream>>>(partial, nan_partial, nblocks, npass, st, picks);
   }
   GPBO_HIP(ctx, hipGetLastError());
@@ -559,6 +562,35 @@ int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, 
     const bool valid = hpicks[t].i != INT64_MAX;   // fewer than k candidates
     seed_idx[t] = valid ? hpicks[t].i + offset : -1;
     seed_val[t] = hpicks[t].v;
+  }
+  return GPBO_OK;
+}
+
+// gpbo_sample_paths: arg-best of each of n_rows rows of M keys (rows[r * ld ...]) by the selection launches above, one row after the
+// other on the context's stream; the rows' results cross in the selection's pinned window and are read after ONE synchronisation.
+int launch_argbest_rows(gpbo_ctx* ctx, double* rows, int64_t ld, int n_rows, int64_t M, int64_t offset, int64_t* best_idx,
+                        double* best_val) {
+  constexpr size_t REC = sizeof(SelState) + sizeof(Key);
+  static_assert(REC * GPBO_MAX_PATHS <= PIN_AUX_SEL_OUT_BYTES, "the rows' selection results outgrew their window");
+  if (n_rows < 1 || n_rows > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "argbest_rows: row count out of range");
+  char* hp = (char*)ctx->pinned_aux + PIN_AUX_SEL_OUT;
+  for (int r = 0; r < n_rows; ++r) {
+    SelState* st; Key* picks;
+    int rc = enqueue_select(ctx, M, 1, false, &st, &picks, nullptr, rows + (int64_t)r * ld);
+    if (rc) return rc;
+    GPBO_HIP(ctx, hipMemcpyAsync(hp + REC * r, st, REC, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int r = 0; r < n_rows; ++r) {
+    const SelState* hst = (const SelState*)(hp + REC * r);
+    const Key* hpick = (const Key*)(hp + REC * r + sizeof(SelState));
+    if (hst->first_nan != INT64_MAX) {      // numpy argmin/min: the first NaN wins
+      best_idx[r] = hst->first_nan + offset;
+      best_val[r] = std::numeric_limits<double>::quiet_NaN();
+    } else {
+      best_idx[r] = hpick->i + offset;
+      best_val[r] = hpick->v;
+    }
   }
   return GPBO_OK;
 }

@@ -230,7 +230,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1210,6 +1210,35 @@ int gpbo_posterior_refresh(gpbo_ctx* ctx, int slot, double y_mean, double y_std,
   m.ystd_post = y_std;
   if (route) *route = 1;
   return fetch_posterior(ctx, m, mu, sd);
+}
+
+int gpbo_sample_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n_paths, int n_features, const double* omega,
+                      const double* phase, const double* weights, const double* eps, int64_t index_offset, int64_t* best_idx,
+                      double* best_val, double* values_out) {
+  int rc = check_slot(ctx, slot);
+  if (rc) return rc;
+  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sample_paths: n_paths out of range [1, 16]");
+  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sample_paths: n_features out of range [1, 4096]");
+  if (!omega || !phase || !weights || !eps || !best_idx || !best_val) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sample_paths: NULL argument");
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sample_paths: y_std must be finite and positive, y_mean finite");
+  if ((rc = no_pending_fit(ctx, slot, "sample_paths"))) return rc;
+  if ((rc = need_fitted(ctx, slot))) return rc;
+  const Model& m = ctx->models[slot];
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "sample_paths: no candidates resident (call gpbo_set_candidates)");
+  if (ctx->d_c != m.d) GPBO_FAIL(ctx, GPBO_ERR_STATE, "sample_paths: the resident candidates' dimension differs from the fitted model's");
+  const int64_t M = ctx->M;
+  if ((rc = launch_sample_paths(ctx, m, M, y_mean, y_std, n_paths, n_features, omega, phase, weights, eps))) return rc;
+  if ((rc = launch_argbest_rows(ctx, ctx->ys, M, n_paths, M, index_offset, best_idx, best_val))) return rc;
+  for (int s = 0; s < n_paths; ++s) best_val[s] = -best_val[s];      // the key is -f
+  if (values_out) {
+    const int64_t n = (int64_t)n_paths * M;
+    GPBO_HIP(ctx, hipMemcpyAsync(values_out, ctx->ys, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < n; ++i) values_out[i] = -values_out[i];
+  }
+  return GPBO_OK;
 }
 
 int gpbo_predict(gpbo_ctx* ctx, int slot, const double* Xc, int64_t M, int d, double y_mean,

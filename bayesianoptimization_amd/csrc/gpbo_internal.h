@@ -165,8 +165,10 @@ struct gpbo_ctx {
   int64_t cap_mu_part = 0;
   double* kst = nullptr;   // materialised k* slab [NP][slab width] (the posterior's slab paths)
   int64_t cap_kst = 0;
-  double* ys = nullptr;    // [M] negated acquisition values
+  double* ys = nullptr;    // [M] negated acquisition values ([n_paths][M] negated path values during gpbo_sample_paths)
   int64_t cap_ys = 0;
+  double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
+  int64_t cap_paths = 0;
   void* red = nullptr;     // reduction scratch
   int64_t cap_red = 0;
   int* info_dev = nullptr; // potrf info word
@@ -583,6 +585,9 @@ int launch_slab_gemm_i8(gpbo_ctx* ctx, Model& m, const void* slab, int64_t ldk, 
 int prepare_posterior_i8(gpbo_ctx* ctx, Model& m);   // before the first int8 slab: W's digit planes (once per fit), the device's compute units
 // posterior_refresh.hip: the resident mu / sd of m brought from m.N_post to m.N rows (gpbo_posterior_refresh's incremental route)
 int launch_posterior_refresh(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y_std);
+// posterior_paths.hip: the negated values of n_paths posterior function draws over the M resident candidates into ctx->ys [n_paths][M]
+int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int n_paths, int n_features,
+                        const double* omega, const double* phase, const double* weights, const double* eps);
 // posterior_cov.hip
 int launch_posterior_cov(gpbo_ctx* ctx, Model& m, int64_t M, double y_std, double** cov_dev, int64_t* ld_cov);
 // posterior_kernel_f32.hip
@@ -595,6 +600,9 @@ struct AcqArgs {
 };
 int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, int64_t offset,
                        int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val);
+// acq_kernels.hip: the arg-best of each of n_rows rows of M keys (rows + r * ld), the rules of launch_acq_argbest; synchronises
+int launch_argbest_rows(gpbo_ctx* ctx, double* rows, int64_t ld, int n_rows, int64_t M, int64_t offset, int64_t* best_idx,
+                        double* best_val);
 // (value, global index) records of one shard, as they travel between GPUs: record 0 = the arg-best (value NaN: "my
 // first NaN sits at this index"), records 1..k = argsort[:k] (index -1 = padding)
 struct BestRecord { double v; int64_t i; };

@@ -137,6 +137,8 @@ class GpEngine:
         info = C.c_int(0)
         self._settle(slot)
         self._touch(slot)
+        self._n_obs = getattr(self, "_n_obs", {})
+        self._n_obs[int(slot)] = (int(X.shape[0]), int(X.shape[1]))      # sample_paths checks the shapes of its draws against it
         if scaled:
             # gpbo_fit_begin has no scaled twin: inside overlapped_fits() a scaled fit runs here and now, on the context's own stream
             # (its slot is settled above; the fits pending on OTHER slots keep running on their streams and are waited for as usual)
@@ -232,6 +234,8 @@ class GpEngine:
         rc = self._lib.gpbo_fit_append(self._h, int(slot), dptr(x_new) if x_new.shape[0] else None, x_new.shape[0],
                                        x_new.shape[1], dptr(y_norm), y_norm.shape[0], C.byref(info))
         self._check(rc, info.value)
+        self._n_obs = getattr(self, "_n_obs", {})
+        self._n_obs[int(slot)] = (int(y_norm.shape[0]), int(x_new.shape[1]))
         return self._touch(slot)
 
     def lml_batch(self, X, y_norm, kernel: int, length_scales, noise: float, eval_gradient=True, reuse_inputs=False):
@@ -373,6 +377,7 @@ class GpEngine:
         ls = np.ascontiguousarray(np.atleast_1d(np.asarray(length_scale, dtype=np.float64)))
         val = C.c_double(0.0)
         self._scaled.pop(int(slot), None)
+        getattr(self, "_n_obs", {}).pop(int(slot), None)      # the slot is left unfitted
         if scaled or (scaled is None and _is_scaled(amplitude, white)):
             grad = np.zeros(ls.shape[0] + 2)
             info = C.c_int(0)
@@ -560,6 +565,37 @@ class GpEngine:
         self._check(self._lib.gpbo_posterior_refresh(self._h, int(slot), float(y_mean), float(y_std), dptr(mu), dptr(sd),
                                                      C.byref(route)))
         return (mu, sd, int(route.value)) if return_route else (mu, sd)
+
+    def sample_paths(self, omega, phase, weights, eps, slot=0, y_mean=0.0, y_std=1.0, index_offset=0, return_values=False):
+        """S = weights.shape[0] <= 16 function draws from the slot's posterior over the resident candidates and each draw's
+        maximiser (gpbo_sample_paths: Matheron's rule over F random Fourier features; include/gpbo.h has the formulas).
+        omega (F, d): frequencies in turns per unit of the length-scaled input; phase (F,): turns; weights (S, F); eps (S, N): the
+        noise draws in normalised-target units.  Returns (best_idx (S,) int64, best_val (S,), values (S, M) or None).  A reader:
+        the slot's fit, its resident posterior and the candidates stay as they were."""
+        self._settle(slot)
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        phase = np.ascontiguousarray(phase, dtype=np.float64).ravel()
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        eps = np.ascontiguousarray(eps, dtype=np.float64)
+        if omega.ndim != 2 or weights.ndim != 2 or eps.ndim != 2:
+            raise ValueError("sample_paths: omega (F, d), weights (S, F) and eps (S, N) must be 2-D")
+        F, S = omega.shape[0], weights.shape[0]
+        if phase.shape[0] != F or weights.shape[1] != F or eps.shape[0] != S:
+            raise ValueError("sample_paths: phase (F,), weights (S, F) and eps (S, N) do not fit omega (F, d)")
+        shape = getattr(self, "_n_obs", {}).get(int(slot))
+        if shape is None:
+            raise _lib.GpboError("sample_paths: model slot has not been fitted")
+        if (eps.shape[1], omega.shape[1]) != shape:
+            raise ValueError(f"sample_paths: eps (S, {eps.shape[1]}) / omega (F, {omega.shape[1]}) do not fit the slot's model of "
+                             f"{shape[0]} observations in {shape[1]} dimensions")
+        M = max(int(self.n_candidates), 0)
+        best_idx = np.empty(max(S, 1), dtype=np.int64)
+        best_val = np.empty(max(S, 1))
+        values = np.empty((S, M)) if return_values and S >= 1 and M >= 1 else None
+        self._check(self._lib.gpbo_sample_paths(self._h, int(slot), float(y_mean), float(y_std), int(S), int(F), dptr(omega),
+                                                dptr(phase), dptr(weights), dptr(eps), int(index_offset), iptr(best_idx),
+                                                dptr(best_val), dptr(values)))
+        return best_idx[:S], best_val[:S], values
 
     def predict(self, Xc, slot=0, y_mean=0.0, y_std=1.0):
         self.set_candidates(Xc)
@@ -1164,6 +1200,9 @@ class GroupEngine(GpEngine):
         sd = np.empty(M) if fetch else None
         self._gcheck(self._lib.gpbo_group_posterior(self._g, int(slot), float(y_mean), float(y_std), dptr(mu), dptr(sd)))
         return (mu[:self.n_candidates], sd[:self.n_candidates]) if fetch else (None, None)
+
+    def sample_paths(self, omega, phase, weights, eps, slot=0, y_mean=0.0, y_std=1.0, index_offset=0, return_values=False):
+        raise NotImplementedError("a device group has no path sampler (gpbo_sample_paths is per context); use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
         raise NotImplementedError("a device group has no posterior refresh path (gpbo_posterior_refresh is per context); "

@@ -1,0 +1,127 @@
+"""suggest_thompson(optimizer, q) — q points to probe in parallel by Thompson sampling: q function draws from the GP posterior over
+ONE candidate set, each draw's maximiser a pick.
+
+The other standard way to a batch besides a constant liar (batch.py): no lie, no incumbent, no acquisition formula — the posterior's
+own spread keeps the picks apart.  scikit-learn's route to a posterior draw is GaussianProcessRegressor.sample_y (_gpr.py):
+predict(return_cov=True), an M x M covariance and its factorisation on the host, which ends at a few thousand candidates.  Here a
+draw is conditioned pathwise (Matheron's rule; Wilson et al. 2020, "Efficiently sampling functions from Gaussian process
+posteriors"): a random-Fourier-feature draw from the prior plus an exact data-dependent update, evaluated by the engine's
+`sample_paths` (gpbo_sample_paths) at O((N + F) d) per candidate for 16 draws at once.  Only the prior part is approximate, through
+the F features; include/gpbo.h has the formulas.
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+
+from . import fused_acquisition as A
+from .engine import GroupEngine
+from .gpr import HipGPR
+
+#: the kernel kinds of include/gpbo.h -> Matern nu (RBF: the Gaussian spectrum)
+_NU = {1: 2.5, 2: 1.5, 3: 0.5}
+MAX_PATHS = 16                  # GPBO_MAX_PATHS: draws one sample_paths call evaluates side by side
+MAX_FEATURES = 4096             # GPBO_MAX_PATH_FEATURES
+
+
+def spectral_draw(kind: int, n_features: int, d: int, random_state):
+    """(omega (F, d), phase (F,)) of F random Fourier features of a unit-length-scale kernel of `kind` (0 RBF, 1 / 2 / 3 Matern
+    nu = 2.5 / 1.5 / 0.5) in d dimensions, in the units gpbo_sample_paths takes: omega in TURNS per unit of the length-scaled input
+    (the angular frequency / 2 pi), phase in turns, so that  2 / F  sum_j cos(2 pi (omega_j . a + phase_j)) cos(2 pi (omega_j . b +
+    phase_j))  estimates k(a, b) for length-scaled a, b.
+
+    Angular frequencies from the kernel's spectral density: RBF w = z, z ~ N(0, I); Matern nu: w = z / sqrt(u / (2 nu)), u ~
+    chi^2(2 nu), one u per feature (a multivariate t with 2 nu degrees of freedom; nu = 0.5 is Cauchy-tailed).
+
+    The draws from `random_state` (a numpy RandomState), in this fixed order:
+        standard_normal((F, d));  chisquare(2 nu, F) — Matern only;  uniform(size=F)."""
+    kind, F, d = int(kind), int(n_features), int(d)
+    if kind != 0 and kind not in _NU:
+        raise ValueError(f"spectral_draw: unknown kernel kind {kind}")
+    if F < 1 or d < 1:
+        raise ValueError("spectral_draw: n_features and d must be >= 1")
+    w = random_state.standard_normal((F, d))
+    if kind != 0:
+        nu2 = 2.0 * _NU[kind]
+        u = random_state.chisquare(nu2, F)
+        w = w / np.sqrt(u / nu2)[:, None]
+    phase = random_state.uniform(size=F)
+    return np.ascontiguousarray(w / (2.0 * np.pi)), phase
+
+
+def suggest_thompson(optimizer, q: int, n_random: int = 10_000, n_features: int = 1024):
+    """q parameter dicts to probe side by side, as `suggest_batch` returns them; `optimizer` has been `accelerate()`d.
+
+      1. the checks of `suggest_batch`, with its exception types (below).  The acquisition policy is neither consulted nor advanced.
+      2. `gp.fit` on the real data, theta search (and its RandomState draws) included.
+      3. ONE candidate draw of `n_random` points from the optimizer's RandomState, on the device.
+      4. ceil(q / 16) `sample_paths` calls of up to 16 draws.  Each call draws from the optimizer's RandomState, in this order:
+         `spectral_draw` (fresh features per call), `standard_normal((S, F))` — the feature weights — and `standard_normal((S, N))`
+         scaled by sqrt(noise) — the noise draws, noise = the estimator's alpha (+ the WhiteKernel's level for a scaled model).
+      5. the picked rows are fetched from the device.
+    No posterior pass and no local search: the picks are the draws' maximisers AMONG THE CANDIDATES.  Two draws may pick the same
+    candidate (a sharply peaked posterior: every draw agrees); that is kept — the caller sees how decided the model is.
+    `n_features` = 1024: at 256 the variance of the draws is already off by 25 % for Matern nu = 1.5 / 2.5 (tests/test_thompson_host.py).
+    Afterwards `gp.predict` answers for the real data as before; the slot holds the fit of step 2.
+
+    ValueError: q not an integer >= 1, n_random < 1, n_features outside [1, 4096].  TargetSpaceEmptyError on an empty space,
+    ConstraintNotSupportedError with a constraint.  NotImplementedError, never a host fallback, for: a GP that is not on the engine's
+    slot 0, a space with an input transform (int / categorical parameters), a model in host mode, a device group."""
+    if isinstance(q, bool) or not isinstance(q, (int, np.integer)):
+        raise ValueError("q must be an integer >= 1")
+    q = int(q)
+    if q < 1:
+        raise ValueError("q must be >= 1")
+    n_random, n_features = int(n_random), int(n_features)
+    if n_random < 1:
+        raise ValueError("n_random must be >= 1")
+    if not 1 <= n_features <= MAX_FEATURES:
+        raise ValueError(f"n_features must be in [1, {MAX_FEATURES}]")
+    gp = optimizer._gp
+    space = optimizer._space
+    if not isinstance(gp, HipGPR) or gp.slot != 0:
+        raise NotImplementedError("suggest_thompson: the optimizer's GP is not on the engine (call accelerate(optimizer) first)")
+    if len(space) == 0:
+        raise A.TargetSpaceEmptyError("Cannot suggest a point without previous samples. Use "
+                                      " target_space.random_sample() to generate a point and "
+                                      " target_space.probe(*) to evaluate it.")
+    if space.constraint is not None:
+        raise A.ConstraintNotSupportedError("Received constraints, but suggest_thompson does not support constrained optimization.")
+    if gp.transform is not None:
+        raise NotImplementedError("suggest_thompson: the space has an input transform (int / categorical parameters); "
+                                  "only all-float spaces are sampled")
+    eng = gp._engine()
+    if isinstance(eng, GroupEngine):
+        raise NotImplementedError("suggest_thompson: a device group has no path sampler; use a single device")
+    if not hasattr(eng, "sample_paths"):
+        raise NotImplementedError("suggest_thompson: the engine has no sample_paths")
+    from sklearn.base import clone
+
+    reason = None if gp.kernel is None else gp._unsupported_reason(clone(gp.kernel), space.target, space.params)
+    if reason is not None:
+        raise NotImplementedError(f"suggest_thompson: the model runs on the host ({reason}); only models on the device path are sampled")
+    rng = optimizer._random_state
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        gp.fit(space.params, space.target)
+    if gp._host_mode:      # (unreachable after the check above; a host model must not get this far silently)
+        raise NotImplementedError("suggest_thompson: the model was fitted on the host")
+    d = int(space.bounds.shape[0])
+    N = int(gp.X_train_.shape[0])
+    y_mean, y_std = float(gp._y_train_mean), float(gp._y_train_std)
+    scale = gp.__dict__.get("_scale")
+    noise = float(gp.alpha) + (0.0 if scale is None else float(scale[1]))
+    eng.generate_candidates_like(n_random, space.bounds[:, 0], space.bounds[:, 1], rng)
+    picks = []
+    for first in range(0, q, MAX_PATHS):
+        S = min(MAX_PATHS, q - first)
+        omega, phase = spectral_draw(gp._kind, n_features, d, rng)
+        weights = rng.standard_normal((S, n_features))
+        eps = rng.standard_normal((S, N)) * np.sqrt(noise)
+        gp._ensure_resident()
+        best, _val, _values = eng.sample_paths(omega, phase, weights, eps, slot=gp.slot, y_mean=y_mean, y_std=y_std)
+        picks.extend(int(i) for i in best)
+    rows = np.asarray(eng.get_candidate_rows(np.array(picks, dtype=np.int64), d), dtype=np.float64)
+    return [space.array_to_params(x) for x in rows]

@@ -274,6 +274,33 @@ int gpbo_posterior(gpbo_ctx* ctx, int slot, double y_mean, double y_std, double*
  * fp64 whatever the slot's precision: the refreshed sigma of a GPBO_F32 slot inherits the accuracy of the fp32 pass it started from. */
 int gpbo_posterior_refresh(gpbo_ctx* ctx, int slot, double y_mean, double y_std, double* mu, double* sd, int* route);
 
+/* n_paths function draws from the slot's posterior over the resident candidates, and each draw's maximiser: Thompson sampling.
+ * Replaces GaussianProcessRegressor.sample_y (_gpr.py: predict(return_cov=True), then an M x M factorisation on the host), which
+ * gpbo_predict_cov bounds at M <= 16384.  A draw is conditioned pathwise (Matheron's rule; Wilson et al. 2020, "Efficiently sampling
+ * functions from Gaussian process posteriors"): a random-Fourier-feature draw g_s from the prior plus a data-dependent update that
+ * is exact.  With c = the slot's amplitude (1 for a unit model), xs = x / length_scale as the slot scales it, fs = sqrt(2 c / F):
+ *   phi_j(x) = cos(2 pi (omega_j . xs + phase_j))         omega (F, d) in turns per unit of the LENGTH-SCALED input, phase (F,) in turns
+ *   g_s(x)   = fs sum_j weights[s, j] phi_j(x)            weights (S, F)
+ *   u_s      = g_s(X) + eps_s                             eps (S, N) in normalised-target units
+ *   v_s      = alpha - W^T (W u_s)                        the device's unit-model alpha and W: (K + eta I)^-1 (y_n - u_s)
+ *   f_s(x)   = y_std (g_s(x) + sum_i k(xs, Xs_i) v_s,i) + y_mean      the LATENT function: a scaled slot's white part is not added
+ * best_idx[s] / best_val[s]: the first index of the maximum of f_s over the resident candidates (+ index_offset) and its value — the
+ * rules of gpbo_acq_argbest on the key -f_s: ties -> lowest index, the first NaN wins.  values_out (S, M) path-major, or NULL.
+ * The caller draws omega from the kernel's spectral density (frequencies / 2 pi), phase ~ U[0, 1), weights ~ N(0, 1) and
+ * eps ~ N(0, white + alpha).  Arguments in turns keep the reduction r = t - rint(t) exact whatever the frequency (a Matern nu = 0.5
+ * spectrum is Cauchy-tailed).  fp64 whatever the slot's precision; every sum has a fixed order, and path s's values are the same
+ * bits whether it is evaluated alone or among 16.  Per candidate O((N + F) d) for all paths together.
+ * A reader: the slot's fit, its resident mu / sd, what gpbo_posterior_refresh may still refresh, the candidates and the
+ * negative-variance flag stay as they were (the context's acquisition values, gpbo_acq_argbest's ys, are overwritten).
+ * GPBO_ERR_INVALID: n_paths outside [1, GPBO_MAX_PATHS], n_features outside [1, GPBO_MAX_PATH_FEATURES], a NULL input, y_std not
+ * finite or not positive.  GPBO_ERR_STATE: an unfitted slot, a fit pending on the slot, no resident candidates, candidates of
+ * another d.  There is no gpbo_group_* / gpbo_comm_* form. */
+#define GPBO_MAX_PATHS 16
+#define GPBO_MAX_PATH_FEATURES 4096
+int gpbo_sample_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n_paths, int n_features,
+                      const double* omega, const double* phase, const double* weights, const double* eps,
+                      int64_t index_offset, int64_t* best_idx, double* best_val, double* values_out);
+
 /* Convenience: set_candidates + posterior for a host batch (the HipGPR.predict path). */
 int gpbo_predict(gpbo_ctx* ctx, int slot, const double* Xc, int64_t M, int d, double y_mean,
                  double y_std, double* mu, double* sd);
