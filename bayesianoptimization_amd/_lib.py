@@ -21,7 +21,8 @@ MAX_DIM = 64
 MAX_SEEDS = 64
 MAX_PATHS = 16
 MAX_PATH_FEATURES = 4096
-ABI_VERSION = 2
+MAX_PATH_STARTS = 8
+ABI_VERSION = 3
 
 _c_double_p = C.POINTER(C.c_double)
 _c_int64_p = C.POINTER(C.c_int64)
@@ -75,6 +76,9 @@ SIGNATURES = {
     "gpbo_posterior_refresh": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, _c_double_p, _c_double_p, C.POINTER(C.c_int)]),
     "gpbo_sample_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p, C.c_int64, _c_int64_p, _c_double_p, _c_double_p]),
+    "gpbo_ascend_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _c_double_p, _c_double_p,
+                                    _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int64,
+                                    _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int_p, _c_int_p, _c_int64_p]),
     "gpbo_predict": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int64, C.c_int, C.c_double, C.c_double,
                                _c_double_p, _c_double_p]),
     "gpbo_take_negative_variance_flag": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),

@@ -595,6 +595,37 @@ int launch_argbest_rows(gpbo_ctx* ctx, double* rows, int64_t ld, int n_rows, int
   return GPBO_OK;
 }
 
+// gpbo_ascend_paths: launch_argbest_rows with k picks per row (the k-pass selection: its first pick is the one-pass pick, same
+// launches, same keys).  The rows' records come back through a host buffer of the call's own — 16 rows of 8 picks are more than the
+// selection's pinned window holds — after ONE synchronisation.
+int launch_topk_rows(gpbo_ctx* ctx, double* rows, int64_t ld, int n_rows, int64_t M, int k, int64_t offset, int64_t* best_idx,
+                     double* best_val, int64_t* top_idx) {
+  if (n_rows < 1 || n_rows > GPBO_MAX_PATHS || k < 1 || k > GPBO_MAX_PATH_STARTS || k > M)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "topk_rows: row or pick count out of range");
+  const size_t rec = sizeof(SelState) + sizeof(Key) * (size_t)k;
+  std::vector<char> host(rec * (size_t)n_rows);
+  for (int r = 0; r < n_rows; ++r) {
+    SelState* st; Key* picks;
+    int rc = enqueue_select(ctx, M, k, false, &st, &picks, nullptr, rows + (int64_t)r * ld);
+    if (rc) return rc;
+    GPBO_HIP(ctx, hipMemcpyAsync(host.data() + rec * r, st, rec, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int r = 0; r < n_rows; ++r) {
+    const SelState* hst = (const SelState*)(host.data() + rec * r);
+    const Key* hpick = (const Key*)(host.data() + rec * r + sizeof(SelState));
+    if (hst->first_nan != INT64_MAX) {      // numpy argmin/min: the first NaN wins
+      best_idx[r] = hst->first_nan + offset;
+      best_val[r] = std::numeric_limits<double>::quiet_NaN();
+    } else {
+      best_idx[r] = hpick->i + offset;
+      best_val[r] = hpick->v;
+    }
+    for (int t = 0; t < k; ++t) top_idx[(size_t)r * k + t] = hpick[t].i != INT64_MAX ? hpick[t].i : -1;
+  }
+  return GPBO_OK;
+}
+
 // SelState + picks -> the 1 + k records a shard contributes to the exchange (global indices), still on the device
 __global__ void pack_records_kernel(const SelState* __restrict__ st, const Key* __restrict__ picks, int k_seeds,
                                     int64_t offset, BestRecord* __restrict__ out) {

@@ -1241,6 +1241,51 @@ int gpbo_sample_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int 
   return GPBO_OK;
 }
 
+int gpbo_ascend_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n_paths, int n_features, const double* omega,
+                      const double* phase, const double* weights, const double* eps, int n_starts, const double* starts,
+                      const double* box_lo, const double* box_hi, int max_iter, int64_t index_offset, int64_t* best_idx,
+                      double* best_val, double* x_out, double* f_out, double* g_out, int* status_out, int* n_eval_out,
+                      int64_t* start_idx_out) {
+  int rc = check_slot(ctx, slot);
+  if (rc) return rc;
+  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: n_paths out of range [1, 16]");
+  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: n_features out of range [1, 4096]");
+  if (n_starts < 1 || n_starts > GPBO_MAX_PATH_STARTS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: n_starts out of range [1, 8]");
+  if (!omega || !phase || !weights || !eps || !box_lo || !box_hi || !x_out || !f_out || !status_out || !start_idx_out)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: NULL argument");
+  if (!starts && (!best_idx || !best_val)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: NULL argument (best_idx / best_val without starts)");
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: y_std must be finite and positive, y_mean finite");
+  if ((rc = no_pending_fit(ctx, slot, "ascend_paths"))) return rc;
+  if ((rc = need_fitted(ctx, slot))) return rc;
+  const Model& m = ctx->models[slot];
+  for (int t = 0; t < m.d; ++t)
+    if (!std::isfinite(box_lo[t]) || !std::isfinite(box_hi[t]) || !(box_lo[t] < box_hi[t]))
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: the box must be finite with box_lo < box_hi in every coordinate");
+  if (max_iter < 0) max_iter = 15000;
+  const int R = n_paths * n_starts;
+  const int64_t extra = path_ascent_doubles(R, m.d);
+  PathWorkspace ws{};
+  std::vector<int64_t> top;
+  if (!starts) {
+    if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ascend_paths: no candidates resident (call gpbo_set_candidates, or pass starts)");
+    if (ctx->d_c != m.d) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ascend_paths: the resident candidates' dimension differs from the fitted model's");
+    const int64_t M = ctx->M;
+    if (n_starts > M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: n_starts exceeds the number of resident candidates");
+    if ((rc = launch_sample_paths(ctx, m, M, y_mean, y_std, n_paths, n_features, omega, phase, weights, eps, extra, &ws))) return rc;
+    top.resize((size_t)R);
+    if ((rc = launch_topk_rows(ctx, ctx->ys, M, n_paths, M, n_starts, index_offset, best_idx, best_val, top.data()))) return rc;
+    for (int s = 0; s < n_paths; ++s) best_val[s] = -best_val[s];      // the key is -f
+    for (int r = 0; r < R; ++r) start_idx_out[r] = top[r] >= 0 ? top[r] + index_offset : -1;
+  } else {
+    if ((rc = launch_path_weights(ctx, m, n_paths, n_features, omega, phase, weights, eps, extra, &ws))) return rc;
+    for (int r = 0; r < R; ++r) start_idx_out[r] = -1;
+  }
+  return launch_path_ascent(ctx, m, ws, n_paths, n_starts, n_features, y_mean, y_std, starts, starts ? nullptr : top.data(), box_lo,
+                            box_hi, max_iter, x_out, f_out, g_out, status_out, n_eval_out);
+}
+
 int gpbo_predict(gpbo_ctx* ctx, int slot, const double* Xc, int64_t M, int d, double y_mean,
                  double y_std, double* mu, double* sd) {
   int rc = gpbo_set_candidates(ctx, Xc, M, d);

@@ -1,7 +1,7 @@
 // The optimiser of gpbo_polish_seeds: the host's walk of it (polish.hip: the runs advance in lockstep, a batched device
 // evaluation per round) and everything the device's walk shares with it — constants, min / max, the acquisition's value and
 // gradient coefficients.  polish_fused.hip (one workgroup per run, evaluations and optimiser in one launch) restates the same
-// algorithm with lane i of a wave owning variable i (pr_advance there follows polish_new_direction / polish_advance here
+// algorithm with lane i of a wave owning variable i (pr_advance, polish_lane_opt.h, follows polish_new_direction / polish_advance here
 // decision by decision); since round 6 its sums over the variables are wave reductions, not this file's left-to-right chains, so
 // the two walks agree to rounding, not to the bit: tests/test_gpu_polish_fused.py holds whole searches to "the same optimum or a
 // better one" and single evaluations to their error bar.

@@ -192,15 +192,23 @@ static int launch_path_eval(gpbo_ctx* ctx, const Model& m, const PathEvalArgs& a
   return launch_path_eval_ns<GPBO_MAX_PATHS>(ctx, m, a);
 }
 
-// The S paths of gpbo_sample_paths over the M resident candidates: the negated values land in ctx->ys as S rows of M (the
-// selection's keys), nothing of the slot or the candidates is written.  The caller has checked every argument.
-int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int S, int F, const double* omega,
-                        const double* phase, const double* weights, const double* eps) {
+static PathEvalArgs path_eval_args(const Model& m, const PathWorkspace& ws, int S, int F) {
+  PathEvalArgs a{};
+  a.Xs = m.Xs; a.V = ws.V; a.omega = ws.omega; a.phase = ws.phase; a.weights = ws.weights;
+  a.NP = (int)m.NP; a.F = F; a.d = m.d; a.S = S;
+  a.fs = sqrt(2.0 * m.amplitude / (double)F);
+  return a;
+}
+
+// The draws' inputs made resident and V = alpha - W^T (W (g(X) + eps)) of the S paths: everything a path's value (path_eval_kernel)
+// or its ascent (path_ascent.hip) reads, in the context's paths workspace, with `extra` doubles behind it for the caller (ws->extra).
+int launch_path_weights(gpbo_ctx* ctx, const Model& m, int S, int F, const double* omega, const double* phase, const double* weights,
+                        const double* eps, int64_t extra, PathWorkspace* ws) {
   const int N = (int)m.N, NP = (int)m.NP, d = m.d;
   int rc;
-  // workspace: omega (F, d) | phase (F) | weights (S, F) | eps (S, N) | G [S][NP] | T [S][NP] | V [S][NP]
+  // workspace: omega (F, d) | phase (F) | weights (S, F) | eps (S, N) | G [S][NP] | T [S][NP] | V [S][NP] | extra
   const int64_t n_omega = (int64_t)F * d, n_w = (int64_t)S * F, n_eps = (int64_t)S * N, n_sq = (int64_t)S * NP;
-  if ((rc = ensure(ctx, &ctx->paths, &ctx->cap_paths, n_omega + F + n_w + n_eps + 3 * n_sq))) return rc;
+  if ((rc = ensure(ctx, &ctx->paths, &ctx->cap_paths, n_omega + F + n_w + n_eps + 3 * n_sq + extra))) return rc;
   double* om_d = ctx->paths;
   double* ph_d = om_d + n_omega;
   double* w_d = ph_d + F;
@@ -212,23 +220,34 @@ int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean,
   GPBO_HIP(ctx, hipMemcpyAsync(ph_d, phase, (size_t)F * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   GPBO_HIP(ctx, hipMemcpyAsync(w_d, weights, (size_t)n_w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   GPBO_HIP(ctx, hipMemcpyAsync(eps_d, eps, (size_t)n_eps * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const int64_t Mp = round_up(M, POST_CANDS);
-  if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * m.DP))) return rc;
-  if ((rc = launch_prescale(ctx, ctx->Xc, M, m.d, m.DP, m.ls, ctx->Xcs, Mp))) return rc;
-  if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, (int64_t)S * M))) return rc;
-  PathEvalArgs a{};
-  a.Xs = m.Xs; a.V = V; a.omega = om_d; a.phase = ph_d; a.weights = w_d;
-  a.NP = NP; a.F = F; a.d = d; a.S = S;
-  a.fs = sqrt(2.0 * m.amplitude / (double)F);
+  ws->omega = om_d; ws->phase = ph_d; ws->weights = w_d; ws->V = V; ws->extra = V + n_sq;
   // g_s(X): the prior draws at the train points, by the kernel the candidates get
+  PathEvalArgs a = path_eval_args(m, *ws, S, F);
   a.P = m.Xs; a.out = G; a.M = N; a.ld = NP; a.N = 0; a.negate = 0; a.y_mean = 0.0; a.y_std = 1.0;
   if ((rc = launch_path_eval(ctx, m, a))) return rc;
   path_t_kernel<<<dim3((unsigned)((NP + 3) / 4), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, G, eps_d, T, N, NP);
   GPBO_HIP(ctx, hipGetLastError());
   path_v_kernel<<<dim3((unsigned)(NP / 64), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, T, m.alpha, V, N, NP);
   GPBO_HIP(ctx, hipGetLastError());
+  return GPBO_OK;
+}
+
+// The S paths of gpbo_sample_paths over the M resident candidates: the negated values land in ctx->ys as S rows of M (the
+// selection's keys), nothing of the slot or the candidates is written.  The caller has checked every argument.  extra / ws: as
+// launch_path_weights (gpbo_ascend_paths goes on from the same workspace).
+int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int S, int F, const double* omega,
+                        const double* phase, const double* weights, const double* eps, int64_t extra, PathWorkspace* ws_out) {
+  int rc;
+  PathWorkspace ws{};
+  if ((rc = launch_path_weights(ctx, m, S, F, omega, phase, weights, eps, extra, &ws))) return rc;
+  if (ws_out) *ws_out = ws;
+  const int64_t Mp = round_up(M, POST_CANDS);
+  if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * m.DP))) return rc;
+  if ((rc = launch_prescale(ctx, ctx->Xc, M, m.d, m.DP, m.ls, ctx->Xcs, Mp))) return rc;
+  if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, (int64_t)S * M))) return rc;
   // the paths over the candidates
-  a.P = ctx->Xcs; a.out = ctx->ys; a.M = M; a.ld = M; a.N = N; a.negate = 1; a.y_mean = y_mean; a.y_std = y_std;
+  PathEvalArgs a = path_eval_args(m, ws, S, F);
+  a.P = ctx->Xcs; a.out = ctx->ys; a.M = M; a.ld = M; a.N = (int)m.N; a.negate = 1; a.y_mean = y_mean; a.y_std = y_std;
   return launch_path_eval(ctx, m, a);
 }
 

@@ -54,6 +54,19 @@ def _is_scaled(amplitude, white) -> bool:
     return float(amplitude) != 1.0 or float(white) != 0.0
 
 
+def path_winners(x, f) -> dict:
+    """Per draw the winning run of `ascend_paths`: x (S, K, d), f (S, K) -> winner (S,) = the start with the largest finite f, ties
+    to the lowest start (-1: none is finite), x_best (S, d), f_best (S,) (NaN where winner is -1)."""
+    x, f = np.asarray(x, dtype=np.float64), np.asarray(f, dtype=np.float64)
+    key = np.where(np.isfinite(f), f, -np.inf)
+    winner = key.argmax(axis=1).astype(np.int64)          # the first index of the maximum
+    rows = np.arange(f.shape[0])
+    ok = np.isfinite(f[rows, winner])
+    x_best = np.where(ok[:, None], x[rows, winner], np.nan)
+    f_best = np.where(ok, f[rows, winner], np.nan)
+    return {"winner": np.where(ok, winner, -1), "x_best": x_best, "f_best": f_best}
+
+
 class GpEngine:
     """One engine context = one GPU, one HIP stream, 8 model slots (0 = target GP, 1.. = constraint GPs) and one resident
     candidate matrix.  Calls are synchronous from the host's point of view unless noted (`posterior(fetch=False)` only
@@ -596,6 +609,70 @@ class GpEngine:
                                                 dptr(phase), dptr(weights), dptr(eps), int(index_offset), iptr(best_idx),
                                                 dptr(best_val), dptr(values)))
         return best_idx[:S], best_val[:S], values
+
+    def ascend_paths(self, omega, phase, weights, eps, box_lo, box_hi, n_starts=4, starts=None, max_iter=-1, slot=0, y_mean=0.0,
+                     y_std=1.0, index_offset=0, return_gradient=False):
+        """The S draws of `sample_paths`, each climbed from K starts to a local maximiser inside [box_lo, box_hi] in ONE launch
+        (gpbo_ascend_paths: a workgroup per (draw, start), evaluations and the projected L-BFGS of `polish_seeds` inside it;
+        include/gpbo.h has the formulas).  starts=None: K = n_starts and the starts are each draw's K best resident candidates
+        (what `sample_paths` evaluates; `best_idx` / `best_val` are its answers, bit for bit).  starts (S, K, d): no candidates
+        are needed, `best_idx` / `best_val` are None.  max_iter < 0: 15 000 iterations; 0: the value and gradient at the (clipped)
+        starts, no search.  Returns a dict:
+            x (S, K, d), f (S, K) = the draw's value at x, status (S, K) 0 / 1 converged, 2 iteration limit or non-finite start, 3
+            line search exhausted, n_eval (S, K), start_idx (S, K) candidate indices (+ index_offset) or -1, g (S, K, d) with
+            return_gradient, best_idx, best_val;
+            winner (S,), x_best (S, d), f_best (S,): per draw the run with the largest finite f, ties to the lowest start
+            (winner -1, NaN rows: no run of the draw has a finite value).
+        A reader: the slot's fit, its resident posterior and the candidates stay as they were."""
+        self._settle(slot)
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        phase = np.ascontiguousarray(phase, dtype=np.float64).ravel()
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        eps = np.ascontiguousarray(eps, dtype=np.float64)
+        if omega.ndim != 2 or weights.ndim != 2 or eps.ndim != 2:
+            raise ValueError("ascend_paths: omega (F, d), weights (S, F) and eps (S, N) must be 2-D")
+        F, S = omega.shape[0], weights.shape[0]
+        if phase.shape[0] != F or weights.shape[1] != F or eps.shape[0] != S:
+            raise ValueError("ascend_paths: phase (F,), weights (S, F) and eps (S, N) do not fit omega (F, d)")
+        shape = getattr(self, "_n_obs", {}).get(int(slot))
+        if shape is None:
+            raise _lib.GpboError("ascend_paths: model slot has not been fitted")
+        if (eps.shape[1], omega.shape[1]) != shape:
+            raise ValueError(f"ascend_paths: eps (S, {eps.shape[1]}) / omega (F, {omega.shape[1]}) do not fit the slot's model of "
+                             f"{shape[0]} observations in {shape[1]} dimensions")
+        d = int(shape[1])
+        lo = np.ascontiguousarray(box_lo, dtype=np.float64).ravel()
+        hi = np.ascontiguousarray(box_hi, dtype=np.float64).ravel()
+        if lo.shape[0] != d or hi.shape[0] != d:
+            raise ValueError(f"ascend_paths: box_lo / box_hi must have {d} entries")
+        if starts is not None:
+            starts = np.ascontiguousarray(starts, dtype=np.float64)
+            if starts.ndim != 3 or starts.shape[0] != S or starts.shape[2] != d:
+                raise ValueError(f"ascend_paths: starts must be (S = {S}, K, d = {d})")
+            K = int(starts.shape[1])
+        else:
+            K = int(n_starts)
+        R = max(S, 1) * max(K, 1)
+        best_idx = np.empty(max(S, 1), dtype=np.int64) if starts is None else None
+        best_val = np.empty(max(S, 1)) if starts is None else None
+        x = np.empty((R, d))
+        f = np.empty(R)
+        g = np.empty((R, d)) if return_gradient else None
+        status = np.zeros(R, dtype=np.int32)
+        n_eval = np.zeros(R, dtype=np.int32)
+        start_idx = np.empty(R, dtype=np.int64)
+        self._check(self._lib.gpbo_ascend_paths(self._h, int(slot), float(y_mean), float(y_std), int(S), int(F), dptr(omega),
+                                                dptr(phase), dptr(weights), dptr(eps), K, dptr(starts), dptr(lo), dptr(hi),
+                                                int(max_iter), int(index_offset), iptr(best_idx), dptr(best_val), dptr(x), dptr(f),
+                                                dptr(g), status.ctypes.data_as(C.POINTER(C.c_int)),
+                                                n_eval.ctypes.data_as(C.POINTER(C.c_int)), iptr(start_idx)))
+        out = {"x": x.reshape(S, K, d), "f": f.reshape(S, K), "status": status.reshape(S, K), "n_eval": n_eval.reshape(S, K),
+               "start_idx": start_idx.reshape(S, K), "best_idx": None if best_idx is None else best_idx[:S],
+               "best_val": None if best_val is None else best_val[:S]}
+        if return_gradient:
+            out["g"] = g.reshape(S, K, d)
+        out.update(path_winners(out["x"], out["f"]))
+        return out
 
     def predict(self, Xc, slot=0, y_mean=0.0, y_std=1.0):
         self.set_candidates(Xc)
@@ -1203,6 +1280,10 @@ class GroupEngine(GpEngine):
 
     def sample_paths(self, omega, phase, weights, eps, slot=0, y_mean=0.0, y_std=1.0, index_offset=0, return_values=False):
         raise NotImplementedError("a device group has no path sampler (gpbo_sample_paths is per context); use a single device")
+
+    def ascend_paths(self, omega, phase, weights, eps, box_lo, box_hi, n_starts=4, starts=None, max_iter=-1, slot=0, y_mean=0.0,
+                     y_std=1.0, index_offset=0, return_gradient=False):
+        raise NotImplementedError("a device group has no path ascent (gpbo_ascend_paths is per context); use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
         raise NotImplementedError("a device group has no posterior refresh path (gpbo_posterior_refresh is per context); "

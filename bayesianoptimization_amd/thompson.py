@@ -7,7 +7,9 @@ predict(return_cov=True), an M x M covariance and its factorisation on the host,
 draw is conditioned pathwise (Matheron's rule; Wilson et al. 2020, "Efficiently sampling functions from Gaussian process
 posteriors"): a random-Fourier-feature draw from the prior plus an exact data-dependent update, evaluated by the engine's
 `sample_paths` (gpbo_sample_paths) at O((N + F) d) per candidate for 16 draws at once.  Only the prior part is approximate, through
-the F features; include/gpbo.h has the formulas.
+the F features; include/gpbo.h has the formulas.  A draw is a closed-form function, so with `refine=K` each one is also CLIMBED from
+its K best candidates to a local maximiser inside the bounds (the engine's `ascend_paths`, gpbo_ascend_paths: value and gradient
+at O((N + F) d) per evaluation, optimiser and evaluations in one launch) — the local-search stage of the reference's suggest().
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ from .gpr import HipGPR
 _NU = {1: 2.5, 2: 1.5, 3: 0.5}
 MAX_PATHS = 16                  # GPBO_MAX_PATHS: draws one sample_paths call evaluates side by side
 MAX_FEATURES = 4096             # GPBO_MAX_PATH_FEATURES
+MAX_STARTS = 8                  # GPBO_MAX_PATH_STARTS: starts per draw one ascend_paths call climbs from
 
 
 def spectral_draw(kind: int, n_features: int, d: int, random_state):
@@ -50,7 +53,7 @@ def spectral_draw(kind: int, n_features: int, d: int, random_state):
     return np.ascontiguousarray(w / (2.0 * np.pi)), phase
 
 
-def suggest_thompson(optimizer, q: int, n_random: int = 10_000, n_features: int = 1024):
+def suggest_thompson(optimizer, q: int, n_random: int = 10_000, n_features: int = 1024, refine: int = 0, max_iter=None):
     """q parameter dicts to probe side by side, as `suggest_batch` returns them; `optimizer` has been `accelerate()`d.
 
       1. the checks of `suggest_batch`, with its exception types (below).  The acquisition policy is neither consulted nor advanced.
@@ -60,12 +63,19 @@ def suggest_thompson(optimizer, q: int, n_random: int = 10_000, n_features: int 
          `spectral_draw` (fresh features per call), `standard_normal((S, F))` — the feature weights — and `standard_normal((S, N))`
          scaled by sqrt(noise) — the noise draws, noise = the estimator's alpha (+ the WhiteKernel's level for a scaled model).
       5. the picked rows are fetched from the device.
-    No posterior pass and no local search: the picks are the draws' maximisers AMONG THE CANDIDATES.  Two draws may pick the same
-    candidate (a sharply peaked posterior: every draw agrees); that is kept — the caller sees how decided the model is.
+    No posterior pass.  With `refine=0` (the default) there is no local search either: the picks are the draws' maximisers AMONG THE
+    CANDIDATES.  Two draws may pick the same candidate (a sharply peaked posterior: every draw agrees); that is kept — the caller sees
+    how decided the model is.
+    `refine=K`, 1 <= K <= 8: each group of up to 16 draws is ONE `ascend_paths` call in place of its `sample_paths` call (steps 4 and
+    5; no candidate rows are fetched): every draw is climbed from its K best candidates to a local maximiser inside `space.bounds` on
+    the device, and the pick is the best of its K runs.  The optimiser accepts no worse point, so a pick's value under its draw is at
+    least its best candidate's.  The refinement draws nothing: the optimizer's RandomState ends where `refine=0` leaves it.
+    `max_iter` (None: 15 000) bounds the iterations of a run.
     `n_features` = 1024: at 256 the variance of the draws is already off by 25 % for Matern nu = 1.5 / 2.5 (tests/test_thompson_host.py).
     Afterwards `gp.predict` answers for the real data as before; the slot holds the fit of step 2.
 
-    ValueError: q not an integer >= 1, n_random < 1, n_features outside [1, 4096].  TargetSpaceEmptyError on an empty space,
+    ValueError: q not an integer >= 1, n_random < 1, n_features outside [1, 4096], refine not an integer in [0, 8] (or larger than
+    `n_random`: a draw has no more starts than candidates).  TargetSpaceEmptyError on an empty space,
     ConstraintNotSupportedError with a constraint.  NotImplementedError, never a host fallback, for: a GP that is not on the engine's
     slot 0, a space with an input transform (int / categorical parameters), a model in host mode, a device group."""
     if isinstance(q, bool) or not isinstance(q, (int, np.integer)):
@@ -101,6 +111,11 @@ def suggest_thompson(optimizer, q: int, n_random: int = 10_000, n_features: int 
     reason = None if gp.kernel is None else gp._unsupported_reason(clone(gp.kernel), space.target, space.params)
     if reason is not None:
         raise NotImplementedError(f"suggest_thompson: the model runs on the host ({reason}); only models on the device path are sampled")
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= MAX_STARTS:
+        raise ValueError(f"refine must be an integer in [0, {MAX_STARTS}]")
+    refine = int(refine)
+    if refine and not hasattr(eng, "ascend_paths"):
+        raise NotImplementedError("suggest_thompson: the engine has no ascend_paths")
     rng = optimizer._random_state
 
     with warnings.catch_warnings():
@@ -121,7 +136,16 @@ def suggest_thompson(optimizer, q: int, n_random: int = 10_000, n_features: int 
         weights = rng.standard_normal((S, n_features))
         eps = rng.standard_normal((S, N)) * np.sqrt(noise)
         gp._ensure_resident()
+        if refine:
+            out = eng.ascend_paths(omega, phase, weights, eps, space.bounds[:, 0], space.bounds[:, 1], n_starts=refine,
+                                   max_iter=-1 if max_iter is None else int(max_iter), slot=gp.slot, y_mean=y_mean, y_std=y_std)
+            # (a draw without a finite run keeps its first start: its best candidate)
+            picks.extend(out["x_best"][s] if out["winner"][s] >= 0 else out["x"][s, 0] for s in range(S))
+            continue
         best, _val, _values = eng.sample_paths(omega, phase, weights, eps, slot=gp.slot, y_mean=y_mean, y_std=y_std)
         picks.extend(int(i) for i in best)
-    rows = np.asarray(eng.get_candidate_rows(np.array(picks, dtype=np.int64), d), dtype=np.float64)
+    if refine:
+        rows = np.asarray(picks, dtype=np.float64).reshape(q, d)
+    else:
+        rows = np.asarray(eng.get_candidate_rows(np.array(picks, dtype=np.int64), d), dtype=np.float64)
     return [space.array_to_params(x) for x in rows]

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GPBO_ABI_VERSION 2
+#define GPBO_ABI_VERSION 3
 
 enum gpbo_status {
   GPBO_OK = 0,
@@ -300,6 +300,46 @@ int gpbo_posterior_refresh(gpbo_ctx* ctx, int slot, double y_mean, double y_std,
 int gpbo_sample_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n_paths, int n_features,
                       const double* omega, const double* phase, const double* weights, const double* eps,
                       int64_t index_offset, int64_t* best_idx, double* best_val, double* values_out);
+
+/* The draws of gpbo_sample_paths, each CLIMBED from n_starts starts to a local maximiser inside a box — Thompson sampling with the
+ * local-search stage the reference's suggest() never goes without (Wilson et al. 2020 maximise their draws by gradient ascent: a
+ * pathwise-conditioned draw is a closed-form function).  Arguments up to eps, and f_s itself, as gpbo_sample_paths.  With
+ * xs = x / length_scale, t_j = omega_j . xs + phase_j in turns and r_i = |xs - Xs_i|:
+ *   f_s(x)        = y_std (fs sum_j weights[s, j] cos(2 pi t_j) + sum_i v_s,i k(r_i)) + y_mean
+ *   d f_s / d x_t = y_std (-2 pi fs sum_j weights[s, j] sin(2 pi t_j) omega_j,t + sum_i v_s,i k'(r_i) (xs_t - Xs_i,t) / r_i) / length_scale_t
+ *   k'(r) / r     = -k (RBF);  -(5/3) (1 + sqrt5 r) exp(-sqrt5 r) (nu = 2.5);  -3 exp(-sqrt3 r) (nu = 1.5);  -exp(-r) / r (nu = 0.5,
+ *                   and 0 at r = 0: a point exactly ON a training point takes no slope from it, the project's convention)
+ * One run per (path s, start k), S x K <= 16 x 8 runs in ONE launch, a workgroup each, the evaluations — O((N + F) d), no pass over
+ * W, no N limit — and the optimiser inside it: gpbo_polish_seeds' projected L-BFGS on -f_s (10 correction pairs, projected gradient
+ * 1e-5, relative reduction 1e7 eps, 20 line-search steps, Armijo on the projected path; iterates always inside the box).
+ * starts == NULL: the call does what gpbo_sample_paths does (the paths over the resident candidates; best_idx / best_val (S,) come
+ *   back with the same bits), takes each path's n_starts best candidates by the selection's rules (ties -> lowest index, NaNs last;
+ *   n_starts > M is GPBO_ERR_INVALID) and ascends from them: start_idx_out (S, K) = their indices + index_offset, column 0 =
+ *   best_idx unless a NaN won it.
+ * starts (S, K, d) on the host, clipped into the box: no resident candidates are needed, best_idx / best_val may be NULL,
+ *   start_idx_out = -1.
+ * box_lo < box_hi (d,), finite.  max_iter < 0: 15 000 iterations; max_iter == 0: no search — x_out = the clipped starts, f_out / g_out
+ * = value and gradient there (one evaluation per run; status 0 where the projected gradient is already below tolerance, else 2).
+ * Outputs per run: x_out (S, K, d) inside the box; f_out (S, K) = f_s(x_out), not negated; g_out (S, K, d) or NULL = d f_s / d x at
+ * x_out (a non-finite component reads 0, as the optimiser took it); status_out (S, K) as gpbo_polish_seeds: 0 projected gradient below
+ * tolerance, 1 relative reduction below tolerance / no further progress, 2 iteration limit or a non-finite start (x_out = the start),
+ * 3 line search exhausted; n_eval_out (S, K) or NULL = evaluations, at most 4 max_iter + 64.  Every sum has a fixed order: a run's
+ * bits do not depend on which other runs share the launch.  fp64 whatever the slot's precision.
+ * A reader, as gpbo_sample_paths: the slot, its resident mu / sd, what gpbo_posterior_refresh may still refresh, the candidates (the
+ * trial points live in the kernel; the candidate buffer is NOT borrowed, unlike gpbo_polish_seeds) and the negative-variance flag
+ * stay as they were; the context's acquisition values are overwritten when starts == NULL.
+ * The call returns when its longest run has stopped: the calling thread and the context's stream are held for that long (a run is
+ * bounded by 4 max_iter + 64 evaluations of a few microseconds each at N + F of a few thousand; with the default 15 000 iterations a
+ * pathological run is a fraction of a second) — callers that need a tighter bound pass a smaller max_iter (status 2 marks the cut).
+ * GPBO_ERR_INVALID: the refusals of gpbo_sample_paths, n_starts outside [1, GPBO_MAX_PATH_STARTS], a box that is not finite or not
+ * lo < hi, a NULL box / x_out / f_out / status_out / start_idx_out (and best_idx / best_val with starts == NULL).  GPBO_ERR_STATE: as
+ * gpbo_sample_paths (no candidates / candidates of another d only with starts == NULL).  There is no gpbo_group_* / gpbo_comm_* form. */
+#define GPBO_MAX_PATH_STARTS 8
+int gpbo_ascend_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n_paths, int n_features,
+                      const double* omega, const double* phase, const double* weights, const double* eps,
+                      int n_starts, const double* starts, const double* box_lo, const double* box_hi, int max_iter,
+                      int64_t index_offset, int64_t* best_idx, double* best_val, double* x_out, double* f_out, double* g_out,
+                      int* status_out, int* n_eval_out, int64_t* start_idx_out);
 
 /* Convenience: set_candidates + posterior for a host batch (the HipGPR.predict path). */
 int gpbo_predict(gpbo_ctx* ctx, int slot, const double* Xc, int64_t M, int d, double y_mean,
