@@ -539,6 +539,13 @@ int debug_select(gpbo_ctx* ctx, const double* ys_host, int64_t M, int k, int var
   return GPBO_OK;
 }
 
+// the arg-best a selection's records (on the host) give, as numpy argmin / min: the first NaN wins, else the first pick
+static void best_of_selection(const SelState& st, const Key& first, int64_t offset, int64_t* best_idx, double* best_val) {
+  const bool nan = st.first_nan != INT64_MAX;
+  *best_idx = (nan ? st.first_nan : first.i) + offset;
+  *best_val = nan ? std::numeric_limits<double>::quiet_NaN() : first.v;
+}
+
 int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, int64_t offset,
                        int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val) {
   SelState* st; Key* picks; int npass;
@@ -549,15 +556,8 @@ int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, 
   char* hp = (char*)ctx->pinned_aux + PIN_AUX_SEL_OUT;
   GPBO_HIP(ctx, hipMemcpyAsync(hp, st, sizeof(SelState) + sizeof(Key) * npass, hipMemcpyDeviceToHost, ctx->stream));
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const SelState* hst = (const SelState*)hp;
   const Key* hpicks = (const Key*)(hp + sizeof(SelState));
-  if (hst->first_nan != INT64_MAX) {      // numpy argmin/min: the first NaN wins
-    *best_idx = hst->first_nan + offset;
-    *best_val = std::numeric_limits<double>::quiet_NaN();
-  } else {
-    *best_idx = hpicks[0].i + offset;
-    *best_val = hpicks[0].v;
-  }
+  best_of_selection(*(const SelState*)hp, hpicks[0], offset, best_idx, best_val);
   for (int t = 0; t < k_seeds; ++t) {
     const bool valid = hpicks[t].i != INT64_MAX;   // fewer than k candidates
     seed_idx[t] = valid ? hpicks[t].i + offset : -1;
@@ -566,62 +566,33 @@ int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, 
   return GPBO_OK;
 }
 
-// gpbo_sample_paths: arg-best of each of n_rows rows of M keys (rows[r * ld ...]) by the selection launches above, one row after the
-// other on the context's stream; the rows' results cross in the selection's pinned window and are read after ONE synchronisation.
-int launch_argbest_rows(gpbo_ctx* ctx, double* rows, int64_t ld, int n_rows, int64_t M, int64_t offset, int64_t* best_idx,
-                        double* best_val) {
-  constexpr size_t REC = sizeof(SelState) + sizeof(Key);
-  static_assert(REC * GPBO_MAX_PATHS <= PIN_AUX_SEL_OUT_BYTES, "the rows' selection results outgrew their window");
-  if (n_rows < 1 || n_rows > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "argbest_rows: row count out of range");
-  char* hp = (char*)ctx->pinned_aux + PIN_AUX_SEL_OUT;
-  for (int r = 0; r < n_rows; ++r) {
-    SelState* st; Key* picks;
-    int rc = enqueue_select(ctx, M, 1, false, &st, &picks, nullptr, rows + (int64_t)r * ld);
-    if (rc) return rc;
-    GPBO_HIP(ctx, hipMemcpyAsync(hp + REC * r, st, REC, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (int r = 0; r < n_rows; ++r) {
-    const SelState* hst = (const SelState*)(hp + REC * r);
-    const Key* hpick = (const Key*)(hp + REC * r + sizeof(SelState));
-    if (hst->first_nan != INT64_MAX) {      // numpy argmin/min: the first NaN wins
-      best_idx[r] = hst->first_nan + offset;
-      best_val[r] = std::numeric_limits<double>::quiet_NaN();
-    } else {
-      best_idx[r] = hpick->i + offset;
-      best_val[r] = hpick->v;
-    }
-  }
-  return GPBO_OK;
-}
-
-// gpbo_ascend_paths: launch_argbest_rows with k picks per row (the k-pass selection: its first pick is the one-pass pick, same
-// launches, same keys).  The rows' records come back through a host buffer of the call's own — 16 rows of 8 picks are more than the
-// selection's pinned window holds — after ONE synchronisation.
+// gpbo_sample_paths (k = 1, top_idx null) / gpbo_ascend_paths: the k best of each of n_rows rows of M keys (rows[r * ld ...]) by the
+// selection launches above (the k-pass selection: its first pick is the one-pass pick), one row after the other on the context's
+// stream.  The rows' records cross in the selection's pinned window when they fit it (k = 1 always does), else — 16 rows of 8 picks
+// are more than it holds — in a host buffer of the call's own, and are read after ONE synchronisation.
 int launch_topk_rows(gpbo_ctx* ctx, double* rows, int64_t ld, int n_rows, int64_t M, int k, int64_t offset, int64_t* best_idx,
                      double* best_val, int64_t* top_idx) {
+  static_assert((sizeof(SelState) + sizeof(Key)) * GPBO_MAX_PATHS <= PIN_AUX_SEL_OUT_BYTES, "the rows' arg-bests outgrew their window");
   if (n_rows < 1 || n_rows > GPBO_MAX_PATHS || k < 1 || k > GPBO_MAX_PATH_STARTS || k > M)
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "topk_rows: row or pick count out of range");
   const size_t rec = sizeof(SelState) + sizeof(Key) * (size_t)k;
-  std::vector<char> host(rec * (size_t)n_rows);
+  std::vector<char> own;
+  char* hp = (char*)ctx->pinned_aux + PIN_AUX_SEL_OUT;
+  if (rec * (size_t)n_rows > PIN_AUX_SEL_OUT_BYTES) {
+    own.resize(rec * (size_t)n_rows);
+    hp = own.data();
+  }
   for (int r = 0; r < n_rows; ++r) {
     SelState* st; Key* picks;
     int rc = enqueue_select(ctx, M, k, false, &st, &picks, nullptr, rows + (int64_t)r * ld);
     if (rc) return rc;
-    GPBO_HIP(ctx, hipMemcpyAsync(host.data() + rec * r, st, rec, hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipMemcpyAsync(hp + rec * r, st, rec, hipMemcpyDeviceToHost, ctx->stream));
   }
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int r = 0; r < n_rows; ++r) {
-    const SelState* hst = (const SelState*)(host.data() + rec * r);
-    const Key* hpick = (const Key*)(host.data() + rec * r + sizeof(SelState));
-    if (hst->first_nan != INT64_MAX) {      // numpy argmin/min: the first NaN wins
-      best_idx[r] = hst->first_nan + offset;
-      best_val[r] = std::numeric_limits<double>::quiet_NaN();
-    } else {
-      best_idx[r] = hpick->i + offset;
-      best_val[r] = hpick->v;
-    }
-    for (int t = 0; t < k; ++t) top_idx[(size_t)r * k + t] = hpick[t].i != INT64_MAX ? hpick[t].i : -1;
+    const Key* hpick = (const Key*)(hp + rec * r + sizeof(SelState));
+    best_of_selection(*(const SelState*)(hp + rec * r), hpick[0], offset, best_idx + r, best_val + r);
+    for (int t = 0; top_idx && t < k; ++t) top_idx[(size_t)r * k + t] = hpick[t].i != INT64_MAX ? hpick[t].i : -1;
   }
   return GPBO_OK;
 }

@@ -1212,28 +1212,59 @@ int gpbo_posterior_refresh(gpbo_ctx* ctx, int slot, double y_mean, double y_std,
   return fetch_posterior(ctx, m, mu, sd);
 }
 
+// The refusals gpbo_sample_paths (n_starts = 1) and gpbo_ascend_paths share, in their order; `missing`: what to say of a NULL
+// argument, or null.  Hands back the slot's model.
+static int check_path_args(gpbo_ctx* ctx, const char* who, int slot, double y_mean, double y_std, int n_paths, int n_features,
+                           int n_starts, const char* missing, const Model** m) {
+  int rc = check_slot(ctx, slot);
+  if (rc) return rc;
+  const std::string w = std::string(who) + ": ";
+  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_paths out of range [1, 16]");
+  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_features out of range [1, 4096]");
+  if (n_starts < 1 || n_starts > GPBO_MAX_PATH_STARTS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_starts out of range [1, 8]");
+  if (missing) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + missing);
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "y_std must be finite and positive, y_mean finite");
+  if ((rc = no_pending_fit(ctx, slot, who))) return rc;
+  if ((rc = need_fitted(ctx, slot))) return rc;
+  *m = &ctx->models[slot];
+  return GPBO_OK;
+}
+
+// The draws over the resident candidates (their negated values stay in ctx->ys) and the k best of each: best_idx / best_val the draws'
+// maximisers, top_idx the rows' picks (null with k = 1: gpbo_sample_paths; else gpbo_ascend_paths' starts, and *ws has room for its runs)
+static int draw_over_candidates(gpbo_ctx* ctx, const char* who, const Model& m, double y_mean, double y_std, int n_paths,
+                                int n_features, const double* omega, const double* phase, const double* weights, const double* eps,
+                                int k, int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* top_idx,
+                                PathWorkspace* ws) {
+  int rc;
+  const std::string w = std::string(who) + ": ";
+  if (ctx->M < 1)
+    GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates" + (top_idx ? ", or pass starts)" : ")"));
+  if (ctx->d_c != m.d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from the fitted model's");
+  const int64_t M = ctx->M;
+  if (k > M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_starts exceeds the number of resident candidates");
+  if ((rc = launch_sample_paths(ctx, m, M, y_mean, y_std, n_paths, n_features, omega, phase, weights, eps, top_idx ? n_paths * k : 0,
+                                ws)))
+    return rc;
+  if ((rc = launch_topk_rows(ctx, ctx->ys, M, n_paths, M, k, index_offset, best_idx, best_val, top_idx))) return rc;
+  for (int s = 0; s < n_paths; ++s) best_val[s] = -best_val[s];      // the key is -f
+  return GPBO_OK;
+}
+
 int gpbo_sample_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n_paths, int n_features, const double* omega,
                       const double* phase, const double* weights, const double* eps, int64_t index_offset, int64_t* best_idx,
                       double* best_val, double* values_out) {
-  int rc = check_slot(ctx, slot);
+  const Model* m;
+  PathWorkspace ws{};
+  const bool given = omega && phase && weights && eps && best_idx && best_val;
+  int rc = check_path_args(ctx, "sample_paths", slot, y_mean, y_std, n_paths, n_features, 1, given ? nullptr : "NULL argument", &m);
   if (rc) return rc;
-  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sample_paths: n_paths out of range [1, 16]");
-  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES)
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sample_paths: n_features out of range [1, 4096]");
-  if (!omega || !phase || !weights || !eps || !best_idx || !best_val) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sample_paths: NULL argument");
-  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sample_paths: y_std must be finite and positive, y_mean finite");
-  if ((rc = no_pending_fit(ctx, slot, "sample_paths"))) return rc;
-  if ((rc = need_fitted(ctx, slot))) return rc;
-  const Model& m = ctx->models[slot];
-  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "sample_paths: no candidates resident (call gpbo_set_candidates)");
-  if (ctx->d_c != m.d) GPBO_FAIL(ctx, GPBO_ERR_STATE, "sample_paths: the resident candidates' dimension differs from the fitted model's");
-  const int64_t M = ctx->M;
-  if ((rc = launch_sample_paths(ctx, m, M, y_mean, y_std, n_paths, n_features, omega, phase, weights, eps))) return rc;
-  if ((rc = launch_argbest_rows(ctx, ctx->ys, M, n_paths, M, index_offset, best_idx, best_val))) return rc;
-  for (int s = 0; s < n_paths; ++s) best_val[s] = -best_val[s];      // the key is -f
+  if ((rc = draw_over_candidates(ctx, "sample_paths", *m, y_mean, y_std, n_paths, n_features, omega, phase, weights, eps, 1,
+                                 index_offset, best_idx, best_val, nullptr, &ws)))
+    return rc;
   if (values_out) {
-    const int64_t n = (int64_t)n_paths * M;
+    const int64_t n = (int64_t)n_paths * ctx->M;
     GPBO_HIP(ctx, hipMemcpyAsync(values_out, ctx->ys, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t i = 0; i < n; ++i) values_out[i] = -values_out[i];
@@ -1246,43 +1277,31 @@ int gpbo_ascend_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int 
                       const double* box_lo, const double* box_hi, int max_iter, int64_t index_offset, int64_t* best_idx,
                       double* best_val, double* x_out, double* f_out, double* g_out, int* status_out, int* n_eval_out,
                       int64_t* start_idx_out) {
-  int rc = check_slot(ctx, slot);
-  if (rc) return rc;
-  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: n_paths out of range [1, 16]");
-  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES)
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: n_features out of range [1, 4096]");
-  if (n_starts < 1 || n_starts > GPBO_MAX_PATH_STARTS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: n_starts out of range [1, 8]");
+  const Model* m;
+  const char* missing = nullptr;
   if (!omega || !phase || !weights || !eps || !box_lo || !box_hi || !x_out || !f_out || !status_out || !start_idx_out)
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: NULL argument");
-  if (!starts && (!best_idx || !best_val)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: NULL argument (best_idx / best_val without starts)");
-  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: y_std must be finite and positive, y_mean finite");
-  if ((rc = no_pending_fit(ctx, slot, "ascend_paths"))) return rc;
-  if ((rc = need_fitted(ctx, slot))) return rc;
-  const Model& m = ctx->models[slot];
-  for (int t = 0; t < m.d; ++t)
+    missing = "NULL argument";
+  else if (!starts && (!best_idx || !best_val)) missing = "NULL argument (best_idx / best_val without starts)";
+  int rc = check_path_args(ctx, "ascend_paths", slot, y_mean, y_std, n_paths, n_features, n_starts, missing, &m);
+  if (rc) return rc;
+  for (int t = 0; t < m->d; ++t)
     if (!std::isfinite(box_lo[t]) || !std::isfinite(box_hi[t]) || !(box_lo[t] < box_hi[t]))
       GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: the box must be finite with box_lo < box_hi in every coordinate");
-  if (max_iter < 0) max_iter = 15000;
+  if (max_iter < 0) max_iter = PATH_DEFAULT_MAX_ITER;
   const int R = n_paths * n_starts;
-  const int64_t extra = path_ascent_doubles(R, m.d);
   PathWorkspace ws{};
   std::vector<int64_t> top;
   if (!starts) {
-    if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ascend_paths: no candidates resident (call gpbo_set_candidates, or pass starts)");
-    if (ctx->d_c != m.d) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ascend_paths: the resident candidates' dimension differs from the fitted model's");
-    const int64_t M = ctx->M;
-    if (n_starts > M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ascend_paths: n_starts exceeds the number of resident candidates");
-    if ((rc = launch_sample_paths(ctx, m, M, y_mean, y_std, n_paths, n_features, omega, phase, weights, eps, extra, &ws))) return rc;
     top.resize((size_t)R);
-    if ((rc = launch_topk_rows(ctx, ctx->ys, M, n_paths, M, n_starts, index_offset, best_idx, best_val, top.data()))) return rc;
-    for (int s = 0; s < n_paths; ++s) best_val[s] = -best_val[s];      // the key is -f
+    if ((rc = draw_over_candidates(ctx, "ascend_paths", *m, y_mean, y_std, n_paths, n_features, omega, phase, weights, eps, n_starts,
+                                   index_offset, best_idx, best_val, top.data(), &ws)))
+      return rc;
     for (int r = 0; r < R; ++r) start_idx_out[r] = top[r] >= 0 ? top[r] + index_offset : -1;
   } else {
-    if ((rc = launch_path_weights(ctx, m, n_paths, n_features, omega, phase, weights, eps, extra, &ws))) return rc;
+    if ((rc = launch_path_weights(ctx, *m, n_paths, n_features, omega, phase, weights, eps, R, &ws))) return rc;
     for (int r = 0; r < R; ++r) start_idx_out[r] = -1;
   }
-  return launch_path_ascent(ctx, m, ws, n_paths, n_starts, n_features, y_mean, y_std, starts, starts ? nullptr : top.data(), box_lo,
+  return launch_path_ascent(ctx, *m, ws, n_paths, n_starts, n_features, y_mean, y_std, starts, starts ? nullptr : top.data(), box_lo,
                             box_hi, max_iter, x_out, f_out, g_out, status_out, n_eval_out);
 }
 

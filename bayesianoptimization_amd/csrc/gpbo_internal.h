@@ -16,6 +16,7 @@
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
+#include "path_plan.h"        // the posterior function draws' workspace layout and dispatch rules
 
 namespace gpbo {
 
@@ -585,19 +586,18 @@ int launch_slab_gemm_i8(gpbo_ctx* ctx, Model& m, const void* slab, int64_t ldk, 
 int prepare_posterior_i8(gpbo_ctx* ctx, Model& m);   // before the first int8 slab: W's digit planes (once per fit), the device's compute units
 // posterior_refresh.hip: the resident mu / sd of m brought from m.N_post to m.N rows (gpbo_posterior_refresh's incremental route)
 int launch_posterior_refresh(gpbo_ctx* ctx, Model& m, int64_t M, double y_mean, double y_std);
-// posterior_paths.hip: the negated values of n_paths posterior function draws over the M resident candidates into ctx->ys [n_paths][M]
-// (extra / ws: that many doubles behind the call's workspace for the caller, and where the draws' resident inputs and V lie)
-struct PathWorkspace { double *omega, *phase, *weights, *V, *extra; };
+// posterior_paths.hip: the negated values of n_paths posterior function draws over the M resident candidates into ctx->ys [n_paths][M].
+// The call's workspace (path_plan.h: path_block, with room for n_runs ascent runs behind V; 0: none) is handed back in *ws.
+struct PathWorkspace { double* base; PathBlock at; double* p(int64_t off) const { return base + off; } };   // base = ctx->paths
 int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int n_paths, int n_features,
-                        const double* omega, const double* phase, const double* weights, const double* eps, int64_t extra = 0,
-                        PathWorkspace* ws = nullptr);
+                        const double* omega, const double* phase, const double* weights, const double* eps, int n_runs,
+                        PathWorkspace* ws);
 // ... and the first half of it alone: the draws' inputs and V = alpha - W^T (W (g(X) + eps)) made resident, no candidates needed
 int launch_path_weights(gpbo_ctx* ctx, const Model& m, int n_paths, int n_features, const double* omega, const double* phase,
-                        const double* weights, const double* eps, int64_t extra, PathWorkspace* ws);
+                        const double* weights, const double* eps, int n_runs, PathWorkspace* ws);
 // path_ascent.hip: gpbo_ascend_paths' runs, n_paths x n_starts workgroups in one launch, from host starts (n_paths n_starts, d) or —
-// starts null — from the rows start_idx (local indices, host) of the resident candidates; ws.extra holds at least
-// path_ascent_doubles(n_paths * n_starts, d) doubles.  Synchronises.
-int64_t path_ascent_doubles(int n_runs, int d);
+// starts null — from the rows start_idx (local indices, host) of the resident candidates; ws was laid out for n_runs =
+// n_paths * n_starts.  Synchronises.
 int launch_path_ascent(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, int n_paths, int n_starts, int n_features,
                        double y_mean, double y_std, const double* starts, const int64_t* start_idx, const double* box_lo,
                        const double* box_hi, int max_iter, double* x_out, double* f_out, double* g_out, int* status_out,
@@ -614,11 +614,9 @@ struct AcqArgs {
 };
 int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, int64_t offset,
                        int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val);
-// acq_kernels.hip: the arg-best of each of n_rows rows of M keys (rows + r * ld), the rules of launch_acq_argbest; synchronises
-int launch_argbest_rows(gpbo_ctx* ctx, double* rows, int64_t ld, int n_rows, int64_t M, int64_t offset, int64_t* best_idx,
-                        double* best_val);
-// acq_kernels.hip: the same with the k best of each row: best_idx / best_val (n_rows) exactly as launch_argbest_rows gives them,
-// top_idx (n_rows, k) the rows' k smallest keys in order (ties to the lowest index, NaNs last) as LOCAL indices; synchronises
+// acq_kernels.hip: the k best of each of n_rows rows of M keys (rows + r * ld), the rules of launch_acq_argbest: best_idx / best_val
+// (n_rows) the arg-best, top_idx (n_rows, k; may be null) the rows' k smallest keys in order (ties to the lowest index, NaNs last)
+// as LOCAL indices; synchronises
 int launch_topk_rows(gpbo_ctx* ctx, double* rows, int64_t ld, int n_rows, int64_t M, int k, int64_t offset, int64_t* best_idx,
                      double* best_val, int64_t* top_idx);
 // (value, global index) records of one shard, as they travel between GPUs: record 0 = the arg-best (value NaN: "my

@@ -175,37 +175,30 @@ __global__ __launch_bounds__(PA_THREADS) void path_ascend_kernel(const PathAscen
 
 }  // namespace
 
-int64_t path_ascent_doubles(int n_runs, int d) { return 2 * (int64_t)d + 3 * (int64_t)n_runs * d + 4 * (int64_t)n_runs; }
-
-// The runs of gpbo_ascend_paths over the path weights `ws` left by launch_path_weights / launch_sample_paths (ws.extra: at least
-// path_ascent_doubles(S K, d) doubles).  starts (S K, d) on the host, or null: the rows start_idx (S K, local indices, host) of the
+// The runs of gpbo_ascend_paths over the path weights `ws` left by launch_path_weights / launch_sample_paths, laid out for S K runs
+// (path_plan.h).  starts (S K, d) on the host, or null: the rows start_idx (S K, local indices, host) of the
 // resident candidates.  Synchronises; the results land in the caller's arrays (g_out / eval_out may be null).
 int launch_path_ascent(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, int S, int K, int F, double y_mean, double y_std,
                        const double* starts, const int64_t* start_idx, const double* box_lo, const double* box_hi, int max_iter,
                        double* x_out, double* f_out, double* g_out, int* status_out, int* eval_out) {
   const int d = m.d, R = S * K;
   const int64_t n_x = (int64_t)R * d;
-  // extra: lo (d) | hi (d) | starts (R d) | x (R d) | g (R d) | f (R) | start_idx (R int64) | status (R ints) | evals (R ints)
-  double* lo_d = ws.extra;
-  double* hi_d = lo_d + d;
-  double* st_d = hi_d + d;
-  double* x_d = st_d + n_x;
-  double* g_d = x_d + n_x;
-  double* f_d = g_d + n_x;
-  int64_t* idx_d = reinterpret_cast<int64_t*>(f_d + R);
-  int* status_d = reinterpret_cast<int*>(idx_d + R);
-  int* eval_d = reinterpret_cast<int*>(f_d + 3 * (int64_t)R);
+  const PathBlock& b = ws.at;
+  double *lo_d = ws.p(b.lo), *hi_d = ws.p(b.hi), *st_d = ws.p(b.starts), *x_d = ws.p(b.x), *g_d = ws.p(b.g), *f_d = ws.p(b.f);
+  int64_t* idx_d = reinterpret_cast<int64_t*>(ws.p(b.start_idx));
+  int* status_d = reinterpret_cast<int*>(ws.base) + b.status;
+  int* eval_d = reinterpret_cast<int*>(ws.base) + b.evals;
   GPBO_HIP(ctx, hipMemcpyAsync(lo_d, box_lo, (size_t)d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   GPBO_HIP(ctx, hipMemcpyAsync(hi_d, box_hi, (size_t)d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (starts) GPBO_HIP(ctx, hipMemcpyAsync(st_d, starts, (size_t)n_x * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   else GPBO_HIP(ctx, hipMemcpyAsync(idx_d, start_idx, (size_t)R * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
   PathAscentArgs a{};
-  a.Xs = m.Xs; a.V = ws.V; a.omega = ws.omega; a.phase = ws.phase; a.weights = ws.weights; a.ls = m.ls;
+  a.Xs = m.Xs; a.V = ws.p(b.V); a.omega = ws.p(b.omega); a.phase = ws.p(b.phase); a.weights = ws.p(b.weights); a.ls = m.ls;
   a.starts = starts ? st_d : nullptr; a.start_idx = idx_d; a.Xc = ctx->Xc; a.M = starts ? 0 : ctx->M;
   a.lo = lo_d; a.hi = hi_d;
   a.x_out = x_d; a.f_out = f_d; a.g_out = g_d; a.status_out = status_d; a.eval_out = eval_d;
   a.N = (int)m.N; a.NP = (int)m.NP; a.F = F; a.d = d; a.K = K; a.max_iter = max_iter;
-  a.fs = sqrt(2.0 * m.amplitude / (double)F);
+  a.fs = path_feature_scale(m.amplitude, F);
   a.y_mean = y_mean; a.y_std = y_std;
   if (const int rc = with_dp_kernel(ctx, m.DP, m.kernel, [&](auto dp, auto k) {
         path_ascend_kernel<decltype(dp)::value, decltype(k)::value><<<dim3((unsigned)R), dim3(PA_THREADS), 0, ctx->stream>>>(a);

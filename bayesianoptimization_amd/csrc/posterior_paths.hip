@@ -175,8 +175,7 @@ __global__ __launch_bounds__(256) void path_v_kernel(const double* __restrict__ 
 
 template <int NS>
 static int launch_path_eval_ns(gpbo_ctx* ctx, const Model& m, const PathEvalArgs& a) {
-  // as the refresh launcher: one workgroup per 256 points fills the device from ~2^17 points on; below, single-wave workgroups
-  const unsigned threads = a.M >= (1 << 17) ? 256u : 64u;
+  const unsigned threads = path_eval_threads(a.M);
   const int64_t blocks = (a.M + threads - 1) / threads;
   if (blocks > 0x7fffffffLL) GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "sample_paths: grid too large; shard the candidates");
   return with_dp_kernel(ctx, m.DP, m.kernel, [&](auto dp, auto k) {
@@ -187,60 +186,54 @@ static int launch_path_eval_ns(gpbo_ctx* ctx, const Model& m, const PathEvalArgs
 }
 
 static int launch_path_eval(gpbo_ctx* ctx, const Model& m, const PathEvalArgs& a) {
-  if (a.S == 1) return launch_path_eval_ns<1>(ctx, m, a);
-  if (a.S <= 4) return launch_path_eval_ns<4>(ctx, m, a);
-  return launch_path_eval_ns<GPBO_MAX_PATHS>(ctx, m, a);
+  switch (path_eval_ns(a.S)) {
+    case 1: return launch_path_eval_ns<1>(ctx, m, a);
+    case 4: return launch_path_eval_ns<4>(ctx, m, a);
+    default: return launch_path_eval_ns<GPBO_MAX_PATHS>(ctx, m, a);
+  }
 }
 
 static PathEvalArgs path_eval_args(const Model& m, const PathWorkspace& ws, int S, int F) {
   PathEvalArgs a{};
-  a.Xs = m.Xs; a.V = ws.V; a.omega = ws.omega; a.phase = ws.phase; a.weights = ws.weights;
+  a.Xs = m.Xs; a.V = ws.p(ws.at.V); a.omega = ws.p(ws.at.omega); a.phase = ws.p(ws.at.phase); a.weights = ws.p(ws.at.weights);
   a.NP = (int)m.NP; a.F = F; a.d = m.d; a.S = S;
-  a.fs = sqrt(2.0 * m.amplitude / (double)F);
+  a.fs = path_feature_scale(m.amplitude, F);
   return a;
 }
 
 // The draws' inputs made resident and V = alpha - W^T (W (g(X) + eps)) of the S paths: everything a path's value (path_eval_kernel)
-// or its ascent (path_ascent.hip) reads, in the context's paths workspace, with `extra` doubles behind it for the caller (ws->extra).
+// or its ascent (path_ascent.hip) reads, in the context's paths workspace (path_plan.h), with room for n_runs ascent runs behind it.
 int launch_path_weights(gpbo_ctx* ctx, const Model& m, int S, int F, const double* omega, const double* phase, const double* weights,
-                        const double* eps, int64_t extra, PathWorkspace* ws) {
-  const int N = (int)m.N, NP = (int)m.NP, d = m.d;
+                        const double* eps, int n_runs, PathWorkspace* ws) {
+  const int N = (int)m.N, NP = (int)m.NP;
   int rc;
-  // workspace: omega (F, d) | phase (F) | weights (S, F) | eps (S, N) | G [S][NP] | T [S][NP] | V [S][NP] | extra
-  const int64_t n_omega = (int64_t)F * d, n_w = (int64_t)S * F, n_eps = (int64_t)S * N, n_sq = (int64_t)S * NP;
-  if ((rc = ensure(ctx, &ctx->paths, &ctx->cap_paths, n_omega + F + n_w + n_eps + 3 * n_sq + extra))) return rc;
-  double* om_d = ctx->paths;
-  double* ph_d = om_d + n_omega;
-  double* w_d = ph_d + F;
-  double* eps_d = w_d + n_w;
-  double* G = eps_d + n_eps;
-  double* T = G + n_sq;
-  double* V = T + n_sq;
-  GPBO_HIP(ctx, hipMemcpyAsync(om_d, omega, (size_t)n_omega * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  GPBO_HIP(ctx, hipMemcpyAsync(ph_d, phase, (size_t)F * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  GPBO_HIP(ctx, hipMemcpyAsync(w_d, weights, (size_t)n_w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  GPBO_HIP(ctx, hipMemcpyAsync(eps_d, eps, (size_t)n_eps * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ws->omega = om_d; ws->phase = ph_d; ws->weights = w_d; ws->V = V; ws->extra = V + n_sq;
+  const PathBlock b = path_block(S, F, N, NP, m.d, n_runs);
+  if ((rc = ensure(ctx, &ctx->paths, &ctx->cap_paths, b.doubles))) return rc;
+  *ws = {ctx->paths, b};
+  double *eps_d = ws->p(b.eps), *G = ws->p(b.G), *T = ws->p(b.T);
+  GPBO_HIP(ctx, hipMemcpyAsync(ws->p(b.omega), omega, (size_t)(b.phase - b.omega) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  GPBO_HIP(ctx, hipMemcpyAsync(ws->p(b.phase), phase, (size_t)F * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  GPBO_HIP(ctx, hipMemcpyAsync(ws->p(b.weights), weights, (size_t)(b.eps - b.weights) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  GPBO_HIP(ctx, hipMemcpyAsync(eps_d, eps, (size_t)(b.G - b.eps) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   // g_s(X): the prior draws at the train points, by the kernel the candidates get
   PathEvalArgs a = path_eval_args(m, *ws, S, F);
   a.P = m.Xs; a.out = G; a.M = N; a.ld = NP; a.N = 0; a.negate = 0; a.y_mean = 0.0; a.y_std = 1.0;
   if ((rc = launch_path_eval(ctx, m, a))) return rc;
   path_t_kernel<<<dim3((unsigned)((NP + 3) / 4), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, G, eps_d, T, N, NP);
   GPBO_HIP(ctx, hipGetLastError());
-  path_v_kernel<<<dim3((unsigned)(NP / 64), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, T, m.alpha, V, N, NP);
+  path_v_kernel<<<dim3((unsigned)(NP / 64), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, T, m.alpha, ws->p(b.V), N, NP);
   GPBO_HIP(ctx, hipGetLastError());
   return GPBO_OK;
 }
 
 // The S paths of gpbo_sample_paths over the M resident candidates: the negated values land in ctx->ys as S rows of M (the
-// selection's keys), nothing of the slot or the candidates is written.  The caller has checked every argument.  extra / ws: as
+// selection's keys), nothing of the slot or the candidates is written.  The caller has checked every argument.  n_runs / ws: as
 // launch_path_weights (gpbo_ascend_paths goes on from the same workspace).
 int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int S, int F, const double* omega,
-                        const double* phase, const double* weights, const double* eps, int64_t extra, PathWorkspace* ws_out) {
+                        const double* phase, const double* weights, const double* eps, int n_runs, PathWorkspace* ws_out) {
   int rc;
-  PathWorkspace ws{};
-  if ((rc = launch_path_weights(ctx, m, S, F, omega, phase, weights, eps, extra, &ws))) return rc;
-  if (ws_out) *ws_out = ws;
+  if ((rc = launch_path_weights(ctx, m, S, F, omega, phase, weights, eps, n_runs, ws_out))) return rc;
+  const PathWorkspace& ws = *ws_out;
   const int64_t Mp = round_up(M, POST_CANDS);
   if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * m.DP))) return rc;
   if ((rc = launch_prescale(ctx, ctx->Xc, M, m.d, m.DP, m.ls, ctx->Xcs, Mp))) return rc;

@@ -83,13 +83,22 @@ class GpEngine:
             _lib.raise_for_status(self._lib, None, rc)
         self._h = h
         self.device = int(device)
+        self._init_state()
+
+    def _init_state(self):
+        """Every host-side attribute of an engine whose context exists (a device group: its first device's)."""
         self.n_candidates = 0
         self.world_size = 1
         self.rank = 0
         self._serial: dict[int, int] = {}    # slot -> number of times its factorisation was rewritten
         self._overlap_depth = 0              # > 0 inside overlapped_fits()
         self._pending_fits: set[int] = set()  # slots with a gpbo_fit_begin not yet waited for
+        self._pending_inputs: dict[int, tuple] = {}   # ... and the arrays that fit reads until it is waited for
         self._scaled: dict[int, tuple[float, float]] = {}   # slot -> (amplitude, white) of its scaled fit (absent: 1, 0)
+        self._n_obs: dict[int, tuple[int, int]] = {}   # slot -> (observations, dimensions) of its fit: the path draws' shapes
+        self._cand_dim = None                # columns of the resident candidates the engine generated itself
+        self._resident = False               # (device groups: the candidate shards are in place)
+        self.last_polish: dict = {}          # nit / nfev / rounds of the last polish_seeds
         self.timing = True                   # the calls record their HIP event pairs (set_timing)
 
     # -- lifecycle ---------------------------------------------------------------------------
@@ -150,7 +159,6 @@ class GpEngine:
         info = C.c_int(0)
         self._settle(slot)
         self._touch(slot)
-        self._n_obs = getattr(self, "_n_obs", {})
         self._n_obs[int(slot)] = (int(X.shape[0]), int(X.shape[1]))      # sample_paths checks the shapes of its draws against it
         if scaled:
             # gpbo_fit_begin has no scaled twin: inside overlapped_fits() a scaled fit runs here and now, on the context's own stream
@@ -171,7 +179,6 @@ class GpEngine:
             self._check(rc)
             self._pending_fits.add(int(slot))
             # gpbo_fit_begin copies X / y asynchronously: the arrays it was given stay referenced until the fit is waited for
-            self._pending_inputs = getattr(self, "_pending_inputs", {})
             self._pending_inputs[int(slot)] = (X, y_norm, ls)
             return self._touch(slot)
         rc = self._lib.gpbo_fit(self._h, int(slot), dptr(X), dptr(y_norm), X.shape[0], X.shape[1], int(kernel),
@@ -218,7 +225,7 @@ class GpEngine:
         self._pending_fits.discard(int(slot))
         info = C.c_int(0)
         rc = self._lib.gpbo_fit_wait(self._h, int(slot), C.byref(info))
-        getattr(self, "_pending_inputs", {}).pop(int(slot), None)
+        self._pending_inputs.pop(int(slot), None)
         self._check(rc, info.value)
 
     def _settle(self, slot=None):
@@ -247,7 +254,6 @@ class GpEngine:
         rc = self._lib.gpbo_fit_append(self._h, int(slot), dptr(x_new) if x_new.shape[0] else None, x_new.shape[0],
                                        x_new.shape[1], dptr(y_norm), y_norm.shape[0], C.byref(info))
         self._check(rc, info.value)
-        self._n_obs = getattr(self, "_n_obs", {})
         self._n_obs[int(slot)] = (int(y_norm.shape[0]), int(x_new.shape[1]))
         return self._touch(slot)
 
@@ -390,7 +396,7 @@ class GpEngine:
         ls = np.ascontiguousarray(np.atleast_1d(np.asarray(length_scale, dtype=np.float64)))
         val = C.c_double(0.0)
         self._scaled.pop(int(slot), None)
-        getattr(self, "_n_obs", {}).pop(int(slot), None)      # the slot is left unfitted
+        self._n_obs.pop(int(slot), None)      # the slot is left unfitted
         if scaled or (scaled is None and _is_scaled(amplitude, white)):
             grad = np.zeros(ls.shape[0] + 2)
             info = C.c_int(0)
@@ -579,28 +585,35 @@ class GpEngine:
                                                      C.byref(route)))
         return (mu, sd, int(route.value)) if return_route else (mu, sd)
 
-    def sample_paths(self, omega, phase, weights, eps, slot=0, y_mean=0.0, y_std=1.0, index_offset=0, return_values=False):
-        """S = weights.shape[0] <= 16 function draws from the slot's posterior over the resident candidates and each draw's
-        maximiser (gpbo_sample_paths: Matheron's rule over F random Fourier features; include/gpbo.h has the formulas).
-        omega (F, d): frequencies in turns per unit of the length-scaled input; phase (F,): turns; weights (S, F); eps (S, N): the
-        noise draws in normalised-target units.  Returns (best_idx (S,) int64, best_val (S,), values (S, M) or None).  A reader:
-        the slot's fit, its resident posterior and the candidates stay as they were."""
+    def _path_inputs(self, who, omega, phase, weights, eps, slot):
+        """The draws of `sample_paths` / `ascend_paths` as contiguous float64 arrays, checked against each other and against the
+        slot's fit; with the fit's (observations, dimensions)."""
         self._settle(slot)
         omega = np.ascontiguousarray(omega, dtype=np.float64)
         phase = np.ascontiguousarray(phase, dtype=np.float64).ravel()
         weights = np.ascontiguousarray(weights, dtype=np.float64)
         eps = np.ascontiguousarray(eps, dtype=np.float64)
         if omega.ndim != 2 or weights.ndim != 2 or eps.ndim != 2:
-            raise ValueError("sample_paths: omega (F, d), weights (S, F) and eps (S, N) must be 2-D")
+            raise ValueError(f"{who}: omega (F, d), weights (S, F) and eps (S, N) must be 2-D")
         F, S = omega.shape[0], weights.shape[0]
         if phase.shape[0] != F or weights.shape[1] != F or eps.shape[0] != S:
-            raise ValueError("sample_paths: phase (F,), weights (S, F) and eps (S, N) do not fit omega (F, d)")
-        shape = getattr(self, "_n_obs", {}).get(int(slot))
+            raise ValueError(f"{who}: phase (F,), weights (S, F) and eps (S, N) do not fit omega (F, d)")
+        shape = self._n_obs.get(int(slot))
         if shape is None:
-            raise _lib.GpboError("sample_paths: model slot has not been fitted")
+            raise _lib.GpboError(f"{who}: model slot has not been fitted")
         if (eps.shape[1], omega.shape[1]) != shape:
-            raise ValueError(f"sample_paths: eps (S, {eps.shape[1]}) / omega (F, {omega.shape[1]}) do not fit the slot's model of "
+            raise ValueError(f"{who}: eps (S, {eps.shape[1]}) / omega (F, {omega.shape[1]}) do not fit the slot's model of "
                              f"{shape[0]} observations in {shape[1]} dimensions")
+        return omega, phase, weights, eps, shape
+
+    def sample_paths(self, omega, phase, weights, eps, slot=0, y_mean=0.0, y_std=1.0, index_offset=0, return_values=False):
+        """S = weights.shape[0] <= 16 function draws from the slot's posterior over the resident candidates and each draw's
+        maximiser (gpbo_sample_paths: Matheron's rule over F random Fourier features; include/gpbo.h has the formulas).
+        omega (F, d): frequencies in turns per unit of the length-scaled input; phase (F,): turns; weights (S, F); eps (S, N): the
+        noise draws in normalised-target units.  Returns (best_idx (S,) int64, best_val (S,), values (S, M) or None).  A reader:
+        the slot's fit, its resident posterior and the candidates stay as they were."""
+        omega, phase, weights, eps, _ = self._path_inputs("sample_paths", omega, phase, weights, eps, slot)
+        F, S = omega.shape[0], weights.shape[0]
         M = max(int(self.n_candidates), 0)
         best_idx = np.empty(max(S, 1), dtype=np.int64)
         best_val = np.empty(max(S, 1))
@@ -624,22 +637,8 @@ class GpEngine:
             winner (S,), x_best (S, d), f_best (S,): per draw the run with the largest finite f, ties to the lowest start
             (winner -1, NaN rows: no run of the draw has a finite value).
         A reader: the slot's fit, its resident posterior and the candidates stay as they were."""
-        self._settle(slot)
-        omega = np.ascontiguousarray(omega, dtype=np.float64)
-        phase = np.ascontiguousarray(phase, dtype=np.float64).ravel()
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        eps = np.ascontiguousarray(eps, dtype=np.float64)
-        if omega.ndim != 2 or weights.ndim != 2 or eps.ndim != 2:
-            raise ValueError("ascend_paths: omega (F, d), weights (S, F) and eps (S, N) must be 2-D")
+        omega, phase, weights, eps, shape = self._path_inputs("ascend_paths", omega, phase, weights, eps, slot)
         F, S = omega.shape[0], weights.shape[0]
-        if phase.shape[0] != F or weights.shape[1] != F or eps.shape[0] != S:
-            raise ValueError("ascend_paths: phase (F,), weights (S, F) and eps (S, N) do not fit omega (F, d)")
-        shape = getattr(self, "_n_obs", {}).get(int(slot))
-        if shape is None:
-            raise _lib.GpboError("ascend_paths: model slot has not been fitted")
-        if (eps.shape[1], omega.shape[1]) != shape:
-            raise ValueError(f"ascend_paths: eps (S, {eps.shape[1]}) / omega (F, {omega.shape[1]}) do not fit the slot's model of "
-                             f"{shape[0]} observations in {shape[1]} dimensions")
         d = int(shape[1])
         lo = np.ascontiguousarray(box_lo, dtype=np.float64).ravel()
         hi = np.ascontiguousarray(box_hi, dtype=np.float64).ravel()
@@ -1050,15 +1049,10 @@ class GroupEngine(GpEngine):
         self._h = C.c_void_p(self._lib.gpbo_group_ctx(g, 0))     # borrowed: the first device's context
         self.devices = devices
         self.device = devices[0]
-        self.n_candidates = 0
+        # as a single engine's: fits are synchronous on every device and scaled kernels refused, so _pending_fits and _scaled stay
+        # empty and overlapped_fits() is a plain block; _resident: the shards are in place (a small predict on device 0 clobbers them)
+        self._init_state()
         self.world_size = len(devices)
-        self.rank = 0
-        self._serial = {}
-        self._overlap_depth = 0     # group fits are synchronous on every device: overlapped_fits() is a plain block
-        self._pending_fits = set()  # (never filled: the inherited accessors only look at it)
-        self._scaled = {}           # (never filled: a device group refuses scaled kernels)
-        self.timing = True
-        self._resident = False      # the group's candidate shards are in place (a small predict on device 0 clobbers them)
         self.collective = self._lib.gpbo_group_collective(g).decode()
         self._orphans = []          # arrays of failed calls (see _gcheck)
 

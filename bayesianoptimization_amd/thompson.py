@@ -18,14 +18,13 @@ import warnings
 import numpy as np
 
 from . import fused_acquisition as A
+# draws one sample_paths call evaluates side by side, features per draw, starts per draw one ascend_paths call climbs from
+from ._lib import MAX_PATH_FEATURES as MAX_FEATURES, MAX_PATH_STARTS as MAX_STARTS, MAX_PATHS
 from .engine import GroupEngine
 from .gpr import HipGPR
 
 #: the kernel kinds of include/gpbo.h -> Matern nu (RBF: the Gaussian spectrum)
 _NU = {1: 2.5, 2: 1.5, 3: 0.5}
-MAX_PATHS = 16                  # GPBO_MAX_PATHS: draws one sample_paths call evaluates side by side
-MAX_FEATURES = 4096             # GPBO_MAX_PATH_FEATURES
-MAX_STARTS = 8                  # GPBO_MAX_PATH_STARTS: starts per draw one ascend_paths call climbs from
 
 
 def spectral_draw(kind: int, n_features: int, d: int, random_state):

@@ -173,6 +173,9 @@ def test_abi_version_and_load():
     assert lib.gpbo_abi_version() == _lib.ABI_VERSION
     hdr = open(HEADER).read()
     assert f"#define GPBO_ABI_VERSION {_lib.ABI_VERSION}" in hdr
+    # ... and the limits the Python side restates
+    for name in ("MAX_MODELS", "MAX_DIM", "MAX_SEEDS", "MAX_PATHS", "MAX_PATH_FEATURES", "MAX_PATH_STARTS"):
+        assert re.search(rf"^#define GPBO_{name} {getattr(_lib, name)}\b", hdr, flags=re.M), name
 
 
 def test_no_gpu_means_loud_failure():

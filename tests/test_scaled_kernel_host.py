@@ -346,7 +346,8 @@ def test_gpengine_runs_a_scaled_fit_synchronously_inside_overlapped_fits():
             return call
 
     eng = object.__new__(E.GpEngine)
-    eng._lib, eng._h, eng._serial, eng._overlap_depth, eng._pending_fits, eng._scaled = Lib(), None, {}, 0, set(), {}
+    eng._lib, eng._h = Lib(), None
+    eng._init_state()
     X, y = S.data(8, 2)
     with eng.overlapped_fits():
         eng.fit(X, y, E.MATERN25, 1.0, S.ALPHA, slot=1)
