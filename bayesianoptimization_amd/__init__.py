@@ -7,7 +7,8 @@ built library and an AMD GPU.
 __version__ = "0.1.0"
 
 __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate", "suggest_batch", "UpperConfidenceBound",
-           "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement", "suggest_thompson"]
+           "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement", "suggest_thompson",
+           "suggest_mes"]
 
 
 def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must not need sklearn/scipy
@@ -32,6 +33,9 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name == "suggest_thompson":
         from .thompson import suggest_thompson
         return suggest_thompson
+    if name == "suggest_mes":
+        from .mes import suggest_mes
+        return suggest_mes
     if name in ("UpperConfidenceBound", "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement",
                 "AcquisitionFunction"):
         from . import fused_acquisition as acquisition

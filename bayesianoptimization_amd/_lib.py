@@ -22,7 +22,8 @@ MAX_SEEDS = 64
 MAX_PATHS = 16
 MAX_PATH_FEATURES = 4096
 MAX_PATH_STARTS = 8
-ABI_VERSION = 3
+MAX_MES_SAMPLES = 64
+ABI_VERSION = 4
 
 _c_double_p = C.POINTER(C.c_double)
 _c_int64_p = C.POINTER(C.c_int64)
@@ -88,6 +89,8 @@ SIGNATURES = {
                                     _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "gpbo_acq_argbest": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, _c_double_p,
                                    _c_double_p, C.c_int, C.c_int64, _c_int64_p, _c_double_p, _c_int64_p,
+                                   _c_double_p, _c_double_p]),
+    "gpbo_mes_argbest": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int64, _c_int64_p, _c_double_p, _c_int64_p,
                                    _c_double_p, _c_double_p]),
     "gpbo_last_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
     "gpbo_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -46,6 +46,7 @@ SOURCES = {
     "fused_small.hip": [],                     # fit / LML evaluation of a small problem (NP <= 64) as ONE launch of ONE workgroup
     "mid_fit.hip": [],                         # 64 < NP <= 768: inputs, quarter-tile K, W = L^-1 by column strips, alpha (~15 launches per fit)
     "acq_kernels.hip": ["-ffp-contract=off"],  # elementwise formulas follow NumPy op by op
+    "mes.hip": ["-ffp-contract=off"],         # gpbo_mes_argbest: max-value entropy search values (acq_formulas.h's pieces, the bits they have in acq_kernels.hip)
     "candidates.hip": [],
     "mt19937.hip": ["-ffp-contract=off"],      # lo + (hi - lo) * u as NumPy computes it
     "mt_jump.hip": [],                         # jump-ahead polynomials (host) + sub-stream start states (device)

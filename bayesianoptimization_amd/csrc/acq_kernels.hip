@@ -546,12 +546,9 @@ static void best_of_selection(const SelState& st, const Key& first, int64_t offs
   *best_val = nan ? std::numeric_limits<double>::quiet_NaN() : first.v;
 }
 
-int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, int64_t offset,
-                       int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val) {
-  SelState* st; Key* picks; int npass;
-  int rc = enqueue_acq_select(ctx, a, M, k_seeds, &st, &picks, &npass);
-  if (rc) return rc;
-  // results -> pinned host staging
+// an enqueued selection's records -> the caller's arg-best and seeds, through the pinned host staging; synchronises
+static int fetch_selection(gpbo_ctx* ctx, const SelState* st, int npass, int k_seeds, int64_t offset, int64_t* best_idx,
+                           double* best_val, int64_t* seed_idx, double* seed_val) {
   static_assert(sizeof(SelState) + sizeof(Key) * (GPBO_MAX_SEEDS + 1) <= PIN_AUX_SEL_OUT_BYTES, "selection results outgrew their window");
   char* hp = (char*)ctx->pinned_aux + PIN_AUX_SEL_OUT;
   GPBO_HIP(ctx, hipMemcpyAsync(hp, st, sizeof(SelState) + sizeof(Key) * npass, hipMemcpyDeviceToHost, ctx->stream));
@@ -564,6 +561,25 @@ int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, 
     seed_val[t] = hpicks[t].v;
   }
   return GPBO_OK;
+}
+
+int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, int64_t offset,
+                       int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val) {
+  SelState* st; Key* picks; int npass;
+  int rc = enqueue_acq_select(ctx, a, M, k_seeds, &st, &picks, &npass);
+  if (rc) return rc;
+  return fetch_selection(ctx, st, npass, k_seeds, offset, best_idx, best_val, seed_idx, seed_val);
+}
+
+// gpbo_mes_argbest: launch_acq_argbest's selection and outputs over the values ALREADY in ctx->ys[0..M) (mes.hip wrote them), by
+// the same choice of form (one or two picks: the passes; more: threshold + ranks, reading the stored values)
+int launch_values_argbest(gpbo_ctx* ctx, int64_t M, int k_seeds, int64_t offset, int64_t* best_idx, double* best_val,
+                          int64_t* seed_idx, double* seed_val) {
+  SelState* st; Key* picks;
+  const int npass = k_seeds > 0 ? k_seeds : 1;
+  int rc = enqueue_select(ctx, M, npass, select_v2_enabled() && npass >= 3, &st, &picks);
+  if (rc) return rc;
+  return fetch_selection(ctx, st, npass, k_seeds, offset, best_idx, best_val, seed_idx, seed_val);
 }
 
 // gpbo_sample_paths (k = 1, top_idx null) / gpbo_ascend_paths: the k best of each of n_rows rows of M keys (rows[r * ld ...]) by the

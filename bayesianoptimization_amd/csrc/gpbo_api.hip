@@ -1383,6 +1383,30 @@ int gpbo_acq_argbest(gpbo_ctx* ctx, int acq, double acq_param, double y_max, int
   return GPBO_OK;
 }
 
+int gpbo_mes_argbest(gpbo_ctx* ctx, int n_samples, const double* y_star, int k_seeds, int64_t index_offset, int64_t* best_idx,
+                     double* best_val, int64_t* seed_idx, double* seed_val, double* ys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (n_samples < 1 || n_samples > GPBO_MAX_MES_SAMPLES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mes_argbest: n_samples out of range [1, 64]");
+  if (!y_star) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mes_argbest: NULL y_star");
+  for (int s = 0; s < n_samples; ++s)
+    if (!std::isfinite(y_star[s])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mes_argbest: y_star must be finite");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mes_argbest: k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mes_argbest: NULL output");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  const Model& m = ctx->models[0];
+  if (!m.fitted || m.M_post != ctx->M || ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "mes_argbest: run gpbo_posterior for slot 0 first");
+  ev_begin(ctx, T_ACQ);
+  int rc = launch_mes_values(ctx, m, ctx->M, n_samples, y_star);
+  if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  ev_end(ctx, T_ACQ);
+  if (rc) return rc;
+  if (ys_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(ys_out, ctx->ys, (size_t)ctx->M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GPBO_OK;
+}
+
 int gpbo_set_timing(gpbo_ctx* ctx, int on) {
   if (!ctx) return GPBO_ERR_INVALID;
   ctx->timing_off = !on;

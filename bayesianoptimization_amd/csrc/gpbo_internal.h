@@ -614,6 +614,12 @@ struct AcqArgs {
 };
 int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, int64_t offset,
                        int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val);
+// acq_kernels.hip: launch_acq_argbest's selection and outputs over the values already in ctx->ys[0..M); synchronises
+int launch_values_argbest(gpbo_ctx* ctx, int64_t M, int k_seeds, int64_t offset, int64_t* best_idx, double* best_val,
+                          int64_t* seed_idx, double* seed_val);
+// mes.hip: ctx->ys[i] = -a(x_i), the negated max-value entropy search value of the M resident candidates from m's resident mu / sd
+// and n_samples <= GPBO_MAX_MES_SAMPLES sampled maxima y_star (host; they travel in the kernel's arguments)
+int launch_mes_values(gpbo_ctx* ctx, const Model& m, int64_t M, int n_samples, const double* y_star);
 // acq_kernels.hip: the k best of each of n_rows rows of M keys (rows + r * ld), the rules of launch_acq_argbest: best_idx / best_val
 // (n_rows) the arg-best, top_idx (n_rows, k; may be null) the rows' k smallest keys in order (ties to the lowest index, NaNs last)
 // as LOCAL indices; synchronises

@@ -827,6 +827,23 @@ class GpEngine:
         self._check(rc)
         return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
 
+    def mes_argbest(self, y_star, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
+        """Max-value entropy search over the resident candidates (gpbo_mes_argbest; include/gpbo.h has the formulas): ys = -a, a
+        the mean over the S <= 64 sampled maxima `y_star` (raw target units) of h((y* - mu) / sd), from slot 0's resident
+        posterior.  Returns (best_idx, best_val, seed_idx, seed_val, ys|None) as `acq_argbest`.  A reader: the fit, the resident
+        posterior and the candidates stay as they were."""
+        y_star = np.ascontiguousarray(np.atleast_1d(np.asarray(y_star, dtype=np.float64)))
+        if y_star.ndim != 1:
+            raise ValueError("mes_argbest: y_star must be one-dimensional")
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        k_seeds = int(k_seeds)
+        seed_idx = np.full(max(k_seeds, 1), -1, dtype=np.int64)
+        seed_val = np.full(max(k_seeds, 1), np.nan)
+        ys = np.empty(max(int(self.n_candidates), 0)) if return_values else None
+        self._check(self._lib.gpbo_mes_argbest(self._h, int(y_star.shape[0]), dptr(y_star), k_seeds, int(index_offset),
+                                               C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
+        return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
+
     # -- timing / probes (debug_* and the latency / hybrid probes need GpEngine(debug=True)) ----------------------------
     def _need_debug(self, what: str):
         if not getattr(self, "debug", False):
@@ -1278,6 +1295,9 @@ class GroupEngine(GpEngine):
     def ascend_paths(self, omega, phase, weights, eps, box_lo, box_hi, n_starts=4, starts=None, max_iter=-1, slot=0, y_mean=0.0,
                      y_std=1.0, index_offset=0, return_gradient=False):
         raise NotImplementedError("a device group has no path ascent (gpbo_ascend_paths is per context); use a single device")
+
+    def mes_argbest(self, y_star, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
+        raise NotImplementedError("a device group has no max-value entropy search (gpbo_mes_argbest is per context); use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
         raise NotImplementedError("a device group has no posterior refresh path (gpbo_posterior_refresh is per context); "

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GPBO_ABI_VERSION 3
+#define GPBO_ABI_VERSION 4
 
 enum gpbo_status {
   GPBO_OK = 0,
@@ -428,6 +428,37 @@ int gpbo_acq_argbest(gpbo_ctx* ctx, int acq, double acq_param, double y_max, int
                      const double* lb, const double* ub, int k_seeds, int64_t index_offset,
                      int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val,
                      double* ys_out);
+
+/* Max-value entropy search (MES; Wang & Jegelka 2017, "Max-value entropy search for efficient Bayesian optimization") over the
+ * resident candidates: the acquisition built on the VALUE of a posterior draw's maximum, which Thompson sampling discards.  No
+ * incumbent, no xi or kappa.  From slot 0's resident mu / sd (gpbo_posterior / gpbo_posterior_refresh) and n_samples = S sampled
+ * maxima y_star (S,), in raw target units — the units of that mu; gpbo_ascend_paths' f_out / gpbo_sample_paths' best_val supply them:
+ *   gamma_s(x) = (y_star[s] - mu(x)) / sd(x)
+ *   a(x)       = 1/S sum_s h(gamma_s(x)),      h(g) = g phi(g) / (2 Phi(g)) - log Phi(g)
+ *   ys         = -a                            the reduction of the maximum's entropy from observing x, negated
+ * h >= 0 is strictly decreasing, so ys <= 0.  It is evaluated over three ranges:
+ *   -1 < g <= 0   as written (Phi, phi as gpbo_acq_argbest's EI evaluates them);
+ *   g > 0         through the complement q = Phi(-g) = erfc(g / sqrt2) / 2: h = g phi / (2 (1 - q)) - log1p(-q) — log of a Phi rounded
+ *                 next to 1 is 0.2 % off at g = 8 and 0.9 % at g = 15; h is subnormal above g ~ 37 and exactly 0 from g = 40 on;
+ *   g <= -1       the two halves each grow like g^2 / 2 and cancel: with r = 1 + g Phi / phi as GPBO_ACQ_LOG_EI forms it (erfcx down
+ *                 to g = -28, the asymptotic series below) and the lower-tail Mills ratio m = (1 - r) / (-g) = Phi / phi,
+ *                 h = g r / (2 m) + log(2 pi) / 2 - log m, which grows like log|g| (below g = -1e150 its limit
+ *                 -1/2 + log(2 pi) / 2 + log(-g) is taken; +inf at -inf).
+ * Relative error against a (1 + g^2) eps model: the division that made g carries that much.
+ * Conventions: a clipped variance (sd == 0) gives a = 0 — the point carries no information — unless mu is NaN; a NaN mu or sd gives
+ * NaN, and the selection's "first NaN wins" rule applies.  The sum over s runs s = 0 .. S - 1 in that order, then one division by S:
+ * a candidate's bits depend neither on M nor on the other candidates.  fp64 whatever the slot's precision.
+ * Outputs as gpbo_acq_argbest on the key ys: best_idx / best_val = argmin / min (first NaN wins); seed_idx / seed_val (k_seeds,) =
+ * argsort(ys)[:k] with ties -> lowest index and NaNs last (k_seeds may be 0, seed_* NULL); ys_out (M,) optional; index_offset is
+ * added to every returned index.
+ * A reader: the slot's fit, its resident mu / sd, what gpbo_posterior_refresh may still refresh, the candidates and the
+ * negative-variance flag stay as they were; only the context's acquisition values (gpbo_acq_argbest's ys) are overwritten.
+ * GPBO_ERR_INVALID: n_samples outside [1, GPBO_MAX_MES_SAMPLES], a NULL or non-finite y_star, k_seeds outside [0, GPBO_MAX_SEEDS],
+ * a NULL best_idx / best_val (seed_idx / seed_val with k_seeds > 0).  GPBO_ERR_STATE: as gpbo_acq_argbest — slot 0 unfitted, no
+ * candidates, no resident posterior for them.  There is no gpbo_group_* / gpbo_comm_* form. */
+#define GPBO_MAX_MES_SAMPLES 64
+int gpbo_mes_argbest(gpbo_ctx* ctx, int n_samples, const double* y_star, int k_seeds, int64_t index_offset,
+                     int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val, double* ys_out);
 
 /* ---- timing (HIP events on the context stream) ------------------------------------------ */
 /* Milliseconds spent in the last call's kernels: [0] fit total, [1] posterior main kernel,
