@@ -1,0 +1,98 @@
+"""What suggest_batch (batch.py), suggest_thompson (thompson.py) and suggest_mes (mes.py) share, each thing once: the check of a count
+argument, the gate an optimizer passes before anything runs, the frame of the fitted model, and the loop over groups of posterior
+draws.  The ORDER of the refusals is part of the three functions' contract: a caller's own argument checks come
+first, then `gate`, then whatever it checks about `refine` — so an un-accelerated optimizer is refused as such, whatever else is
+wrong with the call.
+"""
+from __future__ import annotations
+
+import warnings
+from collections import namedtuple
+
+import numpy as np
+
+from . import fused_acquisition as A
+from ._lib import MAX_PATHS
+from .engine import GroupEngine
+from .gpr import HipGPR
+
+
+def count(value, lo: int, hi, message: str, out_of_range=None) -> int:
+    """`value` as an int if it is an integer (a bool is none) in [lo, hi] (hi None: no upper end), else ValueError(message) — an
+    integer outside the range says `out_of_range` where that is given."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError(message)
+    value = int(value)
+    if value < lo or (hi is not None and value > hi):
+        raise ValueError(message if out_of_range is None else out_of_range)
+    return value
+
+
+def gate(optimizer, who: str, word: str, calls, group: str):
+    """(gp, space, engine) of an optimizer whose model `who` can work on, else the refusal — in this order: the GP is not a HipGPR on
+    slot 0, the space is empty, it has a constraint, it has an input transform, the engine is a device group (`group`: the sentence
+    that says what a group lacks), the engine lacks one of `calls`, the model runs on the host.  `word`: "sampled" / "batched"."""
+    gp, space = optimizer._gp, optimizer._space
+    if not isinstance(gp, HipGPR) or gp.slot != 0:
+        raise NotImplementedError(f"{who}: the optimizer's GP is not on the engine (call accelerate(optimizer) first)")
+    if len(space) == 0:
+        raise A.TargetSpaceEmptyError(A.EMPTY_SPACE_MESSAGE)
+    if space.constraint is not None:
+        raise A.ConstraintNotSupportedError(f"Received constraints, but {who} does not support constrained optimization.")
+    if gp.transform is not None:
+        raise NotImplementedError(f"{who}: the space has an input transform (int / categorical parameters); "
+                                  f"only all-float spaces are {word}")
+    eng = gp._engine()
+    if isinstance(eng, GroupEngine):
+        raise NotImplementedError(f"{who}: {group}")
+    if not all(hasattr(eng, call) for call in calls):
+        raise NotImplementedError(f"{who}: the engine has no {' / '.join(calls)}")
+    from sklearn.base import clone
+
+    reason = None if gp.kernel is None else gp._unsupported_reason(clone(gp.kernel), space.target, space.params)
+    if reason is not None:
+        raise NotImplementedError(f"{who}: the model runs on the host ({reason}); only models on the device path are {word}")
+    return gp, space, eng
+
+
+#: the fitted model as the suggest functions read it.  scale: the slot's (amplitude, white), None for a unit model; noise: the
+#: estimator's alpha (+ the WhiteKernel's level for a scaled model)
+Model = namedtuple("Model", "d N y_mean y_std scale noise")
+
+
+def read_model(gp, space, who: str) -> Model:
+    """The frame of a model that has just been fitted (by `fit_model`, or by the policy's own suggest)."""
+    if gp._host_mode:      # (unreachable after the gate; a host model must not get this far silently)
+        raise NotImplementedError(f"{who}: the model was fitted on the host")
+    scale = gp.__dict__.get("_scale")
+    return Model(d=int(space.bounds.shape[0]), N=int(gp.X_train_.shape[0]), y_mean=float(gp._y_train_mean),
+                 y_std=float(gp._y_train_std), scale=scale, noise=float(gp.alpha) + (0.0 if scale is None else float(scale[1])))
+
+
+def fit_model(gp, space, who: str) -> Model:
+    """`gp.fit` on the real data, warnings silenced (theta search and its RandomState draws included), and its frame."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        gp.fit(space.params, space.target)
+    return read_model(gp, space, who)
+
+
+def draw_groups(gp, space, eng, rng, model: Model, n_draws: int, n_features: int, refine: int, max_iter):
+    """`n_draws` posterior function draws over the resident candidates in groups of at most 16, one engine call per group: yields
+    (first, S, result) with result what `ascend_paths(n_starts=refine)` returns, or with refine = 0 `sample_paths`.  Per group the
+    draws from `rng`, in this order: `spectral_draw` (fresh features), `standard_normal((S, F))` — the feature weights —,
+    `standard_normal((S, N))` scaled by sqrt(noise) — the noise draws.  The engine call draws nothing."""
+    from .thompson import spectral_draw
+
+    for first in range(0, n_draws, MAX_PATHS):
+        S = min(MAX_PATHS, n_draws - first)
+        omega, phase = spectral_draw(gp._kind, n_features, model.d, rng)
+        weights = rng.standard_normal((S, n_features))
+        eps = rng.standard_normal((S, model.N)) * np.sqrt(model.noise)
+        gp._ensure_resident()
+        if refine:
+            yield first, S, eng.ascend_paths(omega, phase, weights, eps, space.bounds[:, 0], space.bounds[:, 1], n_starts=refine,
+                                             max_iter=-1 if max_iter is None else int(max_iter), slot=gp.slot,
+                                             y_mean=model.y_mean, y_std=model.y_std)
+        else:
+            yield first, S, eng.sample_paths(omega, phase, weights, eps, slot=gp.slot, y_mean=model.y_mean, y_std=model.y_std)

@@ -14,9 +14,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _suggest as S
 from . import fused_acquisition as A
-from .engine import GroupEngine
-from .gpr import HipGPR
 
 _STOCK = (A.UpperConfidenceBound, A.ExpectedImprovement, A.ProbabilityOfImprovement, A.LogExpectedImprovement)
 
@@ -59,55 +58,27 @@ def suggest_batch(optimizer, q: int, strategy="max", n_random: int | None = None
     NotImplementedError, never a host fallback, for: a space with an input transform (int / categorical parameters), a policy
     other than stock UCB / EI / POI / log EI, a model in host mode (a kernel outside the device path), a device group.  q = 1 is valid;
     q < 1 is a ValueError."""
-    if isinstance(q, bool) or not isinstance(q, (int, np.integer)):
-        raise ValueError("q must be an integer >= 1")
-    q = int(q)
-    if q < 1:
-        raise ValueError("q must be >= 1")
+    q = S.count(q, 1, None, "q must be an integer >= 1", "q must be >= 1")
     fn = optimizer._acquisition_function
-    gp = optimizer._gp
-    space = optimizer._space
     if type(fn) not in _STOCK:
         raise NotImplementedError(f"suggest_batch: the policy is {type(fn).__name__}; only stock UpperConfidenceBound / "
                                   "ExpectedImprovement / ProbabilityOfImprovement / LogExpectedImprovement of an accelerate()d "
                                   "optimizer are batched")
-    if not isinstance(gp, HipGPR) or gp.slot != 0:
-        raise NotImplementedError("suggest_batch: the optimizer's GP is not on the engine (call accelerate(optimizer) first)")
-    if len(space) == 0:
-        raise A.TargetSpaceEmptyError("Cannot suggest a point without previous samples. Use "
-                                      " target_space.random_sample() to generate a point and "
-                                      " target_space.probe(*) to evaluate it.")
-    if space.constraint is not None:
-        raise A.ConstraintNotSupportedError("Received constraints, but suggest_batch does not support constrained optimization.")
-    if gp.transform is not None:
-        raise NotImplementedError("suggest_batch: the space has an input transform (int / categorical parameters); "
-                                  "only all-float spaces are batched")
-    eng = gp._engine()
-    if isinstance(eng, GroupEngine):
-        raise NotImplementedError("suggest_batch: a device group has no posterior refresh path; use a single device")
-    if not hasattr(eng, "posterior_refresh"):
-        raise NotImplementedError("suggest_batch: the engine has no posterior_refresh")
-    from sklearn.base import clone
-
-    reason = None if gp.kernel is None else gp._unsupported_reason(clone(gp.kernel), space.target, space.params)
-    if reason is not None:
-        raise NotImplementedError(f"suggest_batch: the model runs on the host ({reason}); only models on the device path are batched")
+    gp, space, eng = S.gate(optimizer, "suggest_batch", "batched", ("posterior_refresh",),
+                            "a device group has no posterior refresh path; use a single device")
     lie = _lie(strategy, space.target)
     rng = optimizer._random_state
 
     # pick 1: the policy's own suggest(n_smart=0) — checks, fit, draw, full posterior, arg-best, bookkeeping
     picks = [np.asarray(fn.suggest(gp=gp, target_space=space, n_random=n_random, n_smart=0, fit_gp=True, random_state=rng),
                         dtype=np.float64)]
-    if gp._host_mode:      # (unreachable after the check above; a host model must not get this far silently)
-        raise NotImplementedError("suggest_batch: the model was fitted on the host")
+    model = S.read_model(gp, space, "suggest_batch")
     if q == 1:
         return [space.array_to_params(picks[0])]
-    d = int(space.bounds.shape[0])
-    y_mean, y_std = float(gp._y_train_mean), float(gp._y_train_std)
+    y_mean, y_std = model.y_mean, model.y_std
     y_real = np.asarray(gp.y_train_, dtype=np.float64).ravel()
     lie_norm = (lie - y_mean) / y_std
-    scale = gp.__dict__.get("_scale")
-    extra = {} if scale is None else {"amplitude": scale[0], "white": scale[1]}
+    extra = {} if model.scale is None else {"amplitude": model.scale[0], "white": model.scale[1]}
     improvement = isinstance(fn, A._ImprovementBased)
     if improvement:
         fn.y_max = max(float(fn.y_max), lie)       # the incumbent of a space that holds the lies (acquisition.py:1130-1143)
@@ -121,7 +92,7 @@ def suggest_batch(optimizer, q: int, strategy="max", n_random: int | None = None
             fn.i += 1
             best, _val, _seeds, _sv, _ys = eng.acq_argbest(fn._acq_kind, fn._acq_param(), fn.y_max if improvement else 0.0,
                                                            None, None, k_seeds=0)
-            picks.append(np.asarray(eng.get_candidate_rows(np.array([int(best)]), d)[0], dtype=np.float64))
+            picks.append(np.asarray(eng.get_candidate_rows(np.array([int(best)]), model.d)[0], dtype=np.float64))
             fn.decay_exploration()
     finally:
         # the slot goes back to the real data at the held theta, whatever happened above

@@ -54,6 +54,30 @@ def _is_scaled(amplitude, white) -> bool:
     return float(amplitude) != 1.0 or float(white) != 0.0
 
 
+def _model_arrays(X, y_norm, length_scale, check=True):
+    """(X, y_norm, length scales) as the library reads them: contiguous float64, y flat, the scales 1-D.  check: a fit's two refusals."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if check and X.ndim != 2:
+        raise ValueError("X must be 2-D (n_samples, n_features)")
+    y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
+    if check and y_norm.shape[0] != X.shape[0]:
+        raise ValueError("X and y have inconsistent numbers of samples")
+    return X, y_norm, np.ascontiguousarray(np.atleast_1d(np.asarray(length_scale, dtype=np.float64)))
+
+
+def _argbest_frame(lb, ub, k_seeds, n_values=None):
+    """The arrays every arg-best call hands to the library: (lb, ub, n_c, seed_idx, seed_val, ys).  lb / ub: contiguous float64 or None,
+    n_c their count; the seed records hold at least one entry (-1 / NaN: none); ys: room for `n_values` values (None: not asked for)."""
+    lb = np.ascontiguousarray(np.atleast_1d(np.asarray(lb, dtype=np.float64))) if lb is not None else None
+    ub = np.ascontiguousarray(np.atleast_1d(np.asarray(ub, dtype=np.float64))) if ub is not None else None
+    n_c = 0 if lb is None else lb.shape[0]
+    if n_c and (ub is None or ub.shape[0] != n_c):
+        raise ValueError("lb and ub must have the same length")
+    seed_idx = np.full(max(k_seeds, 1), -1, dtype=np.int64)
+    seed_val = np.full(max(k_seeds, 1), np.nan)
+    return lb, ub, n_c, seed_idx, seed_val, (None if n_values is None else np.empty(n_values))
+
+
 def path_winners(x, f) -> dict:
     """Per draw the winning run of `ascend_paths`: x (S, K, d), f (S, K) -> winner (S,) = the start with the largest finite f, ties
     to the lowest start (-1: none is finite), x_best (S, d), f_best (S,) (NaN where winner is -1)."""
@@ -149,13 +173,7 @@ class GpEngine:
         amplitude / white other than 1 / 0: the scaled model amplitude * k + (white + noise) * I (ConstantKernel * k + WhiteKernel
         under an estimator whose alpha is `noise`; gpbo_fit_scaled) — the slot's posteriors then carry amplitude and white."""
         scaled = _is_scaled(amplitude, white)
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        if X.ndim != 2:
-            raise ValueError("X must be 2-D (n_samples, n_features)")
-        y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
-        if y_norm.shape[0] != X.shape[0]:
-            raise ValueError("X and y have inconsistent numbers of samples")
-        ls = np.ascontiguousarray(np.atleast_1d(np.asarray(length_scale, dtype=np.float64)))
+        X, y_norm, ls = _model_arrays(X, y_norm, length_scale)
         info = C.c_int(0)
         self._settle(slot)
         self._touch(slot)
@@ -391,9 +409,7 @@ class GpEngine:
         in [log amplitude, log length_scale ..., log white].  scaled=True asks for that form whatever the two values are (a search
         over amplitude passes through 1)."""
         self._settle(slot)
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
-        ls = np.ascontiguousarray(np.atleast_1d(np.asarray(length_scale, dtype=np.float64)))
+        X, y_norm, ls = _model_arrays(X, y_norm, length_scale, check=False)
         val = C.c_double(0.0)
         self._scaled.pop(int(slot), None)
         self._n_obs.pop(int(slot), None)      # the slot is left unfitted
@@ -811,15 +827,8 @@ class GpEngine:
     def acq_argbest(self, acq: int, param: float, y_max: float = 0.0, lb=None, ub=None, k_seeds: int = 0,
                     index_offset: int = 0, return_values: bool = False):
         """ys = -acq [* p_c]; returns (best_idx, best_val, seed_idx, seed_val, ys|None)."""
-        lb = np.ascontiguousarray(np.atleast_1d(np.asarray(lb, dtype=np.float64))) if lb is not None else None
-        ub = np.ascontiguousarray(np.atleast_1d(np.asarray(ub, dtype=np.float64))) if ub is not None else None
-        n_c = 0 if lb is None else lb.shape[0]
-        if n_c and (ub is None or ub.shape[0] != n_c):
-            raise ValueError("lb and ub must have the same length")
+        lb, ub, n_c, seed_idx, seed_val, ys = _argbest_frame(lb, ub, k_seeds, self.n_candidates if return_values else None)
         best_idx, best_val = C.c_int64(0), C.c_double(0.0)
-        seed_idx = np.full(max(k_seeds, 1), -1, dtype=np.int64)
-        seed_val = np.full(max(k_seeds, 1), np.nan)
-        ys = np.empty(self.n_candidates) if return_values else None
         rc = self._lib.gpbo_acq_argbest(self._h, int(acq), float(param), float(y_max if y_max is not None else 0.0),
                                         n_c, dptr(lb), dptr(ub), int(k_seeds), int(index_offset),
                                         C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val),
@@ -835,11 +844,9 @@ class GpEngine:
         y_star = np.ascontiguousarray(np.atleast_1d(np.asarray(y_star, dtype=np.float64)))
         if y_star.ndim != 1:
             raise ValueError("mes_argbest: y_star must be one-dimensional")
-        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
         k_seeds = int(k_seeds)
-        seed_idx = np.full(max(k_seeds, 1), -1, dtype=np.int64)
-        seed_val = np.full(max(k_seeds, 1), np.nan)
-        ys = np.empty(max(int(self.n_candidates), 0)) if return_values else None
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
         self._check(self._lib.gpbo_mes_argbest(self._h, int(y_star.shape[0]), dptr(y_star), k_seeds, int(index_offset),
                                                C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
         return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
@@ -1006,15 +1013,8 @@ class GpEngine:
         """`acq_argbest` over the union of every rank's shard (gpbo_comm_acq_argbest): the shard's records are packed on
         the device, all-gathered over RCCL and merged identically on every rank.  Same return tuple; `ys` is this
         rank's shard."""
-        lb = np.ascontiguousarray(np.atleast_1d(np.asarray(lb, dtype=np.float64))) if lb is not None else None
-        ub = np.ascontiguousarray(np.atleast_1d(np.asarray(ub, dtype=np.float64))) if ub is not None else None
-        n_c = 0 if lb is None else lb.shape[0]
-        if n_c and (ub is None or ub.shape[0] != n_c):
-            raise ValueError("lb and ub must have the same length")
+        lb, ub, n_c, seed_idx, seed_val, ys = _argbest_frame(lb, ub, k_seeds, self.n_candidates if return_values else None)
         best_idx, best_val = C.c_int64(0), C.c_double(0.0)
-        seed_idx = np.full(max(k_seeds, 1), -1, dtype=np.int64)
-        seed_val = np.full(max(k_seeds, 1), np.nan)
-        ys = np.empty(self.n_candidates) if return_values else None
         rc = self._lib.gpbo_comm_acq_argbest(self._h, int(acq), float(param), float(y_max if y_max is not None else 0.0),
                                              n_c, dptr(lb), dptr(ub), int(k_seeds), int(index_offset),
                                              C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys))
@@ -1063,7 +1063,7 @@ class GroupEngine(GpEngine):
         if rc != _lib.GPBO_OK:
             _lib.raise_for_status(self._lib, None, rc)
         self._g = g
-        self._h = C.c_void_p(self._lib.gpbo_group_ctx(g, 0))     # borrowed: the first device's context
+        self._h = self._member(0)     # borrowed: the first device's context
         self.devices = devices
         self.device = devices[0]
         # as a single engine's: fits are synchronous on every device and scaled kernels refused, so _pending_fits and _scaled stay
@@ -1088,21 +1088,23 @@ class GroupEngine(GpEngine):
                 self._orphans.append(borrowed)
             _lib.raise_for_status(self._lib, None, rc, info, group=self._g)
 
+    def _member(self, r: int):
+        """The context of member r (borrowed from the group, as `_h` is member 0's)."""
+        return C.c_void_p(self._lib.gpbo_group_ctx(self._g, int(r)))
+
     def per_device_info(self) -> list:
         """`device_info()` of every device of the group: PCI bus id, rank / world and what RCCL says its communicator has
         (ncclCommCount) — a multi-GPU bench line quotes these, not what the launcher asked for."""
         out = []
         for r in range(self.world_size):
             buf = C.create_string_buffer(1024)
-            h = C.c_void_p(self._lib.gpbo_group_ctx(self._g, r))
-            self._check(self._lib.gpbo_device_info(h, buf, 1024))
+            self._check(self._lib.gpbo_device_info(self._member(r), buf, 1024))
             out.append(json.loads(buf.value.decode()))
         return out
 
     def set_timing(self, on: bool):
         for r in range(self.world_size):
-            h = C.c_void_p(self._lib.gpbo_group_ctx(self._g, r))
-            self._check(self._lib.gpbo_set_timing(h, 1 if on else 0))
+            self._check(self._lib.gpbo_set_timing(self._member(r), 1 if on else 0))
         self.timing = bool(on)
 
     def per_device_timings(self) -> list:
@@ -1110,8 +1112,7 @@ class GroupEngine(GpEngine):
         out = []
         for r in range(self.world_size):
             ms = (C.c_float * 8)()
-            h = C.c_void_p(self._lib.gpbo_group_ctx(self._g, r))
-            self._check(self._lib.gpbo_last_timings(h, ms, 8))
+            self._check(self._lib.gpbo_last_timings(self._member(r), ms, 8))
             out.append({n: float(ms[i]) for i, n in enumerate(TIMING_NAMES)})
         return out
 
@@ -1130,15 +1131,13 @@ class GroupEngine(GpEngine):
         any_seen = False
         for r in range(self.world_size):
             seen = C.c_int(0)
-            h = C.c_void_p(self._lib.gpbo_group_ctx(self._g, r))
-            self._check(self._lib.gpbo_take_negative_variance_flag(h, C.byref(seen)))
+            self._check(self._lib.gpbo_take_negative_variance_flag(self._member(r), C.byref(seen)))
             any_seen = any_seen or bool(seen.value)
         return any_seen
 
     def member_timings(self, rank: int) -> dict:
         ms = (C.c_float * 8)()
-        h = C.c_void_p(self._lib.gpbo_group_ctx(self._g, int(rank)))
-        self._check(self._lib.gpbo_last_timings(h, ms, 8))
+        self._check(self._lib.gpbo_last_timings(self._member(rank), ms, 8))
         return {n: float(ms[i]) for i, n in enumerate(TIMING_NAMES)}
 
     def shard(self, rank: int) -> tuple[int, int]:
@@ -1161,13 +1160,7 @@ class GroupEngine(GpEngine):
     def fit(self, X, y_norm, kernel: int, length_scale, noise: float, slot: int = 0, precision: int = F64,
             amplitude: float = 1.0, white: float = 0.0):
         self._refuse_scaled(amplitude, white)
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        if X.ndim != 2:
-            raise ValueError("X must be 2-D (n_samples, n_features)")
-        y_norm = np.ascontiguousarray(y_norm, dtype=np.float64).ravel()
-        if y_norm.shape[0] != X.shape[0]:
-            raise ValueError("X and y have inconsistent numbers of samples")
-        ls = np.ascontiguousarray(np.atleast_1d(np.asarray(length_scale, dtype=np.float64)))
+        X, y_norm, ls = _model_arrays(X, y_norm, length_scale)
         info = C.c_int(0)
         self._touch(slot)
         rc = self._lib.gpbo_group_fit(self._g, int(slot), dptr(X), dptr(y_norm), X.shape[0], X.shape[1], int(kernel),
@@ -1324,15 +1317,8 @@ class GroupEngine(GpEngine):
         if index_offset:
             raise ValueError("a device group numbers its candidates globally; index_offset must be 0")
         self._need_resident()
-        lb = np.ascontiguousarray(np.atleast_1d(np.asarray(lb, dtype=np.float64))) if lb is not None else None
-        ub = np.ascontiguousarray(np.atleast_1d(np.asarray(ub, dtype=np.float64))) if ub is not None else None
-        n_c = 0 if lb is None else lb.shape[0]
-        if n_c and (ub is None or ub.shape[0] != n_c):
-            raise ValueError("lb and ub must have the same length")
+        lb, ub, n_c, seed_idx, seed_val, ys = _argbest_frame(lb, ub, k_seeds, self._M_pad if return_values else None)
         best_idx, best_val = np.zeros(1, dtype=np.int64), np.zeros(1)
-        seed_idx = np.full(max(k_seeds, 1), -1, dtype=np.int64)
-        seed_val = np.full(max(k_seeds, 1), np.nan)
-        ys = np.empty(self._M_pad) if return_values else None
         rc = self._lib.gpbo_group_acq_argbest(self._g, int(acq), float(param), float(y_max if y_max is not None else 0.0),
                                               n_c, dptr(lb), dptr(ub), int(k_seeds), iptr(best_idx), dptr(best_val),
                                               iptr(seed_idx), dptr(seed_val), dptr(ys))

@@ -48,6 +48,11 @@ except Exception:  # pragma: no cover - exercised on boxes without bayes_opt
     class TargetSpaceEmptyError(BayesianOptimizationError):
         """bayes_opt/exception.py:30."""
 
+#: what every suggest says with TargetSpaceEmptyError on a space without observations (the reference's text, acquisition.py)
+EMPTY_SPACE_MESSAGE = ("Cannot suggest a point without previous samples. Use "
+                       " target_space.random_sample() to generate a point and "
+                       " target_space.probe(*) to evaluate it.")
+
 _SQRT_2PI = np.sqrt(2.0 * np.pi)
 _FD_EPS = 1e-8                       # scipy.optimize._lbfgsb_py._minimize_lbfgsb: eps=1e-8 -> abs_step
 _SQRT_EPS = np.finfo(np.float64).eps ** 0.5
@@ -325,10 +330,7 @@ class AcquisitionFunction(abc.ABC):
         """Next point to probe (acquisition.py:116-169); `n_random=None` -> `default_n_random` (10_000 there)."""
         rng = ensure_rng(random_state)
         if len(target_space) == 0:
-            raise TargetSpaceEmptyError(
-                "Cannot suggest a point without previous samples. Use "
-                " target_space.random_sample() to generate a point and "
-                " target_space.probe(*) to evaluate it.")
+            raise TargetSpaceEmptyError(EMPTY_SPACE_MESSAGE)
         self.i += 1
         if fit_gp:
             self._fit_gp(gp=gp, target_space=target_space)
@@ -901,10 +903,7 @@ class GPHedge(AcquisitionFunction):
 
     def suggest(self, gp, target_space, n_random: int = 10_000, n_smart: int = 10, fit_gp: bool = True, random_state=None):
         if len(target_space) == 0:
-            raise TargetSpaceEmptyError(
-                "Cannot suggest a point without previous samples. Use "
-                " target_space.random_sample() to generate a point and "
-                " target_space.probe(*) to evaluate it.")
+            raise TargetSpaceEmptyError(EMPTY_SPACE_MESSAGE)
         self.i += 1
         rng = ensure_rng(random_state)
         if fit_gp:

@@ -13,15 +13,10 @@ No incumbent, no xi or kappa.  The values come from ONE posterior pass over the 
 """
 from __future__ import annotations
 
-import warnings
-
 import numpy as np
 
-from . import fused_acquisition as A
-from ._lib import MAX_MES_SAMPLES as MAX_SAMPLES, MAX_PATH_FEATURES as MAX_FEATURES, MAX_PATH_STARTS as MAX_STARTS, MAX_PATHS
-from .engine import GroupEngine
-from .gpr import HipGPR
-from .thompson import spectral_draw
+from . import _suggest as S
+from ._lib import MAX_MES_SAMPLES as MAX_SAMPLES, MAX_PATH_FEATURES as MAX_FEATURES, MAX_PATH_STARTS as MAX_STARTS
 
 
 def suggest_mes(optimizer, n_samples: int = 16, n_random: int = 10_000, n_features: int = 1024, refine: int = 4, max_iter=None,
@@ -49,9 +44,7 @@ def suggest_mes(optimizer, n_samples: int = 16, n_random: int = 10_000, n_featur
     refine not an integer in [0, 8] (or larger than `n_random`).  TargetSpaceEmptyError on an empty space,
     ConstraintNotSupportedError with a constraint.  NotImplementedError, never a host fallback, for: a GP that is not on the engine's
     slot 0, a space with an input transform (int / categorical parameters), a model in host mode, a device group."""
-    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or not 1 <= int(n_samples) <= MAX_SAMPLES:
-        raise ValueError(f"n_samples must be an integer in [1, {MAX_SAMPLES}]")
-    n_samples = int(n_samples)
+    n_samples = S.count(n_samples, 1, MAX_SAMPLES, f"n_samples must be an integer in [1, {MAX_SAMPLES}]")
     n_random, n_features = int(n_random), int(n_features)
     if n_random < 1:
         raise ValueError("n_random must be >= 1")
@@ -60,69 +53,29 @@ def suggest_mes(optimizer, n_samples: int = 16, n_random: int = 10_000, n_featur
     floor_sigmas = float(floor_sigmas)
     if not np.isfinite(floor_sigmas) or floor_sigmas < 0.0:
         raise ValueError("floor_sigmas must be finite and >= 0")
-    gp = optimizer._gp
-    space = optimizer._space
-    if not isinstance(gp, HipGPR) or gp.slot != 0:
-        raise NotImplementedError("suggest_mes: the optimizer's GP is not on the engine (call accelerate(optimizer) first)")
-    if len(space) == 0:
-        raise A.TargetSpaceEmptyError("Cannot suggest a point without previous samples. Use "
-                                      " target_space.random_sample() to generate a point and "
-                                      " target_space.probe(*) to evaluate it.")
-    if space.constraint is not None:
-        raise A.ConstraintNotSupportedError("Received constraints, but suggest_mes does not support constrained optimization.")
-    if gp.transform is not None:
-        raise NotImplementedError("suggest_mes: the space has an input transform (int / categorical parameters); "
-                                  "only all-float spaces are sampled")
-    eng = gp._engine()
-    if isinstance(eng, GroupEngine):
-        raise NotImplementedError("suggest_mes: a device group has no path sampler; use a single device")
-    if not hasattr(eng, "sample_paths") or not hasattr(eng, "mes_argbest"):
-        raise NotImplementedError("suggest_mes: the engine has no sample_paths / mes_argbest")
-    from sklearn.base import clone
-
-    reason = None if gp.kernel is None else gp._unsupported_reason(clone(gp.kernel), space.target, space.params)
-    if reason is not None:
-        raise NotImplementedError(f"suggest_mes: the model runs on the host ({reason}); only models on the device path are sampled")
-    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= MAX_STARTS:
-        raise ValueError(f"refine must be an integer in [0, {MAX_STARTS}]")
-    refine = int(refine)
+    gp, space, eng = S.gate(optimizer, "suggest_mes", "sampled", ("sample_paths", "mes_argbest"),
+                            "a device group has no path sampler; use a single device")
+    refine = S.count(refine, 0, MAX_STARTS, f"refine must be an integer in [0, {MAX_STARTS}]")
     if refine and not hasattr(eng, "ascend_paths"):
         raise NotImplementedError("suggest_mes: the engine has no ascend_paths")
     rng = optimizer._random_state
 
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        gp.fit(space.params, space.target)
-    if gp._host_mode:      # (unreachable after the check above; a host model must not get this far silently)
-        raise NotImplementedError("suggest_mes: the model was fitted on the host")
-    d = int(space.bounds.shape[0])
-    N = int(gp.X_train_.shape[0])
-    y_mean, y_std = float(gp._y_train_mean), float(gp._y_train_std)
-    scale = gp.__dict__.get("_scale")
-    noise = float(gp.alpha) + (0.0 if scale is None else float(scale[1]))
+    model = S.fit_model(gp, space, "suggest_mes")
     eng.generate_candidates_like(n_random, space.bounds[:, 0], space.bounds[:, 1], rng)
     gp._ensure_resident()
-    eng.posterior(slot=gp.slot, y_mean=y_mean, y_std=y_std, fetch=False)
+    eng.posterior(slot=gp.slot, y_mean=model.y_mean, y_std=model.y_std, fetch=False)
     y_star = np.empty(n_samples)
-    for first in range(0, n_samples, MAX_PATHS):
-        S = min(MAX_PATHS, n_samples - first)
-        omega, phase = spectral_draw(gp._kind, n_features, d, rng)
-        weights = rng.standard_normal((S, n_features))
-        eps = rng.standard_normal((S, N)) * np.sqrt(noise)
-        gp._ensure_resident()
+    for first, n, out in S.draw_groups(gp, space, eng, rng, model, n_samples, n_features, refine, max_iter):
         if refine:
-            out = eng.ascend_paths(omega, phase, weights, eps, space.bounds[:, 0], space.bounds[:, 1], n_starts=refine,
-                                   max_iter=-1 if max_iter is None else int(max_iter), slot=gp.slot, y_mean=y_mean, y_std=y_std)
             f = np.where(np.isfinite(out["f"]), out["f"], -np.inf).max(axis=1)
             # (a draw without a finite run keeps its maximum among the candidates)
-            y_star[first:first + S] = np.where(np.isfinite(f), f, np.asarray(out["best_val"], dtype=np.float64))
+            y_star[first:first + n] = np.where(np.isfinite(f), f, np.asarray(out["best_val"], dtype=np.float64))
         else:
-            _best, val, _values = eng.sample_paths(omega, phase, weights, eps, slot=gp.slot, y_mean=y_mean, y_std=y_std)
-            y_star[first:first + S] = val
-    floor = float(np.max(space.target)) + floor_sigmas * np.sqrt(noise) * y_std
+            y_star[first:first + n] = out[1]
+    floor = float(np.max(space.target)) + floor_sigmas * np.sqrt(model.noise) * model.y_std
     y_star = np.where(np.isfinite(y_star) & (y_star > floor), y_star, floor)
     index, value, _seed_idx, _seed_val, _ys = eng.mes_argbest(y_star)
-    row = np.asarray(eng.get_candidate_rows(np.array([index], dtype=np.int64), d), dtype=np.float64)[0]
+    row = np.asarray(eng.get_candidate_rows(np.array([index], dtype=np.int64), model.d), dtype=np.float64)[0]
     params = space.array_to_params(row)
     if return_info:
         return params, {"y_star": y_star, "value": -float(value), "index": int(index)}

@@ -13,15 +13,11 @@ at O((N + F) d) per evaluation, optimiser and evaluations in one launch) — the
 """
 from __future__ import annotations
 
-import warnings
-
 import numpy as np
 
-from . import fused_acquisition as A
-# draws one sample_paths call evaluates side by side, features per draw, starts per draw one ascend_paths call climbs from
-from ._lib import MAX_PATH_FEATURES as MAX_FEATURES, MAX_PATH_STARTS as MAX_STARTS, MAX_PATHS
-from .engine import GroupEngine
-from .gpr import HipGPR
+from . import _suggest as S
+# features per draw, starts per draw one ascend_paths call climbs from (draws per call: _suggest.draw_groups)
+from ._lib import MAX_PATH_FEATURES as MAX_FEATURES, MAX_PATH_STARTS as MAX_STARTS
 
 #: the kernel kinds of include/gpbo.h -> Matern nu (RBF: the Gaussian spectrum)
 _NU = {1: 2.5, 2: 1.5, 3: 0.5}
@@ -77,74 +73,30 @@ def suggest_thompson(optimizer, q: int, n_random: int = 10_000, n_features: int 
     `n_random`: a draw has no more starts than candidates).  TargetSpaceEmptyError on an empty space,
     ConstraintNotSupportedError with a constraint.  NotImplementedError, never a host fallback, for: a GP that is not on the engine's
     slot 0, a space with an input transform (int / categorical parameters), a model in host mode, a device group."""
-    if isinstance(q, bool) or not isinstance(q, (int, np.integer)):
-        raise ValueError("q must be an integer >= 1")
-    q = int(q)
-    if q < 1:
-        raise ValueError("q must be >= 1")
+    q = S.count(q, 1, None, "q must be an integer >= 1", "q must be >= 1")
     n_random, n_features = int(n_random), int(n_features)
     if n_random < 1:
         raise ValueError("n_random must be >= 1")
     if not 1 <= n_features <= MAX_FEATURES:
         raise ValueError(f"n_features must be in [1, {MAX_FEATURES}]")
-    gp = optimizer._gp
-    space = optimizer._space
-    if not isinstance(gp, HipGPR) or gp.slot != 0:
-        raise NotImplementedError("suggest_thompson: the optimizer's GP is not on the engine (call accelerate(optimizer) first)")
-    if len(space) == 0:
-        raise A.TargetSpaceEmptyError("Cannot suggest a point without previous samples. Use "
-                                      " target_space.random_sample() to generate a point and "
-                                      " target_space.probe(*) to evaluate it.")
-    if space.constraint is not None:
-        raise A.ConstraintNotSupportedError("Received constraints, but suggest_thompson does not support constrained optimization.")
-    if gp.transform is not None:
-        raise NotImplementedError("suggest_thompson: the space has an input transform (int / categorical parameters); "
-                                  "only all-float spaces are sampled")
-    eng = gp._engine()
-    if isinstance(eng, GroupEngine):
-        raise NotImplementedError("suggest_thompson: a device group has no path sampler; use a single device")
-    if not hasattr(eng, "sample_paths"):
-        raise NotImplementedError("suggest_thompson: the engine has no sample_paths")
-    from sklearn.base import clone
-
-    reason = None if gp.kernel is None else gp._unsupported_reason(clone(gp.kernel), space.target, space.params)
-    if reason is not None:
-        raise NotImplementedError(f"suggest_thompson: the model runs on the host ({reason}); only models on the device path are sampled")
-    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= MAX_STARTS:
-        raise ValueError(f"refine must be an integer in [0, {MAX_STARTS}]")
-    refine = int(refine)
+    gp, space, eng = S.gate(optimizer, "suggest_thompson", "sampled", ("sample_paths",),
+                            "a device group has no path sampler; use a single device")
+    refine = S.count(refine, 0, MAX_STARTS, f"refine must be an integer in [0, {MAX_STARTS}]")
     if refine and not hasattr(eng, "ascend_paths"):
         raise NotImplementedError("suggest_thompson: the engine has no ascend_paths")
     rng = optimizer._random_state
 
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        gp.fit(space.params, space.target)
-    if gp._host_mode:      # (unreachable after the check above; a host model must not get this far silently)
-        raise NotImplementedError("suggest_thompson: the model was fitted on the host")
-    d = int(space.bounds.shape[0])
-    N = int(gp.X_train_.shape[0])
-    y_mean, y_std = float(gp._y_train_mean), float(gp._y_train_std)
-    scale = gp.__dict__.get("_scale")
-    noise = float(gp.alpha) + (0.0 if scale is None else float(scale[1]))
+    model = S.fit_model(gp, space, "suggest_thompson")
     eng.generate_candidates_like(n_random, space.bounds[:, 0], space.bounds[:, 1], rng)
     picks = []
-    for first in range(0, q, MAX_PATHS):
-        S = min(MAX_PATHS, q - first)
-        omega, phase = spectral_draw(gp._kind, n_features, d, rng)
-        weights = rng.standard_normal((S, n_features))
-        eps = rng.standard_normal((S, N)) * np.sqrt(noise)
-        gp._ensure_resident()
+    for _first, n, out in S.draw_groups(gp, space, eng, rng, model, q, n_features, refine, max_iter):
         if refine:
-            out = eng.ascend_paths(omega, phase, weights, eps, space.bounds[:, 0], space.bounds[:, 1], n_starts=refine,
-                                   max_iter=-1 if max_iter is None else int(max_iter), slot=gp.slot, y_mean=y_mean, y_std=y_std)
             # (a draw without a finite run keeps its first start: its best candidate)
-            picks.extend(out["x_best"][s] if out["winner"][s] >= 0 else out["x"][s, 0] for s in range(S))
-            continue
-        best, _val, _values = eng.sample_paths(omega, phase, weights, eps, slot=gp.slot, y_mean=y_mean, y_std=y_std)
-        picks.extend(int(i) for i in best)
+            picks.extend(out["x_best"][s] if out["winner"][s] >= 0 else out["x"][s, 0] for s in range(n))
+        else:
+            picks.extend(int(i) for i in out[0])
     if refine:
-        rows = np.asarray(picks, dtype=np.float64).reshape(q, d)
+        rows = np.asarray(picks, dtype=np.float64).reshape(q, model.d)
     else:
-        rows = np.asarray(eng.get_candidate_rows(np.array(picks, dtype=np.int64), d), dtype=np.float64)
+        rows = np.asarray(eng.get_candidate_rows(np.array(picks, dtype=np.int64), model.d), dtype=np.float64)
     return [space.array_to_params(x) for x in rows]

@@ -1,5 +1,6 @@
 """Test infrastructure for suggest_batch (never imported by the product): the truth its picks are held to, and a stand-in for the
-slice of bayes_opt.BayesianOptimization that suggest_batch reads, so that the same tests run with and without the reference.
+slice of bayes_opt.BayesianOptimization that suggest_batch reads, so that the same tests run with and without the reference — with
+the data, the driver factory and the RandomState comparison the host tests of suggest_batch / suggest_thompson / suggest_mes share.
 
 The truth of a batch: constant liar at HELD theta and HELD target normalisation over ONE candidate set, with nothing incremental
 in it — for every pick a from-scratch oracle fit of X u picks (the picks' targets = the lie, normalised with the real data's mean
@@ -89,6 +90,87 @@ class Driver:
         """one suggest(n_smart=0) of the policy, as BayesianOptimization.suggest() calls it"""
         return self._acquisition_function.suggest(gp=self._gp, target_space=self._space, n_random=n_random, n_smart=0, fit_gp=True,
                                                   random_state=self._random_state)
+
+
+#: the space of the suggest functions' host tests: d = 3, N = 30 observations
+SUGGEST_BOUNDS = np.array([[0.0, 1.0], [-1.0, 2.0], [0.5, 1.5]])
+SUGGEST_N = 30
+
+
+def suggest_data(seed=0):
+    lo, hi = SUGGEST_BOUNDS[:, 0], SUGGEST_BOUNDS[:, 1]
+    rng = np.random.RandomState(seed)
+    X = lo + rng.uniform(size=(SUGGEST_N, lo.shape[0])) * (hi - lo)
+    y = np.sin(3.0 * X[:, 0]) * np.cos(2.0 * X[:, 1]) + X[:, 2] ** 2 + 0.05 * rng.standard_normal(SUGGEST_N)
+    return X, y
+
+
+def suggest_driver(engine_class, policy=None, seed=3, n_random=1500, **kw):
+    """(driver, engine, X, y): a Driver over `suggest_data` and a fresh `engine_class()`, a decaying UCB where no policy is given."""
+    from bayesianoptimization_amd import fused_acquisition as A
+
+    X, y = suggest_data()
+    eng = engine_class()
+    policy = A.UpperConfidenceBound(kappa=2.0, exploration_decay=0.9, exploration_decay_delay=0) if policy is None else policy
+    return Driver(eng, X, y, SUGGEST_BOUNDS, policy, seed=seed, n_random=n_random, lml_on_device=False, **kw), eng, X, y
+
+
+def same_state(a, b):
+    """Are two RandomStates in the same state?"""
+    a, b = a.get_state(), b.get_state()
+    return a[0] == b[0] and np.array_equal(a[1], b[1]) and a[2:] == b[2:]
+
+
+def check_shared_refusals(suggest, make, who):
+    """`suggest(driver)`, a valid call of the suggest function named `who`, in every state the suggest functions refuse alike — an
+    empty space, a constraint, an int parameter, a foreign GP, slot 1, a kernel outside the device path, a device group: the
+    exception type, the text that names the function and the reason, and no engine call (no host fallback).  `make(**kw)` ->
+    (driver, engine, X, y).  Returns the device-group driver's engine, for the caller's check of the GroupEngine method itself."""
+    import pytest
+    from sklearn.gaussian_process.kernels import RationalQuadratic
+
+    from bayesianoptimization_amd import fused_acquisition as A
+    from bayesianoptimization_amd.constraint_model import HipConstraintModel
+    from bayesianoptimization_amd.engine import GroupEngine
+    from bayesianoptimization_amd.float_space import FloatSpace, MixedSpace
+
+    empty = {f"x{j}": tuple(b) for j, b in enumerate(SUGGEST_BOUNDS)}
+
+    def no_points(drv, eng, X, y):
+        drv._space = FloatSpace(empty)
+
+    def constraint(drv, eng, X, y):
+        cm = HipConstraintModel(None, np.array([-np.inf]), np.array([0.5]), engine=eng, random_state=np.random.RandomState(3))
+        drv._space = FloatSpace(empty, constraint=cm)
+        drv._space.register_bulk(X, y, np.cos(X.sum(1)))
+
+    def int_parameter(drv, eng, X, y):
+        drv._gp.transform = MixedSpace({"x0": (0.0, 1.0), "x1": (-1, 2, int), "x2": (0.5, 1.5)}).kernel_transform
+
+    def foreign_gp(drv, eng, X, y):
+        drv._gp = object()
+
+    def slot_1(drv, eng, X, y):
+        drv._gp.slot = 1
+
+    def device_group(drv, eng, X, y):
+        drv._gp.engine = object.__new__(GroupEngine)          # (no devices opened: the type is what is refused)
+        drv._gp.engine.__dict__.update(_g=None, _h=None)
+
+    scenarios = [(no_points, {}, A.TargetSpaceEmptyError, "without previous samples"),
+                 (constraint, {}, A.ConstraintNotSupportedError, f"but {who} does not support constrained"),
+                 (int_parameter, {}, NotImplementedError, f"{who}: the space has an input transform"),
+                 (foreign_gp, {}, NotImplementedError, f"{who}: .*accelerate"),
+                 (slot_1, {}, NotImplementedError, f"{who}: .*accelerate"),
+                 (lambda *a: None, {"kernel": RationalQuadratic()}, NotImplementedError, f"{who}: the model runs on the host"),
+                 (device_group, {}, NotImplementedError, f"{who}: a device group")]
+    for spoil, kw, error, match in scenarios:
+        drv, eng, X, y = make(**kw)
+        spoil(drv, eng, X, y)
+        with pytest.raises(error, match=match):
+            suggest(drv)
+        assert not eng.calls, (spoil.__name__, eng.calls)      # refused before anything ran
+    return drv._gp.engine
 
 
 def rows_to_indices(picks, Xc):

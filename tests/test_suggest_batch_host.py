@@ -14,7 +14,7 @@ from oracle import gp_oracle as O
 from oracle.refenv import have_reference, import_reference
 
 D, N, M = 3, 30, 1500          # M * D >= 4096: the candidates are drawn on the engine from the optimizer's RandomState
-BOUNDS = np.array([[0.0, 1.0], [-1.0, 2.0], [0.5, 1.5]])
+BOUNDS = B.SUGGEST_BOUNDS
 
 
 class RefreshFakeEngine(FakeEngine):
@@ -29,22 +29,13 @@ class RefreshFakeEngine(FakeEngine):
         return (*out, 1) if return_route else out
 
 
-def _data(seed=0):
-    rng = np.random.RandomState(seed)
-    X = BOUNDS[:, 0] + rng.uniform(size=(N, D)) * (BOUNDS[:, 1] - BOUNDS[:, 0])
-    y = np.sin(3.0 * X[:, 0]) * np.cos(2.0 * X[:, 1]) + X[:, 2] ** 2 + 0.05 * rng.standard_normal(N)
-    return X, y
-
-
 def _policy(name, **kw):
     return {"ucb": lambda: A.UpperConfidenceBound(kappa=2.0, **kw), "ei": lambda: A.ExpectedImprovement(xi=0.01, **kw),
             "poi": lambda: A.ProbabilityOfImprovement(xi=0.5, **kw)}[name]()
 
 
 def _driver(policy, seed=3, **kw):
-    X, y = _data()
-    eng = RefreshFakeEngine()
-    return B.Driver(eng, X, y, BOUNDS, policy, seed=seed, n_random=M, lml_on_device=False, **kw), eng, X, y
+    return B.suggest_driver(RefreshFakeEngine, policy, seed=seed, n_random=M, **kw)
 
 
 def _theta(gp):
@@ -149,35 +140,15 @@ def test_engine_calls_of_a_batch():
 
 
 def test_refusals():
-    from sklearn.gaussian_process.kernels import RationalQuadratic
-
-    from bayesianoptimization_amd.constraint_model import HipConstraintModel
-    from bayesianoptimization_amd.float_space import FloatSpace, MixedSpace
-
     drv, eng, X, y = _driver(_policy("ucb"))
     for bad in (0, -1, 1.5, True):
         with pytest.raises(ValueError):
             suggest_batch(drv, bad)
     with pytest.raises(ValueError, match="strategy"):
         suggest_batch(drv, 2, strategy="median")
-    # empty space
-    drv._space = FloatSpace({f"x{j}": tuple(b) for j, b in enumerate(BOUNDS)})
-    with pytest.raises(A.TargetSpaceEmptyError):
-        suggest_batch(drv, 2)
-    # a constraint
-    drv, eng, X, y = _driver(_policy("ei"))
-    cm = HipConstraintModel(None, np.array([-np.inf]), np.array([0.5]), engine=eng, random_state=np.random.RandomState(3))
-    sp = FloatSpace({f"x{j}": tuple(b) for j, b in enumerate(BOUNDS)}, constraint=cm)
-    sp.register_bulk(X, y, np.cos(X.sum(1)))
-    drv._space = sp
-    with pytest.raises(A.ConstraintNotSupportedError):
-        suggest_batch(drv, 2)
-    # an input transform (int parameter)
-    drv, eng, X, y = _driver(_policy("ucb"))
-    ms = MixedSpace({"x0": (0.0, 1.0), "x1": (-1, 2, int), "x2": (0.5, 1.5)})
-    drv._gp.transform = ms.kernel_transform
-    with pytest.raises(NotImplementedError, match="transform"):
-        suggest_batch(drv, 2)
+    group = B.check_shared_refusals(lambda d: suggest_batch(d, 2), lambda **kw: _driver(_policy("ei"), **kw), "suggest_batch")
+    with pytest.raises(NotImplementedError, match="device group"):
+        type(group).posterior_refresh(group)
     # another policy
     drv, eng, X, y = _driver(A.GPHedge([_policy("ucb"), _policy("ei")]))
     with pytest.raises(NotImplementedError, match="GPHedge"):
@@ -189,24 +160,6 @@ def test_refusals():
     drv, eng, X, y = _driver(Mine())
     with pytest.raises(NotImplementedError, match="Mine"):
         suggest_batch(drv, 2)
-    # a model in host mode (a kernel outside the device path)
-    drv, eng, X, y = _driver(_policy("ucb"), kernel=RationalQuadratic())
-    with pytest.raises(NotImplementedError, match="host"):
-        suggest_batch(drv, 2)
-    assert not eng.calls                                  # refused before anything ran: no host fallback
-    # a device group
-    from bayesianoptimization_amd.engine import GroupEngine
-
-    drv, eng, X, y = _driver(_policy("ucb"))
-    drv._gp.engine = object.__new__(GroupEngine)          # (no devices opened: the type is what is refused)
-    try:
-        with pytest.raises(NotImplementedError, match="device group"):
-            suggest_batch(drv, 2)
-        with pytest.raises(NotImplementedError, match="device group"):
-            GroupEngine.posterior_refresh(drv._gp.engine)
-    finally:
-        drv._gp.engine.__dict__["_g"] = None
-        drv._gp.engine.__dict__["_h"] = None
 
 
 @pytest.mark.skipif(not have_reference(), reason="bayes_opt (the reference) is not importable here")

@@ -2,6 +2,7 @@
 digits, and `suggest_thompson` over an oracle-backed engine double whose `ascend_paths` is SciPy L-BFGS-B over that truth: the
 engine calls, the untouched RandomState, the picks against their draws' candidate maxima, every refusal.
 The device's arithmetic is checked in tests/test_gpu_path_ascent.py."""
+import functools
 import warnings
 
 import numpy as np
@@ -11,7 +12,6 @@ import batch_truth as B
 import matern_family_truth as F
 import paths_ascent_truth as T
 import paths_truth as P
-from bayesianoptimization_amd import fused_acquisition as A
 from bayesianoptimization_amd import suggest_thompson
 from bayesianoptimization_amd.engine import GroupEngine, path_winners
 from bayesianoptimization_amd.thompson import spectral_draw
@@ -88,26 +88,11 @@ def test_projected_gradient_norm_and_winners():
 
 # ---- suggest_thompson over the engine double ---------------------------------------------------------------------------------------
 D, N, M = 3, 30, 600
-BOUNDS = np.array([[0.0, 1.0], [-1.0, 2.0], [0.5, 1.5]])
+BOUNDS = B.SUGGEST_BOUNDS
 
 
-def _data(seed=0):
-    rng = np.random.RandomState(seed)
-    X = BOUNDS[:, 0] + rng.uniform(size=(N, D)) * (BOUNDS[:, 1] - BOUNDS[:, 0])
-    y = np.sin(3.0 * X[:, 0]) * np.cos(2.0 * X[:, 1]) + X[:, 2] ** 2 + 0.05 * rng.standard_normal(N)
-    return X, y
-
-
-def _driver(policy=None, seed=3, **kw):
-    X, y = _data()
-    eng = T.AscentFakeEngine()
-    policy = A.UpperConfidenceBound(kappa=2.0, exploration_decay=0.9, exploration_decay_delay=0) if policy is None else policy
-    return B.Driver(eng, X, y, BOUNDS, policy, seed=seed, n_random=M, lml_on_device=False, **kw), eng, X, y
-
-
-def _same_state(a, b):
-    a, b = a.get_state(), b.get_state()
-    return a[0] == b[0] and np.array_equal(a[1], b[1]) and a[2:] == b[2:]
+_driver = functools.partial(B.suggest_driver, T.AscentFakeEngine, n_random=M)
+_same_state = B.same_state
 
 
 def test_refine_zero_is_the_old_call():
@@ -175,11 +160,6 @@ def test_refined_picks_calls_and_randomstate(q):
 
 
 def test_refusals():
-    from sklearn.gaussian_process.kernels import RationalQuadratic
-
-    from bayesianoptimization_amd.constraint_model import HipConstraintModel
-    from bayesianoptimization_amd.float_space import FloatSpace, MixedSpace
-
     drv, eng, X, y = _driver()
     for bad in (-1, 9, 1.5, True):
         with pytest.raises(ValueError, match="refine"):
@@ -193,43 +173,12 @@ def test_refusals():
         with pytest.raises(ValueError):
             suggest_thompson(drv, 2, refine=2, **kw)
     assert not eng.calls
-    drv._space = FloatSpace({f"x{j}": tuple(b) for j, b in enumerate(BOUNDS)})
-    with pytest.raises(A.TargetSpaceEmptyError):
-        suggest_thompson(drv, 2, refine=2)
-    drv, eng, X, y = _driver()
-    cm = HipConstraintModel(None, np.array([-np.inf]), np.array([0.5]), engine=eng, random_state=np.random.RandomState(3))
-    sp = FloatSpace({f"x{j}": tuple(b) for j, b in enumerate(BOUNDS)}, constraint=cm)
-    sp.register_bulk(X, y, np.cos(X.sum(1)))
-    drv._space = sp
-    with pytest.raises(A.ConstraintNotSupportedError):
-        suggest_thompson(drv, 2, refine=2)
-    drv, eng, X, y = _driver()
-    ms = MixedSpace({"x0": (0.0, 1.0), "x1": (-1, 2, int), "x2": (0.5, 1.5)})
-    drv._gp.transform = ms.kernel_transform
-    with pytest.raises(NotImplementedError, match="transform"):
-        suggest_thompson(drv, 2, refine=2)
-    assert not eng.calls
-    drv, eng, X, y = _driver()
-    drv._gp = object()
-    with pytest.raises(NotImplementedError, match="accelerate"):
-        suggest_thompson(drv, 2, refine=2)
-    drv, eng, X, y = _driver(kernel=RationalQuadratic())
-    with pytest.raises(NotImplementedError, match="host"):
-        suggest_thompson(drv, 2, refine=2)
-    assert not eng.calls
+    group = B.check_shared_refusals(lambda d: suggest_thompson(d, 2, refine=2), _driver, "suggest_thompson")
+    assert isinstance(group, GroupEngine)
+    with pytest.raises(NotImplementedError, match="device group"):
+        GroupEngine.ascend_paths(group, None, None, None, None, None, None)
     # an engine without the ascent: refused, never a silent refine=0
     drv, eng, X, y = _driver()
     drv._gp.engine = P.PathsFakeEngine()
     with pytest.raises(NotImplementedError, match="ascend_paths"):
         suggest_thompson(drv, 2, refine=2)
-    # a device group
-    drv, eng, X, y = _driver()
-    drv._gp.engine = object.__new__(GroupEngine)          # (no devices opened: the type is what is refused)
-    try:
-        with pytest.raises(NotImplementedError, match="device group"):
-            suggest_thompson(drv, 2, refine=2)
-        with pytest.raises(NotImplementedError, match="device group"):
-            GroupEngine.ascend_paths(drv._gp.engine, None, None, None, None, None, None)
-    finally:
-        drv._gp.engine.__dict__["_g"] = None
-        drv._gp.engine.__dict__["_h"] = None

@@ -128,26 +128,11 @@ def test_the_two_fp64_routes_and_the_50_digit_truth_agree():
 
 # ---- suggest_thompson over the engine double ---------------------------------------------------------------------------------------
 D, N, M = 3, 30, 1500
-BOUNDS = np.array([[0.0, 1.0], [-1.0, 2.0], [0.5, 1.5]])
+BOUNDS = B.SUGGEST_BOUNDS
 
 
-def _data(seed=0):
-    rng = np.random.RandomState(seed)
-    X = BOUNDS[:, 0] + rng.uniform(size=(N, D)) * (BOUNDS[:, 1] - BOUNDS[:, 0])
-    y = np.sin(3.0 * X[:, 0]) * np.cos(2.0 * X[:, 1]) + X[:, 2] ** 2 + 0.05 * rng.standard_normal(N)
-    return X, y
-
-
-def _driver(policy=None, seed=3, **kw):
-    X, y = _data()
-    eng = P.PathsFakeEngine()
-    policy = A.UpperConfidenceBound(kappa=2.0, exploration_decay=0.9, exploration_decay_delay=0) if policy is None else policy
-    return B.Driver(eng, X, y, BOUNDS, policy, seed=seed, n_random=M, lml_on_device=False, **kw), eng, X, y
-
-
-def _same_state(a, b):
-    a, b = a.get_state(), b.get_state()
-    return a[0] == b[0] and np.array_equal(a[1], b[1]) and a[2:] == b[2:]
+_driver = functools.partial(B.suggest_driver, P.PathsFakeEngine, n_random=M)
+_same_state = B.same_state
 
 
 def _replay(twin, teng, q, n_features):
@@ -212,11 +197,6 @@ def test_predict_answers_for_the_real_data_afterwards():
 
 
 def test_refusals():
-    from sklearn.gaussian_process.kernels import RationalQuadratic
-
-    from bayesianoptimization_amd.constraint_model import HipConstraintModel
-    from bayesianoptimization_amd.float_space import FloatSpace, MixedSpace
-
     drv, eng, X, y = _driver()
     for bad in (0, -1, 1.5, True):
         with pytest.raises(ValueError):
@@ -224,50 +204,12 @@ def test_refusals():
     for kw in ({"n_features": 0}, {"n_features": 4097}, {"n_random": 0}):
         with pytest.raises(ValueError):
             suggest_thompson(drv, 2, **kw)
-    # empty space
-    drv._space = FloatSpace({f"x{j}": tuple(b) for j, b in enumerate(BOUNDS)})
-    with pytest.raises(A.TargetSpaceEmptyError):
-        suggest_thompson(drv, 2)
-    # a constraint
-    drv, eng, X, y = _driver()
-    cm = HipConstraintModel(None, np.array([-np.inf]), np.array([0.5]), engine=eng, random_state=np.random.RandomState(3))
-    sp = FloatSpace({f"x{j}": tuple(b) for j, b in enumerate(BOUNDS)}, constraint=cm)
-    sp.register_bulk(X, y, np.cos(X.sum(1)))
-    drv._space = sp
-    with pytest.raises(A.ConstraintNotSupportedError):
-        suggest_thompson(drv, 2)
-    # an input transform (int parameter)
-    drv, eng, X, y = _driver()
-    ms = MixedSpace({"x0": (0.0, 1.0), "x1": (-1, 2, int), "x2": (0.5, 1.5)})
-    drv._gp.transform = ms.kernel_transform
-    with pytest.raises(NotImplementedError, match="transform"):
-        suggest_thompson(drv, 2)
-    # a GP that is not the engine's
-    drv, eng, X, y = _driver()
-    drv._gp = object()
-    with pytest.raises(NotImplementedError, match="accelerate"):
-        suggest_thompson(drv, 2)
-    # a model in host mode (a kernel outside the device path)
-    drv, eng, X, y = _driver(kernel=RationalQuadratic())
-    with pytest.raises(NotImplementedError, match="host"):
-        suggest_thompson(drv, 2)
-    assert not eng.calls                                  # refused before anything ran: no host fallback
+    group = B.check_shared_refusals(lambda d: suggest_thompson(d, 2), _driver, "suggest_thompson")
+    with pytest.raises(NotImplementedError, match="device group"):
+        type(group).sample_paths(group, None, None, None, None)
     # any policy is fine: it is not consulted
     drv, eng, X, y = _driver(A.GPHedge([A.UpperConfidenceBound(kappa=2.0), A.ExpectedImprovement(xi=0.01)]))
     assert len(suggest_thompson(drv, 2, n_random=M, n_features=16)) == 2
-    # a device group
-    from bayesianoptimization_amd.engine import GroupEngine
-
-    drv, eng, X, y = _driver()
-    drv._gp.engine = object.__new__(GroupEngine)          # (no devices opened: the type is what is refused)
-    try:
-        with pytest.raises(NotImplementedError, match="device group"):
-            suggest_thompson(drv, 2)
-        with pytest.raises(NotImplementedError, match="device group"):
-            GroupEngine.sample_paths(drv._gp.engine, None, None, None, None)
-    finally:
-        drv._gp.engine.__dict__["_g"] = None
-        drv._gp.engine.__dict__["_h"] = None
 
 
 def test_exported():
