@@ -8,7 +8,7 @@ __version__ = "0.1.0"
 
 __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate", "suggest_batch", "UpperConfidenceBound",
            "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement", "suggest_thompson",
-           "suggest_mes"]
+           "suggest_mes", "suggest_kg"]
 
 
 def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must not need sklearn/scipy
@@ -36,6 +36,9 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name == "suggest_mes":
         from .mes import suggest_mes
         return suggest_mes
+    if name == "suggest_kg":
+        from .kg import suggest_kg
+        return suggest_kg
     if name in ("UpperConfidenceBound", "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement",
                 "AcquisitionFunction"):
         from . import fused_acquisition as acquisition

@@ -47,6 +47,7 @@ SOURCES = {
     "mid_fit.hip": [],                         # 64 < NP <= 768: inputs, quarter-tile K, W = L^-1 by column strips, alpha (~15 launches per fit)
     "acq_kernels.hip": ["-ffp-contract=off"],  # elementwise formulas follow NumPy op by op
     "mes.hip": ["-ffp-contract=off"],         # gpbo_mes_argbest: max-value entropy search values (acq_formulas.h's pieces, the bits they have in acq_kernels.hip)
+    "kg.hip": ["-ffp-contract=off"],          # gpbo_kg_argbest: knowledge gradient values (candidate x point covariances, upper envelope of J + 1 lines; acq_formulas.h's pieces)
     "candidates.hip": [],
     "mt19937.hip": ["-ffp-contract=off"],      # lo + (hi - lo) * u as NumPy computes it
     "mt_jump.hip": [],                         # jump-ahead polynomials (host) + sub-stream start states (device)

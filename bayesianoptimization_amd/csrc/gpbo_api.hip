@@ -222,6 +222,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->lml_stream) if (st) (void)hipStreamDestroy(st);
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
+  for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
   if (ctx->small_pinned) (void)hipHostFree(ctx->small_pinned);
   if (ctx->polish_pinned) (void)hipHostFree(ctx->polish_pinned);
   if (ctx->fused_stage) (void)hipHostFree(ctx->fused_stage);
@@ -230,7 +231,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->kg, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1407,6 +1408,39 @@ int gpbo_mes_argbest(gpbo_ctx* ctx, int n_samples, const double* y_star, int k_s
   return GPBO_OK;
 }
 
+int gpbo_kg_argbest(gpbo_ctx* ctx, const double* points, int n_points, int d, double y_mean, double y_std, int k_seeds,
+                    int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val, double* ys_out,
+                    double* mu_points_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (n_points < 1 || n_points > GPBO_MAX_KG_POINTS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: n_points out of range [1, 64]");
+  if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: d out of range");
+  if (!points) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: NULL points");
+  for (int64_t e = 0; e < (int64_t)n_points * d; ++e)
+    if (!std::isfinite(points[e])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: points must be finite");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: NULL output");
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: y_std must be finite and positive, y_mean finite");
+  int rc = no_pending_fit(ctx, 0, "kg_argbest");
+  if (rc) return rc;
+  if ((rc = need_fitted(ctx, 0))) return rc;
+  const Model& m = ctx->models[0];
+  if (d != m.d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: the points' dimension differs from the fitted model's");
+  if (ctx->M < 1 || m.M_post != ctx->M) GPBO_FAIL(ctx, GPBO_ERR_STATE, "kg_argbest: run gpbo_posterior for slot 0 first");
+  if (y_std != m.ystd_post)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: y_std is not the one the resident posterior was scaled with");
+  ev_begin(ctx, T_ACQ);
+  rc = launch_kg_values(ctx, m, ctx->M, points, n_points, y_mean, y_std, mu_points_out);
+  if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  ev_end(ctx, T_ACQ);
+  if (rc) return rc;
+  if (ys_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(ys_out, ctx->ys, (size_t)ctx->M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GPBO_OK;
+}
+
 int gpbo_set_timing(gpbo_ctx* ctx, int on) {
   if (!ctx) return GPBO_ERR_INVALID;
   ctx->timing_off = !on;
@@ -1552,6 +1586,21 @@ int gpbo_debug_latency_probe(gpbo_ctx* ctx, long long* out, int n) {
   if (!ctx || !out || n < 1) return GPBO_ERR_INVALID;
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
   return run_latency_probe(ctx, out, n);
+}
+
+int gpbo_debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!a || !b || !out || R < 1 || R > (1 << 24) || n_lines < 1 || n_lines > GPBO_MAX_KG_POINTS + 1)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_kg_lines: bad arguments");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  return debug_kg_lines(ctx, a, b, R, n_lines, out);
+}
+
+int gpbo_debug_kg_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_kg_stage_ms: NULL output");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  return debug_kg_stage_ms(ctx, ms);
 }
 
 #endif  // GPBO_DEBUG

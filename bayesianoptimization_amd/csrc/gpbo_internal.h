@@ -168,6 +168,10 @@ struct gpbo_ctx {
   int64_t cap_kst = 0;
   double* ys = nullptr;    // [M] negated acquisition values ([n_paths][M] negated path values during gpbo_sample_paths)
   int64_t cap_ys = 0;
+  double* kg = nullptr;    // gpbo_kg_argbest: the call's points, their solves and the candidate x point covariances (kg.hip)
+  int64_t cap_kg = 0;
+  hipEvent_t kg_ev[4] = {};   // debug build: around the three stages of the last gpbo_kg_argbest (the fields exist in both builds: one layout)
+  bool kg_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
   int64_t cap_paths = 0;
   void* red = nullptr;     // reduction scratch
@@ -209,7 +213,7 @@ namespace gpbo {
 
 constexpr size_t SMALL_PIN_IN = 128 * 1024, SMALL_PIN_OUT = 32 * 1024;   // bytes: candidates in; mu, sd out (each)
 constexpr size_t SMALL_PIN_BYTES = SMALL_PIN_IN + 2 * SMALL_PIN_OUT;
-constexpr unsigned ATTR_GEMM128 = 4u, ATTR_CHOL128 = 16u, ATTR_FUSED = 32u, ATTR_MID = 64u, ATTR_KINV_GRAD = 128u, ATTR_POLISH_FUSED = 256u, ATTR_GEMM_FAT = 512u, ATTR_EVOLVE = 2048u;
+constexpr unsigned ATTR_GEMM128 = 4u, ATTR_CHOL128 = 16u, ATTR_FUSED = 32u, ATTR_MID = 64u, ATTR_KINV_GRAD = 128u, ATTR_POLISH_FUSED = 256u, ATTR_GEMM_FAT = 512u, ATTR_EVOLVE = 2048u, ATTR_KG = 4096u;
 // pinned staging of a small host-side fit's X (N, d) | y (N), read by the first kernel directly (one window per PIN window)
 constexpr int STAGE_NP_CAP = MID_NP_CAP;
 static_assert(STAGE_NP_CAP >= FUSED_NP_CAP, "the staging window serves both small paths");
@@ -595,6 +599,8 @@ int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean,
 // ... and the first half of it alone: the draws' inputs and V = alpha - W^T (W (g(X) + eps)) made resident, no candidates needed
 int launch_path_weights(gpbo_ctx* ctx, const Model& m, int n_paths, int n_features, const double* omega, const double* phase,
                         const double* weights, const double* eps, int n_runs, PathWorkspace* ws);
+// ... and the solve inside it: V[s] = a - W^T (W (G[s] + eps[s])), S columns (G, T, V [S][NP], eps [S][N], a [NP]; all on the device)
+int launch_path_solve(gpbo_ctx* ctx, const Model& m, int S, const double* G, const double* eps, const double* a, double* T, double* V);
 // path_ascent.hip: gpbo_ascend_paths' runs, n_paths x n_starts workgroups in one launch, from host starts (n_paths n_starts, d) or —
 // starts null — from the rows start_idx (local indices, host) of the resident candidates; ws was laid out for n_runs =
 // n_paths * n_starts.  Synchronises.
@@ -620,6 +626,15 @@ int launch_values_argbest(gpbo_ctx* ctx, int64_t M, int k_seeds, int64_t offset,
 // mes.hip: ctx->ys[i] = -a(x_i), the negated max-value entropy search value of the M resident candidates from m's resident mu / sd
 // and n_samples <= GPBO_MAX_MES_SAMPLES sampled maxima y_star (host; they travel in the kernel's arguments)
 int launch_mes_values(gpbo_ctx* ctx, const Model& m, int64_t M, int n_samples, const double* y_star);
+// kg.hip: ctx->ys[i] = -KG(x_i), the negated knowledge gradient of the M resident candidates over themselves and the J reference
+// points `points` (J, d; host, parameter space) from m's resident mu / sd; mu_points_out (J,; host) or null.  The caller has checked
+// every argument.  The call's workspace is ctx->kg (kg.hip: kg_block).
+int launch_kg_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, int J, double y_mean, double y_std,
+                     double* mu_points_out);
+#ifdef GPBO_DEBUG
+int debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out);
+int debug_kg_stage_ms(gpbo_ctx* ctx, float* ms3);
+#endif
 // acq_kernels.hip: the k best of each of n_rows rows of M keys (rows + r * ld), the rules of launch_acq_argbest: best_idx / best_val
 // (n_rows) the arg-best, top_idx (n_rows, k; may be null) the rows' k smallest keys in order (ties to the lowest index, NaNs last)
 // as LOCAL indices; synchronises

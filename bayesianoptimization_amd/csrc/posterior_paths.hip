@@ -201,6 +201,17 @@ static PathEvalArgs path_eval_args(const Model& m, const PathWorkspace& ws, int 
   return a;
 }
 
+// V[s] = a - W^T (W (G[s] + eps[s])) for S columns: G, T, V [S][NP], eps [S][N], a [NP] (the slot's alpha; kg.hip passes zeros for
+// eps and a and gets -K'^-1 G[s]).  Each column's arithmetic is its own: S columns or one give the same bits.
+int launch_path_solve(gpbo_ctx* ctx, const Model& m, int S, const double* G, const double* eps, const double* a, double* T, double* V) {
+  const int N = (int)m.N, NP = (int)m.NP;
+  path_t_kernel<<<dim3((unsigned)((NP + 3) / 4), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, G, eps, T, N, NP);
+  GPBO_HIP(ctx, hipGetLastError());
+  path_v_kernel<<<dim3((unsigned)(NP / 64), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, T, a, V, N, NP);
+  GPBO_HIP(ctx, hipGetLastError());
+  return GPBO_OK;
+}
+
 // The draws' inputs made resident and V = alpha - W^T (W (g(X) + eps)) of the S paths: everything a path's value (path_eval_kernel)
 // or its ascent (path_ascent.hip) reads, in the context's paths workspace (path_plan.h), with room for n_runs ascent runs behind it.
 int launch_path_weights(gpbo_ctx* ctx, const Model& m, int S, int F, const double* omega, const double* phase, const double* weights,
@@ -219,11 +230,7 @@ int launch_path_weights(gpbo_ctx* ctx, const Model& m, int S, int F, const doubl
   PathEvalArgs a = path_eval_args(m, *ws, S, F);
   a.P = m.Xs; a.out = G; a.M = N; a.ld = NP; a.N = 0; a.negate = 0; a.y_mean = 0.0; a.y_std = 1.0;
   if ((rc = launch_path_eval(ctx, m, a))) return rc;
-  path_t_kernel<<<dim3((unsigned)((NP + 3) / 4), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, G, eps_d, T, N, NP);
-  GPBO_HIP(ctx, hipGetLastError());
-  path_v_kernel<<<dim3((unsigned)(NP / 64), (unsigned)S), dim3(256), 0, ctx->stream>>>(m.W, T, m.alpha, ws->p(b.V), N, NP);
-  GPBO_HIP(ctx, hipGetLastError());
-  return GPBO_OK;
+  return launch_path_solve(ctx, m, S, G, eps_d, m.alpha, T, ws->p(b.V));
 }
 
 // The S paths of gpbo_sample_paths over the M resident candidates: the negated values land in ctx->ys as S rows of M (the

@@ -851,6 +851,48 @@ class GpEngine:
                                                C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
         return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
 
+    def kg_argbest(self, points, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
+                   return_values: bool = False, return_point_means: bool = False):
+        """Knowledge gradient over the resident candidates (gpbo_kg_argbest; include/gpbo.h has the formulas): ys = -KG, the
+        expected rise of the maximum of the posterior mean over the candidate itself and the J <= 64 reference `points` (J, d),
+        parameter space, from observing the candidate — from slot 0's resident posterior; `y_mean` / `y_std` are those of the pass
+        that left it.  Returns (best_idx, best_val, seed_idx, seed_val, ys|None) as `acq_argbest`, with `return_point_means` a
+        sixth entry: the posterior mean at the points (J,).  A reader: the fit, the resident posterior and the candidates stay as
+        they were.  A fit pending on slot 0 (`overlapped_fits`) is waited for first, as every reader of a slot does; the new fit has
+        no posterior over the candidates, so the call is then refused as such."""
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        if points.ndim != 2:
+            raise ValueError("kg_argbest: points must be two-dimensional (J, d)")
+        k_seeds = int(k_seeds)
+        self._settle(0)
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        mu_points = np.empty(points.shape[0]) if return_point_means else None
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        self._check(self._lib.gpbo_kg_argbest(self._h, dptr(points), int(points.shape[0]), int(points.shape[1]), float(y_mean),
+                                              float(y_std), k_seeds, int(index_offset), C.byref(best_idx), C.byref(best_val),
+                                              iptr(seed_idx), dptr(seed_val), dptr(ys), dptr(mu_points)))
+        out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
+        return out + (mu_points,) if return_point_means else out
+
+    def debug_kg_lines(self, a, b):
+        """gpbo_debug_kg_lines (debug build): the envelope of `kg_argbest` alone on R sets of n lines, a / b (R, n) intercepts /
+        slopes: (R,) E[max_j (a_j + b_j Z)] - max_j a_j."""
+        self._need_debug("gpbo_debug_kg_lines")
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64)))
+        b = np.ascontiguousarray(np.atleast_2d(np.asarray(b, dtype=np.float64)))
+        if a.shape != b.shape:
+            raise ValueError("debug_kg_lines: a and b must have one shape (R, n_lines)")
+        out = np.empty(a.shape[0])
+        self._check(self._lib.gpbo_debug_kg_lines(self._h, dptr(a), dptr(b), int(a.shape[0]), int(a.shape[1]), dptr(out)))
+        return out
+
+    def debug_kg_stage_ms(self):
+        """gpbo_debug_kg_stage_ms (debug build): kernel ms of the last `kg_argbest`'s stages, (points, covariances, envelopes)."""
+        self._need_debug("gpbo_debug_kg_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gpbo_debug_kg_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
     # -- timing / probes (debug_* and the latency / hybrid probes need GpEngine(debug=True)) ----------------------------
     def _need_debug(self, what: str):
         if not getattr(self, "debug", False):
@@ -1291,6 +1333,10 @@ class GroupEngine(GpEngine):
 
     def mes_argbest(self, y_star, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         raise NotImplementedError("a device group has no max-value entropy search (gpbo_mes_argbest is per context); use a single device")
+
+    def kg_argbest(self, points, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
+                   return_values: bool = False, return_point_means: bool = False):
+        raise NotImplementedError("a device group has no knowledge gradient (gpbo_kg_argbest is per context); use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
         raise NotImplementedError("a device group has no posterior refresh path (gpbo_posterior_refresh is per context); "

@@ -460,6 +460,41 @@ int gpbo_acq_argbest(gpbo_ctx* ctx, int acq, double acq_param, double y_max, int
 int gpbo_mes_argbest(gpbo_ctx* ctx, int n_samples, const double* y_star, int k_seeds, int64_t index_offset,
                      int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val, double* ys_out);
 
+/* Knowledge gradient (KG; Frazier, Powell & Dayanik 2009, "The knowledge-gradient policy for correlated normal beliefs"; Scott,
+ * Frazier & Powell 2011 for continuous parameters) over the resident candidates, in its discrete form: a candidate is scored by how
+ * much OBSERVING it would raise the maximum of the posterior MEAN over itself and n_points = J reference points — the look-ahead
+ * acquisition for noisy objectives, where EI's incumbent is itself a noisy number.  From slot 0's resident mu / sd (y_mean / y_std:
+ * those of the pass that left them; y_std must be the recorded one) and `points` (J, d), host, in parameter space (scaled by the
+ * slot's length scales on the device).  c, w: the slot's amplitude and white (1, 0 for a unit model); eta: the diagonal noise of
+ * the slot's unit model; lambda = c eta the observation noise in normalised-target units (white + alpha of gpbo_fit_scaled, `noise`
+ * of gpbo_fit).  Per candidate x:
+ *   B_j      = W^T (W k*(a_j))                                   the unit model's K'^-1 k*(a_j), once per point
+ *   cov_j(x) = c (k(x, a_j) - sum_i k(x, X_i) B_j,i)             latent posterior covariance, normalised units
+ *   mu_j     = y_std (sum_i alpha_i k(a_j, X_i)) + y_mean        posterior mean at a_j (mu_points_out, (J,) or NULL)
+ *   v(x)     = (sd(x) / y_std)^2                                 resident; includes a scaled slot's white
+ *   den(x)   = sqrt(v(x) + lambda - w)                           sd of the OBSERVATION at x
+ *   lines    : (a_0, b_0) = (mu(x), y_std max(v(x) - w, 0) / den(x)),   (a_j, b_j) = (mu_j, y_std cov_j(x) / den(x)), j = 1 .. J
+ *   KG(x)    = E_Z[max_j (a_j + b_j Z)] - max_j a_j >= 0,  Z ~ N(0, 1);      ys = -KG
+ * evaluated exactly by Frazier's algorithm: the lines ordered by (slope, intercept), among equal slopes the largest intercept kept,
+ * the upper envelope with its breakpoints c_1 < ... < c_{n-1}, KG = sum_i (b_{i+1} - b_i) f(-|c_i|), f(z) = phi(z) + z Phi(z) (Phi,
+ * phi as gpbo_acq_argbest's EI evaluates them).  The lines are ORDERED first, so the result does not depend on the order in which
+ * equal lines arrive.  O(N d + N J) per candidate, against the O(N^2) of the posterior pass that left mu / sd.
+ * Conventions: den(x) == 0 gives KG = 0 (nothing is learned); a NaN mu(x) or sd(x), or a line with a NaN or infinite entry, gives
+ * NaN, and the selection's "first NaN wins" rule applies.  Every sum has a fixed order: a candidate's bits depend neither on M nor
+ * on the other candidates.  fp64 whatever the slot's precision.
+ * Outputs, selection and index_offset exactly as gpbo_mes_argbest, on the key ys.
+ * A reader: the slot's fit, its resident mu / sd, what gpbo_posterior_refresh may still refresh, the candidates and the
+ * negative-variance flag stay as they were; only the context's acquisition values are overwritten.  The points are staged in a
+ * workspace of the call's own (the candidate buffer is not borrowed).
+ * GPBO_ERR_INVALID: n_points outside [1, GPBO_MAX_KG_POINTS], d not the slot's, NULL or non-finite points, k_seeds outside
+ * [0, GPBO_MAX_SEEDS], a NULL best_idx / best_val (seed_idx / seed_val with k_seeds > 0), y_mean not finite, y_std not finite, not
+ * positive or not the one the resident posterior was scaled with.  GPBO_ERR_STATE: slot 0 unfitted or with a fit pending, no
+ * candidates, no resident posterior for them.  There is no gpbo_group_* / gpbo_comm_* form. */
+#define GPBO_MAX_KG_POINTS 64
+int gpbo_kg_argbest(gpbo_ctx* ctx, const double* points, int n_points, int d, double y_mean, double y_std, int k_seeds,
+                    int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val,
+                    double* ys_out, double* mu_points_out);
+
 /* ---- timing (HIP events on the context stream) ------------------------------------------ */
 /* Milliseconds spent in the last call's kernels: [0] fit total, [1] posterior main kernel,
  * [2] posterior finalize, [3] acquisition + arg-best, [4] kmat assembly, [5] cholesky, [6] trtri. */
@@ -560,7 +595,7 @@ int gpbo_hbm_copy_peak(gpbo_ctx* ctx, int64_t bytes, double* gbps);
 /* ==== DEBUG BUILD ONLY (-DGPBO_DEBUG: bayesianoptimization_amd/libgpbo_dbg.so) ==========================================
  * Self-test seams, single-kernel timers and micro-benchmarks the tests and scripts/ use.  The product library
  * (libgpbo.so) exports none of them, reads none of the A/B environment switches (GPBO_CHOL_*, GPBO_POST_*, GPBO_SMALL_MAX,
- * GPBO_SELECT_V2*, GPBO_MT_*, GPBO_GEMM128, GPBO_TRI_GRID, GPBO_LML_GRAPH, GPBO_POLISH_FUSED*) and contains no scratch-using kernel. */
+ * GPBO_SELECT_V2*, GPBO_MT_*, GPBO_GEMM128, GPBO_TRI_GRID, GPBO_LML_GRAPH, GPBO_POLISH_FUSED*, GPBO_KG_NS) and contains no scratch-using kernel. */
 #ifdef GPBO_DEBUG
 /* The optimiser of gpbo_polish_seeds alone, over a host objective (self-test seam: no device, no context): `fg` is called
  * once per lockstep round with the trial points of the runs that are still alive — x (n_live,d) -> f (n_live), g (n_live,d) —
@@ -641,6 +676,14 @@ int gpbo_debug_i8_kstar_digits(gpbo_ctx* ctx, int64_t NP, int64_t m0, int64_t ld
  * gpbo_debug_i8_pack_w returns it, wscale (NP,), Kd (M NP S bytes), M a multiple of 64; part_out [ceil(NP / 128)][M] = the
  * sums of v^2 per 128-row chunk. */
 int gpbo_debug_i8_gemm(gpbo_ctx* ctx, const void* Wd, const double* wscale, const void* Kd, int64_t NP, int64_t M, double* part_out);
+/* The envelope of gpbo_kg_argbest alone (the device function its value kernel calls) on R host-given sets of n_lines lines, a / b
+ * (R, n_lines) intercepts / slopes, 1 <= n_lines <= GPBO_MAX_KG_POINTS + 1: out[r] = E[max_j (a_j + b_j Z)] - max_j a_j, NaN for a
+ * set with a NaN or infinite entry. */
+int gpbo_debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out);
+/* Kernel milliseconds (HIP events) of the three stages of the context's last gpbo_kg_argbest: ms[0] the points (k*, means, solves),
+ * ms[1] the candidate x point covariances (with the candidates' scaling), ms[2] the envelopes.  GPBO_KG_NS = 16 | 32 | 64 forces the
+ * covariance kernel's columns per pass. */
+int gpbo_debug_kg_stage_ms(gpbo_ctx* ctx, float* ms);
 #endif /* GPBO_DEBUG */
 
 #ifdef __cplusplus
