@@ -69,6 +69,9 @@ SIGNATURES = {
                                                        _c_double_p, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_uint32),
                                                        C.POINTER(C.c_int)]),
     "gpbo_mt19937_jump_blocks": (C.c_int, [C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_uint32)]),
+    "gpbo_generate_candidates_trust_region": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _c_double_p, _c_double_p, _c_double_p,
+                                                        C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
+                                                        C.c_uint64]),
     "gpbo_generate_candidate_columns_mt19937": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, _c_double_p, _c_double_p,
                                                           C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "gpbo_set_candidate_columns": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, C.c_int, C.c_int, C.c_int]),
@@ -152,6 +155,7 @@ DEBUG_SIGNATURES = {
     "gpbo_debug_latency_probe": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "gpbo_debug_kg_lines": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, C.c_int, _c_double_p]),
     "gpbo_debug_kg_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "gpbo_debug_generate_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "gpbo_debug_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_float)]),
     "gpbo_debug_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, _c_double_p, _c_double_p,

@@ -1,6 +1,6 @@
-"""What suggest_batch (batch.py), suggest_thompson (thompson.py) and suggest_mes (mes.py) share, each thing once: the check of a count
-argument, the gate an optimizer passes before anything runs, the frame of the fitted model, and the loop over groups of posterior
-draws.  The ORDER of the refusals is part of the three functions' contract: a caller's own argument checks come
+"""What suggest_batch (batch.py), suggest_thompson (thompson.py), suggest_mes (mes.py), suggest_kg (kg.py) and suggest_turbo (turbo.py)
+share, each thing once: the check of a count argument, the gate an optimizer passes before anything runs, the frame of the fitted
+model, the loop over groups of posterior draws, and the picks of a Thompson batch (suggest_thompson, suggest_turbo).  The ORDER of the refusals is part of the three functions' contract: a caller's own argument checks come
 first, then `gate`, then whatever it checks about `refine` — so an un-accelerated optimizer is refused as such, whatever else is
 wrong with the call.
 """
@@ -77,13 +77,15 @@ def fit_model(gp, space, who: str) -> Model:
     return read_model(gp, space, who)
 
 
-def draw_groups(gp, space, eng, rng, model: Model, n_draws: int, n_features: int, refine: int, max_iter):
+def draw_groups(gp, space, eng, rng, model: Model, n_draws: int, n_features: int, refine: int, max_iter, box=None):
     """`n_draws` posterior function draws over the resident candidates in groups of at most 16, one engine call per group: yields
     (first, S, result) with result what `ascend_paths(n_starts=refine)` returns, or with refine = 0 `sample_paths`.  Per group the
     draws from `rng`, in this order: `spectral_draw` (fresh features), `standard_normal((S, F))` — the feature weights —,
-    `standard_normal((S, N))` scaled by sqrt(noise) — the noise draws.  The engine call draws nothing."""
+    `standard_normal((S, N))` scaled by sqrt(noise) — the noise draws.  The engine call draws nothing.  `box`: the (lo, hi) a climb
+    stays inside (None: the space's bounds)."""
     from .thompson import spectral_draw
 
+    box_lo, box_hi = (space.bounds[:, 0], space.bounds[:, 1]) if box is None else box
     for first in range(0, n_draws, MAX_PATHS):
         S = min(MAX_PATHS, n_draws - first)
         omega, phase = spectral_draw(gp._kind, n_features, model.d, rng)
@@ -91,8 +93,25 @@ def draw_groups(gp, space, eng, rng, model: Model, n_draws: int, n_features: int
         eps = rng.standard_normal((S, model.N)) * np.sqrt(model.noise)
         gp._ensure_resident()
         if refine:
-            yield first, S, eng.ascend_paths(omega, phase, weights, eps, space.bounds[:, 0], space.bounds[:, 1], n_starts=refine,
+            yield first, S, eng.ascend_paths(omega, phase, weights, eps, box_lo, box_hi, n_starts=refine,
                                              max_iter=-1 if max_iter is None else int(max_iter), slot=gp.slot,
                                              y_mean=model.y_mean, y_std=model.y_std)
         else:
             yield first, S, eng.sample_paths(omega, phase, weights, eps, slot=gp.slot, y_mean=model.y_mean, y_std=model.y_std)
+
+
+def thompson_picks(gp, space, eng, rng, model: Model, q: int, n_features: int, refine: int, max_iter, box=None):
+    """q parameter dicts, one per posterior draw over the resident candidates (`draw_groups`, its draws from `rng`): refine = 0 the
+    draw's maximiser among the candidates, its row fetched from the device; refine = K the best of its K climbed runs inside `box`
+    (None: the space's bounds) — a draw without a finite run keeps its first start, its best candidate."""
+    picks = []
+    for _first, n, out in draw_groups(gp, space, eng, rng, model, q, n_features, refine, max_iter, box):
+        if refine:
+            picks.extend(out["x_best"][s] if out["winner"][s] >= 0 else out["x"][s, 0] for s in range(n))
+        else:
+            picks.extend(int(i) for i in out[0])
+    if refine:
+        rows = np.asarray(picks, dtype=np.float64).reshape(q, model.d)
+    else:
+        rows = np.asarray(eng.get_candidate_rows(np.array(picks, dtype=np.int64), model.d), dtype=np.float64)
+    return [space.array_to_params(x) for x in rows]

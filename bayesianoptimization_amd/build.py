@@ -49,6 +49,7 @@ SOURCES = {
     "mes.hip": ["-ffp-contract=off"],         # gpbo_mes_argbest: max-value entropy search values (acq_formulas.h's pieces, the bits they have in acq_kernels.hip)
     "kg.hip": ["-ffp-contract=off"],          # gpbo_kg_argbest: knowledge gradient values (candidate x point covariances, upper envelope of J + 1 lines; acq_formulas.h's pieces)
     "candidates.hip": [],
+    "trust_region.hip": ["-ffp-contract=off"],  # gpbo_generate_candidates_trust_region: lo + (hi - lo) * u as NumPy computes it (scrambled Sobol points under a Philox mask)
     "mt19937.hip": ["-ffp-contract=off"],      # lo + (hi - lo) * u as NumPy computes it
     "mt_jump.hip": [],                         # jump-ahead polynomials (host) + sub-stream start states (device)
     "probe.hip": [],                           # calibration: MFMA fp64 peak / sustained clock, HBM copy peak (bench.py's roofline keys)

@@ -5,23 +5,9 @@
 // (M, d) uniform matrix directly in HBM: no host sampling, no H2D copy.  Doubles are formed like NumPy's
 // random_sample: (a >> 5) * 2^26 + (b >> 6) over 2^53, then lo + (hi - lo) * u.
 #include "gpbo_internal.h"
+#include "philox.h"
 
 namespace gpbo {
-
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0;
-    const unsigned n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
-    const unsigned n3 = (unsigned)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
 
 // element index e = m * d + t; each Philox call yields two doubles (elements 2q, 2q+1)
 __global__ __launch_bounds__(256) void generate_candidates_kernel(double* __restrict__ Xc, int64_t total, int d,
@@ -189,8 +175,10 @@ extern "C" int gpbo_generate_candidates(gpbo_ctx* ctx, int64_t M, int d, const d
   for (int t = 0; t < d; ++t) { h[t] = lo[t]; h[GPBO_MAX_DIM + t] = hi[t]; }
   GPBO_HIP(ctx, hipMemcpyAsync(ctx->red, h, 2 * GPBO_MAX_DIM * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   const int64_t total = M * d, nq = (total + 1) / 2;
+  generate_mark(ctx, 0);
   generate_candidates_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream>>>(
       ctx->Xc, total, d, (const double*)ctx->red, (unsigned long long)seed);
+  generate_mark(ctx, 1);
   GPBO_HIP(ctx, hipGetLastError());
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->M = M;

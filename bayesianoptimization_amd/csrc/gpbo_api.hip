@@ -223,6 +223,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   if (ctx->small_pinned) (void)hipHostFree(ctx->small_pinned);
   if (ctx->polish_pinned) (void)hipHostFree(ctx->polish_pinned);
   if (ctx->fused_stage) (void)hipHostFree(ctx->fused_stage);

@@ -172,6 +172,8 @@ struct gpbo_ctx {
   int64_t cap_kg = 0;
   hipEvent_t kg_ev[4] = {};   // debug build: around the three stages of the last gpbo_kg_argbest (the fields exist in both builds: one layout)
   bool kg_ev_used = false;
+  hipEvent_t gen_ev[2] = {};  // debug build: around the kernel of the last gpbo_generate_candidates / _trust_region (generate_mark)
+  bool gen_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
   int64_t cap_paths = 0;
   void* red = nullptr;     // reduction scratch
@@ -635,6 +637,9 @@ int launch_kg_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* poi
 int debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out);
 int debug_kg_stage_ms(gpbo_ctx* ctx, float* ms3);
 #endif
+// trust_region.hip: debug build: records event i (0 before, 1 after) of a candidate generator's kernel for gpbo_debug_generate_ms;
+// the product records nothing
+void generate_mark(gpbo_ctx* ctx, int i);
 // acq_kernels.hip: the k best of each of n_rows rows of M keys (rows + r * ld), the rules of launch_acq_argbest: best_idx / best_val
 // (n_rows) the arg-best, top_idx (n_rows, k; may be null) the rows' k smallest keys in order (ties to the lowest index, NaNs last)
 // as LOCAL indices; synchronises

@@ -473,6 +473,44 @@ class GpEngine:
         self.n_candidates = int(M)
         self._cand_dim = lo.shape[0]
 
+    def generate_candidates_trust_region(self, M: int, centre, lo, hi, sv, shift, bits: int, mask_threshold: int, mask_key: int):
+        """Trust-region mode (gpbo_generate_candidates_trust_region; include/gpbo.h has the definition of an element): M rows equal
+        to `centre` except where a Philox mask under `mask_key` marks a coordinate (word < `mask_threshold`, 0 .. 2^32; a row the
+        mask leaves empty gets one column), which takes the row's point of the scrambled Sobol sequence `sv` (d, bits) uint32 /
+        `shift` (d,) uint32 (turbo.sobol_tables) mapped into [lo, hi].  Quasi-random, NOT the reference's stream; draws nothing on
+        the host.  ValueError: a shape or dtype that does not fit, and every refusal of the library (M, bits, the threshold, a
+        non-finite or inverted box) — the resident candidates then stay as they were."""
+        centre = np.ascontiguousarray(centre, dtype=np.float64)
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        if centre.ndim != 1 or centre.shape[0] < 1 or lo.shape != centre.shape or hi.shape != centre.shape:
+            raise ValueError("centre, lo and hi must be 1-D of one length d >= 1")
+        d = centre.shape[0]
+        if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)):
+            raise ValueError("bits must be an integer")
+        sv, shift = np.asarray(sv), np.asarray(shift)
+        if sv.dtype != np.uint32 or shift.dtype != np.uint32:
+            raise ValueError("sv and shift must be uint32 arrays")
+        if sv.shape != (d, int(bits)) or shift.shape != (d,):
+            raise ValueError("sv must be (d, bits) and shift (d,)")
+        mask_threshold, mask_key = int(mask_threshold), int(mask_key)
+        if not 0 <= mask_threshold <= 2 ** 32:
+            raise ValueError("mask_threshold must be in [0, 2^32]")
+        sv, shift = np.ascontiguousarray(sv), np.ascontiguousarray(shift)
+        u32 = C.POINTER(C.c_uint32)
+        self._check(self._lib.gpbo_generate_candidates_trust_region(
+            self._h, int(M), d, dptr(centre), dptr(lo), dptr(hi), sv.ctypes.data_as(u32), int(bits), shift.ctypes.data_as(u32),
+            mask_threshold, mask_key & 0xFFFFFFFFFFFFFFFF))
+        self.n_candidates = int(M)
+        self._cand_dim = d
+
+    def debug_generate_ms(self):
+        """gpbo_debug_generate_ms (debug build): kernel ms of the last `generate_candidates` / `generate_candidates_trust_region`."""
+        self._need_debug("gpbo_debug_generate_ms")
+        ms = C.c_float(0.0)
+        self._check(self._lib.gpbo_debug_generate_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def generate_candidates_like(self, M: int, lo, hi, random_state):
         """Index-parity mode: what `np.column_stack([random_state.uniform(lo[t], hi[t], M) for t in range(d)])`
         would be, generated on the device from `random_state`'s MT19937 state; `random_state` (a legacy
@@ -1272,6 +1310,10 @@ class GroupEngine(GpEngine):
     def generate_candidates(self, M: int, lo, hi, seed: int):
         raise NotImplementedError("the Philox throughput generator is per device; a device group draws the reference's "
                                   "stream (device_sampling='auto' / False)")
+
+    def generate_candidates_trust_region(self, M: int, centre, lo, hi, sv, shift, bits: int, mask_threshold: int, mask_key: int):
+        raise NotImplementedError("a device group has no trust-region generator (gpbo_generate_candidates_trust_region is per "
+                                  "context); use a single device")
 
     def generate_candidates_like(self, M: int, lo, hi, random_state):
         """The reference's candidate matrix from `random_state` (one uniform(lo_j, hi_j, M) per column, in order —

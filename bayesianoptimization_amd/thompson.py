@@ -88,15 +88,4 @@ def suggest_thompson(optimizer, q: int, n_random: int = 10_000, n_features: int 
 
     model = S.fit_model(gp, space, "suggest_thompson")
     eng.generate_candidates_like(n_random, space.bounds[:, 0], space.bounds[:, 1], rng)
-    picks = []
-    for _first, n, out in S.draw_groups(gp, space, eng, rng, model, q, n_features, refine, max_iter):
-        if refine:
-            # (a draw without a finite run keeps its first start: its best candidate)
-            picks.extend(out["x_best"][s] if out["winner"][s] >= 0 else out["x"][s, 0] for s in range(n))
-        else:
-            picks.extend(int(i) for i in out[0])
-    if refine:
-        rows = np.asarray(picks, dtype=np.float64).reshape(q, model.d)
-    else:
-        rows = np.asarray(eng.get_candidate_rows(np.array(picks, dtype=np.int64), model.d), dtype=np.float64)
-    return [space.array_to_params(x) for x in rows]
+    return S.thompson_picks(gp, space, eng, rng, model, q, n_features, refine, max_iter)

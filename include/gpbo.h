@@ -219,6 +219,26 @@ int gpbo_generate_candidate_rows_mt19937(gpbo_ctx* ctx, int64_t M, int d, int64_
  * gpbo_generate_candidates_mt19937 starts its sub-streams on the device (csrc/mt_jump.hip).  Equivalent to drawing
  * 624 * n_blocks outputs from numpy.random.RandomState and reading get_state()[1], in O(log n_blocks) polynomial products. */
 int gpbo_mt19937_jump_blocks(const uint32_t key_in[624], int64_t n_blocks, uint32_t key_out[624]);
+/* Trust-region mode (TuRBO; Eriksson et al. 2019, "Scalable global optimization via local Bayesian optimization"): the resident
+ * candidate matrix (M, d) row-major becomes the point `centre` with a FEW coordinates of every row replaced by a point of a scrambled
+ * Sobol sequence inside the box [lo, hi] — quasi-random, NOT the reference's stream.  The caller passes the sequence's tables:
+ * sobol_sv (d, bits) row-major, the direction numbers after scrambling, and sobol_shift (d,), the digital shift, each word below
+ * 2^bits (scipy.stats.qmc.Sobol(d, scramble=True, seed, bits): its _sv and _shift).  Row m, column t, element e = m d + t:
+ *   Sobol point  g = m ^ (m >> 1);  w(m, t) = shift[t] XOR over the set bits b of g of sv[t bits + b];  u = w 2^-bits (exact);
+ *                point = lo[t] + (hi[t] - lo[t]) * u, every operation rounded once (no fused multiply-add) — with lo = 0, hi = 1
+ *                the matrix of points equals Sobol(...).random(M) of a fresh engine bit for bit, whatever M.
+ *   mask         philox4x32_10(counter = (q_lo, q_hi, 0, 0), key = mask_key), q = e >> 2, gives four 32-bit words; element e takes
+ *                word e & 3 and is PERTURBED iff word < mask_threshold (2^32: every coordinate, 0: none).
+ *   fallback     a row without a perturbed coordinate gets exactly one: column (w0 d) >> 32, w0 = word 0 of
+ *                philox4x32_10(counter = (m_lo, m_hi, 1, 0), key = mask_key).
+ *   value        the Sobol point where perturbed, else centre[t] bit for bit.
+ * lo <= centre <= hi is not required.  GPBO_ERR_INVALID, with the resident candidates and their posteriors left as they were: a NULL
+ * pointer, M < 1, d outside [1, GPBO_MAX_DIM], bits outside [1, 32], M > 2^bits, mask_threshold > 2^32, a non-finite centre / lo /
+ * hi, lo[t] > hi[t].  On success the context's posteriors are dropped like after gpbo_generate_candidates.  One launch; per device
+ * only (no group and no communicator form). */
+int gpbo_generate_candidates_trust_region(gpbo_ctx* ctx, int64_t M, int d, const double* centre, const double* lo, const double* hi,
+                                          const uint32_t* sobol_sv, int bits, const uint32_t* sobol_shift, uint64_t mask_threshold,
+                                          uint64_t mask_key);
 /* Copy n rows (by index) of the resident candidate matrix back to the host (x_min and the seeds,
  * bayes_opt/acquisition.py:313-317); out is (n, d) row-major; out-of-range indices give NaN rows. */
 int gpbo_get_candidate_rows(gpbo_ctx* ctx, const int64_t* idx, int n, double* out);
@@ -684,6 +704,9 @@ int gpbo_debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t
  * ms[1] the candidate x point covariances (with the candidates' scaling), ms[2] the envelopes.  GPBO_KG_NS = 16 | 32 | 64 forces the
  * covariance kernel's columns per pass. */
 int gpbo_debug_kg_stage_ms(gpbo_ctx* ctx, float* ms);
+/* Kernel milliseconds (HIP events) of the generator kernel of the context's last gpbo_generate_candidates or
+ * gpbo_generate_candidates_trust_region call: the launch alone, without the call's argument upload and synchronise. */
+int gpbo_debug_generate_ms(gpbo_ctx* ctx, float* ms);
 #endif /* GPBO_DEBUG */
 
 #ifdef __cplusplus
