@@ -81,6 +81,9 @@ SIGNATURES = {
     "gpbo_posterior_refresh": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, _c_double_p, _c_double_p, C.POINTER(C.c_int)]),
     "gpbo_sample_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p, C.c_int64, _c_int64_p, _c_double_p, _c_double_p]),
+    "gpbo_sample_paths_constrained": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int,
+                                                C.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64, _c_int64_p,
+                                                _c_double_p, _c_double_p, _c_int_p, _c_double_p, _c_double_p]),
     "gpbo_ascend_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int64,
                                     _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int_p, _c_int_p, _c_int64_p]),

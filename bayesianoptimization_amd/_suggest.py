@@ -1,4 +1,5 @@
-"""What suggest_batch (batch.py), suggest_thompson (thompson.py), suggest_mes (mes.py), suggest_kg (kg.py) and suggest_turbo (turbo.py)
+"""What suggest_batch (batch.py), suggest_thompson (thompson.py), suggest_mes (mes.py), suggest_kg (kg.py), suggest_turbo (turbo.py) and
+the constrained pair suggest_constrained_thompson / suggest_scbo (scbo.py: the gate with `constrained=True`, the frame of a model)
 share, each thing once: the check of a count argument, the gate an optimizer passes before anything runs, the frame of the fitted
 model, the loop over groups of posterior draws, and the picks of a Thompson batch (suggest_thompson, suggest_turbo).  The ORDER of the refusals is part of the three functions' contract: a caller's own argument checks come
 first, then `gate`, then whatever it checks about `refine` — so an un-accelerated optimizer is refused as such, whatever else is
@@ -28,16 +29,17 @@ def count(value, lo: int, hi, message: str, out_of_range=None) -> int:
     return value
 
 
-def gate(optimizer, who: str, word: str, calls, group: str):
+def gate(optimizer, who: str, word: str, calls, group: str, constrained: bool = False):
     """(gp, space, engine) of an optimizer whose model `who` can work on, else the refusal — in this order: the GP is not a HipGPR on
     slot 0, the space is empty, it has a constraint, it has an input transform, the engine is a device group (`group`: the sentence
-    that says what a group lacks), the engine lacks one of `calls`, the model runs on the host.  `word`: "sampled" / "batched"."""
+    that says what a group lacks), the engine lacks one of `calls`, the model runs on the host.  `word`: "sampled" / "batched".
+    `constrained`: a constraint is admitted instead of refused, and checked LAST (`admit_constraint`)."""
     gp, space = optimizer._gp, optimizer._space
     if not isinstance(gp, HipGPR) or gp.slot != 0:
         raise NotImplementedError(f"{who}: the optimizer's GP is not on the engine (call accelerate(optimizer) first)")
     if len(space) == 0:
         raise A.TargetSpaceEmptyError(A.EMPTY_SPACE_MESSAGE)
-    if space.constraint is not None:
+    if space.constraint is not None and not constrained:
         raise A.ConstraintNotSupportedError(f"Received constraints, but {who} does not support constrained optimization.")
     if gp.transform is not None:
         raise NotImplementedError(f"{who}: the space has an input transform (int / categorical parameters); "
@@ -52,7 +54,32 @@ def gate(optimizer, who: str, word: str, calls, group: str):
     reason = None if gp.kernel is None else gp._unsupported_reason(clone(gp.kernel), space.target, space.params)
     if reason is not None:
         raise NotImplementedError(f"{who}: the model runs on the host ({reason}); only models on the device path are {word}")
+    if space.constraint is not None:
+        admit_constraint(space, eng, who, word)
     return gp, space, eng
+
+
+def admit_constraint(space, eng, who: str, word: str):
+    """The constraint model of `space` as the constrained suggest functions need it, else NotImplementedError naming `who`: a
+    HipConstraintModel whose GPs are HipGPRs on `eng`, constraint j in slot j (1..C), without a transform and on the device path."""
+    from sklearn.base import clone
+
+    from .constraint_model import HipConstraintModel
+
+    cons = space.constraint
+    if not isinstance(cons, HipConstraintModel):
+        raise NotImplementedError(f"{who}: the space's constraint model is not a HipConstraintModel on the optimizer's engine")
+    values = getattr(space, "_constraint_values", None)
+    for j, cgp in enumerate(cons.model, start=1):
+        if not isinstance(cgp, HipGPR) or cgp.slot != j or cgp.engine is not eng:
+            raise NotImplementedError(f"{who}: constraint {j}'s GP is not on the optimizer's engine in slot {j}")
+        if cgp.transform is not None:
+            raise NotImplementedError(f"{who}: constraint {j}'s GP has an input transform; only all-float spaces are {word}")
+        column = None if values is None else np.asarray(values).reshape(len(space), -1)[:, j - 1]
+        reason = None if cgp.kernel is None or column is None else cgp._unsupported_reason(clone(cgp.kernel), column, space.params)
+        if reason is not None:
+            raise NotImplementedError(f"{who}: constraint {j}'s model runs on the host ({reason}); only models on the device path "
+                                      f"are {word}")
 
 
 #: the fitted model as the suggest functions read it.  scale: the slot's (amplitude, white), None for a unit model; noise: the

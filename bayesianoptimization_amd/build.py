@@ -40,7 +40,7 @@ SOURCES = {
     "posterior_kernel_f32.hip": [],
     "posterior_cov.hip": [],
     "posterior_refresh.hip": [],               # gpbo_posterior_refresh: the resident posterior after row appends, one k* generation against 1 + n_rows weight vectors
-    "posterior_paths.hip": [],                 # gpbo_sample_paths: posterior function draws over the candidates (Matheron's rule over random Fourier features)
+    "posterior_paths.hip": [],                 # gpbo_sample_paths: posterior function draws over the candidates (Matheron's rule over random Fourier features); gpbo_sample_paths_constrained: the same pass per slot with the violation fold / key epilogue
     "path_ascent.hip": [],                     # gpbo_ascend_paths: each draw climbed to a local maximiser, one workgroup per (path, start), evaluations + optimiser inside
     "lml_kernels.hip": [],
     "fused_small.hip": [],                     # fit / LML evaluation of a small problem (NP <= 64) as ONE launch of ONE workgroup

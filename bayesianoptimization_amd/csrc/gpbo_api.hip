@@ -232,7 +232,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->kg, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1270,6 +1270,90 @@ int gpbo_sample_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int 
     GPBO_HIP(ctx, hipMemcpyAsync(values_out, ctx->ys, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t i = 0; i < n; ++i) values_out[i] = -values_out[i];
+  }
+  return GPBO_OK;
+}
+
+int gpbo_sample_paths_constrained(gpbo_ctx* ctx, int n_constraints, const double* y_mean, const double* y_std, const double* lb,
+                                  const double* ub, int n_paths, int n_features, const double* omega, const double* phase,
+                                  const double* weights, const double* eps, int64_t index_offset, int64_t* best_idx, double* best_val,
+                                  double* best_viol, int* feasible_out, double* values_out, double* viol_out) {
+  const char* who = "sample_paths_constrained";
+  const std::string w = std::string(who) + ": ";
+  if (!ctx) return GPBO_ERR_INVALID;
+  const int C = n_constraints, S = n_paths, F = n_features;
+  if (C < 1 || C > GPBO_MAX_MODELS - 1) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_constraints out of range [1, 7]");
+  if (!y_mean || !y_std || !lb || !ub || !omega || !phase || !weights || !eps || !best_idx || !best_val || !best_viol || !feasible_out) {
+    // the counts first, as check_path_args orders them
+    if (S < 1 || S > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_paths out of range [1, 16]");
+    if (F < 1 || F > GPBO_MAX_PATH_FEATURES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_features out of range [1, 4096]");
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL argument");
+  }
+  int rc;
+  const Model* ms[GPBO_MAX_MODELS];
+  for (int j = 0; j <= C; ++j)
+    if ((rc = check_path_args(ctx, who, j, y_mean[j], y_std[j], S, F, 1, nullptr, &ms[j]))) return rc;
+  for (int j = 0; j < C; ++j)
+    if (lb[j] != lb[j] || ub[j] != ub[j] || !(lb[j] < ub[j]))
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "the bounds must not be NaN, with lb < ub for every constraint");
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates)");
+  for (int j = 0; j <= C; ++j)
+    if (ctx->d_c != ms[j]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from a fitted model's");
+  const int64_t M = ctx->M;
+  const int d = ctx->d_c;
+  const ConstrainedBlock b = constrained_block(S, M, ms[0]->DP, values_out != nullptr);
+  if ((rc = ensure(ctx, &ctx->cpaths, &ctx->cap_cpaths, b.doubles))) return rc;
+  double* viol = ctx->cpaths + b.viol;
+  double* vals = values_out ? ctx->cpaths + b.vals : nullptr;
+  // slot j's draws in the concatenated inputs
+  const double* eps_of[GPBO_MAX_MODELS];
+  {
+    const double* e = eps;
+    for (int j = 0; j <= C; ++j) { eps_of[j] = e; e += (int64_t)S * ms[j]->N; }
+  }
+  // the constraints in slot order (the violation's sum order), the objective last: its keys need the whole sum, and its path
+  // weights stay in the workspace for the rows that fall back to the least violation
+  PathWorkspace ws{};
+  const size_t row_bytes = (size_t)S * (size_t)M * sizeof(double);
+  for (int t = 1; t <= C + 1; ++t) {
+    const int j = t <= C ? t : 0;
+    const PathFold fold{path_epilogue(j), j ? lb[j - 1] : 0.0, j ? ub[j - 1] : 0.0, viol, vals};
+    if ((rc = launch_sample_paths_fold(ctx, *ms[j], M, y_mean[j], y_std[j], S, F, omega + (int64_t)j * F * d, phase + (int64_t)j * F,
+                                       weights + (int64_t)j * S * F, eps_of[j], fold, &ws)))
+      return rc;
+    if (values_out)      // stream order: the next slot's pass overwrites vals after this copy has read it
+      GPBO_HIP(ctx, hipMemcpyAsync(values_out + (int64_t)j * S * M, vals, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (viol_out) GPBO_HIP(ctx, hipMemcpyAsync(viol_out, viol, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  // one selection over the keys; a row whose least key is +inf has no feasible candidate and takes its least violation
+  if ((rc = launch_topk_rows(ctx, ctx->ys, M, S, M, 1, index_offset, best_idx, best_val, nullptr))) return rc;
+  int64_t fallback_idx[GPBO_MAX_PATHS];
+  int fallback_row[GPBO_MAX_PATHS], n_fallback = 0;
+  for (int s = 0; s < S; ++s) {
+    if (best_val[s] != best_val[s]) {
+      best_viol[s] = best_val[s];
+      feasible_out[s] = 0;
+    } else if (best_val[s] == std::numeric_limits<double>::infinity()) {
+      if ((rc = launch_topk_rows(ctx, viol + (int64_t)s * M, M, 1, M, 1, 0, best_idx + s, best_viol + s, nullptr))) return rc;
+      fallback_idx[n_fallback] = best_idx[s];
+      fallback_row[n_fallback++] = s;
+      best_idx[s] += index_offset;
+      feasible_out[s] = 0;
+    } else {
+      best_val[s] = -best_val[s];      // the key is -f
+      best_viol[s] = 0.0;
+      feasible_out[s] = 1;
+    }
+  }
+  if (n_fallback) {
+    double* f = ctx->cpaths + b.f;
+    double host[GPBO_MAX_PATHS * GPBO_MAX_PATHS];
+    if ((rc = launch_paths_at(ctx, *ms[0], ws, y_mean[0], y_std[0], S, F, fallback_idx, n_fallback, ctx->cpaths + b.pts, f,
+                              GPBO_MAX_PATHS)))
+      return rc;
+    GPBO_HIP(ctx, hipMemcpyAsync(host, f, (size_t)S * GPBO_MAX_PATHS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int r = 0; r < n_fallback; ++r) best_val[fallback_row[r]] = host[fallback_row[r] * GPBO_MAX_PATHS + r];
   }
   return GPBO_OK;
 }

@@ -176,6 +176,8 @@ struct gpbo_ctx {
   bool gen_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
   int64_t cap_paths = 0;
+  double* cpaths = nullptr; // gpbo_sample_paths_constrained: viol | one slot's values | the fallback picks' points and values (path_plan.h)
+  int64_t cap_cpaths = 0;
   void* red = nullptr;     // reduction scratch
   int64_t cap_red = 0;
   int* info_dev = nullptr; // potrf info word
@@ -598,6 +600,14 @@ struct PathWorkspace { double* base; PathBlock at; double* p(int64_t off) const 
 int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int n_paths, int n_features,
                         const double* omega, const double* phase, const double* weights, const double* eps, int n_runs,
                         PathWorkspace* ws);
+// gpbo_sample_paths_constrained: one slot's pass with its epilogue (path_plan.h: PathEpilogue), and the last pass's paths again at
+// up to 16 candidates (the picks of the rows without a feasible candidate)
+struct PathFold { int epilogue; double lb, ub; double* viol; double* vals; };
+int launch_sample_paths_fold(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int n_paths, int n_features,
+                             const double* omega, const double* phase, const double* weights, const double* eps, const PathFold& fold,
+                             PathWorkspace* ws);
+int launch_paths_at(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, double y_mean, double y_std, int n_paths, int n_features,
+                    const int64_t* idx, int n, double* pts, double* f, int ld);
 // ... and the first half of it alone: the draws' inputs and V = alpha - W^T (W (g(X) + eps)) made resident, no candidates needed
 int launch_path_weights(gpbo_ctx* ctx, const Model& m, int n_paths, int n_features, const double* omega, const double* phase,
                         const double* weights, const double* eps, int n_runs, PathWorkspace* ws);

@@ -55,4 +55,27 @@ inline PathBlock path_block(int S_, int F_, int N_, int NP_, int d_, int n_runs)
   return b;
 }
 
+// gpbo_sample_paths_constrained: what path_eval_kernel does with a point's S values behind its accumulators.  PLAIN stores them
+// (gpbo_sample_paths); a constraint slot folds its violation terms into viol[S][M] — the first one writes, the later ones add, so
+// the sum's order is the slots' —; the objective reads viol and stores the selection key.
+enum PathEpilogue : int { PATH_PLAIN = 0, PATH_VIOL_WRITE = 1, PATH_VIOL_ADD = 2, PATH_KEY = 3 };
+inline int path_epilogue(int slot) { return slot == 0 ? PATH_KEY : (slot == 1 ? PATH_VIOL_WRITE : PATH_VIOL_ADD); }
+
+// Its own workspace (ctx->cpaths), offsets in doubles from its start:
+//   viol [S][M] | vals [S][M] (only with values_out: one slot's values at a time, on their way to the host) |
+//   pts [GPBO_MAX_PATHS][DP] | f [S][GPBO_MAX_PATHS]
+// pts / f: the scaled candidates the rows WITHOUT a feasible candidate picked, and all S paths evaluated there again (row s reads
+// its own).  Every part starts at an even offset: the kernel reads points as double2.
+struct ConstrainedBlock { int64_t viol, vals, pts, f, doubles; };
+inline ConstrainedBlock constrained_block(int S_, int64_t M, int DP, bool values) {
+  const int64_t S = S_, rows = (S * M + 1) / 2 * 2;
+  ConstrainedBlock b{};
+  b.viol = 0;
+  b.vals = b.viol + rows;
+  b.pts = b.vals + (values ? rows : 0);
+  b.f = b.pts + (int64_t)GPBO_MAX_PATHS * DP;
+  b.doubles = b.f + S * GPBO_MAX_PATHS;
+  return b;
+}
+
 }  // namespace gpbo

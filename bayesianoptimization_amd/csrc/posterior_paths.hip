@@ -17,6 +17,10 @@
 //   path_v_kernel      V = alpha - W^T T: a thread per (column, path), four row groups per workgroup.
 // The two small ones are 2 N^2 S flops each and not the hot path.  Every sum has a fixed order and no path's arithmetic depends on
 // how many paths run beside it: path s alone and path s among 16 give the same bits.  fp64 whatever the slot's precision.
+//
+// gpbo_sample_paths_constrained runs path_eval_kernel once per slot with another EPILOGUE behind the same accumulators (path_plan.h:
+// PathEpilogue): a constraint slot folds its S violation terms per candidate into a resident viol[S][M], the objective reads viol and
+// stores the selection key.  The values themselves are the ones gpbo_sample_paths stores, bit for bit.
 #include "gpbo_internal.h"
 
 namespace gpbo {
@@ -35,6 +39,11 @@ struct PathEvalArgs {
   int N, NP, F, d, S;     // N = 0: no phase 1 (the prior draw alone)
   int negate;
   double fs, y_mean, y_std;
+  // gpbo_sample_paths_constrained (path_plan.h: PathEpilogue; PATH_PLAIN reads none of these)
+  int epilogue;
+  double lb, ub;          // a constraint slot's bounds
+  double* viol;           // [S][ld] the violations: written / added to by a constraint slot, read by the objective
+  double* vals;           // [S][ld] the values themselves, or null
 };
 
 // NS = accumulators held per point (paths c >= S are zero columns: they add nothing and are not written), indexed by unrolled
@@ -128,7 +137,22 @@ __global__ __launch_bounds__(256) void path_eval_kernel(const PathEvalArgs a) {
   for (int c = 0; c < NS; ++c) {
     if (c < a.S) {
       const double f = fma(a.y_std, acc[c], a.y_mean);
-      a.out[(int64_t)c * a.ld + m] = a.negate ? -f : f;
+      const int64_t at = (int64_t)c * a.ld + m;
+      if (a.epilogue == PATH_PLAIN) {
+        a.out[at] = a.negate ? -f : f;
+        continue;
+      }
+      if (a.vals) a.vals[at] = f;
+      if (a.epilogue == PATH_KEY) {
+        // the selection takes the first NaN, else the least key: -f where the constraint draws call the point feasible, +inf elsewhere
+        const double v = a.viol[at];
+        a.out[at] = (f != f || v != v) ? __builtin_nan("") : (v == 0.0 ? -f : __builtin_inf());
+      } else {
+        // t = max(max(lb - c, c - ub), 0) / y_std, a NaN c kept (fmax would drop it)
+        const double g = fmax(a.lb - f, f - a.ub);
+        const double t = (f != f) ? f : fmax(g, 0.0) / a.y_std;
+        a.viol[at] = a.epilogue == PATH_VIOL_WRITE ? t : a.viol[at] + t;
+      }
     }
   }
 }
@@ -236,8 +260,10 @@ int launch_path_weights(gpbo_ctx* ctx, const Model& m, int S, int F, const doubl
 // The S paths of gpbo_sample_paths over the M resident candidates: the negated values land in ctx->ys as S rows of M (the
 // selection's keys), nothing of the slot or the candidates is written.  The caller has checked every argument.  n_runs / ws: as
 // launch_path_weights (gpbo_ascend_paths goes on from the same workspace).
-int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int S, int F, const double* omega,
-                        const double* phase, const double* weights, const double* eps, int n_runs, PathWorkspace* ws_out) {
+// `fold` (null: gpbo_sample_paths): the slot's part of gpbo_sample_paths_constrained instead of the plain store
+static int sample_paths_over_candidates(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int S, int F,
+                                        const double* omega, const double* phase, const double* weights, const double* eps, int n_runs,
+                                        PathWorkspace* ws_out, const PathFold* fold) {
   int rc;
   if ((rc = launch_path_weights(ctx, m, S, F, omega, phase, weights, eps, n_runs, ws_out))) return rc;
   const PathWorkspace& ws = *ws_out;
@@ -248,6 +274,32 @@ int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean,
   // the paths over the candidates
   PathEvalArgs a = path_eval_args(m, ws, S, F);
   a.P = ctx->Xcs; a.out = ctx->ys; a.M = M; a.ld = M; a.N = (int)m.N; a.negate = 1; a.y_mean = y_mean; a.y_std = y_std;
+  if (fold) { a.epilogue = fold->epilogue; a.lb = fold->lb; a.ub = fold->ub; a.viol = fold->viol; a.vals = fold->vals; }
+  return launch_path_eval(ctx, m, a);
+}
+
+int launch_sample_paths(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int S, int F, const double* omega,
+                        const double* phase, const double* weights, const double* eps, int n_runs, PathWorkspace* ws_out) {
+  return sample_paths_over_candidates(ctx, m, M, y_mean, y_std, S, F, omega, phase, weights, eps, n_runs, ws_out, nullptr);
+}
+
+// One slot's pass of gpbo_sample_paths_constrained: the slot's S draws over the M resident candidates, and behind the accumulators
+// what fold->epilogue says (path_plan.h) — a constraint slot's violation terms into fold->viol, the objective's selection keys into
+// ctx->ys.  Nothing but ctx->ys, ctx->Xcs, the two workspaces is written.
+int launch_sample_paths_fold(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int S, int F, const double* omega,
+                             const double* phase, const double* weights, const double* eps, const PathFold& fold, PathWorkspace* ws) {
+  return sample_paths_over_candidates(ctx, m, M, y_mean, y_std, S, F, omega, phase, weights, eps, 0, ws, &fold);
+}
+
+// f[s * ld + r] = path s of the workspace's draws (those of the last pass, the model m's) at the scaled candidate idx[r], r < n <= 16,
+// by the kernel instance and the arithmetic the pass itself ran: the bits the pass had for that candidate.  pts: n * DP doubles.
+int launch_paths_at(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, double y_mean, double y_std, int S, int F,
+                    const int64_t* idx, int n, double* pts, double* f, int ld) {
+  for (int r = 0; r < n; ++r)
+    GPBO_HIP(ctx, hipMemcpyAsync(pts + (int64_t)r * m.DP, ctx->Xcs + idx[r] * m.DP, (size_t)m.DP * sizeof(double),
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+  PathEvalArgs a = path_eval_args(m, ws, S, F);
+  a.P = pts; a.out = f; a.M = n; a.ld = ld; a.N = (int)m.N; a.negate = 0; a.y_mean = y_mean; a.y_std = y_std;
   return launch_path_eval(ctx, m, a);
 }
 

@@ -677,6 +677,48 @@ class GpEngine:
                                                 dptr(best_val), dptr(values)))
         return best_idx[:S], best_val[:S], values
 
+    def sample_paths_constrained(self, draws, lb, ub, y_mean, y_std, index_offset=0, return_values=False):
+        """Constrained Thompson sampling over the resident candidates (gpbo_sample_paths_constrained; include/gpbo.h has the rule):
+        `draws` is a list of 1 + C tuples (omega, phase, weights, eps) as `sample_paths` takes them, entry j for slot j — the
+        objective in slot 0, constraint j in slot j; all with the same S and F.  lb / ub (C,), y_mean / y_std (1 + C,).  Per draw s
+        the best objective value among the candidates the constraint draws call feasible, else the candidate of least total
+        violation.  Returns (idx (S,) int64, val (S,), viol (S,), feasible (S,) bool, values (1 + C, S, M) or None, viol_all
+        (S, M) or None).  A reader, as `sample_paths`."""
+        who = "sample_paths_constrained"
+        draws = list(draws)
+        n_slots = len(draws)
+        lb = np.ascontiguousarray(lb, dtype=np.float64).ravel()
+        ub = np.ascontiguousarray(ub, dtype=np.float64).ravel()
+        y_mean = np.ascontiguousarray(y_mean, dtype=np.float64).ravel()
+        y_std = np.ascontiguousarray(y_std, dtype=np.float64).ravel()
+        if n_slots < 2 or any(len(t) != 4 for t in draws):
+            raise ValueError(f"{who}: draws must be a list of 1 + C tuples (omega, phase, weights, eps), C >= 1")
+        if lb.shape[0] != n_slots - 1 or ub.shape[0] != n_slots - 1 or y_mean.shape[0] != n_slots or y_std.shape[0] != n_slots:
+            raise ValueError(f"{who}: lb / ub must have {n_slots - 1} entries, y_mean / y_std {n_slots}")
+        if n_slots > _lib.MAX_MODELS:
+            raise ValueError(f"{who}: n_constraints out of range [1, {_lib.MAX_MODELS - 1}]")
+        parts = [self._path_inputs(who, *draws[j], j) for j in range(n_slots)]
+        F, S = parts[0][0].shape[0], parts[0][2].shape[0]
+        if any(p[0].shape[0] != F or p[2].shape[0] != S for p in parts):
+            raise ValueError(f"{who}: every slot's draws must have the same S and F")
+        omega = np.ascontiguousarray(np.concatenate([p[0].ravel() for p in parts]))
+        phase = np.ascontiguousarray(np.concatenate([p[1] for p in parts]))
+        weights = np.ascontiguousarray(np.concatenate([p[2].ravel() for p in parts]))
+        eps = np.ascontiguousarray(np.concatenate([p[3].ravel() for p in parts]))
+        M = max(int(self.n_candidates), 0)
+        n = max(S, 1)
+        best_idx = np.empty(n, dtype=np.int64)
+        best_val, best_viol = np.empty(n), np.empty(n)
+        feasible = np.zeros(n, dtype=np.int32)
+        keep = return_values and S >= 1 and M >= 1
+        values = np.empty((n_slots, S, M)) if keep else None
+        viol_all = np.empty((S, M)) if keep else None
+        self._check(self._lib.gpbo_sample_paths_constrained(
+            self._h, n_slots - 1, dptr(y_mean), dptr(y_std), dptr(lb), dptr(ub), int(S), int(F), dptr(omega), dptr(phase),
+            dptr(weights), dptr(eps), int(index_offset), iptr(best_idx), dptr(best_val), dptr(best_viol),
+            feasible.ctypes.data_as(C.POINTER(C.c_int)), dptr(values), dptr(viol_all)))
+        return best_idx[:S], best_val[:S], best_viol[:S], feasible[:S].astype(bool), values, viol_all
+
     def ascend_paths(self, omega, phase, weights, eps, box_lo, box_hi, n_starts=4, starts=None, max_iter=-1, slot=0, y_mean=0.0,
                      y_std=1.0, index_offset=0, return_gradient=False):
         """The S draws of `sample_paths`, each climbed from K starts to a local maximiser inside [box_lo, box_hi] in ONE launch
@@ -1368,6 +1410,10 @@ class GroupEngine(GpEngine):
 
     def sample_paths(self, omega, phase, weights, eps, slot=0, y_mean=0.0, y_std=1.0, index_offset=0, return_values=False):
         raise NotImplementedError("a device group has no path sampler (gpbo_sample_paths is per context); use a single device")
+
+    def sample_paths_constrained(self, draws, lb, ub, y_mean, y_std, index_offset=0, return_values=False):
+        raise NotImplementedError("a device group has no constrained path sampler (gpbo_sample_paths_constrained is per context); "
+                                  "use a single device")
 
     def ascend_paths(self, omega, phase, weights, eps, box_lo, box_hi, n_starts=4, starts=None, max_iter=-1, slot=0, y_mean=0.0,
                      y_std=1.0, index_offset=0, return_gradient=False):

@@ -321,6 +321,39 @@ int gpbo_sample_paths(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int 
                       const double* omega, const double* phase, const double* weights, const double* eps,
                       int64_t index_offset, int64_t* best_idx, double* best_val, double* values_out);
 
+/* Constrained Thompson sampling (the pick of SCBO; Eriksson & Poloczek 2021, "Scalable constrained Bayesian optimization"): n_paths
+ * draws of the objective (slot 0) AND of each of C = n_constraints constraints (slots 1..C) over the resident candidates, and per
+ * draw the best objective value among the candidates its constraint draws call feasible — where none is, the candidate of least
+ * total violation.  Slots 0..C are fitted, with the candidates' d; their N, kernel kind, length scales, scale and precision may
+ * differ.  y_mean / y_std (1 + C,); lb / ub (C,), not NaN, lb < ub, +-inf allowed.  The per-slot inputs of gpbo_sample_paths are
+ * concatenated in slot order: omega (1 + C, F, d), phase (1 + C, F), weights (1 + C, S, F), eps = slot j's block (S, N_j), one after
+ * another.  Slot j's draw c_j,s(x) is gpbo_sample_paths' f_s for that slot and those inputs (j = 0: f_s itself), the same bits.
+ * Per path s and candidate x:
+ *   t_j       = max(max(lb_j - c_j,s(x), c_j,s(x) - ub_j), 0) / y_std_j        a true division
+ *   viol_s(x) = t_1 + ... + t_C                                                added in that order; a NaN c_j makes it NaN
+ *   x is feasible for s  iff  viol_s(x) == 0  iff  lb_j <= c_j,s(x) <= ub_j for every j
+ * Per path, in this order:
+ *   1. a candidate with a NaN f_s or a NaN viol_s: the FIRST such index wins, best_val = best_viol = NaN, feasible_out = 0;
+ *   2. else, some candidate is feasible: the first index of the maximum of f_s over the feasible ones, best_val = f_s there,
+ *      best_viol = 0, feasible_out = 1;
+ *   3. else: the first index of the minimum of viol_s, best_val = f_s there, best_viol = that minimum, feasible_out = 0.
+ * index_offset is added to every returned index.  values_out (1 + C, S, M) or NULL: every slot's draws; viol_out (S, M) or NULL.
+ * An infinite f_s is outside the contract.
+ * On the device the constraints run in slot order — each pass folds its S values per candidate into one resident viol (S, M), the
+ * first writing it, the later ones adding —, then the objective, whose pass reads viol and leaves the selection key (NaN / -f_s /
+ * +inf) as the context's acquisition values; no (1 + C, S, M) block of values exists unless values_out asks for it.  One
+ * selection over the keys, a second over viol for the rows without a feasible candidate.  fp64 whatever a slot's precision.
+ * A reader, as gpbo_sample_paths: every slot's fit, the resident mu / sd, what gpbo_posterior_refresh may still refresh, the
+ * candidates and the negative-variance flag stay as they were; the context's acquisition values are overwritten.
+ * GPBO_ERR_INVALID: n_constraints outside [1, GPBO_MAX_MODELS - 1], n_paths or n_features out of gpbo_sample_paths' ranges, a NULL
+ * among the inputs or best_idx / best_val / best_viol / feasible_out, a y_std not finite or not positive, a y_mean not finite, a
+ * NaN bound, lb_j >= ub_j.  GPBO_ERR_STATE: one of slots 0..C unfitted or with a fit pending, no resident candidates, candidates or
+ * a slot of another d.  There is no gpbo_group_* / gpbo_comm_* form. */
+int gpbo_sample_paths_constrained(gpbo_ctx* ctx, int n_constraints, const double* y_mean, const double* y_std, const double* lb,
+                                  const double* ub, int n_paths, int n_features, const double* omega, const double* phase,
+                                  const double* weights, const double* eps, int64_t index_offset, int64_t* best_idx, double* best_val,
+                                  double* best_viol, int* feasible_out, double* values_out, double* viol_out);
+
 /* The draws of gpbo_sample_paths, each CLIMBED from n_starts starts to a local maximiser inside a box — Thompson sampling with the
  * local-search stage the reference's suggest() never goes without (Wilson et al. 2020 maximise their draws by gradient ascent: a
  * pathwise-conditioned draw is a closed-form function).  Arguments up to eps, and f_s itself, as gpbo_sample_paths.  With
