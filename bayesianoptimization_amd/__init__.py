@@ -9,7 +9,8 @@ __version__ = "0.1.0"
 __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate", "suggest_batch", "UpperConfidenceBound",
            "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement", "suggest_thompson",
            "suggest_mes", "suggest_kg", "suggest_turbo", "TrustRegion", "sobol_tables",
-           "suggest_constrained_thompson", "suggest_scbo", "ConstrainedTrustRegion"]
+           "suggest_constrained_thompson", "suggest_scbo", "ConstrainedTrustRegion",
+           "ParetoOptimizer", "pareto_front", "hypervolume", "box_decomposition"]
 
 
 def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must not need sklearn/scipy
@@ -46,6 +47,9 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name in ("suggest_constrained_thompson", "suggest_scbo", "ConstrainedTrustRegion"):
         from . import scbo
         return getattr(scbo, name)
+    if name in ("ParetoOptimizer", "pareto_front", "hypervolume", "box_decomposition"):
+        from . import multiobjective
+        return getattr(multiobjective, name)
     if name in ("UpperConfidenceBound", "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement",
                 "AcquisitionFunction"):
         from . import fused_acquisition as acquisition

@@ -224,6 +224,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
   if (ctx->small_pinned) (void)hipHostFree(ctx->small_pinned);
   if (ctx->polish_pinned) (void)hipHostFree(ctx->polish_pinned);
   if (ctx->fused_stage) (void)hipHostFree(ctx->fused_stage);
@@ -232,7 +233,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1516,6 +1517,48 @@ int gpbo_kg_argbest(gpbo_ctx* ctx, const double* points, int n_points, int d, do
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "kg_argbest: y_std is not the one the resident posterior was scaled with");
   ev_begin(ctx, T_ACQ);
   rc = launch_kg_values(ctx, m, ctx->M, points, n_points, y_mean, y_std, mu_points_out);
+  if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  ev_end(ctx, T_ACQ);
+  if (rc) return rc;
+  if (ys_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(ys_out, ctx->ys, (size_t)ctx->M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GPBO_OK;
+}
+
+int gpbo_ehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, const double* levels, int64_t n_cells,
+                      const uint8_t* cell_lo, const uint8_t* cell_hi, int k_seeds, int64_t index_offset, int64_t* best_idx,
+                      double* best_val, int64_t* seed_idx, double* seed_val, double* ys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const int nobj = n_objectives;
+  if (nobj < 2 || nobj > GPBO_MAX_EHVI_OBJECTIVES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: n_objectives out of range [2, 3]");
+  if (!n_levels || !levels || !cell_lo || !cell_hi) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: NULL levels or cells");
+  for (int j = 0; j < nobj; ++j) {
+    if (n_levels[j] < 2 || n_levels[j] > GPBO_MAX_EHVI_LEVELS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: a level count out of range [2, 130]");
+    const double* row = levels + (size_t)j * GPBO_MAX_EHVI_LEVELS;
+    for (int l = 0; l + 1 < n_levels[j]; ++l)
+      if (!std::isfinite(row[l]) || !(row[l] < row[l + 1]))
+        GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: levels must be finite and strictly increasing up to the last");
+    if (!(row[n_levels[j] - 1] == INFINITY)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: the last level must be +inf");
+  }
+  if (n_cells < 1 || n_cells > GPBO_MAX_EHVI_CELLS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: n_cells out of range [1, 16641]");
+  for (int64_t k = 0; k < n_cells; ++k)
+    for (int j = 0; j < nobj; ++j)
+      if ((int)cell_hi[k * nobj + j] >= n_levels[j] || cell_lo[k * nobj + j] >= cell_hi[k * nobj + j])
+        GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: a cell needs lo < hi < the objective's level count");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: NULL output");
+  int rc;
+  for (int j = 0; j < nobj; ++j) {
+    if ((rc = no_pending_fit(ctx, j, "ehvi_argbest"))) return rc;
+    if ((rc = need_fitted(ctx, j))) return rc;
+  }
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ehvi_argbest: no candidates");
+  for (int j = 0; j < nobj; ++j)
+    if (ctx->models[j].M_post != ctx->M) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ehvi_argbest: run gpbo_posterior for every objective's slot first");
+  ev_begin(ctx, T_ACQ);
+  rc = launch_ehvi_values(ctx, nobj, ctx->M, n_levels, levels, n_cells, cell_lo, cell_hi);
   if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
   ev_end(ctx, T_ACQ);
   if (rc) return rc;

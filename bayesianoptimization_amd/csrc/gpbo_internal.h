@@ -170,10 +170,14 @@ struct gpbo_ctx {
   int64_t cap_ys = 0;
   double* kg = nullptr;    // gpbo_kg_argbest: the call's points, their solves and the candidate x point covariances (kg.hip)
   int64_t cap_kg = 0;
+  double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
+  int64_t cap_ehvi = 0;
   hipEvent_t kg_ev[4] = {};   // debug build: around the three stages of the last gpbo_kg_argbest (the fields exist in both builds: one layout)
   bool kg_ev_used = false;
   hipEvent_t gen_ev[2] = {};  // debug build: around the kernel of the last gpbo_generate_candidates / _trust_region (generate_mark)
   bool gen_ev_used = false;
+  hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
+  bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
   int64_t cap_paths = 0;
   double* cpaths = nullptr; // gpbo_sample_paths_constrained: viol | one slot's values | the fallback picks' points and values (path_plan.h)
@@ -217,7 +221,7 @@ namespace gpbo {
 
 constexpr size_t SMALL_PIN_IN = 128 * 1024, SMALL_PIN_OUT = 32 * 1024;   // bytes: candidates in; mu, sd out (each)
 constexpr size_t SMALL_PIN_BYTES = SMALL_PIN_IN + 2 * SMALL_PIN_OUT;
-constexpr unsigned ATTR_GEMM128 = 4u, ATTR_CHOL128 = 16u, ATTR_FUSED = 32u, ATTR_MID = 64u, ATTR_KINV_GRAD = 128u, ATTR_POLISH_FUSED = 256u, ATTR_GEMM_FAT = 512u, ATTR_EVOLVE = 2048u, ATTR_KG = 4096u;
+constexpr unsigned ATTR_GEMM128 = 4u, ATTR_CHOL128 = 16u, ATTR_FUSED = 32u, ATTR_MID = 64u, ATTR_KINV_GRAD = 128u, ATTR_POLISH_FUSED = 256u, ATTR_GEMM_FAT = 512u, ATTR_EVOLVE = 2048u, ATTR_KG = 4096u, ATTR_EHVI = 8192u;
 // pinned staging of a small host-side fit's X (N, d) | y (N), read by the first kernel directly (one window per PIN window)
 constexpr int STAGE_NP_CAP = MID_NP_CAP;
 static_assert(STAGE_NP_CAP >= FUSED_NP_CAP, "the staging window serves both small paths");
@@ -643,6 +647,11 @@ int launch_mes_values(gpbo_ctx* ctx, const Model& m, int64_t M, int n_samples, c
 // every argument.  The call's workspace is ctx->kg (kg.hip: kg_block).
 int launch_kg_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, int J, double y_mean, double y_std,
                      double* mu_points_out);
+// ehvi.hip: ctx->ys[i] = -EHVI(x_i), the negated expected hypervolume improvement of the M resident candidates from the resident
+// mu / sd of slots 0 .. n_obj - 1, the level rows `levels` (n_obj, GPBO_MAX_EHVI_LEVELS) and the boxes cell_lo / cell_hi (n_cells, n_obj)
+// of level indices (all host).  The caller has checked every argument.  The call's workspace is ctx->ehvi.
+int launch_ehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels, const double* levels, int64_t n_cells,
+                       const uint8_t* cell_lo, const uint8_t* cell_hi);
 #ifdef GPBO_DEBUG
 int debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out);
 int debug_kg_stage_ms(gpbo_ctx* ctx, float* ms3);

@@ -954,6 +954,52 @@ class GpEngine:
         out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
         return out + (mu_points,) if return_point_means else out
 
+    def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
+        """Expected hypervolume improvement over the resident candidates (gpbo_ehvi_argbest; include/gpbo.h has the formulas, the
+        conventions and the order of the sum): ys = -EHVI for m = 2 or 3 maximised objectives, objective j from slot j's resident
+        posterior (raw target units).  `levels`: m rows of strictly increasing values, the last +inf (a sequence of m 1-D arrays, or
+        one (m, L) array whose rows end at their first +inf); `cell_lo` / `cell_hi` (K, m): the boxes of the non-dominated region
+        as level indices, lo < hi (`multiobjective.box_decomposition` makes all three).  Returns (best_idx, best_val, seed_idx,
+        seed_val, ys|None) as `mes_argbest`.  A reader: the fits, the resident posteriors and the candidates stay as they were.  A
+        fit pending on one of the slots (`overlapped_fits`) is waited for first, as every reader of a slot does; the new fit has no
+        posterior over the candidates, so the call is then refused as such."""
+        rows = [np.asarray(r, dtype=np.float64).ravel() for r in levels]
+        m = len(rows)
+        rows = [r[:int(np.argmax(np.isposinf(r))) + 1] if np.isposinf(r).any() else r for r in rows]      # a row ends at its first +inf
+        if not 2 <= m <= _lib.MAX_EHVI_OBJECTIVES:
+            raise ValueError("ehvi_argbest: levels must have 2 or 3 rows, one per objective")
+        if any(not 2 <= r.shape[0] <= _lib.MAX_EHVI_LEVELS for r in rows):
+            raise ValueError(f"ehvi_argbest: a row of levels needs 2 to {_lib.MAX_EHVI_LEVELS} entries")
+        lo = np.ascontiguousarray(np.asarray(cell_lo, dtype=np.int64))
+        hi = np.ascontiguousarray(np.asarray(cell_hi, dtype=np.int64))
+        if lo.ndim != 2 or lo.shape != hi.shape or lo.shape[1] != m:
+            raise ValueError("ehvi_argbest: cell_lo and cell_hi must both be (K, m)")
+        if lo.size and (min(lo.min(), hi.min()) < 0 or max(lo.max(), hi.max()) > 255):
+            raise ValueError("ehvi_argbest: a cell index is not a level index")
+        table = np.zeros((m, _lib.MAX_EHVI_LEVELS))
+        n_levels = np.zeros(m, dtype=np.intc)
+        for j, r in enumerate(rows):
+            table[j, :r.shape[0]] = r
+            n_levels[j] = r.shape[0]
+        lo8, hi8 = lo.astype(np.uint8), hi.astype(np.uint8)
+        k_seeds = int(k_seeds)
+        for j in range(m):
+            self._settle(j)
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.gpbo_ehvi_argbest(self._h, m, n_levels.ctypes.data_as(C.POINTER(C.c_int)), dptr(table), int(lo.shape[0]),
+                                                lo8.ctypes.data_as(u8), hi8.ctypes.data_as(u8), k_seeds, int(index_offset),
+                                                C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
+        return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
+
+    def debug_ehvi_ms(self):
+        """gpbo_debug_ehvi_ms (debug build): kernel ms of the last `ehvi_argbest`'s value kernel (tables and cell sum)."""
+        self._need_debug("gpbo_debug_ehvi_ms")
+        ms = C.c_float(0.0)
+        self._check(self._lib.gpbo_debug_ehvi_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def debug_kg_lines(self, a, b):
         """gpbo_debug_kg_lines (debug build): the envelope of `kg_argbest` alone on R sets of n lines, a / b (R, n) intercepts /
         slopes: (R,) E[max_j (a_j + b_j Z)] - max_j a_j."""
@@ -1425,6 +1471,10 @@ class GroupEngine(GpEngine):
     def kg_argbest(self, points, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                    return_values: bool = False, return_point_means: bool = False):
         raise NotImplementedError("a device group has no knowledge gradient (gpbo_kg_argbest is per context); use a single device")
+
+    def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
+        raise NotImplementedError("a device group has no expected hypervolume improvement (gpbo_ehvi_argbest is per context); "
+                                  "use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
         raise NotImplementedError("a device group has no posterior refresh path (gpbo_posterior_refresh is per context); "

@@ -548,6 +548,47 @@ int gpbo_kg_argbest(gpbo_ctx* ctx, const double* points, int n_points, int d, do
                     int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val,
                     double* ys_out, double* mu_points_out);
 
+/* Expected hypervolume improvement (EHVI; Emmerich, Giannakoglou & Naujoks 2006; the box form of Yang, Emmerich, Deutz & Bäck 2019)
+ * over the resident candidates: the acquisition for m = n_objectives objectives at once, ALL MAXIMISED, raw target units.  Objective j
+ * is slot j (0 .. m - 1); each slot's resident mu / sd (gpbo_posterior / gpbo_posterior_refresh) gives an independent posterior
+ * Y_j ~ N(mu_j(x), sd_j(x)^2).  For a reference point r and a non-dominated front P strictly above r, the region above r that P does
+ * not dominate is cut into K = n_cells disjoint boxes [l_k, u_k); every bound along objective j is an entry of objective j's level
+ * list: r_j, the distinct front values, +inf last.
+ *   levels   (m, GPBO_MAX_EHVI_LEVELS) row-major; row j holds n_levels[j] strictly increasing values, the last +inf, the others finite
+ *   cell_lo / cell_hi   (K, m) level indices, lo < hi < n_levels[j].  The device does NOT check that the boxes are disjoint or tile
+ *            anything: that is host policy (bayesianoptimization_amd/multiobjective.py: box_decomposition)
+ *   g_j(a)  = E[(Y_j - a)^+] = sd_j f((mu_j - a) / sd_j),   f(z) = phi(z) + z Phi(z),   g_j(+inf) = 0
+ *   EHVI(x) = sum_k prod_j (g_j(l_kj) - g_j(u_kj))            each factor is E[clip(Y_j, l, u) - l] >= 0
+ *   ys      = -EHVI                                           so ys <= 0
+ * f is evaluated over two ranges: z > -1 as written (Phi, phi as gpbo_acq_argbest's EI evaluates them); z <= -1 as phi(z) r(z),
+ * r = 1 + z Phi / phi as GPBO_ACQ_LOG_EI forms it (erfcx down to z = -28, the asymptotic series below) — a candidate far below the
+ * front keeps a relatively accurate, correctly ordered value instead of a cancelled one.  Where phi underflows (z < ~ -38.6) f is 0.
+ * Every g_j(level) is evaluated once per candidate, not once per box.
+ * Conventions: sd_j == 0 gives g_j(a) = max(mu_j - a, 0) — with every sd zero the value is the hypervolume improvement of the mean;
+ * a NaN mu or sd in ANY objective gives NaN, and the selection's "first NaN wins" rule applies.  fp64 whatever a slot's precision.
+ * The order of the sum.  With T = m * max_j n_levels[j], a workgroup serves C candidates and splits the boxes over G = 512 / C groups:
+ *   T <= 80: C = 256, G = 2      T <= 160: C = 128, G = 4      T <= 320: C = 64, G = 8      T > 320: C = 32, G = 16
+ * (the largest C whose tables T * C * 8 bytes fit 160 KiB of LDS; m = 2: max n_levels 40 | 41, 80 | 81; m = 3: 26 | 27, 53 | 54,
+ * 106 | 107).  Group g sums the boxes [g P, min(K, (g + 1) P)), P = ceil(K / G), k ascending into one accumulator from 0; the G sums
+ * are then added g = 0 .. G - 1 in that order.  C, G and P depend on m, the level counts and K only: a candidate's bits depend
+ * neither on M, nor on the launch geometry, nor on the other candidates.
+ * Outputs, selection and index_offset exactly as gpbo_mes_argbest, on the key ys.
+ * A reader: the slots' fits, their resident mu / sd, what gpbo_posterior_refresh may still refresh, the candidates and the
+ * negative-variance flag stay as they were; only the context's acquisition values are overwritten.  Levels and boxes are staged in a
+ * workspace of the call's own.
+ * GPBO_ERR_INVALID: n_objectives outside [2, GPBO_MAX_EHVI_OBJECTIVES]; a NULL n_levels / levels / cell_lo / cell_hi; a level count
+ * outside [2, GPBO_MAX_EHVI_LEVELS]; levels not strictly increasing, a non-final level not finite, a final level other than +inf;
+ * n_cells outside [1, GPBO_MAX_EHVI_CELLS]; a box index >= n_levels[j] or lo >= hi; k_seeds outside [0, GPBO_MAX_SEEDS]; a NULL
+ * best_idx / best_val (seed_idx / seed_val with k_seeds > 0).  GPBO_ERR_STATE: one of the slots 0 .. m - 1 unfitted or with a fit
+ * pending, no candidates, a slot without a resident posterior for them.  There is no gpbo_group_* / gpbo_comm_* form. */
+#define GPBO_MAX_EHVI_OBJECTIVES 3
+#define GPBO_MAX_EHVI_LEVELS     130      /* r_j, up to 128 distinct front values, +inf */
+#define GPBO_MAX_EHVI_CELLS      16641    /* 129^2: the grid decomposition's worst case at m = 3 */
+int gpbo_ehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, const double* levels,
+                      int64_t n_cells, const uint8_t* cell_lo, const uint8_t* cell_hi,
+                      int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val,
+                      int64_t* seed_idx, double* seed_val, double* ys_out);
+
 /* ---- timing (HIP events on the context stream) ------------------------------------------ */
 /* Milliseconds spent in the last call's kernels: [0] fit total, [1] posterior main kernel,
  * [2] posterior finalize, [3] acquisition + arg-best, [4] kmat assembly, [5] cholesky, [6] trtri. */
@@ -740,6 +781,9 @@ int gpbo_debug_kg_stage_ms(gpbo_ctx* ctx, float* ms);
 /* Kernel milliseconds (HIP events) of the generator kernel of the context's last gpbo_generate_candidates or
  * gpbo_generate_candidates_trust_region call: the launch alone, without the call's argument upload and synchronise. */
 int gpbo_debug_generate_ms(gpbo_ctx* ctx, float* ms);
+/* Kernel milliseconds (HIP events) of the value kernel of the context's last gpbo_ehvi_argbest: the tables and the sum over the
+ * boxes, without the upload of levels and boxes and without the selection. */
+int gpbo_debug_ehvi_ms(gpbo_ctx* ctx, float* ms);
 #endif /* GPBO_DEBUG */
 
 #ifdef __cplusplus
