@@ -1,4 +1,5 @@
-"""What suggest_batch (batch.py), suggest_thompson (thompson.py), suggest_mes (mes.py), suggest_kg (kg.py), suggest_turbo (turbo.py) and
+"""What suggest_batch (batch.py), suggest_thompson (thompson.py), suggest_mes (mes.py), suggest_kg (kg.py), suggest_turbo (turbo.py),
+suggest_qnei (qnei.py: the count check, the gate and the frame of a model) and
 the constrained pair suggest_constrained_thompson / suggest_scbo (scbo.py: the gate with `constrained=True`, the frame of a model)
 share, each thing once: the check of a count argument, the gate an optimizer passes before anything runs, the frame of the fitted
 model, the loop over groups of posterior draws, and the picks of a Thompson batch (suggest_thompson, suggest_turbo).  The ORDER of the refusals is part of the three functions' contract: a caller's own argument checks come

@@ -49,6 +49,7 @@ SOURCES = {
     "mes.hip": ["-ffp-contract=off"],         # gpbo_mes_argbest: max-value entropy search values (acq_formulas.h's pieces, the bits they have in acq_kernels.hip)
     "kg.hip": ["-ffp-contract=off"],          # gpbo_kg_argbest: knowledge gradient values (candidate x point covariances, upper envelope of J + 1 lines; acq_formulas.h's pieces)
     "ehvi.hip": ["-ffp-contract=off"],        # gpbo_ehvi_argbest: expected hypervolume improvement values (per-candidate level tables in LDS, the sum over the boxes; acq_formulas.h's pieces)
+    "qnei.hip": ["-ffp-contract=off"],        # gpbo_qnei_greedy: greedy batch noisy expected improvement over a resident (T, M) block of posterior draws (the score kernel streams it once per pick; incumbents updated in-stream)
     "candidates.hip": [],
     "trust_region.hip": ["-ffp-contract=off"],  # gpbo_generate_candidates_trust_region: lo + (hi - lo) * u as NumPy computes it (scrambled Sobol points under a Philox mask)
     "mt19937.hip": ["-ffp-contract=off"],      # lo + (hi - lo) * u as NumPy computes it

@@ -72,11 +72,7 @@ __global__ __launch_bounds__(256) void acq_kernel(AcqDev a, int64_t M, double* _
 // ------------------------------------------------------------------------------------------------
 // Selection.  Sort key = (value, index) with NaN greater than everything (NumPy sorts NaN last) and
 // -0.0 == 0.0; ties break to the lowest index.  One pass finds the smallest key strictly greater
-// than the previous pick, so k passes yield argsort(ys)[:k] deterministically.
-struct Key {
-  double v;
-  int64_t i;
-};
+// than the previous pick, so k passes yield argsort(ys)[:k] deterministically.  (Key and SelState: gpbo_internal.h.)
 
 __device__ __forceinline__ bool key_less(const Key& a, const Key& b) {
   const bool an = a.v != a.v, bn = b.v != b.v;
@@ -84,11 +80,6 @@ __device__ __forceinline__ bool key_less(const Key& a, const Key& b) {
   if (!an && a.v != b.v) return a.v < b.v;
   return a.i < b.i;
 }
-
-struct SelState {     // lives in device memory, carried from pass to pass
-  Key prev;           // last pick (i = -1 before the first pass)
-  int64_t first_nan;  // lowest index holding NaN (INT64_MAX if none)
-};
 
 constexpr int SEL_BLOCK = 256;
 constexpr int SEL_ITEMS = 16;   // elements per thread per block sweep
@@ -580,6 +571,15 @@ int launch_values_argbest(gpbo_ctx* ctx, int64_t M, int k_seeds, int64_t offset,
   int rc = enqueue_select(ctx, M, npass, select_v2_enabled() && npass >= 3, &st, &picks);
   if (rc) return rc;
   return fetch_selection(ctx, st, npass, k_seeds, offset, best_idx, best_val, seed_idx, seed_val);
+}
+
+// gpbo_qnei_greedy: that selection for one pick, enqueued and left on the device (qnei_update_kernel reads the record there)
+int enqueue_values_select(gpbo_ctx* ctx, int64_t M, const SelState** st_out, const Key** pick_out) {
+  SelState* st; Key* picks;
+  int rc = enqueue_select(ctx, M, 1, false, &st, &picks);
+  if (rc) return rc;
+  *st_out = st; *pick_out = picks;
+  return GPBO_OK;
 }
 
 // gpbo_sample_paths (k = 1, top_idx null) / gpbo_ascend_paths: the k best of each of n_rows rows of M keys (rows[r * ld ...]) by the

@@ -223,6 +223,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : ctx->qnei_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
   if (ctx->small_pinned) (void)hipHostFree(ctx->small_pinned);
@@ -233,7 +234,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->qnei, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1569,6 +1570,32 @@ int gpbo_ehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, cons
   return GPBO_OK;
 }
 
+int gpbo_qnei_greedy(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n_groups, int n_paths, int n_features,
+                     const double* omega, const double* phase, const double* weights, const double* eps, int noisy, double y_best,
+                     const double* pending, int n_pending, int d, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain,
+                     double* baseline_out, double* values_out, double* keys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const char* who = "qnei_greedy";
+  const std::string w = std::string(who) + ": ";
+  if (n_groups < 1 || n_groups > GPBO_MAX_QNEI_GROUPS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups out of range [1, 16]");
+  const Model* m;
+  const bool given = omega && phase && weights && eps && pick_idx && pick_gain && baseline_out;
+  int rc = check_path_args(ctx, who, slot, y_mean, y_std, n_paths, n_features, 1, given ? nullptr : "NULL argument", &m);
+  if (rc) return rc;
+  if (!noisy && !std::isfinite(y_best)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "y_best must be finite when noisy == 0");
+  if (n_pending < 0 || n_pending > GPBO_MAX_QNEI_POINTS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_pending out of range [0, 64]");
+  if (n_pending > 0 && !pending) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL pending with n_pending > 0");
+  if (d != m->d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "d differs from the fitted model's");
+  for (int64_t i = 0; i < (int64_t)n_pending * d; ++i)
+    if (!std::isfinite(pending[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "pending must be finite");
+  if (q < 1 || q > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q out of range [1, 64]");
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates)");
+  if (ctx->d_c != m->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from the fitted model's");
+  if (q > ctx->M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q exceeds the number of resident candidates");
+  return launch_qnei_greedy(ctx, *m, ctx->M, y_mean, y_std, n_groups, n_paths, n_features, omega, phase, weights, eps, noisy, y_best,
+                            pending, n_pending, q, index_offset, pick_idx, pick_gain, baseline_out, values_out, keys_out);
+}
+
 int gpbo_set_timing(gpbo_ctx* ctx, int on) {
   if (!ctx) return GPBO_ERR_INVALID;
   ctx->timing_off = !on;
@@ -1729,6 +1756,13 @@ int gpbo_debug_kg_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_kg_stage_ms: NULL output");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
   return debug_kg_stage_ms(ctx, ms);
+}
+
+int gpbo_debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_qnei_stage_ms: NULL output");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  return debug_qnei_stage_ms(ctx, ms);
 }
 
 #endif  // GPBO_DEBUG

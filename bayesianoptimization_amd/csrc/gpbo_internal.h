@@ -17,6 +17,7 @@
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
 #include "path_plan.h"        // the posterior function draws' workspace layout and dispatch rules
+#include "qnei_plan.h"        // gpbo_qnei_greedy's workspace layout and the score kernel's thread / candidate rule
 
 namespace gpbo {
 
@@ -172,10 +173,14 @@ struct gpbo_ctx {
   int64_t cap_kg = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
+  double* qnei = nullptr;  // gpbo_qnei_greedy: the draws' values (T, M), their incumbents, the pending points, mask and records (qnei_plan.h)
+  int64_t cap_qnei = 0;
   hipEvent_t kg_ev[4] = {};   // debug build: around the three stages of the last gpbo_kg_argbest (the fields exist in both builds: one layout)
   bool kg_ev_used = false;
   hipEvent_t gen_ev[2] = {};  // debug build: around the kernel of the last gpbo_generate_candidates / _trust_region (generate_mark)
   bool gen_ev_used = false;
+  hipEvent_t qnei_ev[3] = {}; // debug build: before the draws, between the baselines and the greedy steps, behind the last step of the last gpbo_qnei_greedy
+  bool qnei_ev_used = false;
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -612,6 +617,9 @@ int launch_sample_paths_fold(gpbo_ctx* ctx, const Model& m, int64_t M, double y_
                              PathWorkspace* ws);
 int launch_paths_at(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, double y_mean, double y_std, int n_paths, int n_features,
                     const int64_t* idx, int n, double* pts, double* f, int ld);
+// ... the workspace's draws at n points of the caller's (P [>= n][DP], scaled, on the device): out[s * ld + r] = f_s(P_r), the plain store
+int launch_paths_over(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, double y_mean, double y_std, int n_paths, int n_features,
+                      const double* P, int64_t n, double* out, int64_t ld);
 // ... and the first half of it alone: the draws' inputs and V = alpha - W^T (W (g(X) + eps)) made resident, no candidates needed
 int launch_path_weights(gpbo_ctx* ctx, const Model& m, int n_paths, int n_features, const double* omega, const double* phase,
                         const double* weights, const double* eps, int n_runs, PathWorkspace* ws);
@@ -636,6 +644,19 @@ struct AcqArgs {
 };
 int launch_acq_argbest(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_seeds, int64_t offset,
                        int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val);
+// acq_kernels.hip: the selection's sort key and its device record.  Key = (value, index) with NaN greater than everything (NumPy
+// sorts NaN last) and -0.0 == 0.0; ties break to the lowest index.
+struct Key {
+  double v;
+  int64_t i;
+};
+struct SelState {     // lives in device memory, carried from pass to pass
+  Key prev;           // last pick (i = -1 before the first pass)
+  int64_t first_nan;  // lowest index holding NaN (INT64_MAX if none)
+};
+// acq_kernels.hip: launch_values_argbest's selection of ONE pick over ctx->ys[0..M) enqueued on ctx->stream and nothing fetched:
+// *st_out / *pick_out are the device record (the arg-best is st->first_nan where that is not INT64_MAX, else *pick_out)
+int enqueue_values_select(gpbo_ctx* ctx, int64_t M, const SelState** st_out, const Key** pick_out);
 // acq_kernels.hip: launch_acq_argbest's selection and outputs over the values already in ctx->ys[0..M); synchronises
 int launch_values_argbest(gpbo_ctx* ctx, int64_t M, int k_seeds, int64_t offset, int64_t* best_idx, double* best_val,
                           int64_t* seed_idx, double* seed_val);
@@ -652,7 +673,13 @@ int launch_kg_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* poi
 // of level indices (all host).  The caller has checked every argument.  The call's workspace is ctx->ehvi.
 int launch_ehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels, const double* levels, int64_t n_cells,
                        const uint8_t* cell_lo, const uint8_t* cell_hi);
+// qnei.hip: gpbo_qnei_greedy behind its argument checks (include/gpbo.h has the formulas; qnei_plan.h the workspace, ctx->qnei)
+int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int n_groups, int n_paths, int n_features,
+                       const double* omega, const double* phase, const double* weights, const double* eps, int noisy, double y_best,
+                       const double* pending, int n_pending, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain,
+                       double* baseline_out, double* values_out, double* keys_out);
 #ifdef GPBO_DEBUG
+int debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms2);
 int debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out);
 int debug_kg_stage_ms(gpbo_ctx* ctx, float* ms3);
 #endif

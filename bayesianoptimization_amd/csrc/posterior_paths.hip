@@ -298,8 +298,15 @@ int launch_paths_at(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, doub
   for (int r = 0; r < n; ++r)
     GPBO_HIP(ctx, hipMemcpyAsync(pts + (int64_t)r * m.DP, ctx->Xcs + idx[r] * m.DP, (size_t)m.DP * sizeof(double),
                                  hipMemcpyDeviceToDevice, ctx->stream));
+  return launch_paths_over(ctx, m, ws, y_mean, y_std, S, F, pts, n, f, ld);
+}
+
+// f[s * ld + r] = path s of the workspace's draws at the scaled point P_r, r < n: path_eval_kernel with both phases and the plain
+// store — over the scaled candidates with ld = M these are the values gpbo_sample_paths has, before their negation.
+int launch_paths_over(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, double y_mean, double y_std, int S, int F,
+                      const double* P, int64_t n, double* f, int64_t ld) {
   PathEvalArgs a = path_eval_args(m, ws, S, F);
-  a.P = pts; a.out = f; a.M = n; a.ld = ld; a.N = (int)m.N; a.negate = 0; a.y_mean = y_mean; a.y_std = y_std;
+  a.P = P; a.out = f; a.M = n; a.ld = ld; a.N = (int)m.N; a.negate = 0; a.y_mean = y_mean; a.y_std = y_std;
   return launch_path_eval(ctx, m, a);
 }
 

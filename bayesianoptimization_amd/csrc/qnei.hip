@@ -1,0 +1,184 @@
+// gpbo_qnei_greedy (gfx950): a batch of q candidates by greedy noisy expected improvement over T joint posterior draws
+// (include/gpbo.h has the formulas and the conventions; qnei_plan.h the workspace and the score kernel's thread rule).
+//
+// The draws' values are made by the kernels of gpbo_sample_paths (posterior_paths.hip: launch_path_weights, then path_eval_kernel
+// through launch_paths_over) — per group over the candidates into rows [g S, (g + 1) S) of a resident (T, M) block, and over the
+// training and the pending points into a small [T][N + P] buffer.  New here:
+//   qnei_baseline_kernel   a wave per draw: m_t = the fmax fold of the draw's row of that buffer (or of y_best and its pending part)
+//   qnei_score_kernel      the hot loop, once per greedy step: thread = one or two candidates (qnei_items), walking the T rows of
+//                          the block — consecutive lanes read consecutive 8 or 16 bytes of a row — with the m_t staged in LDS and read
+//                          back as broadcasts.  Per value one subtract, one compare / select and one add; the kernel is the stream of
+//                          the block's 8 T M bytes.  It applies the picked mask and writes key_j into ctx->ys
+//   qnei_update_kernel     one workgroup behind the step's selection: reads the pick from the selection's device record (the first
+//                          NaN wins, as best_of_selection has it), files {gain, index}, marks the mask, and folds column `pick` of
+//                          the block into the m_t
+// No multiply-add in any of them (the file is compiled with -ffp-contract=off as well): tests replay the keys bit for bit.
+#include "gpbo_internal.h"
+
+#include <cmath>
+#include <limits>
+
+namespace gpbo {
+
+struct QneiRecord { double gain; int64_t idx; };
+static_assert(sizeof(QneiRecord) == 16, "a record is two doubles of the workspace");
+static_assert(sizeof(QneiRecord) * GPBO_MAX_SEEDS <= PIN_AUX_SEL_OUT_BYTES, "the picks' records outgrew the selection's pinned window");
+
+// m[t] = m0[t] = fmax fold of (y_best unless noisy) and base[t][c0 .. ldb): lane l takes c0 + l, c0 + l + 64, ..., the 64 partial
+// maxima meet in a butterfly.  fmax drops a NaN operand and orders numbers totally up to a zero's sign, so the fold's value is the
+// index-order fold's.
+__global__ __launch_bounds__(64) void qnei_baseline_kernel(const double* __restrict__ base, int64_t ldb, int c0, int noisy, double y_best,
+                                                           double* __restrict__ m, double* __restrict__ m0) {
+  const int t = blockIdx.x, lane = threadIdx.x;
+  const double* row = base + (int64_t)t * ldb;
+  double acc = std::numeric_limits<double>::quiet_NaN();
+  for (int64_t c = c0 + lane; c < ldb; c += 64) acc = fmax(acc, row[c]);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc = fmax(acc, __shfl_xor(acc, off));
+  if (!noisy) acc = fmax(y_best, acc);
+  if (lane == 0) { m[t] = acc; m0[t] = acc; }
+}
+
+// term_t = f - m_t where that is > 0, 0 where it is not, NaN for a NaN f
+__device__ __forceinline__ double qnei_term(double f, double mt) {
+  const double d = f - mt;
+  return d > 0.0 ? d : (f != f ? f : 0.0);
+}
+
+// key_j over the candidates: ITEMS (qnei_plan.h: qnei_items) neighbouring candidates per thread, read as one load per row
+template <int ITEMS>
+__global__ __launch_bounds__(QNEI_BLOCK) void qnei_score_kernel(const double* __restrict__ vals, int64_t M, int T,
+                                                                const double* __restrict__ m, const uint8_t* __restrict__ mask,
+                                                                double* __restrict__ ys) {
+  __shared__ double ms[QNEI_MAX_DRAWS];
+  for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) ms[t] = m[t];
+  __syncthreads();
+  const int64_t i = qnei_first_candidate(blockIdx.x, threadIdx.x, ITEMS);
+  if (i >= M) return;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double* col = vals + i;
+  if (ITEMS == 2) {      // M is even: i + 1 < M, and every row's pair sits on a 16-byte boundary
+    double s0 = 0.0, s1 = 0.0;
+#pragma unroll 8
+    for (int t = 0; t < T; ++t) {
+      const double2 f = *reinterpret_cast<const double2*>(col + (int64_t)t * M);
+      const double mt = ms[t];
+      s0 += qnei_term(f.x, mt);
+      s1 += qnei_term(f.y, mt);
+    }
+    const uchar2 picked = *reinterpret_cast<const uchar2*>(mask + i);
+    double2 key;
+    key.x = picked.x ? inf : -(s0 / (double)T);
+    key.y = picked.y ? inf : -(s1 / (double)T);
+    *reinterpret_cast<double2*>(ys + i) = key;
+  } else {
+    double s0 = 0.0;
+#pragma unroll 8
+    for (int t = 0; t < T; ++t) s0 += qnei_term(col[(int64_t)t * M], ms[t]);
+    ys[i] = mask[i] ? inf : -(s0 / (double)T);
+  }
+}
+
+// Behind step j's selection: the pick (the first NaN wins, else the selection's first pick), its record, the mask, the incumbents.
+__global__ __launch_bounds__(QNEI_BLOCK) void qnei_update_kernel(const SelState* __restrict__ st, const Key* __restrict__ first,
+                                                                 const double* __restrict__ vals, int64_t M, int T, int64_t offset, int j,
+                                                                 double* __restrict__ m, uint8_t* __restrict__ mask,
+                                                                 QneiRecord* __restrict__ rec) {
+  const bool nan = st->first_nan != INT64_MAX;
+  const int64_t pick = nan ? st->first_nan : first->i;
+  const bool valid = pick >= 0 && pick < M;      // (always, with q <= M: a pick outside the candidates touches nothing)
+  if (threadIdx.x == 0) {
+    QneiRecord r;
+    r.gain = (nan || !valid) ? std::numeric_limits<double>::quiet_NaN() : -first->v;
+    r.idx = valid ? pick + offset : -1;
+    rec[j] = r;
+    if (valid) mask[pick] = 1;
+  }
+  if (!valid) return;
+  for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) m[t] = fmax(m[t], vals[(int64_t)t * M + pick]);
+}
+
+// debug build: an event before the draws, between the baselines and the steps, and behind the last step of the last call
+// (gpbo_debug_qnei_stage_ms); the product records nothing
+static inline void qnei_mark(gpbo_ctx* ctx, int i) {
+#ifdef GPBO_DEBUG
+  if (!ctx->qnei_ev[i]) (void)hipEventCreate(&ctx->qnei_ev[i]);
+  (void)hipEventRecord(ctx->qnei_ev[i], ctx->stream);
+  ctx->qnei_ev_used = (i == 2);
+#else
+  (void)ctx; (void)i;
+#endif
+}
+
+#ifdef GPBO_DEBUG
+int debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx->qnei_ev_used) GPBO_FAIL(ctx, GPBO_ERR_STATE, "debug_qnei_stage_ms: no gpbo_qnei_greedy call to report");
+  GPBO_HIP(ctx, hipEventSynchronize(ctx->qnei_ev[2]));
+  for (int i = 0; i < 2; ++i) GPBO_HIP(ctx, hipEventElapsedTime(&ms[i], ctx->qnei_ev[i], ctx->qnei_ev[i + 1]));
+  return GPBO_OK;
+}
+#endif
+
+int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int G, int S, int F, const double* omega,
+                       const double* phase, const double* weights, const double* eps, int noisy, double y_best, const double* pending,
+                       int P, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain, double* baseline_out,
+                       double* values_out, double* keys_out) {
+  int rc;
+  const int N = (int)m.N, d = m.d, T = G * S;
+  const QneiBlock b = qnei_block(T, M, N, P, d, m.DP, q);
+  if ((rc = ensure(ctx, &ctx->qnei, &ctx->cap_qnei, b.doubles))) return rc;
+  double* w = ctx->qnei;
+  double *vals = w + b.vals, *base = w + b.base, *mt = w + b.m, *pend_s = w + b.pend_s;
+  uint8_t* mask = (uint8_t*)(w + b.mask);
+  QneiRecord* rec = (QneiRecord*)(w + b.rec);
+  // the scaled candidates (the draws' workspace of the context, as gpbo_sample_paths fills it) and the scaled pending points
+  const int64_t Mp = round_up(M, POST_CANDS);
+  if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * m.DP))) return rc;
+  qnei_mark(ctx, 0);
+  if ((rc = launch_prescale(ctx, ctx->Xc, M, d, m.DP, m.ls, ctx->Xcs, Mp))) return rc;
+  if (P > 0) {
+    GPBO_HIP(ctx, hipMemcpyAsync(w + b.pend, pending, (size_t)P * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = launch_prescale(ctx, w + b.pend, P, d, m.DP, m.ls, pend_s, P))) return rc;
+  }
+  if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, M))) return rc;
+  GPBO_HIP(ctx, hipMemsetAsync(mask, 0, (size_t)((M + 7) / 8 * 8), ctx->stream));
+  // the draws, group by group: the group's inputs and path weights into the paths workspace, then its S rows of each buffer
+  for (int g = 0; g < G; ++g) {
+    PathWorkspace ws{};
+    if ((rc = launch_path_weights(ctx, m, S, F, omega + (int64_t)g * F * d, phase + (int64_t)g * F, weights + (int64_t)g * S * F,
+                                  eps + (int64_t)g * S * N, 0, &ws)))
+      return rc;
+    if ((rc = launch_paths_over(ctx, m, ws, y_mean, y_std, S, F, ctx->Xcs, M, vals + (int64_t)g * S * M, M))) return rc;
+    double* rows = base + (int64_t)g * S * b.ldb;
+    if (noisy && (rc = launch_paths_over(ctx, m, ws, y_mean, y_std, S, F, m.Xs, N, rows, b.ldb))) return rc;
+    if (P > 0 && (rc = launch_paths_over(ctx, m, ws, y_mean, y_std, S, F, pend_s, P, rows + N, b.ldb))) return rc;
+  }
+  qnei_baseline_kernel<<<dim3((unsigned)T), dim3(64), 0, ctx->stream>>>(base, b.ldb, noisy ? 0 : N, noisy, y_best, mt, w + b.m0);
+  GPBO_HIP(ctx, hipGetLastError());
+  qnei_mark(ctx, 1);
+  // the greedy steps, all on the stream
+  const int items = qnei_items(M);
+  const dim3 grid((unsigned)qnei_score_blocks(M)), block(QNEI_BLOCK);
+  for (int j = 0; j < q; ++j) {
+    if (items == 2) qnei_score_kernel<2><<<grid, block, 0, ctx->stream>>>(vals, M, T, mt, mask, ctx->ys);
+    else qnei_score_kernel<1><<<grid, block, 0, ctx->stream>>>(vals, M, T, mt, mask, ctx->ys);
+    GPBO_HIP(ctx, hipGetLastError());
+    if (keys_out)
+      GPBO_HIP(ctx, hipMemcpyAsync(keys_out + (int64_t)j * M, ctx->ys, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const SelState* st; const Key* first;
+    if ((rc = enqueue_values_select(ctx, M, &st, &first))) return rc;
+    qnei_update_kernel<<<dim3(1), block, 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, mt, mask, rec);
+    GPBO_HIP(ctx, hipGetLastError());
+  }
+  qnei_mark(ctx, 2);
+  QneiRecord* hrec = (QneiRecord*)((char*)ctx->pinned_aux + PIN_AUX_SEL_OUT);
+  GPBO_HIP(ctx, hipMemcpyAsync(hrec, rec, sizeof(QneiRecord) * (size_t)q, hipMemcpyDeviceToHost, ctx->stream));
+  GPBO_HIP(ctx, hipMemcpyAsync(baseline_out, w + b.m0, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (values_out)
+    GPBO_HIP(ctx, hipMemcpyAsync(values_out, vals, (size_t)T * (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int j = 0; j < q; ++j) { pick_idx[j] = hrec[j].idx; pick_gain[j] = hrec[j].gain; }
+  return GPBO_OK;
+}
+
+}  // namespace gpbo

@@ -993,6 +993,56 @@ class GpEngine:
                                                 C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
         return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
 
+    def qnei_greedy(self, groups, q, noisy=True, y_best=0.0, pending=None, slot=0, y_mean=0.0, y_std=1.0, index_offset=0,
+                    return_values=False, return_keys=False):
+        """A batch of q resident candidates by greedy noisy expected improvement over T joint posterior draws (gpbo_qnei_greedy;
+        include/gpbo.h has the formulas, the conventions and the order of every sum).  `groups`: a list of G <= 16 tuples (omega,
+        phase, weights, eps) as `sample_paths` takes them, all with the same S <= 16 and F; draw t = g S + s is `sample_paths`' draw s
+        of group g, the same bits.  noisy: every draw's incumbent is its own maximum over the training points; else `y_best` (finite)
+        is every draw's.  pending (P <= 64, d) or None: points suggested but not yet observed, absorbed into the incumbents first.
+        Returns (pick_idx (q,) int64, pick_gain (q,), baseline (T,), values (T, M) or None, keys (q, M) or None).  A reader, as
+        `sample_paths`."""
+        who = "qnei_greedy"
+        groups = list(groups)
+        G = len(groups)
+        if G < 1 or any(len(t) != 4 for t in groups):
+            raise ValueError(f"{who}: groups must be a non-empty list of tuples (omega, phase, weights, eps)")
+        if G > _lib.MAX_QNEI_GROUPS:
+            raise ValueError(f"{who}: n_groups out of range [1, {_lib.MAX_QNEI_GROUPS}]")
+        parts = [self._path_inputs(who, *t, slot) for t in groups]
+        F, S = parts[0][0].shape[0], parts[0][2].shape[0]
+        if any(p[0].shape[0] != F or p[2].shape[0] != S for p in parts):
+            raise ValueError(f"{who}: every group's draws must have the same S and F")
+        d = parts[0][4][1]
+        if pending is None:
+            P = 0
+        else:
+            pending = np.ascontiguousarray(np.asarray(pending, dtype=np.float64))
+            if pending.ndim != 2:
+                raise ValueError(f"{who}: pending must be two-dimensional (P, d)")
+            P = int(pending.shape[0])
+            if P and pending.shape[1] != d:
+                raise ValueError(f"{who}: pending (P, {pending.shape[1]}) does not fit the slot's model in {d} dimensions")
+            if P == 0:
+                pending = None
+        omega = np.ascontiguousarray(np.concatenate([p[0].ravel() for p in parts]))
+        phase = np.ascontiguousarray(np.concatenate([p[1] for p in parts]))
+        weights = np.ascontiguousarray(np.concatenate([p[2].ravel() for p in parts]))
+        eps = np.ascontiguousarray(np.concatenate([p[3].ravel() for p in parts]))
+        q = int(q)
+        T, M = G * S, max(int(self.n_candidates), 0)
+        n = max(q, 1)
+        pick_idx = np.empty(n, dtype=np.int64)
+        pick_gain = np.empty(n)
+        baseline = np.empty(max(T, 1))
+        values = np.empty((T, M)) if return_values and T >= 1 and M >= 1 else None
+        keys = np.empty((q, M)) if return_keys and q >= 1 and M >= 1 else None
+        self._check(self._lib.gpbo_qnei_greedy(self._h, int(slot), float(y_mean), float(y_std), G, int(S), int(F), dptr(omega),
+                                               dptr(phase), dptr(weights), dptr(eps), int(bool(noisy)), float(y_best), dptr(pending),
+                                               P, int(d), q, int(index_offset), iptr(pick_idx), dptr(pick_gain), dptr(baseline),
+                                               dptr(values), dptr(keys)))
+        return pick_idx[:q], pick_gain[:q], baseline[:T], values, keys
+
     def debug_ehvi_ms(self):
         """gpbo_debug_ehvi_ms (debug build): kernel ms of the last `ehvi_argbest`'s value kernel (tables and cell sum)."""
         self._need_debug("gpbo_debug_ehvi_ms")
@@ -1017,6 +1067,13 @@ class GpEngine:
         self._need_debug("gpbo_debug_kg_stage_ms")
         ms = (C.c_float * 3)()
         self._check(self._lib.gpbo_debug_kg_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+    def debug_qnei_stage_ms(self):
+        """gpbo_debug_qnei_stage_ms (debug build): kernel ms of the last `qnei_greedy`'s stages, (draws and baselines, greedy steps)."""
+        self._need_debug("gpbo_debug_qnei_stage_ms")
+        ms = (C.c_float * 2)()
+        self._check(self._lib.gpbo_debug_qnei_stage_ms(self._h, ms))
         return tuple(float(v) for v in ms)
 
     # -- timing / probes (debug_* and the latency / hybrid probes need GpEngine(debug=True)) ----------------------------
@@ -1474,6 +1531,11 @@ class GroupEngine(GpEngine):
 
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         raise NotImplementedError("a device group has no expected hypervolume improvement (gpbo_ehvi_argbest is per context); "
+                                  "use a single device")
+
+    def qnei_greedy(self, groups, q, noisy=True, y_best=0.0, pending=None, slot=0, y_mean=0.0, y_std=1.0, index_offset=0,
+                    return_values=False, return_keys=False):
+        raise NotImplementedError("a device group has no batch noisy expected improvement (gpbo_qnei_greedy is per context); "
                                   "use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):

@@ -589,6 +589,57 @@ int gpbo_ehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, cons
                       int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val,
                       int64_t* seed_idx, double* seed_val, double* ys_out);
 
+/* Batch noisy expected improvement, built greedily over the resident candidates from joint posterior draws (qNEI: Letham, Karrer,
+ * Ottoni & Bakshy 2019, "Constrained Bayesian optimization with noisy experiments"; the Monte-Carlo qEI of Wilson, Hutter &
+ * Deisenroth 2018).  T = n_groups * n_paths draws f_t of the LATENT function, each with an incumbent m_t of its own; a candidate is
+ * worth the mean over the draws of how far it lifts the incumbent; after a pick every draw's incumbent absorbs the draw's value
+ * there, so the next pick is scored jointly with the earlier ones — no made-up observation, no refit.  Raw target units.
+ * The draws.  G = n_groups groups of S = n_paths draws; a group shares its F = n_features features.  The inputs are the per-group
+ * inputs of gpbo_sample_paths concatenated in group order: omega (G, F, d), phase (G, F), weights (G, S, F), eps (G, S, N).  Draw
+ * t = g S + s is gpbo_sample_paths' f_s for group g's inputs, the same bits (the same kernels write row t of a resident (T, M) block).
+ * values_out (T, M) draw-major, or NULL.
+ * The incumbents.  noisy != 0: m_t = max_i f_t(X_i) over the N training points, the draw evaluated there by the evaluator the
+ * candidates get (y_best is not read) — the best LATENT value among the observations, per draw, instead of one noisy measurement.
+ * noisy == 0: m_t = y_best (finite) for every t: plain Monte-Carlo qEI.  Then m_t = max(m_t, f_t(p)) over the n_pending rows of
+ * `pending` (P, d; host, parameter space — points suggested but not yet observed; scaled by the slot's length scales on the
+ * device; n_pending = 0 with pending NULL is allowed).  The maxima are fmax folds in index order: a NaN value is dropped (m_t is NaN
+ * only when every value is), and a zero's sign reaches no key, so the wave that folds a draw's values lane by lane gives the value
+ * the index-order fold gives.  baseline_out (T,) = m_t before the first pick.
+ * The greedy steps j = 0 .. q - 1, over the resident candidates x:
+ *   term_t(x) = f_t(x) - m_t  where that is > 0;  0 where it is <= 0 (or m_t is NaN);  NaN where f_t(x) is NaN
+ *   key_j(x)  = -((term_0 + term_1 + ... + term_{T-1}) / T)      added in that order into one accumulator from 0, ONE true division;
+ *               +inf for a candidate picked in an earlier step
+ * The pick is the selection's one-pick answer over key_j (gpbo_acq_argbest's rules: the first NaN wins, else the least key, ties
+ * to the lowest index).  pick_idx[j] = its index + index_offset, pick_gain[j] = -key_j there (NaN for a NaN pick).  Then
+ * m_t = fmax(m_t, f_t(pick)) for every t; a NaN value leaves m_t as it is.  Once every draw's maximum over the candidates is
+ * absorbed the best gain is exactly 0 and the rule hands out the lowest unpicked index.  No multiply-add appears anywhere in a key;
+ * a candidate's key bits depend neither on M, nor on the launch geometry, nor on the other candidates.  keys_out (q, M) or NULL:
+ * every step's keys, masks included (a debugging aid: it adds one blocking copy per step).
+ * On the device: per group one launch_path_weights and passes of path_eval_kernel over the candidates, the training points and the
+ * pending points, straight into the call's workspace; one wave per draw folds the incumbent; per step qnei_score_kernel (thread =
+ * candidate(s), a pure stream of the 8 T M bytes of the block, the m_t read from LDS as broadcasts) writes key_j as the context's
+ * acquisition values, the selection launches pick, and qnei_update_kernel reads the pick from the selection's device record, files
+ * {gain, index}, marks the mask and updates the m_t from the pick's column.  All q steps are enqueued on the context's stream; the
+ * q records, baseline_out and values_out cross once, behind ONE synchronisation.  fp64 whatever the slot's precision.
+ * Workspace: the context's own, 8 T M bytes for the block (2 GiB at T = 256 and M = 2^20) + 8 T (N + P) + O(M / 8 + P d) bytes; it is
+ * grown on demand and kept; an allocation that fails is GPBO_ERR_HIP.
+ * A reader, as gpbo_sample_paths: the slot's fit, its resident mu / sd, what gpbo_posterior_refresh may still refresh, the
+ * candidates and the negative-variance flag stay as they were; the context's acquisition values are overwritten.
+ * GPBO_ERR_INVALID: n_groups outside [1, GPBO_MAX_QNEI_GROUPS]; n_paths outside [1, GPBO_MAX_PATHS] or n_features outside
+ * [1, GPBO_MAX_PATH_FEATURES]; a NULL omega / phase / weights / eps / pick_idx / pick_gain / baseline_out; y_std not finite or not
+ * positive, y_mean not finite; noisy == 0 with a y_best that is not finite; n_pending outside [0, GPBO_MAX_QNEI_POINTS], n_pending > 0
+ * with a NULL or non-finite pending, d not the slot's; q outside [1, GPBO_MAX_SEEDS], q > M.  GPBO_ERR_STATE: an unfitted slot, a fit
+ * pending on the slot, no resident candidates, candidates of another d.  There is no gpbo_group_* / gpbo_comm_* form. */
+#define GPBO_MAX_QNEI_GROUPS 16      /* T = n_groups * n_paths <= 256 draws */
+#define GPBO_MAX_QNEI_POINTS 64      /* pending points */
+int gpbo_qnei_greedy(gpbo_ctx* ctx, int slot, double y_mean, double y_std,
+                     int n_groups, int n_paths, int n_features,
+                     const double* omega, const double* phase, const double* weights, const double* eps,
+                     int noisy, double y_best, const double* pending, int n_pending, int d,
+                     int q, int64_t index_offset,
+                     int64_t* pick_idx, double* pick_gain, double* baseline_out,
+                     double* values_out, double* keys_out);
+
 /* ---- timing (HIP events on the context stream) ------------------------------------------ */
 /* Milliseconds spent in the last call's kernels: [0] fit total, [1] posterior main kernel,
  * [2] posterior finalize, [3] acquisition + arg-best, [4] kmat assembly, [5] cholesky, [6] trtri. */
@@ -784,6 +835,11 @@ int gpbo_debug_generate_ms(gpbo_ctx* ctx, float* ms);
 /* Kernel milliseconds (HIP events) of the value kernel of the context's last gpbo_ehvi_argbest: the tables and the sum over the
  * boxes, without the upload of levels and boxes and without the selection. */
 int gpbo_debug_ehvi_ms(gpbo_ctx* ctx, float* ms);
+/* Kernel milliseconds (HIP events) of the two stages of the context's last gpbo_qnei_greedy: ms[0] the draws — the candidates'
+ * and the pending points' scaling, per group the path weights and the passes over candidates, training and pending points, the
+ * baselines —, ms[1] the q greedy steps (score, selection, update; with keys_out their copies too).  The fetch of the results and
+ * the synchronise are in neither. */
+int gpbo_debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms);
 #endif /* GPBO_DEBUG */
 
 #ifdef __cplusplus
