@@ -5,7 +5,9 @@ refusal, and suggest_kg end to end on the real engine.
 
 Bar: |error| <= 1e-9 scale(x), scale(x) = max_j |b_j| (the slopes' size: KG is a sum of slope differences times f <= 0.4).  The
 fixtures use short length scales and noise 1e-2: with the suite's usual ones the median KG is 1e-127 and a test would pass on zeros;
-here the truth itself is asserted to have at least 10 % of the candidates at KG >= 1e-3 scale."""
+here the truth itself is asserted to have at least 10 % of the candidates at KG >= 1e-3 scale.  The instance axis — every (padded width,
+kernel kind) of kg_points_kernel and every (padded width, kernel kind, columns per pass) of kg_cov_kernel — is
+tests/test_gpu_instances.py's."""
 import functools
 
 import numpy as np

@@ -8,7 +8,8 @@ bar max(1e-9, 8 x the spread between the two NumPy routes).  1e-9 is the project
 order.  best_idx is compared only where the truth's own best and second best value are at least 1e-6 of the range apart, asserted
 on the truth alone.  The shapes are the edges of the code: the LDS stage of 64 training points / features on both sides, all three
 fit tiers (one launch NP <= 64, strips NP <= 768, multi-launch), every padded dimension, every accumulator count (1, 4, 16) with
-partly filled ones, the wide workgroup (M >= 2^17), a scaled slot, an F32 slot, a slot after fit_append.
+partly filled ones, the wide workgroup (M >= 2^17), a scaled slot, an F32 slot, a slot after fit_append.  The instance axis — every
+(padded width, kernel kind, accumulator count) of path_eval_kernel — is tests/test_gpu_instances.py's.
 
 Exact properties: bitwise repeatability; path s alone = path s among 16; ties to the lowest index; index_offset; the first NaN wins.
 Reader only: the resident posterior, the refreshable state, the candidates and the negative-variance flag survive the call."""

@@ -5,7 +5,8 @@ state the call leaves behind and every refusal, and `suggest_turbo` on the real 
 The generator's shapes are the smallest that reach every path: a row narrower than (d = 1, 3), equal to (d = 64: 16 lanes is the
 widest ballot group) and not dividing a wave (d = 17), the ballot kernel (d = 16, 64) and the LDS kernel (d = 1, 3, 17), a Philox quad
 that straddles two rows (d = 3, 17), one workgroup with a ragged tail and more than one workgroup (M = 255 / 257 / 4099), a Gray code
-with a bit above 16 (M = 65 539)."""
+with a bit above 16 (M = 65 539).  The other row widths of the ballot kernel (d = 4, 8, 32: ballot groups of 1, 2 and 8 lanes) are
+tests/test_gpu_instances.py's."""
 import numpy as np
 import pytest
 
