@@ -410,7 +410,10 @@ __device__ __forceinline__ double gpbo_kernel_value(double d2) {
     const double s = gpbo_sqrt_pos(d2) * 1.73205080756887729353;
     return (1.0 + s) * gpbo_exp_nonpos(-s);
   } else if (KERNEL == GPBO_KERNEL_MATERN05) {
-    return gpbo_exp_nonpos(-gpbo_sqrt_pos(d2));
+    // An infinite distance (a +-inf coordinate) is exp(-inf) = 0, as sklearn has it; gpbo_sqrt_pos(inf) would be NaN (rsq(inf) = 0,
+    // inf * 0), so the root sees 1e300 at most: exp(-1e150) is the same exact 0.  The comparison is false for NaN, which still
+    // propagates.  (nu = 2.5 / 1.5 keep their NaN there: inf * exp(-inf) is NaN in NumPy too; RBF takes no root.)
+    return gpbo_exp_nonpos(-gpbo_sqrt_pos(d2 > 1e300 ? 1e300 : d2));
   } else {
     return gpbo_exp_nonpos(-0.5 * d2);
   }
