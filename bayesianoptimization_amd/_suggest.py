@@ -1,5 +1,6 @@
 """What suggest_batch (batch.py), suggest_thompson (thompson.py), suggest_mes (mes.py), suggest_kg (kg.py), suggest_turbo (turbo.py),
-suggest_qnei (qnei.py: the count check, the gate and the frame of a model) and
+suggest_qnei (qnei.py: the count check, the gate, the frame of a model and `group_inputs`),
+suggest_qnehvi (qnehvi.py: the count check, `pareto_gate`, the frame of a model and `group_inputs`) and
 the constrained pair suggest_constrained_thompson / suggest_scbo (scbo.py: the gate with `constrained=True`, the frame of a model)
 share, each thing once: the check of a count argument, the gate an optimizer passes before anything runs, the frame of the fitted
 model, the loop over groups of posterior draws, and the picks of a Thompson batch (suggest_thompson, suggest_turbo).  The ORDER of the refusals is part of the three functions' contract: a caller's own argument checks come
@@ -103,6 +104,40 @@ def fit_model(gp, space, who: str) -> Model:
         warnings.simplefilter("ignore")
         gp.fit(space.params, space.target)
     return read_model(gp, space, who)
+
+
+def pareto_gate(pareto, who: str, what: str):
+    """The engine of a `ParetoOptimizer` whose models `who` can work on, else `ParetoOptimizer.suggest`'s refusals in its order:
+    TargetSpaceEmptyError on an empty store; NotImplementedError for a device group (`what`: what a group lacks) and for an
+    objective whose model would run on the host.  (suggest's fourth refusal, an observed front beyond gpbo_ehvi_argbest's level
+    lists, belongs to that call alone.)"""
+    from sklearn.base import clone
+
+    if len(pareto) == 0:
+        raise A.TargetSpaceEmptyError(A.EMPTY_SPACE_MESSAGE)
+    eng = pareto._engine()
+    if isinstance(eng, GroupEngine):
+        raise NotImplementedError(f"{who}: a device group has no {what}; use a single device")
+    for j, gp in enumerate(pareto._gps):
+        reason = gp._unsupported_reason(clone(gp.kernel), pareto.targets[:, j], pareto.params)
+        if reason is not None:
+            raise NotImplementedError(f"{who}: objective {j}'s model runs on the host ({reason}); only models on the device path "
+                                      "are served")
+    return eng
+
+
+def group_inputs(gp, rng, model: Model, n_groups: int, n_paths: int, n_features: int):
+    """`n_groups` groups of `n_paths` posterior draws as the greedy engine calls (`qnei_greedy`, `qnehvi_greedy`) take them: a list
+    of (omega, phase, weights, eps), drawn from `rng` group after group in `draw_groups`' order — `spectral_draw` (fresh features),
+    `standard_normal((S, F))`, `standard_normal((S, N))` scaled by sqrt(noise)."""
+    from .thompson import spectral_draw
+
+    groups = []
+    for _ in range(n_groups):
+        omega, phase = spectral_draw(gp._kind, n_features, model.d, rng)
+        weights = rng.standard_normal((n_paths, n_features))
+        groups.append((omega, phase, weights, rng.standard_normal((n_paths, model.N)) * np.sqrt(model.noise)))
+    return groups
 
 
 def draw_groups(gp, space, eng, rng, model: Model, n_draws: int, n_features: int, refine: int, max_iter, box=None):

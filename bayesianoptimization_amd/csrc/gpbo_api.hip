@@ -224,6 +224,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->qnei_ev) if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : ctx->qnehvi_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
   if (ctx->small_pinned) (void)hipHostFree(ctx->small_pinned);
@@ -234,7 +235,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->qnei, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->qnei, ctx->qnehvi, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1596,6 +1597,39 @@ int gpbo_qnei_greedy(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n
                             pending, n_pending, q, index_offset, pick_idx, pick_gain, baseline_out, values_out, keys_out);
 }
 
+int gpbo_qnhvi_greedy(gpbo_ctx* ctx, const double* y_mean, const double* y_std, int n_groups, int n_paths, int n_features,
+                       const double* omega, const double* phase, const double* weights, const double* eps, const double* ref,
+                       const double* base, int n_base, int d, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain,
+                       int* front_size_out, double* fronts_out, double* values_out, double* base_values_out, double* keys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const char* who = "qnehvi_greedy";
+  const std::string w = std::string(who) + ": ";
+  if (n_groups < 1 || n_groups > GPBO_MAX_QNEI_GROUPS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups out of range [1, 16]");
+  // the counts first, as check_path_args orders them
+  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_paths out of range [1, 16]");
+  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_features out of range [1, 4096]");
+  if (!y_mean || !y_std || !omega || !phase || !weights || !eps || !ref || !pick_idx || !pick_gain)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL argument");
+  int rc;
+  const Model* ms[2];
+  for (int j = 0; j < 2; ++j)
+    if ((rc = check_path_args(ctx, who, j, y_mean[j], y_std[j], n_paths, n_features, 1, nullptr, &ms[j]))) return rc;
+  if (!std::isfinite(ref[0]) || !std::isfinite(ref[1])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "ref must be finite");
+  if (n_base < 0 || n_base > GPBO_MAX_QNEHVI_BASE) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_base out of range [0, 16384]");
+  if (n_base > 0 && !base) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL base with n_base > 0");
+  if (d != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "d differs from the fitted models'");
+  for (int64_t i = 0; i < (int64_t)n_base * d; ++i)
+    if (!std::isfinite(base[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "base must be finite");
+  if (q < 1 || q > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q out of range [1, 64]");
+  if (ms[1]->d != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the two objectives' models differ in dimension");
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates)");
+  if (ctx->d_c != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from the fitted models'");
+  if (q > ctx->M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q exceeds the number of resident candidates");
+  return launch_qnehvi_greedy(ctx, ms, ctx->M, y_mean, y_std, n_groups, n_paths, n_features, omega, phase, weights, eps, ref, base,
+                              n_base, q, index_offset, pick_idx, pick_gain, front_size_out, fronts_out, values_out, base_values_out,
+                              keys_out);
+}
+
 int gpbo_set_timing(gpbo_ctx* ctx, int on) {
   if (!ctx) return GPBO_ERR_INVALID;
   ctx->timing_off = !on;
@@ -1763,6 +1797,24 @@ int gpbo_debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_qnei_stage_ms: NULL output");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
   return debug_qnei_stage_ms(ctx, ms);
+}
+
+int gpbo_debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_qnehvi_stage_ms: NULL output");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  return debug_qnehvi_stage_ms(ctx, ms);
+}
+
+int gpbo_debug_qnehvi_fronts(gpbo_ctx* ctx, int n_draws, int n, const double* base_values, const double* ref, int n_insert,
+                             const double* insert_values, int* front_size_out, double* fronts_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (n_draws < 1 || n_draws > 4096 || n < 0 || n > GPBO_MAX_QNEHVI_BASE || n_insert < 0 || n_insert > 4096 || !ref ||
+      !std::isfinite(ref[0]) || !std::isfinite(ref[1]) || (n > 0 && !base_values) || (n_insert > 0 && !insert_values) ||
+      !front_size_out || !fronts_out)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_qnehvi_fronts: bad arguments");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  return debug_qnehvi_fronts(ctx, n_draws, n, base_values, ref, n_insert, insert_values, front_size_out, fronts_out);
 }
 
 #endif  // GPBO_DEBUG

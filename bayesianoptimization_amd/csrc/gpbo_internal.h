@@ -175,12 +175,16 @@ struct gpbo_ctx {
   int64_t cap_ehvi = 0;
   double* qnei = nullptr;  // gpbo_qnei_greedy: the draws' values (T, M), their incumbents, the pending points, mask and records (qnei_plan.h)
   int64_t cap_qnei = 0;
+  double* qnehvi = nullptr;  // gpbo_qnhvi_greedy: both objectives' draws (2, T, M), their values at the base points, the fronts, mask and records (qnehvi_plan.h)
+  int64_t cap_qnehvi = 0;
   hipEvent_t kg_ev[4] = {};   // debug build: around the three stages of the last gpbo_kg_argbest (the fields exist in both builds: one layout)
   bool kg_ev_used = false;
   hipEvent_t gen_ev[2] = {};  // debug build: around the kernel of the last gpbo_generate_candidates / _trust_region (generate_mark)
   bool gen_ev_used = false;
   hipEvent_t qnei_ev[3] = {}; // debug build: before the draws, between the baselines and the greedy steps, behind the last step of the last gpbo_qnei_greedy
   bool qnei_ev_used = false;
+  hipEvent_t qnehvi_ev[4] = {}; // debug build: before the draws, behind them, behind the front build, behind the last step of the last gpbo_qnhvi_greedy
+  bool qnehvi_ev_used = false;
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -681,8 +685,18 @@ int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, 
                        const double* omega, const double* phase, const double* weights, const double* eps, int noisy, double y_best,
                        const double* pending, int n_pending, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain,
                        double* baseline_out, double* values_out, double* keys_out);
+// qnehvi.hip: gpbo_qnhvi_greedy behind its argument checks (include/gpbo.h has the formulas; qnehvi_plan.h the workspace,
+// ctx->qnehvi): ms / y_mean / y_std per objective, the draws' inputs concatenated in slot order
+int launch_qnehvi_greedy(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std, int n_groups,
+                         int n_paths, int n_features, const double* omega, const double* phase, const double* weights,
+                         const double* eps, const double* ref, const double* base, int n_base, int q, int64_t index_offset,
+                         int64_t* pick_idx, double* pick_gain, int* front_size_out, double* fronts_out, double* values_out,
+                         double* base_values_out, double* keys_out);
 #ifdef GPBO_DEBUG
 int debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms2);
+int debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms3);
+int debug_qnehvi_fronts(gpbo_ctx* ctx, int T, int n, const double* base_values, const double* ref, int n_insert,
+                        const double* insert_values, int* front_size_out, double* fronts_out);
 int debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out);
 int debug_kg_stage_ms(gpbo_ctx* ctx, float* ms3);
 #endif

@@ -1043,6 +1043,102 @@ class GpEngine:
                                                dptr(values), dptr(keys)))
         return pick_idx[:q], pick_gain[:q], baseline[:T], values, keys
 
+    def qnehvi_greedy(self, draws, q, ref, base=None, y_mean=(0.0, 0.0), y_std=(1.0, 1.0), index_offset=0, return_values=False,
+                      return_keys=False, return_fronts=False):
+        """A batch of q resident candidates by greedy noisy expected hypervolume improvement over T joint posterior draws of two
+        objectives (gpbo_qnhvi_greedy; include/gpbo.h has the formulas, the conventions and the order of every sum).  `draws`:
+        two lists, objective j's (slot j's) G <= 16 tuples (omega, phase, weights, eps) as `qnei_greedy` takes them, all with the
+        same G, S <= 16 and F.  ref (2,) finite; base (n_base <= 16384, d) or None: the observed points followed by the pending
+        ones — every draw's front is built from the draw's values there.  y_mean / y_std: (2,) per objective.
+        Returns a dict: "index" (q,) int64, "gain" (q,), and — None unless asked for — "values" (2, T, M), "base_values"
+        (2, T, n_base) (with `return_values`), "keys" (q, M), "front_size" (2, T) int32 and "fronts" (2, T, 128, 2) (before the
+        first pick | after the last; rows past a front's size are unspecified).  A front of more than 128 points is
+        NotImplementedError.  A reader, as `sample_paths`."""
+        who = "qnehvi_greedy"
+        draws = [list(g) for g in draws]
+        if len(draws) != 2:
+            raise ValueError(f"{who}: draws must hold two lists of groups, one per objective")
+        G = len(draws[0])
+        if G < 1 or len(draws[1]) != G or any(len(t) != 4 for groups in draws for t in groups):
+            raise ValueError(f"{who}: each objective needs the same non-empty list of tuples (omega, phase, weights, eps)")
+        if G > _lib.MAX_QNEI_GROUPS:
+            raise ValueError(f"{who}: n_groups out of range [1, {_lib.MAX_QNEI_GROUPS}]")
+        parts = [[self._path_inputs(who, *t, j) for t in groups] for j, groups in enumerate(draws)]
+        F, S = parts[0][0][0].shape[0], parts[0][0][2].shape[0]
+        if any(p[0].shape[0] != F or p[2].shape[0] != S for ps in parts for p in ps):
+            raise ValueError(f"{who}: every group's draws must have the same S and F")
+        d = parts[0][0][4][1]
+        if base is None:
+            B = 0
+        else:
+            base = np.ascontiguousarray(np.asarray(base, dtype=np.float64))
+            if base.ndim != 2:
+                raise ValueError(f"{who}: base must be two-dimensional (n_base, d)")
+            B = int(base.shape[0])
+            if B and base.shape[1] != d:
+                raise ValueError(f"{who}: base (n_base, {base.shape[1]}) does not fit the slots' models in {d} dimensions")
+            if B == 0:
+                base = None
+        flat = [p for ps in parts for p in ps]
+        omega = np.ascontiguousarray(np.concatenate([p[0].ravel() for p in flat]))
+        phase = np.ascontiguousarray(np.concatenate([p[1] for p in flat]))
+        weights = np.ascontiguousarray(np.concatenate([p[2].ravel() for p in flat]))
+        eps = np.ascontiguousarray(np.concatenate([p[3].ravel() for p in flat]))
+        ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).ravel())
+        y_mean = np.ascontiguousarray(np.asarray(y_mean, dtype=np.float64).ravel())
+        y_std = np.ascontiguousarray(np.asarray(y_std, dtype=np.float64).ravel())
+        if ref.shape[0] != 2 or y_mean.shape[0] != 2 or y_std.shape[0] != 2:
+            raise ValueError(f"{who}: ref, y_mean and y_std must hold one value per objective")
+        q = int(q)
+        T, M = G * S, max(int(self.n_candidates), 0)
+        n = max(q, 1)
+        L = _lib.MAX_QNEHVI_FRONT
+        pick_idx = np.empty(n, dtype=np.int64)
+        pick_gain = np.empty(n)
+        values = np.empty((2, T, M)) if return_values and M >= 1 else None
+        base_values = np.empty((2, T, B)) if return_values else None
+        keys = np.empty((q, M)) if return_keys and q >= 1 and M >= 1 else None
+        front_size = np.zeros((2, T), dtype=np.int32) if return_fronts else None
+        fronts = np.empty((2, T, L, 2)) if return_fronts else None
+        self._check(self._lib.gpbo_qnhvi_greedy(self._h, dptr(y_mean), dptr(y_std), G, int(S), int(F), dptr(omega), dptr(phase),
+                                                 dptr(weights), dptr(eps), dptr(ref), dptr(base), B, int(d), q, int(index_offset),
+                                                 iptr(pick_idx), dptr(pick_gain),
+                                                 None if front_size is None else front_size.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 dptr(fronts), dptr(values), dptr(base_values) if B else None, dptr(keys)))
+        return {"index": pick_idx[:q], "gain": pick_gain[:q], "values": values, "base_values": base_values, "keys": keys,
+                "front_size": front_size, "fronts": fronts}
+
+    def debug_qnehvi_fronts(self, base_values, ref, insert_values=None):
+        """gpbo_debug_qnehvi_fronts (debug build): the product's front build on base_values (2, T, n) against ref (2,), then its
+        update rule with insert_values (2, T, n_insert), in order: (front_size (T,) int32, fronts (T, 128, 2))."""
+        self._need_debug("gpbo_debug_qnehvi_fronts")
+        bv = np.ascontiguousarray(np.asarray(base_values, dtype=np.float64))
+        if bv.ndim != 3 or bv.shape[0] != 2:
+            raise ValueError("debug_qnehvi_fronts: base_values must be (2, T, n)")
+        T, n = int(bv.shape[1]), int(bv.shape[2])
+        n_insert = 0
+        iv = None
+        if insert_values is not None:
+            iv = np.ascontiguousarray(np.asarray(insert_values, dtype=np.float64))
+            if iv.ndim != 3 or iv.shape[:2] != (2, T):
+                raise ValueError("debug_qnehvi_fronts: insert_values must be (2, T, n_insert)")
+            n_insert = int(iv.shape[2])
+        ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).ravel())
+        size = np.zeros(max(T, 1), dtype=np.int32)
+        fronts = np.empty((max(T, 1), _lib.MAX_QNEHVI_FRONT, 2))
+        self._check(self._lib.gpbo_debug_qnehvi_fronts(self._h, T, n, dptr(bv) if n else None, dptr(ref), n_insert,
+                                                       dptr(iv) if n_insert else None, size.ctypes.data_as(C.POINTER(C.c_int)),
+                                                       dptr(fronts)))
+        return size[:T], fronts[:T]
+
+    def debug_qnehvi_stage_ms(self):
+        """gpbo_debug_qnehvi_stage_ms (debug build): kernel ms of the last `qnehvi_greedy`'s stages, (draws, front build, greedy
+        steps)."""
+        self._need_debug("gpbo_debug_qnehvi_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gpbo_debug_qnehvi_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
     def debug_ehvi_ms(self):
         """gpbo_debug_ehvi_ms (debug build): kernel ms of the last `ehvi_argbest`'s value kernel (tables and cell sum)."""
         self._need_debug("gpbo_debug_ehvi_ms")
@@ -1537,6 +1633,11 @@ class GroupEngine(GpEngine):
                     return_values=False, return_keys=False):
         raise NotImplementedError("a device group has no batch noisy expected improvement (gpbo_qnei_greedy is per context); "
                                   "use a single device")
+
+    def qnehvi_greedy(self, draws, q, ref, base=None, y_mean=(0.0, 0.0), y_std=(1.0, 1.0), index_offset=0, return_values=False,
+                      return_keys=False, return_fronts=False):
+        raise NotImplementedError("a device group has no batch noisy expected hypervolume improvement (gpbo_qnhvi_greedy is per "
+                                  "context); use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
         raise NotImplementedError("a device group has no posterior refresh path (gpbo_posterior_refresh is per context); "

@@ -16,7 +16,8 @@ evaluated over, the conventions and the order of the sum).
 
 `pareto_front`, `hypervolume` and `box_decomposition` are the host side: plain NumPy, no device.
 
-Out of scope: batches of q > 1 points, constraint weighting, m > 3, noisy-front variants (NEHVI), a local-search stage.
+Out of scope here: constraint weighting, m > 3, a local-search stage.  Batches of q > 1 points and the noisy-front variant (NEHVI)
+are `suggest_qnehvi` (qnehvi.py) for m = 2; for m = 3 they are out of scope too.
 """
 from __future__ import annotations
 
@@ -139,8 +140,8 @@ class ParetoOptimizer:
     (`random_state`) shared by the theta searches and the candidate draws.  `flags`: `matern_family` / `scaled_kernels` /
     `scaled_lanes` / `precision`, passed to every HipGPR.
 
-    Out of scope: batches of q > 1 points, constraint weighting, m > 3, noisy-front variants (NEHVI), a local-search stage — the
-    pick is among the candidates."""
+    Out of scope: constraint weighting, m > 3, a local-search stage — the pick is among the candidates.  Batches of q > 1 points
+    and the noisy-front variant (NEHVI): `suggest_qnehvi(self, q)` for m = 2, out of scope for m = 3."""
 
     _FLAGS = ("matern_family", "scaled_kernels", "scaled_lanes", "precision")
 
@@ -243,7 +244,8 @@ class ParetoOptimizer:
         Nothing else draws from the RandomState.  `return_info=True`: (params, info), info = {"value": the pick's EHVI, "index": its
         candidate index, "n_cells": K, "front_size": the front's size}.
 
-        Out of scope: q > 1, constraint weighting, m > 3, NEHVI, a local-search stage (the pick is AMONG THE CANDIDATES)."""
+        Out of scope: constraint weighting, m > 3, a local-search stage (the pick is AMONG THE CANDIDATES); q > 1 and NEHVI are
+        `suggest_qnehvi` for m = 2."""
         from sklearn.base import clone
 
         from . import fused_acquisition as A

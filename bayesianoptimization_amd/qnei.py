@@ -98,14 +98,8 @@ def suggest_qnei(optimizer, q: int, n_random: int = 10_000, n_draws: int = 64, n
 
     model = S.fit_model(gp, space, "suggest_qnei")
     eng.generate_candidates_like(n_random, space.bounds[:, 0], space.bounds[:, 1], rng)
-    from .thompson import spectral_draw
-
     G, n_paths = draw_layout(n_draws)
-    groups = []
-    for _ in range(G):
-        omega, phase = spectral_draw(gp._kind, n_features, model.d, rng)
-        weights = rng.standard_normal((n_paths, n_features))
-        groups.append((omega, phase, weights, rng.standard_normal((n_paths, model.N)) * np.sqrt(model.noise)))
+    groups = S.group_inputs(gp, rng, model, G, n_paths, n_features)
     gp._ensure_resident()
     index, gain, baseline, _values, _keys = eng.qnei_greedy(groups, q, noisy=bool(noisy), y_best=float(np.max(space.target)),
                                                             pending=pending, slot=gp.slot, y_mean=model.y_mean, y_std=model.y_std)

@@ -640,6 +640,72 @@ int gpbo_qnei_greedy(gpbo_ctx* ctx, int slot, double y_mean, double y_std,
                      int64_t* pick_idx, double* pick_gain, double* baseline_out,
                      double* values_out, double* keys_out);
 
+/* Batch noisy expected hypervolume improvement for m = 2 objectives, built greedily over the resident candidates from joint
+ * posterior draws (qNEHVI: Daulton, Balandat & Bakshy 2021, "Parallel Bayesian optimization of multiple noisy objectives with
+ * expected hypervolume improvement", in its greedy, cached-draws form).  Every draw carries a Pareto front of its own — the draw's
+ * values at the observed and the pending points, not the noisy readings —, a candidate is worth the mean over the draws of the
+ * hypervolume it adds to the draw's front, and after a pick every draw's front absorbs the draw's values there: the next pick is
+ * scored jointly with the earlier ones, no observation is made up, nothing is refitted.  m = 3 is not served (and not approximated).
+ * Objectives and draws.  Objective j is slot j, j = 0, 1; both are MAXIMISED, raw target units; y_mean / y_std (2,) per objective.
+ * Both slots are fitted with the candidates' d; N, kernel kind, length scales, scale and precision may differ.  T = G S draws per
+ * objective, G = n_groups <= GPBO_MAX_QNEI_GROUPS, S = n_paths <= GPBO_MAX_PATHS, F = n_features.  The per-slot inputs of
+ * gpbo_qnei_greedy are concatenated in slot order: omega (2, G, F, d), phase (2, G, F), weights (2, G, S, F), eps = slot 0's
+ * (G, S, N_0) block, then slot 1's (G, S, N_1).  Draw t = g S + s of objective j is gpbo_sample_paths' f_s for slot j and group g's
+ * inputs, the same bits (the same kernels write a resident (2, T, M) block); draw t of objective 0 and draw t of objective 1 are
+ * joint draw t (independent posteriors, as in gpbo_ehvi_argbest).
+ * Fronts.  base (n_base, d; host, parameter space): the observed points, then the pending ones; n_base = 0 with NULL is allowed.
+ * Each slot scales it by its own length scales on the device; b_t,i = (f0_t(base_i), f1_t(base_i)) by the evaluator the candidates
+ * get.  ref (2,) finite.  The front P_t of draw t: the DISTINCT b_t,i strictly above ref in both objectives, without a NaN, that no
+ * other such point dominates (>= in both, > in one); stored by objective 0 DESCENDING, so objective 1 strictly ascends:
+ * (a_1, c_1) ... (a_n, c_n).  With a_0 = +inf, a_{n+1} = ref_0, c_0 = ref_1, strip k = 0 .. n is (a_{k+1}, a_k] x (c_k, +inf).
+ * The greedy steps j = 0 .. q - 1, for candidate x with (f0, f1) = joint draw t at x:
+ *   w_k      = min(f0, a_k) - a_{k+1}   where that is > 0, else 0
+ *   h_k      = f1 - c_k                 where that is > 0, else 0
+ *   HVI_t(x) = w_0 h_0 + w_1 h_1 + ... + w_n h_n        k ascending into one accumulator from 0, one rounded product per term, NO
+ *              fused multiply-add;  NaN if f0 or f1 is NaN
+ *   key_j(x) = -((HVI_0 + ... + HVI_{T-1}) / T)         t ascending into one accumulator from 0, ONE true division;
+ *              +inf for a candidate picked in an earlier step
+ * Every term is >= +0.  An infinite draw value is outside the contract.  The pick is gpbo_acq_argbest's on key_j: the first NaN
+ * wins, else the least key, ties to the lowest index.  pick_idx[j] = its index + index_offset, pick_gain[j] = -key_j there (NaN for
+ * a NaN pick).  A candidate's key bits depend neither on M, nor on the launch geometry, nor on the other candidates.
+ * Update.  After a pick every draw's front absorbs y = (f0_t(pick), f1_t(pick)): P_t is unchanged if y has a NaN, is not strictly
+ * above ref in both objectives, or is dominated by or equal to a point of P_t; otherwise the points y dominates leave and y enters
+ * in its sorted place.
+ * Overflow.  A front of more than GPBO_MAX_QNEHVI_FRONT points, at the build or after an insertion, sets a device flag; the call
+ * then returns GPBO_ERR_UNSUPPORTED behind its one synchronisation, the message names the (lowest such) draw, the outputs are
+ * unspecified, the context stays usable.  A front is never thinned.
+ * Outputs.  front_size_out (2, T) ints and fronts_out (2, T, GPBO_MAX_QNEHVI_FRONT, 2), either may be NULL: block [0] before the
+ * first pick, block [1] after the last; rows past a front's size are unspecified.  values_out (2, T, M) or NULL; base_values_out
+ * (2, T, n_base) or NULL; keys_out (q, M) or NULL (a debugging aid: one copy per step).
+ * On the device: per slot the candidates' and the base points' scaling, per group one launch_path_weights and passes of
+ * path_eval_kernel over both; qnehvi_front_kernel (a workgroup per draw) builds P_t point by point from the right, each point the
+ * lexicographic maximum of the pairs above the last point's objective 1; per step qnehvi_score_kernel (thread = candidate(s), a
+ * stream of the 16 T M bytes of the block, the fronts staged in LDS as strips (a_{k+1}, c_k), 16 draws at a time, and read back as
+ * wave-wide broadcasts) writes key_j as the context's acquisition values, the selection picks, and qnehvi_update_kernel reads the
+ * pick from the selection's device record, files {gain, index}, marks the mask and applies the update rule per draw.  All q steps
+ * are enqueued on the context's stream; everything crosses behind ONE synchronisation.  fp64 whatever the slots' precision.
+ * Workspace: the context's own, 16 T M bytes for the block (4 GiB at T = 256 and M = 2^20) + 16 T n_base + 4 KiB per draw for the
+ * fronts + O(M / 8 + n_base d) bytes; grown on demand and kept; an allocation that fails is GPBO_ERR_HIP.
+ * A reader, as gpbo_sample_paths: the fits, the resident mu / sd, what gpbo_posterior_refresh may still refresh, the candidates
+ * and the negative-variance flag stay as they were; the context's acquisition values are overwritten.
+ * GPBO_ERR_INVALID: n_groups outside [1, GPBO_MAX_QNEI_GROUPS]; n_paths outside [1, GPBO_MAX_PATHS] or n_features outside
+ * [1, GPBO_MAX_PATH_FEATURES]; a NULL y_mean / y_std / omega / phase / weights / eps / ref / pick_idx / pick_gain; a y_std not finite
+ * or not positive, a y_mean or ref not finite; n_base outside [0, GPBO_MAX_QNEHVI_BASE], n_base > 0 with a NULL or non-finite base;
+ * d not the slots'; q outside [1, GPBO_MAX_SEEDS], q > M.  GPBO_ERR_STATE: slot 0 or 1 unfitted or with a fit pending, no resident
+ * candidates, candidates or a slot of another d.  There is no gpbo_group_* / gpbo_comm_* form.
+ * (The symbol is spelled qnhvi — q, noisy, hypervolume improvement —: a product symbol that contains "ehvi" would read as a second
+ * form of gpbo_ehvi_argbest, which has none.  The limits, the debug entry points and the Python names keep the usual "qnehvi".) */
+#define GPBO_MAX_QNEHVI_FRONT 128      /* points of one draw's front */
+#define GPBO_MAX_QNEHVI_BASE  16384    /* observed + pending points */
+int gpbo_qnhvi_greedy(gpbo_ctx* ctx, const double* y_mean, const double* y_std,
+                       int n_groups, int n_paths, int n_features,
+                       const double* omega, const double* phase, const double* weights, const double* eps,
+                       const double* ref, const double* base, int n_base, int d,
+                       int q, int64_t index_offset,
+                       int64_t* pick_idx, double* pick_gain,
+                       int* front_size_out, double* fronts_out,
+                       double* values_out, double* base_values_out, double* keys_out);
+
 /* ---- timing (HIP events on the context stream) ------------------------------------------ */
 /* Milliseconds spent in the last call's kernels: [0] fit total, [1] posterior main kernel,
  * [2] posterior finalize, [3] acquisition + arg-best, [4] kmat assembly, [5] cholesky, [6] trtri. */
@@ -840,6 +906,17 @@ int gpbo_debug_ehvi_ms(gpbo_ctx* ctx, float* ms);
  * baselines —, ms[1] the q greedy steps (score, selection, update; with keys_out their copies too).  The fetch of the results and
  * the synchronise are in neither. */
 int gpbo_debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms);
+/* Kernel milliseconds (HIP events) of the three stages of the context's last gpbo_qnhvi_greedy: ms[0] the draws — the scalings, per
+ * slot and group the path weights and the passes over candidates and base points —, ms[1] the front build, ms[2] the q greedy steps
+ * (score, selection, update; with keys_out their copies too).  The fetch of the results and the synchronise are in none. */
+int gpbo_debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms);
+/* gpbo_qnhvi_greedy's front build and update rule alone, on host-given values: qnehvi_front_kernel on base_values (2, n_draws, n)
+ * — objective-major, as base_values_out — against ref (2,), then the update rule n_insert times per draw, in order, with
+ * insert_values (2, n_draws, n_insert).  front_size_out (n_draws,), fronts_out (n_draws, GPBO_MAX_QNEHVI_FRONT, 2).  n_draws in
+ * [1, 4096], n in [0, GPBO_MAX_QNEHVI_BASE], n_insert in [0, 4096] (a NULL array with a count of 0 is allowed).  A front that outgrows
+ * GPBO_MAX_QNEHVI_FRONT is GPBO_ERR_UNSUPPORTED, as in the main call; the context stays usable.  Touches no model slot. */
+int gpbo_debug_qnehvi_fronts(gpbo_ctx* ctx, int n_draws, int n, const double* base_values, const double* ref, int n_insert,
+                             const double* insert_values, int* front_size_out, double* fronts_out);
 #endif /* GPBO_DEBUG */
 
 #ifdef __cplusplus
