@@ -25,7 +25,28 @@ the 1e-8 / exact arg-best of the acquisition, _same_or_better of test_gpu_polish
 Routes: the int8 GEMM (PostPath::SlabI8) is established as test_gpu_int8_posterior.py does — the debug build's default pass is
 bitwise its GPBO_POST_KERNEL=8 pass (and not its =3 pass); N = 300 is NP = 320 > SEARCH_LDS_NP = 128: SearchMode::WInMemory
 (search_plan.h; tests/test_search_plan_host.py pins the rule), N = 100 is NP = 128: WInLds; N = 800 is NP = 832 > 768:
-FitTier::Blocked, the graph-eligible tier (fit_plan.h)."""
+FitTier::Blocked, the graph-eligible tier (fit_plan.h).
+
+The sampling, batch and Pareto entry points (gpbo_sample_paths, gpbo_sample_paths_constrained, gpbo_ascend_paths, gpbo_mes_argbest,
+gpbo_kg_argbest, gpbo_ehvi_argbest, gpbo_qnei_greedy, gpbo_qnhvi_greedy, gpbo_generate_candidates_trust_region) are held to the same
+contract, against each other, by tests/test_gpu_call_order_sampling.py, which imports Step, W, R, replay and replay_fresh from here.
+The per-context state they share with each other and with gpbo_acq_argbest:
+  ctx->ys            [M] acquisition values for acq_argbest, mes, kg, ehvi and for the qnei / qnehvi keys; [S][M] negated path values
+                     for sample_paths; launch_values_argbest selects over the values ALREADY in it;
+  ctx->Xcs           re-scaled with ONE slot's length scales by posterior, posterior_refresh, kg, sample_paths, qnei and qnehvi
+                     (qnehvi leaves slot 1's scaling behind);
+  ctx->red           the selection's SelState | picks | partial | nan_partial, AND the trust-region generator's Sobol tables, the
+                     MT19937 key, the mixed-space flags and the fit scalars; enqueue_select and the generators call `ensure`, which
+                     frees and reallocates when a later call needs more; qnei_update_kernel and qnehvi_update_kernel take SelState*
+                     and Key* pointers into it at launch time;
+  pinned_aux + PIN_AUX_SEL_OUT   fetch_selection, launch_topk_rows and the qnei / qnehvi pick records cross in this one window;
+  the six workspaces ctx->paths, cpaths, kg, ehvi, qnei, qnehvi: each grown by `ensure` (free, then malloc), laid out by T, M, B, d, q;
+  func_attrs         ATTR_KG and ATTR_EHVI are per-context, first-use settings;
+  the per-slot posterior   M_post, refreshable, M_refresh, N_post, ystd_post: between fit_append and posterior_refresh it is stale
+                     but refreshable, which is where a batch loop sits between two picks.
+
+SCENARIOS lists, per scenario of this file, the library functions it runs as readers; tests/test_call_order_cover_host.py holds the
+two files' lists against include/gpbo.h, so that a new entry point cannot stay outside the contract."""
 import os
 
 import numpy as np
@@ -48,6 +69,22 @@ UNFITTED = (_lib.GpboError, r"has not been fitted|is not fitted|run gpbo_posteri
 
 #: worst error / bar per final state, written as JSON to the file GPBO_CALL_ORDER_REPORT names (if set) at the end of the module
 WORST = {}
+
+
+#: the library functions each scenario below runs as readers (module level, no engine call: the CPU cover test imports it)
+SCENARIOS = {
+    "A: the int8 digit planes of W": ("gpbo_posterior", "gpbo_lml_batch", "gpbo_get_L", "gpbo_get_K", "gpbo_get_Linv", "gpbo_get_alpha",
+                                      "gpbo_predict_grad", "gpbo_acq_argbest"),
+    "B: precision and size switches": ("gpbo_posterior",),
+    "C: W^T in the K buffer": ("gpbo_polish_seeds", "gpbo_evolve_mixed", "gpbo_get_K", "gpbo_predict_cov", "gpbo_predict_grad",
+                               "gpbo_lml_batch"),
+    "D: unfitted means unfitted": ("gpbo_posterior", "gpbo_predict", "gpbo_predict_grad", "gpbo_predict_cov", "gpbo_polish_seeds",
+                                   "gpbo_acq_argbest", "gpbo_get_L"),
+    "E: candidates versus M_post": ("gpbo_posterior", "gpbo_acq_argbest", "gpbo_get_candidate_rows"),
+    "F: the graph pool of gpbo_lml_batch": ("gpbo_lml_batch",),
+    "G: the negative-variance flag": ("gpbo_take_negative_variance_flag", "gpbo_posterior", "gpbo_predict", "gpbo_predict_grad",
+                                      "gpbo_predict_cov", "gpbo_polish_seeds", "gpbo_get_K", "gpbo_lml_batch", "gpbo_acq_argbest"),
+}
 
 
 def record(state, ratio):

@@ -24,6 +24,7 @@ import pytest
 import matern_family_truth as F
 import scaled_kernel_truth as SK
 import test_gpu_sizes as S
+from bayesianoptimization_amd import sobol_tables
 from bayesianoptimization_amd._lib import GpboError
 from bayesianoptimization_amd.engine import F32
 from conftest import rel_err
@@ -275,6 +276,10 @@ def test_never_stale(engine):
     def generate_mt():
         eng.generate_candidates_like(1600, lo, hi, np.random.RandomState(4))
 
+    def generate_trust_region():
+        sv, shift = sobol_tables(d, 3)
+        eng.generate_candidates_trust_region(1300, np.full(d, 0.4), lo, hi, sv, shift, 30, 2 ** 31, 0x1234567_89ABCDEF)
+
     def generate_columns_and_transform():
         eng.generate_candidates_mixed(1400, [(0, 0, d, lo, hi, None)], np.random.RandomState(5))
         eng.transform_candidates(groups)
@@ -298,7 +303,7 @@ def test_never_stale(engine):
                          maxiter=2)
 
     for writer in (refit, fit_begin, fit_scaled, lml_then_fit, set_candidates, generate_philox, generate_mt,
-                   generate_columns_and_transform, predict, predict_cov, predict_grad, polish_seeds, evolve_mixed):
+                   generate_trust_region, generate_columns_and_transform, predict, predict_cov, predict_grad, polish_seeds, evolve_mixed):
         eligible()
         writer()
         _full_pass_expected(eng, ym, ys, writer.__name__)
