@@ -10,7 +10,8 @@ __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate
            "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement", "suggest_thompson",
            "suggest_mes", "suggest_kg", "suggest_turbo", "TrustRegion", "sobol_tables",
            "suggest_constrained_thompson", "suggest_scbo", "ConstrainedTrustRegion",
-           "ParetoOptimizer", "pareto_front", "hypervolume", "box_decomposition", "suggest_qnei", "suggest_qnehvi"]
+           "ParetoOptimizer", "pareto_front", "hypervolume", "box_decomposition", "suggest_qnei", "suggest_qnehvi",
+           "suggest_constrained_qnei"]
 
 
 def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must not need sklearn/scipy
@@ -53,6 +54,9 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name == "suggest_qnei":
         from .qnei import suggest_qnei
         return suggest_qnei
+    if name == "suggest_constrained_qnei":
+        from .cqnei import suggest_constrained_qnei
+        return suggest_constrained_qnei
     if name == "suggest_qnehvi":
         from .qnehvi import suggest_qnehvi
         return suggest_qnehvi

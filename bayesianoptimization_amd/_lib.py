@@ -31,6 +31,7 @@ MAX_QNEI_GROUPS = 16
 MAX_QNEI_POINTS = 64
 MAX_QNEHVI_FRONT = 128
 MAX_QNEHVI_BASE = 16384
+MAX_CNEI_BASE = 16384
 ABI_VERSION = 4
 
 _c_double_p = C.POINTER(C.c_double)
@@ -116,6 +117,10 @@ SIGNATURES = {
     "gpbo_qnhvi_greedy": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int, _c_double_p, _c_double_p,
                                      _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int, C.c_int64,
                                      _c_int64_p, _c_double_p, _c_int_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpbo_cnei_greedy": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int,
+                                   _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_double, _c_double_p, C.c_int, C.c_int,
+                                   C.c_int, C.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                   _c_double_p, _c_double_p]),
     "gpbo_last_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
     "gpbo_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "gpbo_comm_unique_id": (C.c_int, [C.c_char_p]),
@@ -175,6 +180,7 @@ DEBUG_SIGNATURES = {
     "gpbo_debug_kg_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "gpbo_debug_qnei_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "gpbo_debug_qnehvi_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "gpbo_debug_cnei_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "gpbo_debug_qnehvi_fronts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_int_p,
                                            _c_double_p]),
     "gpbo_debug_generate_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),

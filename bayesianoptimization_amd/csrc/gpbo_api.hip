@@ -224,6 +224,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->qnei_ev) if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : ctx->cnei_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->qnehvi_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -235,7 +236,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->qnei, ctx->qnehvi, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->qnei, ctx->cnei, ctx->qnehvi, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1630,6 +1631,45 @@ int gpbo_qnhvi_greedy(gpbo_ctx* ctx, const double* y_mean, const double* y_std, 
                               keys_out);
 }
 
+int gpbo_cnei_greedy(gpbo_ctx* ctx, int n_constraints, const double* y_mean, const double* y_std, const double* lb, const double* ub,
+                     int n_groups, int n_paths, int n_features, const double* omega, const double* phase, const double* weights,
+                     const double* eps, double y_floor, const double* base, int n_base, int d, int q, int64_t index_offset,
+                     int64_t* pick_idx, double* pick_gain, double* pick_feasible, double* baseline_out, double* values_out,
+                     double* viol_out, double* base_values_out, double* keys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const char* who = "cnei_greedy";
+  const std::string w = std::string(who) + ": ";
+  const int C = n_constraints;
+  if (C < 1 || C > GPBO_MAX_MODELS - 1) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_constraints out of range [1, 7]");
+  if (n_groups < 1 || n_groups > GPBO_MAX_QNEI_GROUPS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups out of range [1, 16]");
+  // the counts first, as check_path_args orders them
+  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_paths out of range [1, 16]");
+  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_features out of range [1, 4096]");
+  if (!y_mean || !y_std || !lb || !ub || !omega || !phase || !weights || !eps || !pick_idx || !pick_gain || !pick_feasible || !baseline_out)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL argument");
+  int rc;
+  const Model* ms[GPBO_MAX_MODELS];
+  for (int j = 0; j <= C; ++j)
+    if ((rc = check_path_args(ctx, who, j, y_mean[j], y_std[j], n_paths, n_features, 1, nullptr, &ms[j]))) return rc;
+  for (int j = 0; j < C; ++j)
+    if (lb[j] != lb[j] || ub[j] != ub[j] || !(lb[j] < ub[j]))
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "the bounds must not be NaN, with lb < ub for every constraint");
+  if (!std::isfinite(y_floor)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "y_floor must be finite");
+  if (n_base < 0 || n_base > GPBO_MAX_CNEI_BASE) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_base out of range [0, 16384]");
+  if (n_base > 0 && !base) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL base with n_base > 0");
+  if (d != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "d differs from the fitted models'");
+  for (int64_t i = 0; i < (int64_t)n_base * d; ++i)
+    if (!std::isfinite(base[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "base must be finite");
+  if (q < 1 || q > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q out of range [1, 64]");
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates)");
+  for (int j = 0; j <= C; ++j)
+    if (ctx->d_c != ms[j]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from a fitted model's");
+  if (q > ctx->M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q exceeds the number of resident candidates");
+  return launch_cnei_greedy(ctx, C, ms, ctx->M, y_mean, y_std, lb, ub, n_groups, n_paths, n_features, omega, phase, weights, eps,
+                            y_floor, base, n_base, q, index_offset, pick_idx, pick_gain, pick_feasible, baseline_out, values_out,
+                            viol_out, base_values_out, keys_out);
+}
+
 int gpbo_set_timing(gpbo_ctx* ctx, int on) {
   if (!ctx) return GPBO_ERR_INVALID;
   ctx->timing_off = !on;
@@ -1797,6 +1837,13 @@ int gpbo_debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_qnei_stage_ms: NULL output");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
   return debug_qnei_stage_ms(ctx, ms);
+}
+
+int gpbo_debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_cnei_stage_ms: NULL output");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  return debug_cnei_stage_ms(ctx, ms);
 }
 
 int gpbo_debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms) {

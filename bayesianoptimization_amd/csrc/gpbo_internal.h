@@ -17,6 +17,7 @@
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
 #include "path_plan.h"        // the posterior function draws' workspace layout and dispatch rules
+#include "cnei_plan.h"        // gpbo_cnei_greedy's workspace layout
 #include "qnei_plan.h"        // gpbo_qnei_greedy's workspace layout and the score kernel's thread / candidate rule
 
 namespace gpbo {
@@ -177,12 +178,16 @@ struct gpbo_ctx {
   int64_t cap_qnei = 0;
   double* qnehvi = nullptr;  // gpbo_qnhvi_greedy: both objectives' draws (2, T, M), their values at the base points, the fronts, mask and records (qnehvi_plan.h)
   int64_t cap_qnehvi = 0;
+  double* cnei = nullptr;  // gpbo_cnei_greedy: the masked objective draws (T, M), their incumbents, one group's violations, the base points, mask and records (cnei_plan.h)
+  int64_t cap_cnei = 0;
   hipEvent_t kg_ev[4] = {};   // debug build: around the three stages of the last gpbo_kg_argbest (the fields exist in both builds: one layout)
   bool kg_ev_used = false;
   hipEvent_t gen_ev[2] = {};  // debug build: around the kernel of the last gpbo_generate_candidates / _trust_region (generate_mark)
   bool gen_ev_used = false;
   hipEvent_t qnei_ev[3] = {}; // debug build: before the draws, between the baselines and the greedy steps, behind the last step of the last gpbo_qnei_greedy
   bool qnei_ev_used = false;
+  hipEvent_t cnei_ev[3] = {}; // debug build: the same three events of the last gpbo_cnei_greedy
+  bool cnei_ev_used = false;
   hipEvent_t qnehvi_ev[4] = {}; // debug build: before the draws, behind them, behind the front build, behind the last step of the last gpbo_qnhvi_greedy
   bool qnehvi_ev_used = false;
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
@@ -272,6 +277,7 @@ constexpr size_t PIN_AUX_SEL_OUT_BYTES = 32 + 16 * (GPBO_MAX_SEEDS + 1);
 constexpr size_t PIN_AUX_CAND = 2048;                                // [lo | hi (or hi - lo)][GPBO_MAX_DIM] doubles | MT19937 key[624]
 constexpr size_t PIN_AUX_CAND_BYTES = 2 * GPBO_MAX_DIM * sizeof(double) + 624 * sizeof(uint32_t);
 static_assert(PIN_AUX_SEL_OUT + PIN_AUX_SEL_OUT_BYTES <= PIN_AUX_CAND, "selection results overlap the candidate staging");
+constexpr size_t PIN_AUX_SEL_ROOM = PIN_AUX_CAND - PIN_AUX_SEL_OUT;      // all there is from the selection's window up to the candidate staging (gpbo_cnei_greedy's 24-byte pick records take it)
 constexpr size_t PIN_AUX_NEGVAR = 8192;                              // int: a finalize kernel clipped a NEGATIVE variance (_gpr.py:479-485)
 static_assert(PIN_AUX_CAND + PIN_AUX_CAND_BYTES <= PIN_AUX_NEGVAR, "candidate staging overlaps the clipped-variance flag");
 static_assert(PIN_AUX_NEGVAR + sizeof(int) <= PIN_WINDOW, "clipped-variance flag leaves the window");
@@ -627,6 +633,9 @@ int launch_paths_at(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, doub
 // ... the workspace's draws at n points of the caller's (P [>= n][DP], scaled, on the device): out[s * ld + r] = f_s(P_r), the plain store
 int launch_paths_over(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, double y_mean, double y_std, int n_paths, int n_features,
                       const double* P, int64_t n, double* out, int64_t ld);
+// ... the same with an epilogue (PathFold) behind the accumulators instead of the plain store; fold.viol / fold.vals have out's ld
+int launch_paths_over_fold(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, double y_mean, double y_std, int n_paths,
+                           int n_features, const double* P, int64_t n, double* out, int64_t ld, const PathFold& fold);
 // ... and the first half of it alone: the draws' inputs and V = alpha - W^T (W (g(X) + eps)) made resident, no candidates needed
 int launch_path_weights(gpbo_ctx* ctx, const Model& m, int n_paths, int n_features, const double* omega, const double* phase,
                         const double* weights, const double* eps, int n_runs, PathWorkspace* ws);
@@ -685,6 +694,13 @@ int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, 
                        const double* omega, const double* phase, const double* weights, const double* eps, int noisy, double y_best,
                        const double* pending, int n_pending, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain,
                        double* baseline_out, double* values_out, double* keys_out);
+// qnei.hip: gpbo_cnei_greedy behind its argument checks (include/gpbo.h has the rule; cnei_plan.h the workspace, ctx->cnei): ms /
+// y_mean / y_std per slot 0 .. C, lb / ub per constraint, the draws' inputs concatenated slot-major, then group-major
+int launch_cnei_greedy(gpbo_ctx* ctx, int n_constraints, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std,
+                       const double* lb, const double* ub, int n_groups, int n_paths, int n_features, const double* omega,
+                       const double* phase, const double* weights, const double* eps, double y_floor, const double* base, int n_base,
+                       int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain, double* pick_feasible, double* baseline_out,
+                       double* values_out, double* viol_out, double* base_values_out, double* keys_out);
 // qnehvi.hip: gpbo_qnhvi_greedy behind its argument checks (include/gpbo.h has the formulas; qnehvi_plan.h the workspace,
 // ctx->qnehvi): ms / y_mean / y_std per objective, the draws' inputs concatenated in slot order
 int launch_qnehvi_greedy(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std, int n_groups,
@@ -694,6 +710,7 @@ int launch_qnehvi_greedy(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const
                          double* base_values_out, double* keys_out);
 #ifdef GPBO_DEBUG
 int debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms2);
+int debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms2);
 int debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms3);
 int debug_qnehvi_fronts(gpbo_ctx* ctx, int T, int n, const double* base_values, const double* ref, int n_insert,
                         const double* insert_values, int* front_size_out, double* fronts_out);

@@ -57,8 +57,9 @@ inline PathBlock path_block(int S_, int F_, int N_, int NP_, int d_, int n_runs)
 
 // gpbo_sample_paths_constrained: what path_eval_kernel does with a point's S values behind its accumulators.  PLAIN stores them
 // (gpbo_sample_paths); a constraint slot folds its violation terms into viol[S][M] — the first one writes, the later ones add, so
-// the sum's order is the slots' —; the objective reads viol and stores the selection key.
-enum PathEpilogue : int { PATH_PLAIN = 0, PATH_VIOL_WRITE = 1, PATH_VIOL_ADD = 2, PATH_KEY = 3 };
+// the sum's order is the slots' —; the objective reads viol and stores the selection key.  PATH_MASKED (gpbo_cnei_greedy's objective
+// pass) reads viol as PATH_KEY does and stores the masked VALUE: f where the point is feasible, -inf where it is not, NaN kept.
+enum PathEpilogue : int { PATH_PLAIN = 0, PATH_VIOL_WRITE = 1, PATH_VIOL_ADD = 2, PATH_KEY = 3, PATH_MASKED = 4 };
 inline int path_epilogue(int slot) { return slot == 0 ? PATH_KEY : (slot == 1 ? PATH_VIOL_WRITE : PATH_VIOL_ADD); }
 
 // Its own workspace (ctx->cpaths), offsets in doubles from its start:

@@ -147,6 +147,10 @@ __global__ __launch_bounds__(256) void path_eval_kernel(const PathEvalArgs a) {
         // the selection takes the first NaN, else the least key: -f where the constraint draws call the point feasible, +inf elsewhere
         const double v = a.viol[at];
         a.out[at] = (f != f || v != v) ? __builtin_nan("") : (v == 0.0 ? -f : __builtin_inf());
+      } else if (a.epilogue == PATH_MASKED) {
+        // the value a greedy step scores (gpbo_cnei_greedy): f itself where the point is feasible, -inf elsewhere
+        const double v = a.viol[at];
+        a.out[at] = (f != f || v != v) ? __builtin_nan("") : (v == 0.0 ? f : -__builtin_inf());
       } else {
         // t = max(max(lb - c, c - ub), 0) / y_std, a NaN c kept (fmax would drop it)
         const double g = fmax(a.lb - f, f - a.ub);
@@ -307,6 +311,17 @@ int launch_paths_over(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, do
                       const double* P, int64_t n, double* f, int64_t ld) {
   PathEvalArgs a = path_eval_args(m, ws, S, F);
   a.P = P; a.out = f; a.M = n; a.ld = ld; a.N = (int)m.N; a.negate = 0; a.y_mean = y_mean; a.y_std = y_std;
+  return launch_path_eval(ctx, m, a);
+}
+
+// ... with an epilogue behind the accumulators (path_plan.h: PathEpilogue) instead of the plain store: a constraint slot's terms
+// into fold.viol [S][ld] (f is not written and may be null), the objective's key or masked value into f.  fold.viol and fold.vals
+// have f's leading dimension.  The values are launch_paths_over's, bit for bit.
+int launch_paths_over_fold(gpbo_ctx* ctx, const Model& m, const PathWorkspace& ws, double y_mean, double y_std, int S, int F,
+                           const double* P, int64_t n, double* f, int64_t ld, const PathFold& fold) {
+  PathEvalArgs a = path_eval_args(m, ws, S, F);
+  a.P = P; a.out = f; a.M = n; a.ld = ld; a.N = (int)m.N; a.negate = 0; a.y_mean = y_mean; a.y_std = y_std;
+  a.epilogue = fold.epilogue; a.lb = fold.lb; a.ub = fold.ub; a.viol = fold.viol; a.vals = fold.vals;
   return launch_path_eval(ctx, m, a);
 }
 

@@ -13,6 +13,13 @@
 //                          NaN wins, as best_of_selection has it), files {gain, index}, marks the mask, and folds column `pick` of
 //                          the block into the m_t
 // No multiply-add in any of them (the file is compiled with -ffp-contract=off as well): tests replay the keys bit for bit.
+//
+// gpbo_cnei_greedy (the constrained form; cnei_plan.h has its workspace) lives here too, because it runs the same kernels — a kernel
+// cannot be launched from another translation unit.  Its block holds the MASKED objective draws (path_plan.h: PATH_MASKED: -inf where
+// the constraint draws call a point infeasible), which the baseline and the score kernel take as they are: -inf - m_t is not > 0
+// and fmax(m_t, -inf) = m_t.  New for it:
+//   cnei_update_kernel     qnei_update_kernel's work (the one device function both call) plus the share of draws that call the
+//                          pick feasible, in a record {gain, index, feasible} of its own
 #include "gpbo_internal.h"
 
 #include <cmath>
@@ -23,6 +30,9 @@ namespace gpbo {
 struct QneiRecord { double gain; int64_t idx; };
 static_assert(sizeof(QneiRecord) == 16, "a record is two doubles of the workspace");
 static_assert(sizeof(QneiRecord) * GPBO_MAX_SEEDS <= PIN_AUX_SEL_OUT_BYTES, "the picks' records outgrew the selection's pinned window");
+struct CneiRecord { double gain; int64_t idx; double feasible; };      // gpbo_cnei_greedy's
+static_assert(sizeof(CneiRecord) == 24, "a record is three doubles of the workspace");
+static_assert(sizeof(CneiRecord) * GPBO_MAX_SEEDS <= PIN_AUX_SEL_ROOM, "the picks' records outgrew the room behind the selection's pinned window");
 
 // m[t] = m0[t] = fmax fold of (y_best unless noisy) and base[t][c0 .. ldb): lane l takes c0 + l, c0 + l + 64, ..., the 64 partial
 // maxima meet in a butterfly.  fmax drops a NaN operand and orders numbers totally up to a zero's sign, so the fold's value is the
@@ -79,45 +89,108 @@ __global__ __launch_bounds__(QNEI_BLOCK) void qnei_score_kernel(const double* __
   }
 }
 
-// Behind step j's selection: the pick (the first NaN wins, else the selection's first pick), its record, the mask, the incumbents.
+// Behind step j's selection, for both update kernels: the pick (the first NaN wins, else the selection's first pick), the mask, the
+// incumbents.  Hands back the record's gain and index, and the pick's local index — -1 where it touches nothing.
+__device__ __forceinline__ int64_t qnei_absorb_pick(const SelState* __restrict__ st, const Key* __restrict__ first,
+                                                    const double* __restrict__ vals, int64_t M, int T, int64_t offset,
+                                                    double* __restrict__ m, uint8_t* __restrict__ mask, bool* nan_out, double* gain,
+                                                    int64_t* idx) {
+  const bool nan = st->first_nan != INT64_MAX;
+  const int64_t pick = nan ? st->first_nan : first->i;
+  const bool valid = pick >= 0 && pick < M;      // (always, with q <= M: a pick outside the candidates touches nothing)
+  *nan_out = nan;
+  *gain = (nan || !valid) ? std::numeric_limits<double>::quiet_NaN() : -first->v;
+  *idx = valid ? pick + offset : -1;
+  if (!valid) return -1;
+  if (threadIdx.x == 0) mask[pick] = 1;
+  for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) m[t] = fmax(m[t], vals[(int64_t)t * M + pick]);
+  return pick;
+}
+
 __global__ __launch_bounds__(QNEI_BLOCK) void qnei_update_kernel(const SelState* __restrict__ st, const Key* __restrict__ first,
                                                                  const double* __restrict__ vals, int64_t M, int T, int64_t offset, int j,
                                                                  double* __restrict__ m, uint8_t* __restrict__ mask,
                                                                  QneiRecord* __restrict__ rec) {
-  const bool nan = st->first_nan != INT64_MAX;
-  const int64_t pick = nan ? st->first_nan : first->i;
-  const bool valid = pick >= 0 && pick < M;      // (always, with q <= M: a pick outside the candidates touches nothing)
-  if (threadIdx.x == 0) {
-    QneiRecord r;
-    r.gain = (nan || !valid) ? std::numeric_limits<double>::quiet_NaN() : -first->v;
-    r.idx = valid ? pick + offset : -1;
-    rec[j] = r;
-    if (valid) mask[pick] = 1;
-  }
-  if (!valid) return;
-  for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) m[t] = fmax(m[t], vals[(int64_t)t * M + pick]);
+  bool nan;
+  QneiRecord r;
+  (void)qnei_absorb_pick(st, first, vals, M, T, offset, m, mask, &nan, &r.gain, &r.idx);
+  if (threadIdx.x == 0) rec[j] = r;
 }
 
-// debug build: an event before the draws, between the baselines and the steps, and behind the last step of the last call
-// (gpbo_debug_qnei_stage_ms); the product records nothing
-static inline void qnei_mark(gpbo_ctx* ctx, int i) {
+// ... and, over the masked block, feasible = (the number of draws t whose value at the pick is > -inf) / T: NaN for a NaN pick
+__global__ __launch_bounds__(QNEI_BLOCK) void cnei_update_kernel(const SelState* __restrict__ st, const Key* __restrict__ first,
+                                                                 const double* __restrict__ vals, int64_t M, int T, int64_t offset, int j,
+                                                                 double* __restrict__ m, uint8_t* __restrict__ mask,
+                                                                 CneiRecord* __restrict__ rec) {
+  __shared__ int count;
+  if (threadIdx.x == 0) count = 0;
+  __syncthreads();
+  bool nan;
+  CneiRecord r;
+  const int64_t pick = qnei_absorb_pick(st, first, vals, M, T, offset, m, mask, &nan, &r.gain, &r.idx);
+  if (pick >= 0) {
+    int mine = 0;
+    for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) mine += vals[(int64_t)t * M + pick] > -std::numeric_limits<double>::infinity();
+    if (mine) atomicAdd(&count, mine);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    r.feasible = (nan || pick < 0) ? std::numeric_limits<double>::quiet_NaN() : (double)count / (double)T;
+    rec[j] = r;
+  }
+}
+
+// debug build: an event before the draws, between the baselines and the steps, and behind the last step of the last call, per
+// entry point (ev / used: ctx->qnei_ev, ctx->cnei_ev and their flags); the product records nothing
+static inline void stage_mark(gpbo_ctx* ctx, hipEvent_t* ev, bool* used, int i) {
 #ifdef GPBO_DEBUG
-  if (!ctx->qnei_ev[i]) (void)hipEventCreate(&ctx->qnei_ev[i]);
-  (void)hipEventRecord(ctx->qnei_ev[i], ctx->stream);
-  ctx->qnei_ev_used = (i == 2);
+  if (!ev[i]) (void)hipEventCreate(&ev[i]);
+  (void)hipEventRecord(ev[i], ctx->stream);
+  *used = (i == 2);
 #else
-  (void)ctx; (void)i;
+  (void)ctx; (void)ev; (void)used; (void)i;
 #endif
 }
+static inline void qnei_mark(gpbo_ctx* ctx, int i) { stage_mark(ctx, ctx->qnei_ev, &ctx->qnei_ev_used, i); }
+static inline void cnei_mark(gpbo_ctx* ctx, int i) { stage_mark(ctx, ctx->cnei_ev, &ctx->cnei_ev_used, i); }
 
 #ifdef GPBO_DEBUG
-int debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms) {
-  if (!ctx->qnei_ev_used) GPBO_FAIL(ctx, GPBO_ERR_STATE, "debug_qnei_stage_ms: no gpbo_qnei_greedy call to report");
-  GPBO_HIP(ctx, hipEventSynchronize(ctx->qnei_ev[2]));
-  for (int i = 0; i < 2; ++i) GPBO_HIP(ctx, hipEventElapsedTime(&ms[i], ctx->qnei_ev[i], ctx->qnei_ev[i + 1]));
+// ms[0] the draws and baselines, ms[1] the steps of the call the three events belong to (gpbo_debug_qnei_stage_ms / _cnei_)
+static int stage_ms(gpbo_ctx* ctx, const hipEvent_t* ev, bool used, const char* who, const char* call, float* ms) {
+  if (!used) GPBO_FAIL(ctx, GPBO_ERR_STATE, std::string(who) + ": no " + call + " call to report");
+  GPBO_HIP(ctx, hipEventSynchronize(ev[2]));
+  for (int i = 0; i < 2; ++i) GPBO_HIP(ctx, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
   return GPBO_OK;
 }
+int debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms) {
+  return stage_ms(ctx, ctx->qnei_ev, ctx->qnei_ev_used, "debug_qnei_stage_ms", "gpbo_qnei_greedy", ms);
+}
+int debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms) {
+  return stage_ms(ctx, ctx->cnei_ev, ctx->cnei_ev_used, "debug_cnei_stage_ms", "gpbo_cnei_greedy", ms);
+}
 #endif
+
+// The q greedy steps of both entry points, all on the stream: the keys of step j into ctx->ys, the selection's one pick, and
+// `update(st, first, j)` — the launch of the caller's update kernel behind it.
+template <class Update>
+static int qnei_steps(gpbo_ctx* ctx, const double* vals, int64_t M, int T, const double* mt, const uint8_t* mask, int q,
+                      double* keys_out, Update update) {
+  int rc;
+  const int items = qnei_items(M);
+  const dim3 grid((unsigned)qnei_score_blocks(M)), block(QNEI_BLOCK);
+  for (int j = 0; j < q; ++j) {
+    if (items == 2) qnei_score_kernel<2><<<grid, block, 0, ctx->stream>>>(vals, M, T, mt, mask, ctx->ys);
+    else qnei_score_kernel<1><<<grid, block, 0, ctx->stream>>>(vals, M, T, mt, mask, ctx->ys);
+    GPBO_HIP(ctx, hipGetLastError());
+    if (keys_out)
+      GPBO_HIP(ctx, hipMemcpyAsync(keys_out + (int64_t)j * M, ctx->ys, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const SelState* st; const Key* first;
+    if ((rc = enqueue_values_select(ctx, M, &st, &first))) return rc;
+    update(st, first, j);
+    GPBO_HIP(ctx, hipGetLastError());
+  }
+  return GPBO_OK;
+}
 
 int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int G, int S, int F, const double* omega,
                        const double* phase, const double* weights, const double* eps, int noisy, double y_best, const double* pending,
@@ -156,20 +229,10 @@ int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, 
   qnei_baseline_kernel<<<dim3((unsigned)T), dim3(64), 0, ctx->stream>>>(base, b.ldb, noisy ? 0 : N, noisy, y_best, mt, w + b.m0);
   GPBO_HIP(ctx, hipGetLastError());
   qnei_mark(ctx, 1);
-  // the greedy steps, all on the stream
-  const int items = qnei_items(M);
-  const dim3 grid((unsigned)qnei_score_blocks(M)), block(QNEI_BLOCK);
-  for (int j = 0; j < q; ++j) {
-    if (items == 2) qnei_score_kernel<2><<<grid, block, 0, ctx->stream>>>(vals, M, T, mt, mask, ctx->ys);
-    else qnei_score_kernel<1><<<grid, block, 0, ctx->stream>>>(vals, M, T, mt, mask, ctx->ys);
-    GPBO_HIP(ctx, hipGetLastError());
-    if (keys_out)
-      GPBO_HIP(ctx, hipMemcpyAsync(keys_out + (int64_t)j * M, ctx->ys, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    const SelState* st; const Key* first;
-    if ((rc = enqueue_values_select(ctx, M, &st, &first))) return rc;
-    qnei_update_kernel<<<dim3(1), block, 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, mt, mask, rec);
-    GPBO_HIP(ctx, hipGetLastError());
-  }
+  if ((rc = qnei_steps(ctx, vals, M, T, mt, mask, q, keys_out, [&](const SelState* st, const Key* first, int j) {
+        qnei_update_kernel<<<dim3(1), dim3(QNEI_BLOCK), 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, mt, mask, rec);
+      })))
+    return rc;
   qnei_mark(ctx, 2);
   QneiRecord* hrec = (QneiRecord*)((char*)ctx->pinned_aux + PIN_AUX_SEL_OUT);
   GPBO_HIP(ctx, hipMemcpyAsync(hrec, rec, sizeof(QneiRecord) * (size_t)q, hipMemcpyDeviceToHost, ctx->stream));
@@ -178,6 +241,84 @@ int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, 
     GPBO_HIP(ctx, hipMemcpyAsync(values_out, vals, (size_t)T * (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int j = 0; j < q; ++j) { pick_idx[j] = hrec[j].idx; pick_gain[j] = hrec[j].gain; }
+  return GPBO_OK;
+}
+
+// gpbo_cnei_greedy behind its argument checks: ms / y_mean / y_std per slot (the objective, then the C constraints), the draws'
+// inputs concatenated slot-major, then group-major.
+int launch_cnei_greedy(gpbo_ctx* ctx, int C, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std,
+                       const double* lb, const double* ub, int G, int S, int F, const double* omega, const double* phase,
+                       const double* weights, const double* eps, double y_floor, const double* base_pts, int B, int q,
+                       int64_t index_offset, int64_t* pick_idx, double* pick_gain, double* pick_feasible, double* baseline_out,
+                       double* values_out, double* viol_out, double* base_values_out, double* keys_out) {
+  int rc;
+  const int d = ms[0]->d, DP = ms[0]->DP, T = G * S;
+  const CneiBlock b = cnei_block(T, S, M, B, d, DP, q, values_out != nullptr, base_values_out != nullptr && B > 0);
+  if ((rc = ensure(ctx, &ctx->cnei, &ctx->cap_cnei, b.doubles))) return rc;
+  double* w = ctx->cnei;
+  double *vals = w + b.vals, *base = w + b.base, *mt = w + b.m, *viol = w + b.viol, *violb = w + b.violb, *pts_s = w + b.pts_s;
+  double* stage = values_out ? w + b.stage : nullptr;
+  double* stageb = (base_values_out && B > 0) ? w + b.stageb : nullptr;
+  uint8_t* mask = (uint8_t*)(w + b.mask);
+  CneiRecord* rec = (CneiRecord*)(w + b.rec);
+  const int64_t Mp = round_up(M, POST_CANDS);
+  if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * DP))) return rc;
+  if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, M))) return rc;
+  cnei_mark(ctx, 0);
+  GPBO_HIP(ctx, hipMemsetAsync(mask, 0, (size_t)((M + 7) / 8 * 8), ctx->stream));
+  if (B > 0) GPBO_HIP(ctx, hipMemcpyAsync(w + b.pts, base_pts, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  // slot j's (G, S, N_j) block of eps
+  const double* eps_of[GPBO_MAX_MODELS];
+  {
+    const double* e = eps;
+    for (int j = 0; j <= C; ++j) { eps_of[j] = e; e += (int64_t)G * S * ms[j]->N; }
+  }
+  // the draws, group by group; per group the constraints in slot order (the violation's sum order), the objective last: per slot
+  // the group's path weights, the candidates and the base points scaled by THAT slot's length scales, one pass over each
+  const size_t cand_bytes = (size_t)S * (size_t)M * sizeof(double), base_bytes = (size_t)S * (size_t)B * sizeof(double);
+  for (int g = 0; g < G; ++g) {
+    const int64_t row = (int64_t)g * S;
+    for (int k = 1; k <= C + 1; ++k) {
+      const int j = k <= C ? k : 0;
+      const Model& m = *ms[j];
+      const int64_t jg = (int64_t)j * G + g;
+      PathWorkspace ws{};
+      if ((rc = launch_path_weights(ctx, m, S, F, omega + jg * F * d, phase + jg * F, weights + jg * S * F,
+                                    eps_of[j] + (int64_t)g * S * m.N, 0, &ws)))
+        return rc;
+      if ((rc = launch_prescale(ctx, ctx->Xc, M, d, DP, m.ls, ctx->Xcs, Mp))) return rc;
+      const int epilogue = j == 0 ? (int)PATH_MASKED : path_epilogue(j);
+      const double lo = j ? lb[j - 1] : 0.0, hi = j ? ub[j - 1] : 0.0;
+      if ((rc = launch_paths_over_fold(ctx, m, ws, y_mean[j], y_std[j], S, F, ctx->Xcs, M, j ? nullptr : vals + row * M, M,
+                                       PathFold{epilogue, lo, hi, viol, stage})))
+        return rc;
+      if (values_out)      // stream order: the next pass overwrites the stage after this copy has read it
+        GPBO_HIP(ctx, hipMemcpyAsync(values_out + ((int64_t)j * T + row) * M, stage, cand_bytes, hipMemcpyDeviceToHost, ctx->stream));
+      if (B > 0) {
+        if ((rc = launch_prescale(ctx, w + b.pts, B, d, DP, m.ls, pts_s, B))) return rc;
+        if ((rc = launch_paths_over_fold(ctx, m, ws, y_mean[j], y_std[j], S, F, pts_s, B, j ? nullptr : base + row * b.ldb, b.ldb,
+                                         PathFold{epilogue, lo, hi, violb, stageb})))
+          return rc;
+        if (stageb)
+          GPBO_HIP(ctx, hipMemcpyAsync(base_values_out + ((int64_t)j * T + row) * B, stageb, base_bytes, hipMemcpyDeviceToHost,
+                                       ctx->stream));
+      }
+    }
+    if (viol_out) GPBO_HIP(ctx, hipMemcpyAsync(viol_out + row * M, viol, cand_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  qnei_baseline_kernel<<<dim3((unsigned)T), dim3(64), 0, ctx->stream>>>(base, b.ldb, 0, 0, y_floor, mt, w + b.m0);
+  GPBO_HIP(ctx, hipGetLastError());
+  cnei_mark(ctx, 1);
+  if ((rc = qnei_steps(ctx, vals, M, T, mt, mask, q, keys_out, [&](const SelState* st, const Key* first, int j) {
+        cnei_update_kernel<<<dim3(1), dim3(QNEI_BLOCK), 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, mt, mask, rec);
+      })))
+    return rc;
+  cnei_mark(ctx, 2);
+  CneiRecord* hrec = (CneiRecord*)((char*)ctx->pinned_aux + PIN_AUX_SEL_OUT);      // (behind the last selection: its records are read)
+  GPBO_HIP(ctx, hipMemcpyAsync(hrec, rec, sizeof(CneiRecord) * (size_t)q, hipMemcpyDeviceToHost, ctx->stream));
+  GPBO_HIP(ctx, hipMemcpyAsync(baseline_out, w + b.m0, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int j = 0; j < q; ++j) { pick_idx[j] = hrec[j].idx; pick_gain[j] = hrec[j].gain; pick_feasible[j] = hrec[j].feasible; }
   return GPBO_OK;
 }
 

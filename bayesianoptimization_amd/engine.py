@@ -1108,6 +1108,82 @@ class GpEngine:
         return {"index": pick_idx[:q], "gain": pick_gain[:q], "values": values, "base_values": base_values, "keys": keys,
                 "front_size": front_size, "fronts": fronts}
 
+    def cnei_greedy(self, draws, q, lb, ub, y_floor, base=None, y_mean=None, y_std=None, index_offset=0, return_values=False,
+                    return_keys=False):
+        """A batch of q resident candidates by greedy noisy expected improvement UNDER CONSTRAINTS, over T joint posterior draws of
+        the objective and every constraint (gpbo_cnei_greedy; include/gpbo.h has the rule).  `draws`: 1 + C lists, slot j's G <= 16
+        tuples (omega, phase, weights, eps) as `qnei_greedy` takes them — the objective in slot 0, constraint j in slot j —, all
+        with the same G, S <= 16 and F.  lb / ub (C,); y_mean / y_std (1 + C,) (None: 0 / 1 everywhere); y_floor finite: the
+        incumbent of a draw in which no base point is feasible.  base (n_base <= 16384, d) or None: the observed points followed
+        by the pending ones.
+        Returns a dict: "index" (q,) int64, "gain" (q,), "feasible" (q,) the share of draws that call each pick feasible,
+        "baseline" (T,), and — None unless asked for — "values" (1 + C, T, M) the RAW draws, "viol" (T, M), "base_values"
+        (1 + C, T, n_base) (with `return_values`), "keys" (q, M).  A reader, as `sample_paths`."""
+        who = "cnei_greedy"
+        draws = [list(g) for g in draws]
+        n_slots = len(draws)
+        if n_slots < 2:
+            raise ValueError(f"{who}: draws must hold 1 + C lists of groups, C >= 1: the objective's, then each constraint's")
+        if n_slots > _lib.MAX_MODELS:
+            raise ValueError(f"{who}: n_constraints out of range [1, {_lib.MAX_MODELS - 1}]")
+        G = len(draws[0])
+        if G < 1 or any(len(groups) != G for groups in draws) or any(len(t) != 4 for groups in draws for t in groups):
+            raise ValueError(f"{who}: each slot needs the same non-empty list of tuples (omega, phase, weights, eps)")
+        if G > _lib.MAX_QNEI_GROUPS:
+            raise ValueError(f"{who}: n_groups out of range [1, {_lib.MAX_QNEI_GROUPS}]")
+        lb = np.ascontiguousarray(lb, dtype=np.float64).ravel()
+        ub = np.ascontiguousarray(ub, dtype=np.float64).ravel()
+        y_mean = np.zeros(n_slots) if y_mean is None else np.ascontiguousarray(y_mean, dtype=np.float64).ravel()
+        y_std = np.ones(n_slots) if y_std is None else np.ascontiguousarray(y_std, dtype=np.float64).ravel()
+        if lb.shape[0] != n_slots - 1 or ub.shape[0] != n_slots - 1 or y_mean.shape[0] != n_slots or y_std.shape[0] != n_slots:
+            raise ValueError(f"{who}: lb / ub must have {n_slots - 1} entries, y_mean / y_std {n_slots}")
+        parts = [[self._path_inputs(who, *t, j) for t in groups] for j, groups in enumerate(draws)]
+        F, S = parts[0][0][0].shape[0], parts[0][0][2].shape[0]
+        if any(p[0].shape[0] != F or p[2].shape[0] != S for ps in parts for p in ps):
+            raise ValueError(f"{who}: every group's draws must have the same S and F")
+        d = parts[0][0][4][1]
+        if base is None:
+            B = 0
+        else:
+            base = np.ascontiguousarray(np.asarray(base, dtype=np.float64))
+            if base.ndim != 2:
+                raise ValueError(f"{who}: base must be two-dimensional (n_base, d)")
+            B = int(base.shape[0])
+            if B and base.shape[1] != d:
+                raise ValueError(f"{who}: base (n_base, {base.shape[1]}) does not fit the slots' models in {d} dimensions")
+            if B == 0:
+                base = None
+        flat = [p for ps in parts for p in ps]
+        omega = np.ascontiguousarray(np.concatenate([p[0].ravel() for p in flat]))
+        phase = np.ascontiguousarray(np.concatenate([p[1] for p in flat]))
+        weights = np.ascontiguousarray(np.concatenate([p[2].ravel() for p in flat]))
+        eps = np.ascontiguousarray(np.concatenate([p[3].ravel() for p in flat]))
+        q = int(q)
+        T, M = G * S, max(int(self.n_candidates), 0)
+        n = max(q, 1)
+        pick_idx = np.empty(n, dtype=np.int64)
+        pick_gain, pick_feasible = np.empty(n), np.empty(n)
+        baseline = np.empty(max(T, 1))
+        keep = return_values and T >= 1 and M >= 1
+        values = np.empty((n_slots, T, M)) if keep else None
+        viol = np.empty((T, M)) if keep else None
+        base_values = np.empty((n_slots, T, B)) if return_values else None
+        keys = np.empty((q, M)) if return_keys and q >= 1 and M >= 1 else None
+        self._check(self._lib.gpbo_cnei_greedy(self._h, n_slots - 1, dptr(y_mean), dptr(y_std), dptr(lb), dptr(ub), G, int(S), int(F),
+                                               dptr(omega), dptr(phase), dptr(weights), dptr(eps), float(y_floor), dptr(base), B,
+                                               int(d), q, int(index_offset), iptr(pick_idx), dptr(pick_gain), dptr(pick_feasible),
+                                               dptr(baseline), dptr(values), dptr(viol), dptr(base_values) if B else None,
+                                               dptr(keys)))
+        return {"index": pick_idx[:q], "gain": pick_gain[:q], "feasible": pick_feasible[:q], "baseline": baseline[:T],
+                "values": values, "viol": viol, "base_values": base_values, "keys": keys}
+
+    def debug_cnei_stage_ms(self):
+        """gpbo_debug_cnei_stage_ms (debug build): kernel ms of the last `cnei_greedy`'s stages, (draws and baselines, greedy steps)."""
+        self._need_debug("gpbo_debug_cnei_stage_ms")
+        ms = (C.c_float * 2)()
+        self._check(self._lib.gpbo_debug_cnei_stage_ms(self._h, ms))
+        return float(ms[0]), float(ms[1])
+
     def debug_qnehvi_fronts(self, base_values, ref, insert_values=None):
         """gpbo_debug_qnehvi_fronts (debug build): the product's front build on base_values (2, T, n) against ref (2,), then its
         update rule with insert_values (2, T, n_insert), in order: (front_size (T,) int32, fronts (T, 128, 2))."""
@@ -1637,6 +1713,11 @@ class GroupEngine(GpEngine):
     def qnehvi_greedy(self, draws, q, ref, base=None, y_mean=(0.0, 0.0), y_std=(1.0, 1.0), index_offset=0, return_values=False,
                       return_keys=False, return_fronts=False):
         raise NotImplementedError("a device group has no batch noisy expected hypervolume improvement (gpbo_qnhvi_greedy is per "
+                                  "context); use a single device")
+
+    def cnei_greedy(self, draws, q, lb, ub, y_floor, base=None, y_mean=None, y_std=None, index_offset=0, return_values=False,
+                    return_keys=False):
+        raise NotImplementedError("a device group has no constrained batch noisy expected improvement (gpbo_cnei_greedy is per "
                                   "context); use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):

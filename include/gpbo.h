@@ -906,6 +906,10 @@ int gpbo_debug_ehvi_ms(gpbo_ctx* ctx, float* ms);
  * baselines —, ms[1] the q greedy steps (score, selection, update; with keys_out their copies too).  The fetch of the results and
  * the synchronise are in neither. */
 int gpbo_debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms);
+/* The same two stages of the context's last gpbo_cnei_greedy: ms[0] the draws — per group and slot the path weights, the scalings and
+ * the passes over candidates and base points, the baselines, with values_out / viol_out / base_values_out their copies too —,
+ * ms[1] the q greedy steps. */
+int gpbo_debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms);
 /* Kernel milliseconds (HIP events) of the three stages of the context's last gpbo_qnhvi_greedy: ms[0] the draws — the scalings, per
  * slot and group the path weights and the passes over candidates and base points —, ms[1] the front build, ms[2] the q greedy steps
  * (score, selection, update; with keys_out their copies too).  The fetch of the results and the synchronise are in none. */
@@ -918,6 +922,69 @@ int gpbo_debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms);
 int gpbo_debug_qnehvi_fronts(gpbo_ctx* ctx, int n_draws, int n, const double* base_values, const double* ref, int n_insert,
                              const double* insert_values, int* front_size_out, double* fronts_out);
 #endif /* GPBO_DEBUG */
+
+/* ---- product entry points declared behind the debug block ------------------------------- */
+/* Why here: the order-of-calls contract classifies every function declared BEFORE the debug block in one table
+ * (tests/test_call_order_cover_host.py); entry points added after that table was closed are declared in this trailing section and
+ * classified by its sibling, tests/test_call_order_cover_ext_host.py.  They are product symbols like the ones above: libgpbo.so
+ * exports them, and the ABI version does not change (nothing above changed meaning). */
+
+/* Batch noisy expected improvement UNDER CONSTRAINTS, built greedily over the resident candidates from joint posterior draws of the
+ * objective and of every constraint (Letham, Karrer, Ottoni & Bakshy 2019, "Constrained Bayesian optimization with noisy
+ * experiments", in gpbo_qnei_greedy's greedy, cached-draws form).  gpbo_qnei_greedy with the masked draw g_t in place of f_t.
+ * Slots and inputs.  The objective is slot 0, constraint j is slot j, j = 1 .. C, C = n_constraints in [1, GPBO_MAX_MODELS - 1]; the
+ * slots' N, kernel kind, length scales, scale and precision may differ.  y_mean / y_std (1 + C,); lb / ub (C,) under
+ * gpbo_sample_paths_constrained's rules (no NaN, lb < ub, infinite sides allowed).  T = G S draws, G = n_groups <=
+ * GPBO_MAX_QNEI_GROUPS, S = n_paths <= GPBO_MAX_PATHS, F = n_features.  The inputs are concatenated slot-major, then group-major:
+ * omega (1 + C, G, F, d), phase (1 + C, G, F), weights (1 + C, G, S, F), eps = slot j's (G, S, N_j) block, one after another.
+ * Draws.  Draw t = g S + s of slot j is gpbo_sample_paths' f_s for slot j and group g's inputs, the same bits.  Per draw t and
+ * point x:
+ *   viol_t(x) = gpbo_sample_paths_constrained's rule: the terms max(max(lb_j - c, c - ub_j), 0) / y_std_j, c = constraint j's draw t
+ *               at x, added in constraint order, a NaN kept — the bits that call's viol_out has for group g's inputs
+ *   g_t(x)    = NaN if f_t(x) or viol_t(x) is NaN;  f_t(x) if viol_t(x) == 0;  -inf otherwise
+ * An infinite raw draw value is outside the contract.
+ * Incumbents.  base (n_base, d; host, parameter space): the observed points, then the pending ones; n_base in
+ * [0, GPBO_MAX_CNEI_BASE], n_base = 0 with NULL is allowed.  Each slot scales base by its own length scales on the device, as
+ * gpbo_qnhvi_greedy does.  m_t = fmax(y_floor, the fmax fold in index order of g_t(base_i)), y_floor finite: a draw in which no
+ * observed or pending point is feasible starts from y_floor (Letham et al.'s M); a NaN is dropped by the fold.  baseline_out (T,) =
+ * m_t before the first pick.  There is no `noisy` flag: plain constrained Monte-Carlo qEI is base = the pending points and y_floor =
+ * the best feasible measurement.
+ * Steps, picks, updates: gpbo_qnei_greedy's exactly, with g_t in place of f_t — the same term, the same order of adds, ONE division,
+ * the mask to +inf, the selection's rules (the first NaN wins, else the least key, ties to the lowest index).  -inf needs no special
+ * case: -inf - m_t is not > 0, so the term is 0, and fmax(m_t, -inf) = m_t — an infeasible pick leaves every incumbent as it is.
+ * When no draw finds a feasible candidate above its incumbent every gain is exactly 0 and the zero-gain tail applies (the lowest
+ * unpicked index); there is no least-violation fallback.  pick_feasible[j] = (the number of t with g_t(pick) > -inf) / T: the
+ * share of draws that call the pick feasible, NaN for a NaN pick.
+ * Outputs.  pick_idx, pick_gain, pick_feasible (q,) and baseline_out (T,).  Optional (NULL: not fetched): values_out (1 + C, T, M),
+ * the RAW per-slot draws; viol_out (T, M); base_values_out (1 + C, T, n_base), raw; keys_out (q, M), every step's keys (a debugging
+ * aid: one copy per step).
+ * On the device: per group, in slot order 1 .. C then 0, per slot one launch_path_weights, the candidates and the base points scaled
+ * by THAT slot's length scales, and one pass of path_eval_kernel over each.  The constraint passes fold into one per-group
+ * viol[S][M] and one viol[S][n_base]; the objective's pass reads them and writes rows [g S, (g + 1) S) of the (T, M) block and of
+ * base[T][n_base] through the PATH_MASKED epilogue.  No (1 + C, T, M) block exists: values_out is staged one (slot, group) at a
+ * time.  Then gpbo_qnei_greedy's own stream — qnei_baseline_kernel (y_best = y_floor over the whole row), qnei_score_kernel, the
+ * selection — and cnei_update_kernel, which files {gain, index, feasible}.  Everything crosses behind ONE synchronisation.  fp64
+ * whatever a slot's precision.  Workspace: the context's own — the block 8 T M bytes, one group's violations 8 S M (+ 8 S M for the
+ * stage with values_out), at the base points 8 (T + S) n_base (+ 8 S n_base with base_values_out), the base points as given and
+ * scaled 8 n_base (d + DP) (DP = d padded to the kernels' width), the incumbents 16 T, the records 24 q and the mask M bytes —;
+ * grown on demand and kept; an allocation that fails is GPBO_ERR_HIP.
+ * A reader, as gpbo_sample_paths: the fits, the resident mu / sd, what gpbo_posterior_refresh may still refresh, the candidates and
+ * the negative-variance flag stay as they were; the context's acquisition values are overwritten.
+ * GPBO_ERR_INVALID: n_constraints outside [1, GPBO_MAX_MODELS - 1]; n_groups outside [1, GPBO_MAX_QNEI_GROUPS]; n_paths outside
+ * [1, GPBO_MAX_PATHS] or n_features outside [1, GPBO_MAX_PATH_FEATURES]; a NULL y_mean / y_std / lb / ub / omega / phase / weights /
+ * eps / pick_idx / pick_gain / pick_feasible / baseline_out; a y_std not finite or not positive, a y_mean not finite; a NaN bound
+ * or lb >= ub; y_floor not finite; n_base outside [0, GPBO_MAX_CNEI_BASE], n_base > 0 with a NULL or non-finite base; d not the
+ * slots'; q outside [1, GPBO_MAX_SEEDS], q > M.  GPBO_ERR_STATE: one of the slots 0 .. C unfitted or with a fit pending, no resident
+ * candidates, candidates of another d.  There is no gpbo_group_* / gpbo_comm_* form. */
+#define GPBO_MAX_CNEI_BASE 16384      /* observed + pending points */
+int gpbo_cnei_greedy(gpbo_ctx* ctx, int n_constraints, const double* y_mean, const double* y_std,
+                     const double* lb, const double* ub,
+                     int n_groups, int n_paths, int n_features,
+                     const double* omega, const double* phase, const double* weights, const double* eps,
+                     double y_floor, const double* base, int n_base, int d,
+                     int q, int64_t index_offset,
+                     int64_t* pick_idx, double* pick_gain, double* pick_feasible, double* baseline_out,
+                     double* values_out, double* viol_out, double* base_values_out, double* keys_out);
 
 #ifdef __cplusplus
 }
