@@ -7,7 +7,8 @@ built library and an AMD GPU.
 __version__ = "0.1.0"
 
 __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate", "suggest_batch", "UpperConfidenceBound",
-           "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement", "suggest_thompson",
+           "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement", "LogConstrainedExpectedImprovement",
+           "suggest_thompson",
            "suggest_mes", "suggest_kg", "suggest_turbo", "TrustRegion", "sobol_tables",
            "suggest_constrained_thompson", "suggest_scbo", "ConstrainedTrustRegion",
            "ParetoOptimizer", "pareto_front", "hypervolume", "box_decomposition", "suggest_qnei", "suggest_qnehvi",
@@ -61,6 +62,7 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
         from .qnehvi import suggest_qnehvi
         return suggest_qnehvi
     if name in ("UpperConfidenceBound", "ExpectedImprovement", "ProbabilityOfImprovement", "LogExpectedImprovement",
+                "LogConstrainedExpectedImprovement",
                 "AcquisitionFunction"):
         from . import fused_acquisition as acquisition
         return getattr(acquisition, name)

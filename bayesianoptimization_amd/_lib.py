@@ -201,6 +201,8 @@ DEBUG_SIGNATURES = {
                                          _c_int_p]),
     "gpbo_debug_polish_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _c_double_p, C.c_int, C.c_int,
                                          C.c_int, _c_double_p]),
+    "gpbo_debug_polish_objective": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, _c_double_p, _c_double_p, _c_double_p,
+                                              _c_double_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p]),
     "gpbo_debug_i8_pack_w": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, C.c_int64, C.c_void_p, _c_int_p, _c_double_p]),
     "gpbo_debug_i8_kstar_digits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, _c_double_p, _c_double_p]),
     "gpbo_debug_i8_gemm": (C.c_int, [C.c_void_p, C.c_void_p, _c_double_p, C.c_void_p, C.c_int64, C.c_int64, _c_double_p]),

@@ -35,8 +35,21 @@ struct AcqDev {
   const double* sd[GPBO_MAX_MODELS];
 };
 
-// -1 * base_acq(mean, std) [* p_constraints] of candidate m (acquisition.py:198-217), from the models' resident mu / sd
+// -1 * base_acq(mean, std) [* p_constraints] of candidate m (acquisition.py:198-217), from the models' resident mu / sd.
+// LOG_SUM: the instance of GPBO_ACQ_LOG_CEI / GPBO_ACQ_LOG_FEAS — kernels of their own (acq_is_log_sum picks them), so that the
+// product kinds' kernels are the code, the registers and the bits they were without them.
+__host__ __device__ __forceinline__ bool acq_is_log_sum(int acq) { return acq == GPBO_ACQ_LOG_CEI || acq == GPBO_ACQ_LOG_FEAS; }
+
+template <bool LOG_SUM>
 __device__ __forceinline__ double acq_value(const AcqDev& a, const int64_t m) {
+  if (LOG_SUM) {
+    // -(logEI + sum_j log p_j) (GPBO_ACQ_LOG_CEI), -sum_j log p_j (GPBO_ACQ_LOG_FEAS: slot 0's posterior is not read): a sum of
+    // logarithms, j ascending into one accumulator, where the product below is 0 a few sigma outside a band (include/gpbo.h)
+    double s = 0.0;
+    if (a.acq == GPBO_ACQ_LOG_CEI) s = log_ei_dev(a.mu[0][m] - a.y_max - a.param, a.sd[0][m]);
+    for (int j = 0; j < a.n_constraints; ++j) s = s + log_interval_dev(a.lb[j], a.ub[j], a.mu[j + 1][m], a.sd[j + 1][m]);
+    return -1.0 * s;
+  }
   const double mean = a.mu[0][m], sd = a.sd[0][m];
   double base;
   if (a.acq == GPBO_ACQ_UCB) {
@@ -63,10 +76,11 @@ __device__ __forceinline__ double acq_value(const AcqDev& a, const int64_t m) {
   return v;
 }
 
+template <bool LOG_SUM>
 __global__ __launch_bounds__(256) void acq_kernel(AcqDev a, int64_t M, double* __restrict__ ys) {
   const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (m >= M) return;
-  ys[m] = acq_value(a, m);
+  ys[m] = acq_value<LOG_SUM>(a, m);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -288,7 +302,7 @@ __device__ void sel2_emit(int n_listed, int k, const double* __restrict__ ys, Ke
 // block stage to 16 workgroups at BASELINE config 2 (M = 65 536: 24.6 us; round 6).  ACQ: the values are not read but MADE here —
 // acq_value over the resident mu / sd, written to ys on the way (the separate acq_kernel launch and its pass over ys go away).
 // A grid of ONE workgroup (M <= 256 ITEMS: BASELINE config 1) is its own merge: the picks and the state go straight to `picks` / `st`.
-template <int ITEMS, bool ACQ>
+template <int ITEMS, bool ACQ, bool LOG_SUM = false>
 __global__ __launch_bounds__(SEL_BLOCK) void select_block_topk_v2_kernel(double* __restrict__ ys, int64_t M, int k, int cap,
                                                                          Key* __restrict__ partial,
                                                                          int64_t* __restrict__ nan_partial, AcqDev acq, SelState* st,
@@ -305,7 +319,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void select_block_topk_v2_kernel(double*
   for (int it = 0; it < ITEMS; ++it) {
     const int64_t m = base + (int64_t)it * SEL_BLOCK;
     if (ACQ) {
-      v[it] = (m < M) ? acq_value(acq, m) : 0.0;
+      v[it] = (m < M) ? acq_value<LOG_SUM>(acq, m) : 0.0;
       if (m < M) ys[m] = v[it];
     } else {
       v[it] = (m < M) ? ys[m] : 0.0;
@@ -462,7 +476,10 @@ static int enqueue_select(gpbo_ctx* ctx, int64_t M, int npass, bool v2, SelState
     const int cap = select_v2_cap();
     const AcqDev none{};
     const dim3 grid((unsigned)nblocks), block(SEL_BLOCK);
-    if (items == 4 && acq) select_block_topk_v2_kernel<4, true><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
+    const bool log_sum = acq && acq_is_log_sum(acq->acq);
+    if (items == 4 && log_sum) select_block_topk_v2_kernel<4, true, true><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
+    else if (log_sum) select_block_topk_v2_kernel<16, true, true><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
+    else if (items == 4 && acq) select_block_topk_v2_kernel<4, true><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
     else if (items == 4) select_block_topk_v2_kernel<4, false><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, none, st, picks);
     else if (acq) select_block_topk_v2_kernel<16, true><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, *acq, st, picks);
     else select_block_topk_v2_kernel<16, false><<<grid, block, 0, ctx->stream>>>(ys, M, npass, cap, partial, nan_partial, none, st, picks);
@@ -490,7 +507,9 @@ static int enqueue_acq_select(gpbo_ctx* ctx, const AcqArgs& a, int64_t M, int k_
   // v2 makes the values in its block stage; the two-pass form reads them from a separate acq_kernel launch
   const bool v2 = select_v2_enabled() && npass >= 3;
   if (!v2) {
-    acq_kernel<<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream>>>(d, M, ctx->ys);
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    if (acq_is_log_sum(d.acq)) acq_kernel<true><<<grid, block, 0, ctx->stream>>>(d, M, ctx->ys);
+    else acq_kernel<false><<<grid, block, 0, ctx->stream>>>(d, M, ctx->ys);
     GPBO_HIP(ctx, hipGetLastError());
   }
   if ((rc = enqueue_select(ctx, M, npass, v2, st_out, picks_out, v2 ? &d : nullptr))) return rc;

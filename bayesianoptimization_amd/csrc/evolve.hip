@@ -645,6 +645,8 @@ extern "C" int gpbo_evolve_mixed(gpbo_ctx* ctx, int acq, double acq_param, doubl
       !success_out)
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: NULL argument");
   if (acq == GPBO_ACQ_LOG_EI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: GPBO_ACQ_LOG_EI is not evaluated by the device differential evolution");
+  if (acq == GPBO_ACQ_LOG_CEI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: GPBO_ACQ_LOG_CEI is not evaluated by the device differential evolution");
+  if (acq == GPBO_ACQ_LOG_FEAS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: GPBO_ACQ_LOG_FEAS is not evaluated by the device differential evolution (it takes no constraints)");
   if (acq != GPBO_ACQ_UCB && acq != GPBO_ACQ_EI && acq != GPBO_ACQ_POI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "evolve_mixed: unknown acquisition");
   drop_refreshable(ctx);      // as gpbo_polish_seeds: nothing resident may be refreshed after a search
   EvolveObjective o;

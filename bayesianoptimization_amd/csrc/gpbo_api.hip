@@ -124,10 +124,14 @@ int build_acq_args(gpbo_ctx* ctx, const char* who, int acq, double acq_param, do
                    const void* seed_idx, const void* seed_val, AcqArgs* out) {
   if (!ctx) return GPBO_ERR_INVALID;
   const std::string w(who);
-  if (acq < GPBO_ACQ_UCB || acq > GPBO_ACQ_LOG_EI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": unknown acquisition");
+  const bool known = (acq >= GPBO_ACQ_UCB && acq <= GPBO_ACQ_LOG_EI) || acq == GPBO_ACQ_LOG_CEI || acq == GPBO_ACQ_LOG_FEAS;
+  if (!known) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": unknown acquisition");
   if (n_constraints < 0 || n_constraints >= GPBO_MAX_MODELS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": bad n_constraints");
   if (acq == GPBO_ACQ_LOG_EI && n_constraints > 0)
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": GPBO_ACQ_LOG_EI takes no constraints (n_constraints must be 0)");
+  if (acq == GPBO_ACQ_LOG_FEAS && n_constraints == 0)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": GPBO_ACQ_LOG_FEAS needs at least one constraint (n_constraints must be >= 1)");
+  if (acq == GPBO_ACQ_LOG_CEI && n_constraints == 0) acq = GPBO_ACQ_LOG_EI;      // the same key, made by the same instructions
   if (n_constraints > 0 && (!lb || !ub)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": lb/ub required");
   if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": k_seeds out of range [0, 64]");
   if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": NULL output");

@@ -45,6 +45,24 @@ inline double erfcx_host(double t) {
   const double v = std::exp(s) * std::erfc(t);
   return v + v * e;
 }
+// log_ndtr_of asks for erfcx at every t >= 0.7 (a band 100 sigma away: t = 70, where erfc is 0 and exp(t^2) overflows): from t = 19.8
+// on, the asymptotic series 1 / (t sqrt(pi)) (1 - u + 3 u^2 - 15 u^3 ...), u = 1 / (2 t^2): ten terms, the first one left out below
+// 1e-20 there (t = inf: 0)
+inline double erfcx_tail_host(double t) {
+  if (t < 19.8) return erfcx_host(t);
+  const double u = 1.0 / (2.0 * t * t);
+  double s = -34459425.0;      // (2k - 1)!!, k = 9 ... 0, alternating
+  s = s * u + 2027025.0;
+  s = s * u - 135135.0;
+  s = s * u + 10395.0;
+  s = s * u - 945.0;
+  s = s * u + 105.0;
+  s = s * u - 15.0;
+  s = s * u + 3.0;
+  s = s * u - 1.0;
+  s = s * u + 1.0;
+  return s / (t * 1.77245385090551602730);      // sqrt(pi)
+}
 
 // All runs in lockstep: `eval(batch, live, f, g)` evaluates the objective and its gradient at the `live` trial points of the
 // round (rows of `batch`, d columns) in one go and returns a status code; the runs that are still alive get their answers
@@ -116,6 +134,131 @@ int ensure_polish_pinned(gpbo_ctx* ctx, size_t bytes) {
 
 PolishPlan plan_polish_for(const Model& m) { return plan_polish((int)m.NP, m.d, m.DP, search_np_override()); }
 
+// the acquisition and constraint arguments of gpbo_polish_seeds (and of gpbo_debug_polish_objective) and the state of the slots they
+// name; GPBO_ACQ_LOG_CEI without a constraint IS GPBO_ACQ_LOG_EI and leaves as that kind
+int check_polish_models(gpbo_ctx* ctx, const std::string& w, int* acq, int n_constraints, const double* lb, const double* ub, int d) {
+  const bool known = (*acq >= GPBO_ACQ_UCB && *acq <= GPBO_ACQ_LOG_EI) || *acq == GPBO_ACQ_LOG_CEI || *acq == GPBO_ACQ_LOG_FEAS;
+  if (!known) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": unknown acquisition");
+  if (n_constraints < 0 || n_constraints >= GPBO_MAX_MODELS || (n_constraints > 0 && (!lb || !ub)))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": bad constraint arguments");
+  if (*acq == GPBO_ACQ_LOG_EI && n_constraints > 0)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": GPBO_ACQ_LOG_EI takes no constraints (n_constraints must be 0)");
+  if (*acq == GPBO_ACQ_LOG_FEAS && n_constraints == 0)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": GPBO_ACQ_LOG_FEAS needs at least one constraint (n_constraints must be >= 1)");
+  if (*acq == GPBO_ACQ_LOG_CEI && n_constraints == 0) *acq = GPBO_ACQ_LOG_EI;
+  for (int j = 0; j <= n_constraints; ++j) {
+    if (!ctx->models[j].fitted) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + ": model slot has not been fitted");
+    if (ctx->models[j].d != d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + ": d differs from the fitted model's");
+    if (ctx->pending_info[j]) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + ": a fit of this slot is still in flight (gpbo_fit_wait)");
+  }
+  return GPBO_OK;
+}
+
+// The lockstep rounds' pinned block, device-visible: [the round's points (n_seeds, d)] then per model [dmu | dsd | mu | sd] of a round
+// (pitch = the round's live runs).  The scaling kernel reads the points there and the last kernel of a model's evaluation writes its
+// results there: a round is six launches and ONE stream synchronisation, no copy nodes (round 5; until then: H2D copy + event, D2H copy).
+inline size_t polish_rounds_bytes(int n_seeds, int d, int n_models) {
+  return ((size_t)n_seeds * (size_t)d + (size_t)n_seeds * (2 + 2 * (size_t)d) * (size_t)n_models) * sizeof(double);
+}
+
+// One batched evaluation of gpbo_polish_seeds' objective: f (live) and its gradient (live, d) at the `live` <= n_seeds rows of `batch`,
+// through the pinned block above (sized for n_seeds by the caller).
+int polish_objective(gpbo_ctx* ctx, int acq, double acq_param, double y_max, int n_constraints, const double* lb, const double* ub,
+                     const double* y_mean, const double* y_std, int n_seeds, int d, const double* batch, const int live, double* fv,
+                     double* gv) {
+  const int n_models = 1 + n_constraints;
+  const size_t per_model = (size_t)n_seeds * (2 + 2 * (size_t)d);
+  const size_t pts = (size_t)n_seeds * (size_t)d;
+  double* pts_h = (double*)ctx->polish_pinned;
+  double* land = pts_h + pts;
+  const double* pts_d = (const double*)ctx->polish_pinned_dev;
+  double* land_d = (double*)ctx->polish_pinned_dev + pts;
+  const bool timing0 = ctx->no_timing;
+  const bool log_sum = acq == GPBO_ACQ_LOG_CEI || acq == GPBO_ACQ_LOG_FEAS;
+  // ---- posterior + input gradient of every model at the live runs' trial points (GPBO_ACQ_LOG_FEAS does not look at slot 0's)
+  int rc = GPBO_OK;
+  memcpy(pts_h, batch, (size_t)live * d * sizeof(double));
+  ctx->no_timing = true;      // (no event records between the launches of a round)
+  for (int j = (acq == GPBO_ACQ_LOG_FEAS ? 1 : 0); j < n_models && rc == GPBO_OK; ++j) {
+    Model& m = ctx->models[j];
+    double *dmu_dev = nullptr, *dsd_dev = nullptr;
+    rc = launch_posterior_grad(ctx, m, live, y_mean[j], y_std[j], &dmu_dev, &dsd_dev, nullptr, pts_d, land_d + per_model * (size_t)j);
+  }
+  ctx->no_timing = timing0;
+  if (rc) return rc;
+  GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int t = 0; t < live; ++t) {
+    const double* o0 = land;
+    const double* dmu = o0 + (size_t)t * d;
+    const double* dsd = o0 + (size_t)live * d + (size_t)t * d;
+    double* g = gv + (size_t)t * d;
+    if (log_sum) {
+      // ---- f = -(logEI + sum_j log p_j), or -sum_j log p_j, and its gradient (include/gpbo.h: GPBO_ACQ_LOG_CEI)
+      double s = 0.0;
+      for (int i = 0; i < d; ++i) g[i] = 0.0;
+      if (acq == GPBO_ACQ_LOG_CEI) {
+        const double mu = o0[2 * (size_t)live * d + t], sd = o0[2 * (size_t)live * d + live + t];
+        double ca, cs;
+        polish_acq_coeffs(GPBO_ACQ_LOG_EI, acq_param, y_max, mu, sd, norm_cdf, norm_pdf, erfcx_host, s, ca, cs);
+        for (int i = 0; i < d; ++i) g[i] = polish_acq_grad(ca, cs, dmu[i], dsd[i]);
+      }
+      for (int j = 0; j < n_constraints; ++j) {
+        const double* o = land + per_model * (size_t)(1 + j);
+        const double* dcm = o + (size_t)t * d;
+        const double* dcs = o + (size_t)live * d + (size_t)t * d;
+        const double cm = o[2 * (size_t)live * d + t], csd = o[2 * (size_t)live * d + live + t];
+        double a, b;
+        const double lp = log_interval_of(lb[j], ub[j], cm, csd, norm_cdf, erfcx_tail_host, a, b);
+        s = s + lp;
+        const double qa = polish_log_feas_q(a, lp), qb = polish_log_feas_q(b, lp);
+        for (int i = 0; i < d; ++i) g[i] = g[i] - polish_log_feas_grad(a, b, qa, qb, csd, dcm[i], dcs[i]);
+      }
+      fv[t] = -1.0 * s;
+      continue;
+    }
+    // ---- f = -acq [* prod_j p_j] and its gradient (acquisition.py:198-217, 485, 660-661, 847-849; constraint.py:199-221)
+    const double mu = o0[2 * (size_t)live * d + t], sd = o0[2 * (size_t)live * d + live + t];
+    double a, ca, cs;      // acq value; d acq = ca * dmu + cs * dsd
+    polish_acq_coeffs(acq, acq_param, y_max, mu, sd, norm_cdf, norm_pdf, erfcx_host, a, ca, cs);
+    double f = -a;
+    for (int i = 0; i < d; ++i) g[i] = polish_acq_grad(ca, cs, dmu[i], dsd[i]);
+    if (n_constraints > 0) {
+      double p = 1.0;
+      std::vector<double> pj((size_t)n_constraints), dp((size_t)n_constraints * d, 0.0);
+      for (int j = 0; j < n_constraints; ++j) {
+        const double* o = land + per_model * (size_t)(1 + j);
+        const double* dcm = o + (size_t)t * d;
+        const double* dcs = o + (size_t)live * d + (size_t)t * d;
+        const double cm = o[2 * (size_t)live * d + t], csd = o[2 * (size_t)live * d + live + t];
+        double pv = 0.0;
+        for (int side = 0; side < 2; ++side) {
+          const double bound = side == 0 ? ub[j] : lb[j];
+          const double sign = side == 0 ? 1.0 : -1.0;
+          if (std::isinf(bound)) { if (bound > 0) pv += sign; continue; }   // Phi(+inf) = 1, Phi(-inf) = 0, for either side (constraint.py:202-207)
+          const double z = (bound - cm) / csd;
+          pv += sign * norm_cdf(z);
+          const double w = sign * norm_pdf(z) / csd;
+          for (int i = 0; i < d; ++i) dp[(size_t)j * d + i] += w * (-dcm[i] - z * dcs[i]);
+        }
+        pj[j] = pv;
+        p *= pv;
+      }
+      for (int i = 0; i < d; ++i) {
+        double sum = 0.0;
+        for (int j = 0; j < n_constraints; ++j) {
+          double others = 1.0;
+          for (int k = 0; k < n_constraints; ++k) if (k != j) others *= pj[k];
+          sum += dp[(size_t)j * d + i] * others;
+        }
+        g[i] = g[i] * p + f * sum;
+      }
+      f *= p;
+    }
+    fv[t] = f;
+  }
+  return GPBO_OK;
+}
+
 }  // namespace
 
 }  // namespace gpbo
@@ -143,6 +286,10 @@ extern "C" int gpbo_debug_polish_eval(gpbo_ctx* ctx, int acq, double acq_param, 
   if (!ctx || !points || !out || n < 1 || n > GPBO_MAX_SEEDS || repeat < 1) return GPBO_ERR_INVALID;
   Model& m = ctx->models[0];
   if (!m.fitted || m.d != d) GPBO_FAIL(ctx, GPBO_ERR_STATE, "debug_polish_eval: slot 0 is not fitted for this d");
+  // (the one launch serves no constraint: GPBO_ACQ_LOG_CEI is GPBO_ACQ_LOG_EI here, GPBO_ACQ_LOG_FEAS has nothing to sum)
+  if (acq == GPBO_ACQ_LOG_FEAS)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_polish_eval: GPBO_ACQ_LOG_FEAS needs at least one constraint (gpbo_debug_polish_objective takes them)");
+  if (acq == GPBO_ACQ_LOG_CEI) acq = GPBO_ACQ_LOG_EI;
   const PolishPlan plan = plan_polish_for(m);
   if (plan.mode == SearchMode::NotServed) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_polish_eval: the model is outside the one-launch path's range");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
@@ -155,6 +302,20 @@ extern "C" int gpbo_debug_polish_eval(gpbo_ctx* ctx, int acq, double acq_param, 
   std::copy(dbg, (const double*)ctx->polish_pinned + block.ints, out);
   return GPBO_OK;
 }
+
+// The lockstep rounds' objective — one batched evaluation as gpbo_polish_seeds makes it each round, constraints included — at n points.
+extern "C" int gpbo_debug_polish_objective(gpbo_ctx* ctx, int acq, double acq_param, double y_max, int n_constraints, const double* lb,
+                                           const double* ub, const double* y_mean, const double* y_std, const double* points, int n, int d,
+                                           double* f_out, double* g_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!points || !f_out || !g_out || !y_mean || !y_std || n < 1 || n > GPBO_MAX_SEEDS)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_polish_objective: NULL argument or n out of range [1, 64]");
+  if (const int rc = check_polish_models(ctx, "debug_polish_objective", &acq, n_constraints, lb, ub, d)) return rc;
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  drop_refreshable(ctx);
+  if (const int rc = ensure_polish_pinned(ctx, polish_rounds_bytes(n, d, 1 + n_constraints))) return rc;
+  return polish_objective(ctx, acq, acq_param, y_max, n_constraints, lb, ub, y_mean, y_std, n, d, points, n, f_out, g_out);
+}
 #endif  // GPBO_DEBUG
 
 extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, double y_max, int n_constraints, const double* lb,
@@ -165,38 +326,18 @@ extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, doubl
   if (n_seeds < 1 || n_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: n_seeds out of range [1, 64]");
   if (!seeds || !box_lo || !box_hi || !x_out || !f_out || !status_out || !y_mean || !y_std)
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: NULL argument");
-  if (acq < GPBO_ACQ_UCB || acq > GPBO_ACQ_LOG_EI) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: unknown acquisition");
-  if (n_constraints < 0 || n_constraints >= GPBO_MAX_MODELS || (n_constraints > 0 && (!lb || !ub)))
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: bad constraint arguments");
-  if (acq == GPBO_ACQ_LOG_EI && n_constraints > 0)
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: GPBO_ACQ_LOG_EI takes no constraints (n_constraints must be 0)");
+  if (const int rc = check_polish_models(ctx, "polish_seeds", &acq, n_constraints, lb, ub, d)) return rc;
   max_iter = clamp_max_iter(max_iter);
-  for (int j = 0; j <= n_constraints; ++j) {
-    if (!ctx->models[j].fitted) GPBO_FAIL(ctx, GPBO_ERR_STATE, "polish_seeds: model slot has not been fitted");
-    if (ctx->models[j].d != d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: d differs from the fitted model's");
-    if (ctx->pending_info[j]) GPBO_FAIL(ctx, GPBO_ERR_STATE, "polish_seeds: a fit of this slot is still in flight (gpbo_fit_wait)");
-  }
   if (!box_ok(box_lo, box_hi, d)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "polish_seeds: every bound needs lo < hi");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
   drop_refreshable(ctx);      // the call's trial points take the candidates' place: nothing resident may be refreshed afterwards
 
-  const int n_models = 1 + n_constraints;
-  // pinned block, device-visible: [the round's points (n_seeds, d)] then per model [dmu | dsd | mu | sd] of a round (pitch = the
-  // round's live runs).  The scaling kernel reads the points there and the last kernel of a model's evaluation writes its results
-  // there: a round is six launches and ONE stream synchronisation, no copy nodes (round 5; until then: H2D copy + event, D2H copy).
-  const size_t per_model = (size_t)n_seeds * (2 + 2 * (size_t)d);
-  const size_t pts = (size_t)n_seeds * (size_t)d;
   // (one model that search_plan.h's rule serves: the runs as ONE launch — polish_fused.hip; GPBO_POLISH_FUSED=0, debug build: never)
   const PolishPlan plan = plan_polish_for(ctx->models[0]);
   const PolishBlock block = polish_block(n_seeds, d);
   const bool fused = polish_one_launch(n_constraints, plan.mode, dbg_env("GPBO_POLISH_FUSED"));
-  if (const int rc = ensure_polish_pinned(ctx, std::max((pts + per_model * (size_t)n_models) * sizeof(double), fused ? block.bytes : (size_t)0)))
+  if (const int rc = ensure_polish_pinned(ctx, std::max(polish_rounds_bytes(n_seeds, d, 1 + n_constraints), fused ? block.bytes : (size_t)0)))
     return rc;
-  double* pts_h = (double*)ctx->polish_pinned;
-  double* land = pts_h + pts;
-  const double* pts_d = (const double*)ctx->polish_pinned_dev;
-  double* land_d = (double*)ctx->polish_pinned_dev + pts;
-  const bool timing0 = ctx->no_timing;
 
   if (fused) {
     if (const int rc = launch_polish_fused(ctx, ctx->models[0], plan, block, acq, acq_param, y_max, y_mean[0], y_std[0], seeds, n_seeds,
@@ -218,64 +359,7 @@ extern "C" int gpbo_polish_seeds(gpbo_ctx* ctx, int acq, double acq_param, doubl
   }
 
   auto eval = [&](const double* batch, const int live, double* fv, double* gv) -> int {
-    // ---- one batched evaluation: posterior + input gradient of every model at the live runs' trial points
-    int rc = GPBO_OK;
-    memcpy(pts_h, batch, (size_t)live * d * sizeof(double));
-    ctx->no_timing = true;      // (no event records between the launches of a round)
-    for (int j = 0; j < n_models && rc == GPBO_OK; ++j) {
-      Model& m = ctx->models[j];
-      double *dmu_dev = nullptr, *dsd_dev = nullptr;
-      rc = launch_posterior_grad(ctx, m, live, y_mean[j], y_std[j], &dmu_dev, &dsd_dev, nullptr, pts_d, land_d + per_model * (size_t)j);
-    }
-    ctx->no_timing = timing0;
-    if (rc) return rc;
-    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // ---- f = -acq [* prod_j p_j] and its gradient (acquisition.py:198-217, 485, 660-661, 847-849; constraint.py:199-221)
-    for (int t = 0; t < live; ++t) {
-      const double* o0 = land;
-      const double* dmu = o0 + (size_t)t * d;
-      const double* dsd = o0 + (size_t)live * d + (size_t)t * d;
-      const double mu = o0[2 * (size_t)live * d + t], sd = o0[2 * (size_t)live * d + live + t];
-      double a, ca, cs;      // acq value; d acq = ca * dmu + cs * dsd
-      polish_acq_coeffs(acq, acq_param, y_max, mu, sd, norm_cdf, norm_pdf, erfcx_host, a, ca, cs);
-      double f = -a;
-      double* g = gv + (size_t)t * d;
-      for (int i = 0; i < d; ++i) g[i] = polish_acq_grad(ca, cs, dmu[i], dsd[i]);
-      if (n_constraints > 0) {
-        double p = 1.0;
-        std::vector<double> pj((size_t)n_constraints), dp((size_t)n_constraints * d, 0.0);
-        for (int j = 0; j < n_constraints; ++j) {
-          const double* o = land + per_model * (size_t)(1 + j);
-          const double* dcm = o + (size_t)t * d;
-          const double* dcs = o + (size_t)live * d + (size_t)t * d;
-          const double cm = o[2 * (size_t)live * d + t], csd = o[2 * (size_t)live * d + live + t];
-          double pv = 0.0;
-          for (int side = 0; side < 2; ++side) {
-            const double bound = side == 0 ? ub[j] : lb[j];
-            const double sign = side == 0 ? 1.0 : -1.0;
-            if (std::isinf(bound)) { if (bound > 0) pv += sign; continue; }   // Phi(+inf) = 1, Phi(-inf) = 0, for either side (constraint.py:202-207)
-            const double z = (bound - cm) / csd;
-            pv += sign * norm_cdf(z);
-            const double w = sign * norm_pdf(z) / csd;
-            for (int i = 0; i < d; ++i) dp[(size_t)j * d + i] += w * (-dcm[i] - z * dcs[i]);
-          }
-          pj[j] = pv;
-          p *= pv;
-        }
-        for (int i = 0; i < d; ++i) {
-          double sum = 0.0;
-          for (int j = 0; j < n_constraints; ++j) {
-            double others = 1.0;
-            for (int k = 0; k < n_constraints; ++k) if (k != j) others *= pj[k];
-            sum += dp[(size_t)j * d + i] * others;
-          }
-          g[i] = g[i] * p + f * sum;
-        }
-        f *= p;
-      }
-      fv[t] = f;
-    }
-    return GPBO_OK;
+    return polish_objective(ctx, acq, acq_param, y_max, n_constraints, lb, ub, y_mean, y_std, n_seeds, d, batch, live, fv, gv);
   };
   return lockstep_minimize(eval, seeds, n_seeds, d, box_lo, box_hi, max_iter, x_out, f_out, status_out, n_rounds_out, n_iter_out,
                            n_eval_out);

@@ -265,4 +265,20 @@ GPBO_HD double polish_acq_grad(double ca, double cs, double dmu, double dsd) {
   return -(ca * dmu + cs * dsd);
 }
 
+// GPBO_ACQ_LOG_CEI / GPBO_ACQ_LOG_FEAS: the slope of one constraint's log p_j (acq_formulas.h: log_interval_of gives log p_j and the
+// standardised bounds a, b) from the constraint posterior's input gradient,
+//   d log p_j = (q_b (-dcm - b dcs) - q_a (-dcm - a dcs)) / cs,   q_x = phi(x) / p_j = exp(log phi(x) - log p_j)
+// — never the quotient phi / p_j, which is 0 / 0 a few sigma outside the band.  An infinite bound contributes nothing.
+GPBO_HD double polish_log_feas_q(double x, double log_p) {
+#pragma clang fp contract(off)
+  if (__builtin_isinf(x)) return 0.0;
+  return exp(-(x * x) / 2.0 - LOG_EI_HALF_LOG_2PI - log_p);
+}
+GPBO_HD double polish_log_feas_grad(double a, double b, double qa, double qb, double cs, double dcm, double dcs) {
+#pragma clang fp contract(off)
+  const double tb = __builtin_isinf(b) ? 0.0 : qb * (-dcm - b * dcs);
+  const double ta = __builtin_isinf(a) ? 0.0 : qa * (-dcm - a * dcs);
+  return (tb - ta) / cs;
+}
+
 }  // namespace gpbo

@@ -16,6 +16,7 @@ from ._lib import dptr, iptr
 
 RBF, MATERN25, MATERN15, MATERN05 = 0, 1, 2, 3
 UCB, EI, POI, LOG_EI = 0, 1, 2, 3      # enum gpbo_acq (LOG_EI: never with constraints, never in evolve_mixed)
+LOG_CEI, LOG_FEAS = 5, 6               # log EI + sum_j log p_j; sum_j log p_j alone, >= 1 constraint (4 is unassigned; neither in evolve_mixed)
 F64, F32 = 0, 1
 
 TIMING_NAMES = ("fit", "posterior_main", "posterior_finalize", "acq_argbest", "kmat", "cholesky", "trtri")

@@ -811,6 +811,188 @@ class LogExpectedImprovement(_ImprovementBased):
                                random_state=random_state)
 
 
+_RSQRT2 = 0.70710678118654752440     # acq_formulas.h: LOG_FEAS_RSQRT2
+_LOG_2 = 0.69314718055994530942      # acq_formulas.h: LOG_FEAS_LOG_2
+
+
+def _log_ndtr(x):
+    """log Phi(x): log(ndtr(x)) above -1, -x^2/2 + log(erfcx(-x / sqrt2)) - log 2 from there down (include/gpbo.h)."""
+    x = np.asarray(x, dtype=np.float64)
+    low = x <= -1.0
+    xl = np.where(low, x, -1.0)
+    xh = np.where(low, 0.0, x)
+    return np.where(low, -(xl * xl) / 2.0 + np.log(erfcx(-xl * _RSQRT2)) - _LOG_2, np.log(ndtr(xh)))
+
+
+def _log_band(a, b):
+    """log(Phi(b) - Phi(a)) of finite two-sided bands in standardised units, by the branches of GPBO_ACQ_LOG_CEI (include/gpbo.h):
+    a == b gives -inf, a > b or a NaN gives NaN."""
+    from scipy.special import erf
+
+    bad = np.isnan(a) | np.isnan(b) | (a > b)
+    upper = a >= 0.0                                   # reflected into the lower tail
+    a, b = np.where(upper, -b, a), np.where(upper, -a, b)
+    one_tail = b <= 0.0
+    far = one_tail & (a <= -1.0)
+    af, bf = np.where(far, a, -2.0), np.where(far, b, -1.0)
+    lpb, lpa = _log_ndtr(bf), _log_ndtr(af)
+    v_far = lpb + np.log(-np.expm1(lpa - lpb))
+    v_near = np.log(0.5 * (erf(b * _RSQRT2) - erf(a * _RSQRT2)))
+    v_across = np.log(0.5 * (erf(b * _RSQRT2) + erf(-a * _RSQRT2)))
+    out = np.where(far, v_far, np.where(one_tail, v_near, v_across))
+    return np.where(bad, np.nan, np.where(a == b, -np.inf, out))
+
+
+def _log_interval(lo, hi, mean, std):
+    """(log p, a, b) of one constraint lo <= c <= hi under the posterior N(mean, std^2): p = Phi(b) - Phi(a) with a = (lo - mean) /
+    std, b = (hi - mean) / std (-inf / +inf for an infinite bound), without forming p.  Two infinite bounds give 0 whatever the
+    posterior; otherwise a std that is not > 0 gives NaN."""
+    mean = np.asarray(mean, dtype=np.float64)
+    std = np.asarray(std, dtype=np.float64)
+    has_lo, has_hi = lo != -np.inf, hi != np.inf
+    a = (lo - mean) / std if has_lo else np.full(mean.shape, -np.inf)
+    b = (hi - mean) / std if has_hi else np.full(mean.shape, np.inf)
+    if not has_lo and not has_hi:
+        return np.zeros(mean.shape), a, b
+    value = _log_band(a, b) if has_lo and has_hi else (_log_ndtr(b) if has_hi else _log_ndtr(-a))
+    return np.where(std > 0.0, value, np.nan), a, b
+
+
+def _log_interval_slope(a, b, log_p, std, dmean, dstd):
+    """d log p / dx (n, d) = (q_b (-dmean - b dstd) - q_a (-dmean - a dstd)) / std with q_x = phi(x) / p formed as
+    exp(log phi(x) - log p), never as the quotient (0 / 0 a few sigma outside the band); an infinite bound contributes 0."""
+    out = np.zeros_like(dmean)
+    for x, sign in ((b, 1.0), (a, -1.0)):
+        finite = np.isfinite(x) | np.isnan(x)
+        xs = np.where(finite, x, 0.0)
+        q = np.where(finite, np.exp(-(xs * xs) / 2.0 - _HALF_LOG_2PI - log_p), 0.0)
+        out = out + sign * np.where(finite[:, None], q[:, None] * (-dmean - xs[:, None] * dstd), 0.0)
+    return out / std[:, None]
+
+
+class LogConstrainedExpectedImprovement(LogExpectedImprovement):
+    """log EI(x) + sum_j log p_j(x), the logarithm of the constrained expected improvement EI prod_j p_j — for the runs in which that
+    product is a plateau of zeros: every p_j = Phi(b) - Phi(a) is formed by subtraction, is exactly 0 a few sigma outside the feasible
+    band and cancels inside a narrow one, so the constrained product underflows sooner than EI alone.  The formula, its branches and
+    its conventions are those of GPBO_ACQ_LOG_CEI (include/gpbo.h).  Not a class of the reference.
+
+    On an unconstrained space the policy IS LogExpectedImprovement (the same engine calls, the same host objective).  On a constrained
+    one y_max is the best feasible target, as for EI; the random stage is gpbo_acq_argbest with kind 5, the local searches are
+    gpbo_polish_seeds with kind 5 when `device_polish` applies and SciPy's L-BFGS-B over the host objective and its analytic gradient
+    otherwise; a mixed space runs SciPy's differential evolution over the host objective.  While NO feasible point has been observed
+    there is no y_max: with `feasibility_first` (the default) the step maximises sum_j log p_j alone (GPBO_ACQ_LOG_FEAS, kind 6) — it
+    searches for feasibility first —, without it the step raises NoValidPointRegisteredError as EI does.
+
+    Not offered inside GPHedge: its gains would mix log EI + log p with log p alone; GPHedge raises TypeError."""
+
+    _acq_kind = E.LOG_CEI
+
+    def __init__(self, xi: float = 0.01, exploration_decay=None, exploration_decay_delay=None, feasibility_first: bool = True,
+                 random_state=None) -> None:
+        super().__init__(xi=xi, exploration_decay=exploration_decay, exploration_decay_delay=exploration_decay_delay,
+                         random_state=random_state)
+        self.feasibility_first = bool(feasibility_first)
+
+    def _feasibility_only(self) -> bool:
+        return self._acq_kind == E.LOG_FEAS
+
+    def suggest(self, gp, target_space, n_random=None, n_smart: int = 10, fit_gp: bool = True, random_state=None):
+        if target_space.constraint is None:
+            self._acq_kind = E.LOG_EI
+        elif target_space._target_max() is None and not target_space.empty and self.feasibility_first:
+            # no feasible observation, so no incumbent: the step maximises the log probability of feasibility alone
+            self._acq_kind = E.LOG_FEAS
+            self.y_max = None
+            try:
+                x = AcquisitionFunction.suggest(self, gp=gp, target_space=target_space, n_random=n_random, n_smart=n_smart,
+                                                fit_gp=fit_gp, random_state=random_state)
+            finally:
+                self._acq_kind = E.LOG_CEI
+            self.decay_exploration()
+            return x
+        else:
+            self._acq_kind = E.LOG_CEI
+        try:
+            return _ImprovementBased.suggest(self, gp=gp, target_space=target_space, n_random=n_random, n_smart=n_smart,
+                                             fit_gp=fit_gp, random_state=random_state)
+        finally:
+            self._acq_kind = E.LOG_CEI
+
+    @staticmethod
+    def _posterior_of(model, batch):
+        if isinstance(model, HipGPR) and batch.dtype == np.float64 and np.isfinite(batch).all():
+            return model._posterior_trusted(batch)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return model.predict(batch, return_std=True)
+
+    def log_feasibility(self, constraint, means, stds):
+        """sum_j log p_j from the constraint GPs' posterior means and standard deviations (one array per constraint), j ascending
+        into one accumulator: the constraint model's bounds, not its `predict` (which is the product)."""
+        total = np.zeros(np.shape(means[0]))
+        with np.errstate(all="ignore"):
+            for lo, hi, cm, cs in zip(constraint._lb, constraint._ub, means, stds):
+                total = total + _log_interval(lo, hi, cm, cs)[0]
+        return total
+
+    def _get_acq(self, gp, constraint=None):
+        """Host objective x -> -(log EI(x) + sum_j log p_j(x)), or -sum_j log p_j(x) while nothing feasible has been observed."""
+        if constraint is None:
+            return super()._get_acq(gp=gp, constraint=None)
+        ndim = gp.X_train_.shape[1]
+        feasibility_only = self._feasibility_only()
+
+        def objective(x):
+            batch = x.reshape(-1, ndim)
+            posts = [self._posterior_of(model, batch) for model in constraint._model]
+            if feasibility_only:
+                return -1 * self.log_feasibility(constraint, [p[0] for p in posts], [p[1] for p in posts])
+            mean, std = self._posterior_of(gp, batch)
+            with np.errstate(all="ignore"):
+                value = self.base_acq(mean, std)
+                for lo, hi, (cm, cs) in zip(constraint._lb, constraint._ub, posts):
+                    value = value + _log_interval(lo, hi, cm, cs)[0]
+            return -1 * value
+
+        return objective
+
+    def _value_and_grad(self, models, constraint):
+        """Batch objective X (S, d) -> (-(log EI + sum_j log p_j), its gradient (S, d)) on the engine, one point per evaluation:
+        -(ca dmu + cs dsd) - sum_j dlog p_j (include/gpbo.h)."""
+        if constraint is None:
+            return super()._value_and_grad(models, constraint)
+        target = models[0]
+        feasibility_only = self._feasibility_only()
+
+        def fun(X):
+            X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, target.X_train_.shape[1])
+            with np.errstate(all="ignore"):
+                if feasibility_only:
+                    value, g = np.zeros(X.shape[0]), np.zeros(X.shape)
+                else:
+                    value, da = self.base_acq_grad(*target._posterior_grad_trusted(X))
+                    g = -da
+                for gp, lo, hi in zip(models[1:], constraint._lb, constraint._ub):
+                    cm, cs, dcm, dcs = gp._posterior_grad_trusted(X)
+                    log_p, a, b = _log_interval(lo, hi, cm, cs)
+                    value = value + log_p
+                    g = g - _log_interval_slope(a, b, log_p, cs, dcm, dcs)
+            return -1 * value, np.where(np.isfinite(g), g, 0.0)
+
+        return fun
+
+    def _polish_seeds(self, acq, x_seeds, box):
+        if getattr(self, "_fused_constraint", None) is None:
+            return super()._polish_seeds(acq, x_seeds, box)
+        # where the one library call does not apply, SciPy walks the analytic gradient above, not finite differences of a sum of logs
+        keep = self.analytic_gradient
+        self.analytic_gradient = True
+        try:
+            return super()._polish_seeds(acq, x_seeds, box)
+        finally:
+            self.analytic_gradient = keep
+
+
 class GPHedge(AcquisitionFunction):
     """Portfolio of acquisition policies (bayes_opt/acquisition.py:1181-1360; Brochu et al., arXiv:1009.5419): every
     base policy nominates a point, one nominee is drawn with probability softmax(gains), and at the next step the gains
@@ -834,6 +1016,11 @@ class GPHedge(AcquisitionFunction):
     def __init__(self, base_acquisitions, random_state=None, share_candidates: bool = False) -> None:
         super().__init__(random_state)
         self.base_acquisitions = list(base_acquisitions)
+        for base in self.base_acquisitions:
+            if isinstance(base, LogConstrainedExpectedImprovement):
+                # (the portfolio has no error of its own for a base policy it cannot use: TypeError is the one it raises, `base_acq`)
+                raise TypeError("GPHedge cannot hold LogConstrainedExpectedImprovement: its steps maximise log EI + sum log p or, "
+                                "before the first feasible point, sum log p alone, and the gains would mix the two units.")
         self.n_acq = len(self.base_acquisitions)
         self.gains = np.zeros(self.n_acq)
         self.previous_candidates = None

@@ -67,9 +67,45 @@ enum gpbo_kernel { GPBO_KERNEL_RBF = 0, GPBO_KERNEL_MATERN25 = 1, GPBO_KERNEL_MA
  * selection key is the one of the other kinds, ys = -logEI: +inf is an ordinary double that sorts after every finite value, NaN
  * sorts last and the arg-best is still the first NaN.
  * Checked refusals (GPBO_ERR_INVALID): GPBO_ACQ_LOG_EI with n_constraints > 0 (gpbo_acq_argbest, its gpbo_comm_* / gpbo_group_*
- * forms, gpbo_polish_seeds: the constrained quantity would be logEI + sum_j log p_j, not a product, and is not implemented), and
- * GPBO_ACQ_LOG_EI in gpbo_evolve_mixed (the device differential evolution evaluates UCB / EI / POI only). */
-enum gpbo_acq { GPBO_ACQ_UCB = 0, GPBO_ACQ_EI = 1, GPBO_ACQ_POI = 2, GPBO_ACQ_LOG_EI = 3 };
+ * forms, gpbo_polish_seeds: the constrained quantity would be logEI + sum_j log p_j, not a product: GPBO_ACQ_LOG_CEI below), and
+ * GPBO_ACQ_LOG_EI in gpbo_evolve_mixed (the device differential evolution evaluates UCB / EI / POI only).
+ *
+ * GPBO_ACQ_LOG_CEI and GPBO_ACQ_LOG_FEAS are that constrained quantity and its feasibility part alone.  The constrained product
+ * EI prod_j p_j underflows sooner than EI: every p_j = Phi(b) - Phi(a) is formed by subtraction, is exactly 0 a few sigma outside
+ * the feasible band and cancels inside a narrow one.  The sum of logarithms stays finite and keeps its slope there; its feasibility
+ * part is what to maximise while no feasible point has been observed (EI and POI have no y_max then).  The value 4 is unassigned
+ * and refused as an unknown acquisition; the kinds are 5 and 6.  All arithmetic is fp64 without contraction.
+ * Per constraint j the posterior is (cm, cs) from slot j + 1, a = (lb_j - cm) / cs, b = (ub_j - cm) / cs; an infinite bound gives
+ * -inf / +inf without a division.
+ *   log Phi(x)   x > -1: log(ndtr(x));   x <= -1: -x^2/2 + log(erfcx(-x / sqrt2)) - log 2, which does not underflow
+ *   log p_j      both bounds infinite: 0 (the posterior is not looked at);  lb = -inf: log Phi(b);  ub = +inf: log Phi(-a);
+ *                two-sided: a >= 0 is reflected, (a, b) -> (-b, -a), first; then
+ *                  b <= 0, a <= -1  log Phi(b) + log(-expm1(log Phi(a) - log Phi(b)))       both in one tail
+ *                  b <= 0, a > -1   log((erf(b / sqrt2) - erf(a / sqrt2)) / 2)              both within one sigma of the centre
+ *                  a < 0 < b        log((erf(b / sqrt2) + erf(-a / sqrt2)) / 2)             straddling: two positive terms
+ *                (The second of the three is a branch that moved: the expm1 form loses |log Phi(a)| Phi(a) / (phi(a) |a|) against
+ *                the band's own condition number — 1.2 at a = -1, 3 at -0.3, without bound towards a = 0, where a narrow band
+ *                just below the centre would lose every digit; the two erf, each of size 0.8 |x|, subtract at that condition number.)
+ *   keys         GPBO_ACQ_LOG_CEI: ys = -(logEI + log p_0 + ... + log p_{n-1}), logEI as above, j ascending into one accumulator;
+ *                GPBO_ACQ_LOG_FEAS: ys = -(log p_0 + ...): acq_param, y_max and slot 0's mu / sd are not read (the state checks on
+ *                slot 0 stay those of the other kinds).  With n_constraints == 0 GPBO_ACQ_LOG_CEI IS GPBO_ACQ_LOG_EI, bit for bit.
+ *   gradient     -(ca dmu + cs dsd) - sum_j dlog p_j,  dlog p_j = (q_b (-dcm - b dcs) - q_a (-dcm - a dcs)) / cs_j, with
+ *                q_x = phi(x) / p_j formed as exp(-x^2/2 - log(2 pi)/2 - log p_j), never as the quotient (0 / 0 outside the band);
+ *                an infinite bound contributes 0.  gpbo_polish_seeds forms it on the host side of the ABI (lockstep rounds; the
+ *                one-launch search serves unconstrained models only, GPBO_ACQ_LOG_CEI without constraints as GPBO_ACQ_LOG_EI).
+ * Conventions: cs not > 0 gives NaN (as the product form's norm(cm, cs).cdf), a == b gives -inf, a > b gives NaN, a NaN anywhere
+ * gives NaN.  Selection is that of the other kinds: +inf sorts after every finite key, the first NaN wins the arg-best.
+ * Accepted by gpbo_acq_argbest, gpbo_comm_acq_argbest, gpbo_group_acq_argbest and gpbo_polish_seeds.  Checked refusals
+ * (GPBO_ERR_INVALID, the message names the kind): either kind in gpbo_evolve_mixed, which has no constraint arguments, and
+ * GPBO_ACQ_LOG_FEAS with n_constraints == 0. */
+enum gpbo_acq {
+  GPBO_ACQ_UCB = 0,
+  GPBO_ACQ_EI = 1,
+  GPBO_ACQ_POI = 2,
+  GPBO_ACQ_LOG_EI = 3,
+  GPBO_ACQ_LOG_CEI = 5,  /* logEI + sum_j log p_j; n_constraints >= 0 (4 stays unassigned and refused) */
+  GPBO_ACQ_LOG_FEAS = 6  /* sum_j log p_j alone; n_constraints >= 1 */
+};
 enum gpbo_precision { GPBO_F64 = 0, GPBO_F32 = 1 };
 
 #define GPBO_MAX_MODELS 8   /* slot 0 = target GP, slots 1.. = constraint GPs */
@@ -821,6 +857,14 @@ int gpbo_debug_minimize_box(gpbo_fg_callback fg, void* user, const double* seeds
  * dmu/dx (d) | dsd/dx (d)] — what gpbo_predict_grad's six kernels compute, from the one kernel (the tests require the same bits). */
 int gpbo_debug_polish_eval(gpbo_ctx* ctx, int acq, double acq_param, double y_max, double y_mean, double y_std, const double* points,
                            int n, int d, int repeat, double* out);
+/* The objective of gpbo_polish_seeds' lockstep rounds — the path that serves constraint slots — as ONE batched evaluation at n <= 64
+ * points (n,d): f_out (n,) and g_out (n,d), the gradient before the optimiser zeroes its non-finite components.  Arguments and
+ * refusals as gpbo_polish_seeds (every acquisition kind; GPBO_ACQ_LOG_CEI / GPBO_ACQ_LOG_FEAS with their constraints, which
+ * gpbo_debug_polish_eval — no constraint arguments: GPBO_ACQ_LOG_CEI runs there as GPBO_ACQ_LOG_EI, GPBO_ACQ_LOG_FEAS is refused —
+ * cannot be given). */
+int gpbo_debug_polish_objective(gpbo_ctx* ctx, int acq, double acq_param, double y_max, int n_constraints, const double* lb,
+                                const double* ub, const double* y_mean, const double* y_std, const double* points, int n, int d,
+                                double* f_out, double* g_out);
 
 /* gpbo_evolve_mixed's objective at each of n points (n, D) in parameter space (transform, posterior of slot 0, -base_acq),
  * evaluated by the kernel of the device walk: out (n,). */
