@@ -1,6 +1,8 @@
 """What suggest_batch (batch.py), suggest_thompson (thompson.py), suggest_mes (mes.py), suggest_kg (kg.py), suggest_turbo (turbo.py),
-suggest_qnei (qnei.py: the count check, the gate, the frame of a model and `group_inputs`),
-suggest_qnehvi (qnehvi.py: the count check, `pareto_gate`, the frame of a model and `group_inputs`) and
+the greedy draw batches suggest_qnei (qnei.py: the gate, the frame of a model), suggest_qnehvi (qnehvi.py: `pareto_gate`, the frame of
+a model) and suggest_constrained_qnei (cqnei.py: the gate with `constrained=True`) — which share `greedy_counts` (their count
+checks), `draw_layout` / `MAX_DRAWS`, `pending_rows`, `group_inputs` (the draws of one model's groups, or of several models'
+group-major) and `picked_params` (their tail) — and
 the constrained pair suggest_constrained_thompson / suggest_scbo (scbo.py: the gate with `constrained=True`, the frame of a model)
 share, each thing once: the check of a count argument, the gate an optimizer passes before anything runs, the frame of the fitted
 model, the loop over groups of posterior draws, and the picks of a Thompson batch (suggest_thompson, suggest_turbo).  The ORDER of the refusals is part of the three functions' contract: a caller's own argument checks come
@@ -15,7 +17,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import fused_acquisition as A
-from ._lib import MAX_PATHS
+from ._lib import MAX_PATH_FEATURES, MAX_PATHS, MAX_QNEI_GROUPS, MAX_SEEDS
 from .engine import GroupEngine
 from .gpr import HipGPR
 
@@ -126,18 +128,73 @@ def pareto_gate(pareto, who: str, what: str):
     return eng
 
 
-def group_inputs(gp, rng, model: Model, n_groups: int, n_paths: int, n_features: int):
+#: the most draws a greedy draw batch takes: 16 groups of 16
+MAX_DRAWS = MAX_QNEI_GROUPS * MAX_PATHS
+
+
+def greedy_counts(q, n_random, n_draws, n_features):
+    """(q, n_random, n_draws, n_features) as ints, else ValueError — the count checks of the greedy draw batches, in their order."""
+    q = count(q, 1, MAX_SEEDS, f"q must be an integer in [1, {MAX_SEEDS}]")
+    n_random, n_features = int(n_random), int(n_features)
+    if n_random < 1:
+        raise ValueError("n_random must be >= 1")
+    if q > n_random:
+        raise ValueError("q must not exceed n_random")
+    n_draws = count(n_draws, 1, MAX_DRAWS, f"n_draws must be an integer in [1, {MAX_DRAWS}]")
+    if not 1 <= n_features <= MAX_PATH_FEATURES:
+        raise ValueError(f"n_features must be in [1, {MAX_PATH_FEATURES}]")
+    return q, n_random, n_draws, n_features
+
+
+def draw_layout(n_draws: int):
+    """(G, S): `n_draws` as G = ceil(n_draws / 16) groups of S = ceil(n_draws / G) draws each — every group the same size, as the
+    engine call wants them, so T = G * S >= n_draws (17 -> 2 x 9 = 18, 20 -> 2 x 10, 33 -> 3 x 11, 64 -> 4 x 16, 250 -> 16 x 16)."""
+    G = -(-int(n_draws) // MAX_PATHS)
+    return G, -(-int(n_draws) // G)
+
+
+def pending_rows(pending, space, d: int):
+    """`pending` (a list of parameter dicts, or an array (P, d)) as a float64 (P, d) array, None for no point"""
+    if pending is None:
+        return None
+    if isinstance(pending, (list, tuple)) and len(pending) and all(isinstance(p, dict) for p in pending):
+        try:
+            pending = [[p[k] for k in space.keys] for p in pending]
+        except KeyError as e:
+            raise ValueError(f"pending: a point lacks the parameter {e.args[0]!r}") from None
+    rows = np.asarray(pending, dtype=np.float64)
+    if rows.size == 0:
+        return None
+    if rows.ndim != 2 or rows.shape[1] != d:
+        raise ValueError(f"pending must be a list of parameter dicts or an array (P, {d})")
+    if not np.isfinite(rows).all():
+        raise ValueError("pending must be finite")
+    return np.ascontiguousarray(rows)
+
+
+def group_inputs(gp, rng, model, n_groups: int, n_paths: int, n_features: int):
     """`n_groups` groups of `n_paths` posterior draws as the greedy engine calls (`qnei_greedy`, `qnehvi_greedy`) take them: a list
     of (omega, phase, weights, eps), drawn from `rng` group after group in `draw_groups`' order — `spectral_draw` (fresh features),
-    `standard_normal((S, F))`, `standard_normal((S, N))` scaled by sqrt(noise)."""
+    `standard_normal((S, F))`, `standard_normal((S, N))` scaled by sqrt(noise).  With a list of GPs and the list of their models
+    (`cnei_greedy`'s slots): one such list per slot, drawn GROUP-MAJOR — per group, slot after slot."""
     from .thompson import spectral_draw
 
-    groups = []
+    several = isinstance(gp, (list, tuple))
+    gps, models = (gp, model) if several else ([gp], [model])
+    draws = [[] for _ in gps]
     for _ in range(n_groups):
-        omega, phase = spectral_draw(gp._kind, n_features, model.d, rng)
-        weights = rng.standard_normal((n_paths, n_features))
-        groups.append((omega, phase, weights, rng.standard_normal((n_paths, model.N)) * np.sqrt(model.noise)))
-    return groups
+        for groups, g, m in zip(draws, gps, models):
+            omega, phase = spectral_draw(g._kind, n_features, m.d, rng)
+            weights = rng.standard_normal((n_paths, n_features))
+            groups.append((omega, phase, weights, rng.standard_normal((n_paths, m.N)) * np.sqrt(m.noise)))
+    return draws if several else draws[0]
+
+
+def picked_params(eng, index, d: int, to_params):
+    """The tail of a greedy draw batch: (the picked candidate indices as int64, `to_params` of each picked row, fetched from the device)."""
+    index = np.asarray(index, dtype=np.int64)
+    rows = np.asarray(eng.get_candidate_rows(index, d), dtype=np.float64)
+    return index, [to_params(x) for x in rows]
 
 
 def draw_groups(gp, space, eng, rng, model: Model, n_draws: int, n_features: int, refine: int, max_iter, box=None):

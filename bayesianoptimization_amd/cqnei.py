@@ -18,10 +18,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _suggest as S
-from ._lib import MAX_CNEI_BASE as MAX_BASE, MAX_PATH_FEATURES as MAX_FEATURES, MAX_SEEDS as MAX_Q
-from .qnei import MAX_DRAWS, _pending_rows, draw_layout
+from ._lib import MAX_CNEI_BASE as MAX_BASE
 from .scbo import _fit_models
-from .thompson import spectral_draw
 
 
 def default_floor(target) -> float:
@@ -59,22 +57,14 @@ def suggest_constrained_qnei(optimizer, q: int, n_random: int = 10_000, n_draws:
     points, pending of another shape or not finite, a floor that is not finite, a space without a constraint (use suggest_qnei).
     TargetSpaceEmptyError on an empty space.  NotImplementedError, never a host fallback: `suggest_constrained_thompson`'s cases."""
     who = "suggest_constrained_qnei"
-    q = S.count(q, 1, MAX_Q, f"q must be an integer in [1, {MAX_Q}]")
-    n_random, n_features = int(n_random), int(n_features)
-    if n_random < 1:
-        raise ValueError("n_random must be >= 1")
-    if q > n_random:
-        raise ValueError("q must not exceed n_random")
-    n_draws = S.count(n_draws, 1, MAX_DRAWS, f"n_draws must be an integer in [1, {MAX_DRAWS}]")
-    if not 1 <= n_features <= MAX_FEATURES:
-        raise ValueError(f"n_features must be in [1, {MAX_FEATURES}]")
+    q, n_random, n_draws, n_features = S.greedy_counts(q, n_random, n_draws, n_features)
     if floor is not None and not np.isfinite(floor):
         raise ValueError("floor must be finite")
     gp, space, eng = S.gate(optimizer, who, "batched", ("cnei_greedy",), "a device group has no path sampler; use a single device",
                             constrained=True)
     if space.constraint is None:
         raise ValueError(f"{who}: the space has no constraint; use suggest_qnei")
-    pending = _pending_rows(pending, space, int(space.bounds.shape[0]))
+    pending = S.pending_rows(pending, space, int(space.bounds.shape[0]))
     base = np.asarray(space.params, dtype=np.float64)
     if pending is not None:
         base = np.concatenate([base, pending])
@@ -84,21 +74,14 @@ def suggest_constrained_qnei(optimizer, q: int, n_random: int = 10_000, n_draws:
 
     gps, models = _fit_models(gp, space, eng, who)
     eng.generate_candidates_like(n_random, space.bounds[:, 0], space.bounds[:, 1], rng)
-    G, n_paths = draw_layout(n_draws)
-    draws = [[] for _ in gps]
-    for _ in range(G):
-        for j, (g, m) in enumerate(zip(gps, models)):
-            omega, phase = spectral_draw(g._kind, n_features, m.d, rng)
-            weights = rng.standard_normal((n_paths, n_features))
-            draws[j].append((omega, phase, weights, rng.standard_normal((n_paths, m.N)) * np.sqrt(m.noise)))
+    G, n_paths = S.draw_layout(n_draws)
+    draws = S.group_inputs(list(gps), rng, list(models), G, n_paths, n_features)
     for g in gps:
         g._ensure_resident()
     cons = space.constraint
     out = eng.cnei_greedy(draws, q, cons.lb, cons.ub, default_floor(space.target) if floor is None else float(floor),
                           base=np.ascontiguousarray(base), y_mean=[m.y_mean for m in models], y_std=[m.y_std for m in models])
-    index = np.asarray(out["index"], dtype=np.int64)
-    rows = np.asarray(eng.get_candidate_rows(index, models[0].d), dtype=np.float64)
-    picks = [space.array_to_params(x) for x in rows]
+    index, picks = S.picked_params(eng, out["index"], models[0].d, space.array_to_params)
     if return_info:
         return picks, {"gain": np.asarray(out["gain"], dtype=np.float64), "index": index,
                        "feasible": np.asarray(out["feasible"], dtype=np.float64),

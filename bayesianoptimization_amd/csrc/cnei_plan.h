@@ -7,7 +7,7 @@
 
 namespace gpbo {
 
-// The workspace (ctx->cnei), offsets in doubles from its start, every part at an even offset (the block and the scaled base points
+// The workspace (in ctx->greedy), offsets in doubles from its start, every part at an even offset (the block and the scaled base points
 // are read as double2).  T = G S draws, M candidates, B = n_base base points:
 //   vals [T][M]        the MASKED objective draws over the candidates, row t = g S + s: f, -inf where the draw calls the
 //                      candidate infeasible, NaN kept — 8 T M bytes, the block the score kernel streams

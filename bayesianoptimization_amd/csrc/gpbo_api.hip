@@ -227,9 +227,8 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (auto ev : ctx->qnei_ev) if (ev) (void)hipEventDestroy(ev);
-  for (auto ev : ctx->cnei_ev) if (ev) (void)hipEventDestroy(ev);
-  for (auto ev : ctx->qnehvi_ev) if (ev) (void)hipEventDestroy(ev);
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock})
+    for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
   if (ctx->small_pinned) (void)hipHostFree(ctx->small_pinned);
@@ -240,7 +239,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->qnei, ctx->cnei, ctx->qnehvi, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1576,6 +1575,43 @@ int gpbo_ehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, cons
   return GPBO_OK;
 }
 
+// The refusals the greedy draw batches (gpbo_qnei_greedy, gpbo_qnhvi_greedy, gpbo_cnei_greedy) share, in three pieces that each
+// entry point calls in its own order; w: "<who>: ".
+// ... of the entry points over several slots: the counts (as check_path_args orders them), a NULL argument, then check_path_args
+// per slot 0 .. n_slots - 1
+static int check_greedy_slots(gpbo_ctx* ctx, const char* who, int n_groups, int n_paths, int n_features, bool given, int n_slots,
+                              const double* y_mean, const double* y_std, const Model** ms) {
+  const std::string w = std::string(who) + ": ";
+  if (n_groups < 1 || n_groups > GPBO_MAX_QNEI_GROUPS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups out of range [1, 16]");
+  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_paths out of range [1, 16]");
+  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_features out of range [1, 4096]");
+  if (!given) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL argument");
+  int rc;
+  for (int j = 0; j < n_slots; ++j)
+    if ((rc = check_path_args(ctx, who, j, y_mean[j], y_std[j], n_paths, n_features, 1, nullptr, &ms[j]))) return rc;
+  return GPBO_OK;
+}
+// ... of the call's point set (noun: "pending" / "base"; at most `limit` points in the model's d dimensions, whose: "model's" /
+// "models'")
+static int check_greedy_points(gpbo_ctx* ctx, const std::string& w, const char* noun, const double* pts, int n, int limit, int d,
+                               int model_d, const char* whose) {
+  const std::string count = std::string("n_") + noun;
+  if (n < 0 || n > limit) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + count + " out of range [0, " + std::to_string(limit) + "]");
+  if (n > 0 && !pts) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL " + noun + " with " + count + " > 0");
+  if (d != model_d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "d differs from the fitted " + whose);
+  for (int64_t i = 0; i < (int64_t)n * d; ++i)
+    if (!std::isfinite(pts[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + noun + " must be finite");
+  return GPBO_OK;
+}
+// ... of the resident candidates against every slot's model (whose: "the fitted model's" / "the fitted models'" / "a fitted model's")
+static int check_greedy_candidates(gpbo_ctx* ctx, const std::string& w, int n_slots, const Model* const* ms, const char* whose, int q) {
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates)");
+  for (int j = 0; j < n_slots; ++j)
+    if (ctx->d_c != ms[j]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from " + whose);
+  if (q > ctx->M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q exceeds the number of resident candidates");
+  return GPBO_OK;
+}
+
 int gpbo_qnei_greedy(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n_groups, int n_paths, int n_features,
                      const double* omega, const double* phase, const double* weights, const double* eps, int noisy, double y_best,
                      const double* pending, int n_pending, int d, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain,
@@ -1584,20 +1620,14 @@ int gpbo_qnei_greedy(gpbo_ctx* ctx, int slot, double y_mean, double y_std, int n
   const char* who = "qnei_greedy";
   const std::string w = std::string(who) + ": ";
   if (n_groups < 1 || n_groups > GPBO_MAX_QNEI_GROUPS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups out of range [1, 16]");
-  const Model* m;
+  const Model* m;      // (one slot: a NULL argument is check_path_args' `missing`, behind the slot and the counts)
   const bool given = omega && phase && weights && eps && pick_idx && pick_gain && baseline_out;
   int rc = check_path_args(ctx, who, slot, y_mean, y_std, n_paths, n_features, 1, given ? nullptr : "NULL argument", &m);
   if (rc) return rc;
   if (!noisy && !std::isfinite(y_best)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "y_best must be finite when noisy == 0");
-  if (n_pending < 0 || n_pending > GPBO_MAX_QNEI_POINTS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_pending out of range [0, 64]");
-  if (n_pending > 0 && !pending) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL pending with n_pending > 0");
-  if (d != m->d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "d differs from the fitted model's");
-  for (int64_t i = 0; i < (int64_t)n_pending * d; ++i)
-    if (!std::isfinite(pending[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "pending must be finite");
+  if ((rc = check_greedy_points(ctx, w, "pending", pending, n_pending, GPBO_MAX_QNEI_POINTS, d, m->d, "model's"))) return rc;
   if (q < 1 || q > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q out of range [1, 64]");
-  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates)");
-  if (ctx->d_c != m->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from the fitted model's");
-  if (q > ctx->M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q exceeds the number of resident candidates");
+  if ((rc = check_greedy_candidates(ctx, w, 1, &m, "the fitted model's", q))) return rc;
   return launch_qnei_greedy(ctx, *m, ctx->M, y_mean, y_std, n_groups, n_paths, n_features, omega, phase, weights, eps, noisy, y_best,
                             pending, n_pending, q, index_offset, pick_idx, pick_gain, baseline_out, values_out, keys_out);
 }
@@ -1609,27 +1639,15 @@ int gpbo_qnhvi_greedy(gpbo_ctx* ctx, const double* y_mean, const double* y_std, 
   if (!ctx) return GPBO_ERR_INVALID;
   const char* who = "qnehvi_greedy";
   const std::string w = std::string(who) + ": ";
-  if (n_groups < 1 || n_groups > GPBO_MAX_QNEI_GROUPS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups out of range [1, 16]");
-  // the counts first, as check_path_args orders them
-  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_paths out of range [1, 16]");
-  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_features out of range [1, 4096]");
-  if (!y_mean || !y_std || !omega || !phase || !weights || !eps || !ref || !pick_idx || !pick_gain)
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL argument");
-  int rc;
+  const bool given = y_mean && y_std && omega && phase && weights && eps && ref && pick_idx && pick_gain;
   const Model* ms[2];
-  for (int j = 0; j < 2; ++j)
-    if ((rc = check_path_args(ctx, who, j, y_mean[j], y_std[j], n_paths, n_features, 1, nullptr, &ms[j]))) return rc;
+  int rc = check_greedy_slots(ctx, who, n_groups, n_paths, n_features, given, 2, y_mean, y_std, ms);
+  if (rc) return rc;
   if (!std::isfinite(ref[0]) || !std::isfinite(ref[1])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "ref must be finite");
-  if (n_base < 0 || n_base > GPBO_MAX_QNEHVI_BASE) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_base out of range [0, 16384]");
-  if (n_base > 0 && !base) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL base with n_base > 0");
-  if (d != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "d differs from the fitted models'");
-  for (int64_t i = 0; i < (int64_t)n_base * d; ++i)
-    if (!std::isfinite(base[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "base must be finite");
+  if ((rc = check_greedy_points(ctx, w, "base", base, n_base, GPBO_MAX_QNEHVI_BASE, d, ms[0]->d, "models'"))) return rc;
   if (q < 1 || q > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q out of range [1, 64]");
   if (ms[1]->d != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the two objectives' models differ in dimension");
-  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates)");
-  if (ctx->d_c != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from the fitted models'");
-  if (q > ctx->M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q exceeds the number of resident candidates");
+  if ((rc = check_greedy_candidates(ctx, w, 2, ms, "the fitted models'", q))) return rc;
   return launch_qnehvi_greedy(ctx, ms, ctx->M, y_mean, y_std, n_groups, n_paths, n_features, omega, phase, weights, eps, ref, base,
                               n_base, q, index_offset, pick_idx, pick_gain, front_size_out, fronts_out, values_out, base_values_out,
                               keys_out);
@@ -1645,30 +1663,17 @@ int gpbo_cnei_greedy(gpbo_ctx* ctx, int n_constraints, const double* y_mean, con
   const std::string w = std::string(who) + ": ";
   const int C = n_constraints;
   if (C < 1 || C > GPBO_MAX_MODELS - 1) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_constraints out of range [1, 7]");
-  if (n_groups < 1 || n_groups > GPBO_MAX_QNEI_GROUPS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups out of range [1, 16]");
-  // the counts first, as check_path_args orders them
-  if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_paths out of range [1, 16]");
-  if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_features out of range [1, 4096]");
-  if (!y_mean || !y_std || !lb || !ub || !omega || !phase || !weights || !eps || !pick_idx || !pick_gain || !pick_feasible || !baseline_out)
-    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL argument");
-  int rc;
+  const bool given = y_mean && y_std && lb && ub && omega && phase && weights && eps && pick_idx && pick_gain && pick_feasible && baseline_out;
   const Model* ms[GPBO_MAX_MODELS];
-  for (int j = 0; j <= C; ++j)
-    if ((rc = check_path_args(ctx, who, j, y_mean[j], y_std[j], n_paths, n_features, 1, nullptr, &ms[j]))) return rc;
+  int rc = check_greedy_slots(ctx, who, n_groups, n_paths, n_features, given, C + 1, y_mean, y_std, ms);
+  if (rc) return rc;
   for (int j = 0; j < C; ++j)
     if (lb[j] != lb[j] || ub[j] != ub[j] || !(lb[j] < ub[j]))
       GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "the bounds must not be NaN, with lb < ub for every constraint");
   if (!std::isfinite(y_floor)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "y_floor must be finite");
-  if (n_base < 0 || n_base > GPBO_MAX_CNEI_BASE) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_base out of range [0, 16384]");
-  if (n_base > 0 && !base) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL base with n_base > 0");
-  if (d != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "d differs from the fitted models'");
-  for (int64_t i = 0; i < (int64_t)n_base * d; ++i)
-    if (!std::isfinite(base[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "base must be finite");
+  if ((rc = check_greedy_points(ctx, w, "base", base, n_base, GPBO_MAX_CNEI_BASE, d, ms[0]->d, "models'"))) return rc;
   if (q < 1 || q > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q out of range [1, 64]");
-  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates resident (call gpbo_set_candidates)");
-  for (int j = 0; j <= C; ++j)
-    if (ctx->d_c != ms[j]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the resident candidates' dimension differs from a fitted model's");
-  if (q > ctx->M) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q exceeds the number of resident candidates");
+  if ((rc = check_greedy_candidates(ctx, w, C + 1, ms, "a fitted model's", q))) return rc;
   return launch_cnei_greedy(ctx, C, ms, ctx->M, y_mean, y_std, lb, ub, n_groups, n_paths, n_features, omega, phase, weights, eps,
                             y_floor, base, n_base, q, index_offset, pick_idx, pick_gain, pick_feasible, baseline_out, values_out,
                             viol_out, base_values_out, keys_out);
@@ -1836,25 +1841,27 @@ int gpbo_debug_kg_stage_ms(gpbo_ctx* ctx, float* ms) {
   return debug_kg_stage_ms(ctx, ms);
 }
 
+// The stage clocks of the greedy draw batches (greedy.h: greedy_mark records them): ms[i] the kernel time between events i and
+// i + 1 of `call`'s last run — qnei / cnei: the draws and baselines, the steps; qnehvi: the draws, the front build, the steps
+static int greedy_stage_ms(gpbo_ctx* ctx, const StageClock& c, const std::string& who, const char* call, float* ms) {
+  if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, who + ": NULL output");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  if (!c.used) GPBO_FAIL(ctx, GPBO_ERR_STATE, who + ": no " + call + " call to report");
+  GPBO_HIP(ctx, hipEventSynchronize(c.ev[c.n - 1]));
+  for (int i = 0; i + 1 < c.n; ++i) GPBO_HIP(ctx, hipEventElapsedTime(&ms[i], c.ev[i], c.ev[i + 1]));
+  return GPBO_OK;
+}
 int gpbo_debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
-  if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_qnei_stage_ms: NULL output");
-  GPBO_HIP(ctx, hipSetDevice(ctx->device));
-  return debug_qnei_stage_ms(ctx, ms);
+  return greedy_stage_ms(ctx, ctx->qnei_clock, "debug_qnei_stage_ms", "gpbo_qnei_greedy", ms);
 }
-
 int gpbo_debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
-  if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_cnei_stage_ms: NULL output");
-  GPBO_HIP(ctx, hipSetDevice(ctx->device));
-  return debug_cnei_stage_ms(ctx, ms);
+  return greedy_stage_ms(ctx, ctx->cnei_clock, "debug_cnei_stage_ms", "gpbo_cnei_greedy", ms);
 }
-
 int gpbo_debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
-  if (!ms) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_qnehvi_stage_ms: NULL output");
-  GPBO_HIP(ctx, hipSetDevice(ctx->device));
-  return debug_qnehvi_stage_ms(ctx, ms);
+  return greedy_stage_ms(ctx, ctx->qnehvi_clock, "debug_qnehvi_stage_ms", "gpbo_qnhvi_greedy", ms);
 }
 
 int gpbo_debug_qnehvi_fronts(gpbo_ctx* ctx, int n_draws, int n, const double* base_values, const double* ref, int n_insert,

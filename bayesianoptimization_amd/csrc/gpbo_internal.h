@@ -100,6 +100,13 @@ struct EventPair {
   hipEvent_t a = nullptr, b = nullptr;
   bool used = false;
 };
+// debug build: the n <= 4 events around the stages of an entry point's last call (greedy.h: greedy_mark; gpbo_api.hip: greedy_stage_ms); the
+// product records nothing.  The fields exist in both builds: one layout.
+struct StageClock {
+  int n = 0;
+  hipEvent_t ev[4] = {};
+  bool used = false;
+};
 
 // Cholesky look-ahead (chol_kernels.hip): the bulk stream that carries the far part of a rank-512 trailing update while
 // the next outer panel's chain runs on `main`, and the events the two streams hand each other.  One per main stream
@@ -174,22 +181,15 @@ struct gpbo_ctx {
   int64_t cap_kg = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
-  double* qnei = nullptr;  // gpbo_qnei_greedy: the draws' values (T, M), their incumbents, the pending points, mask and records (qnei_plan.h)
-  int64_t cap_qnei = 0;
-  double* qnehvi = nullptr;  // gpbo_qnhvi_greedy: both objectives' draws (2, T, M), their values at the base points, the fronts, mask and records (qnehvi_plan.h)
-  int64_t cap_qnehvi = 0;
-  double* cnei = nullptr;  // gpbo_cnei_greedy: the masked objective draws (T, M), their incumbents, one group's violations, the base points, mask and records (cnei_plan.h)
-  int64_t cap_cnei = 0;
+  double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
+  int64_t cap_greedy = 0;
   hipEvent_t kg_ev[4] = {};   // debug build: around the three stages of the last gpbo_kg_argbest (the fields exist in both builds: one layout)
   bool kg_ev_used = false;
   hipEvent_t gen_ev[2] = {};  // debug build: around the kernel of the last gpbo_generate_candidates / _trust_region (generate_mark)
   bool gen_ev_used = false;
-  hipEvent_t qnei_ev[3] = {}; // debug build: before the draws, between the baselines and the greedy steps, behind the last step of the last gpbo_qnei_greedy
-  bool qnei_ev_used = false;
-  hipEvent_t cnei_ev[3] = {}; // debug build: the same three events of the last gpbo_cnei_greedy
-  bool cnei_ev_used = false;
-  hipEvent_t qnehvi_ev[4] = {}; // debug build: before the draws, behind them, behind the front build, behind the last step of the last gpbo_qnhvi_greedy
-  bool qnehvi_ev_used = false;
+  gpbo::StageClock qnei_clock{3};   // before the draws, between the baselines and the greedy steps, behind the last step of the last gpbo_qnei_greedy
+  gpbo::StageClock cnei_clock{3};   // the same three events of the last gpbo_cnei_greedy
+  gpbo::StageClock qnehvi_clock{4}; // before the draws, behind them, behind the front build, behind the last step of the last gpbo_qnhvi_greedy
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -689,12 +689,12 @@ int launch_kg_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* poi
 // of level indices (all host).  The caller has checked every argument.  The call's workspace is ctx->ehvi.
 int launch_ehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels, const double* levels, int64_t n_cells,
                        const uint8_t* cell_lo, const uint8_t* cell_hi);
-// qnei.hip: gpbo_qnei_greedy behind its argument checks (include/gpbo.h has the formulas; qnei_plan.h the workspace, ctx->qnei)
+// qnei.hip: gpbo_qnei_greedy behind its argument checks (include/gpbo.h has the formulas; qnei_plan.h the workspace, in ctx->greedy)
 int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int n_groups, int n_paths, int n_features,
                        const double* omega, const double* phase, const double* weights, const double* eps, int noisy, double y_best,
                        const double* pending, int n_pending, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain,
                        double* baseline_out, double* values_out, double* keys_out);
-// qnei.hip: gpbo_cnei_greedy behind its argument checks (include/gpbo.h has the rule; cnei_plan.h the workspace, ctx->cnei): ms /
+// qnei.hip: gpbo_cnei_greedy behind its argument checks (include/gpbo.h has the rule; cnei_plan.h the workspace, in ctx->greedy): ms /
 // y_mean / y_std per slot 0 .. C, lb / ub per constraint, the draws' inputs concatenated slot-major, then group-major
 int launch_cnei_greedy(gpbo_ctx* ctx, int n_constraints, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std,
                        const double* lb, const double* ub, int n_groups, int n_paths, int n_features, const double* omega,
@@ -702,16 +702,13 @@ int launch_cnei_greedy(gpbo_ctx* ctx, int n_constraints, const Model* const* ms,
                        int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain, double* pick_feasible, double* baseline_out,
                        double* values_out, double* viol_out, double* base_values_out, double* keys_out);
 // qnehvi.hip: gpbo_qnhvi_greedy behind its argument checks (include/gpbo.h has the formulas; qnehvi_plan.h the workspace,
-// ctx->qnehvi): ms / y_mean / y_std per objective, the draws' inputs concatenated in slot order
+// in ctx->greedy): ms / y_mean / y_std per objective, the draws' inputs concatenated in slot order
 int launch_qnehvi_greedy(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std, int n_groups,
                          int n_paths, int n_features, const double* omega, const double* phase, const double* weights,
                          const double* eps, const double* ref, const double* base, int n_base, int q, int64_t index_offset,
                          int64_t* pick_idx, double* pick_gain, int* front_size_out, double* fronts_out, double* values_out,
                          double* base_values_out, double* keys_out);
 #ifdef GPBO_DEBUG
-int debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms2);
-int debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms2);
-int debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms3);
 int debug_qnehvi_fronts(gpbo_ctx* ctx, int T, int n, const double* base_values, const double* ref, int n_insert,
                         const double* insert_values, int* front_size_out, double* fronts_out);
 int debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out);

@@ -19,7 +19,7 @@
 //                          NaN wins), files {gain, index}, marks the mask, and thread t inserts column `pick` of the blocks into
 //                          draw t's front (qnehvi_insert)
 // No multiply-add in any of them (the file is compiled with -ffp-contract=off as well): tests replay the keys bit for bit.
-#include "gpbo_internal.h"
+#include "greedy.h"
 #include "qnehvi_plan.h"
 
 #include <cmath>
@@ -28,9 +28,6 @@
 
 namespace gpbo {
 
-struct QnehviRecord { double gain; int64_t idx; };
-static_assert(sizeof(QnehviRecord) == 16, "a record is two doubles of the workspace");
-static_assert(sizeof(QnehviRecord) * GPBO_MAX_SEEDS <= PIN_AUX_SEL_OUT_BYTES, "the picks' records outgrew the selection's pinned window");
 static_assert(QNEI_MAX_DRAWS <= QNEI_BLOCK, "qnehvi_update_kernel gives every draw a thread of its one workgroup");
 
 // (a, c) < (oa, oc) in the lexicographic order of the front's arg-max
@@ -200,38 +197,22 @@ __global__ __launch_bounds__(QNEI_BLOCK) void qnehvi_score_kernel(const double* 
   }
 }
 
-// Behind step j's selection: the pick (the first NaN wins, else the selection's first pick), its record, the mask, the fronts.
+// Behind step j's selection: the pick (greedy_pick), its record, the mask, the fronts.
 __global__ __launch_bounds__(QNEI_BLOCK) void qnehvi_update_kernel(const SelState* __restrict__ st, const Key* __restrict__ first,
                                                                    const double* __restrict__ vals, int64_t M, int T, int64_t offset,
                                                                    int j, double ref0, double ref1, double2* __restrict__ front,
                                                                    int* __restrict__ size, uint8_t* __restrict__ mask,
-                                                                   QnehviRecord* __restrict__ rec, int* __restrict__ flag) {
-  const bool nan = st->first_nan != INT64_MAX;
-  const int64_t pick = nan ? st->first_nan : first->i;
-  const bool valid = pick >= 0 && pick < M;      // (always, with q <= M: a pick outside the candidates touches nothing)
+                                                                   GreedyRecord* __restrict__ rec, int* __restrict__ flag) {
+  const GreedyPick p = greedy_pick(st, first, M, offset);
+  const int64_t pick = p.local;
   const int t = threadIdx.x;
   if (t == 0) {
-    QnehviRecord r;
-    r.gain = (nan || !valid) ? std::numeric_limits<double>::quiet_NaN() : -first->v;
-    r.idx = valid ? pick + offset : -1;
-    rec[j] = r;
-    if (valid) mask[pick] = 1;
+    rec[j] = GreedyRecord{p.gain, p.idx};
+    if (pick >= 0) mask[pick] = 1;
   }
-  if (!valid || t >= T) return;
+  if (pick < 0 || t >= T) return;
   const double y0 = vals[(int64_t)t * M + pick], y1 = vals[((int64_t)T + t) * M + pick];
   if (qnehvi_insert(front + (int64_t)t * QNEHVI_FRONT, size + t, y0, y1, ref0, ref1)) atomicMax(flag, T - t);
-}
-
-// debug build: events before the draws, behind them, behind the front build and behind the last step of the last call
-// (gpbo_debug_qnehvi_stage_ms); the product records nothing
-static inline void qnehvi_mark(gpbo_ctx* ctx, int i) {
-#ifdef GPBO_DEBUG
-  if (!ctx->qnehvi_ev[i]) (void)hipEventCreate(&ctx->qnehvi_ev[i]);
-  (void)hipEventRecord(ctx->qnehvi_ev[i], ctx->stream);
-  ctx->qnehvi_ev_used = (i == 3);
-#else
-  (void)ctx; (void)i;
-#endif
 }
 
 // the refusal behind the call's one synchronisation: flag = T - t for the lowest draw t whose front outgrew its array
@@ -241,13 +222,6 @@ static int qnehvi_overflow(gpbo_ctx* ctx, const char* who, int T, int flag) {
 }
 
 #ifdef GPBO_DEBUG
-int debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms) {
-  if (!ctx->qnehvi_ev_used) GPBO_FAIL(ctx, GPBO_ERR_STATE, "debug_qnehvi_stage_ms: no gpbo_qnhvi_greedy call to report");
-  GPBO_HIP(ctx, hipEventSynchronize(ctx->qnehvi_ev[3]));
-  for (int i = 0; i < 3; ++i) GPBO_HIP(ctx, hipEventElapsedTime(&ms[i], ctx->qnehvi_ev[i], ctx->qnehvi_ev[i + 1]));
-  return GPBO_OK;
-}
-
 // the insertion rule on given values: thread t inserts (ins[t ld + i], ins[(T + t) ld + i]), i = 0 .. n_insert - 1 in order
 __global__ __launch_bounds__(QNEI_BLOCK) void qnehvi_insert_kernel(const double* __restrict__ ins, int64_t ld, int n_insert, int T,
                                                                    double ref0, double ref1, double2* __restrict__ front,
@@ -263,8 +237,8 @@ int debug_qnehvi_fronts(gpbo_ctx* ctx, int T, int n, const double* base_values, 
                         const double* insert_values, int* front_size_out, double* fronts_out) {
   int rc;
   const QnehviBlock b = qnehvi_block(T, n_insert, n, 1, 4, 1);      // the inserted values take the block's place
-  if ((rc = ensure(ctx, &ctx->qnehvi, &ctx->cap_qnehvi, b.doubles))) return rc;
-  double* w = ctx->qnehvi;
+  if ((rc = ensure(ctx, &ctx->greedy, &ctx->cap_greedy, b.doubles))) return rc;
+  double* w = ctx->greedy;
   double2* front = (double2*)(w + b.front);
   int *size = (int*)(w + b.size), *flag = (int*)(w + b.flag);
   GPBO_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
@@ -298,67 +272,60 @@ int launch_qnehvi_greedy(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const
   int rc;
   const int d = ms[0]->d, DP = ms[0]->DP, T = G * S;
   const QnehviBlock b = qnehvi_block(T, M, B, d, DP, q);
-  if ((rc = ensure(ctx, &ctx->qnehvi, &ctx->cap_qnehvi, b.doubles))) return rc;
-  double* w = ctx->qnehvi;
+  if ((rc = ensure(ctx, &ctx->greedy, &ctx->cap_greedy, b.doubles))) return rc;
+  double* w = ctx->greedy;
   double *vals = w + b.vals, *basev = w + b.basev;
   double2 *front = (double2*)(w + b.front), *front0 = (double2*)(w + b.front0);
   int *size = (int*)(w + b.size), *size0 = (int*)(w + b.size0), *flag = (int*)(w + b.flag);
   uint8_t* mask = (uint8_t*)(w + b.mask);
-  QnehviRecord* rec = (QnehviRecord*)(w + b.rec);
+  GreedyRecord* rec = (GreedyRecord*)(w + b.rec);
   const int64_t Mp = round_up(M, POST_CANDS);
   if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * DP))) return rc;
   if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, M))) return rc;
-  qnehvi_mark(ctx, 0);
+  greedy_mark(ctx, ctx->qnehvi_clock, 0);
   GPBO_HIP(ctx, hipMemsetAsync(mask, 0, (size_t)((M + 7) / 8 * 8), ctx->stream));
   GPBO_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
   if (B > 0) GPBO_HIP(ctx, hipMemcpyAsync(w + b.base, base_pts, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   // the draws, slot by slot (the candidates and the base points scaled by the slot's length scales) and group by group: the
   // group's inputs and path weights into the paths workspace, then its S rows of each buffer
-  const double* eps_j = eps;
+  const GreedyDraws draws = greedy_draws(2, ms, G, S, F, omega, phase, weights, eps);
   for (int j = 0; j < 2; ++j) {
     const Model& m = *ms[j];
-    const int N = (int)m.N;
     double* base_s = w + b.base_s + (int64_t)j * B * DP;
     if ((rc = launch_prescale(ctx, ctx->Xc, M, d, DP, m.ls, ctx->Xcs, Mp))) return rc;
     if (B > 0 && (rc = launch_prescale(ctx, w + b.base, B, d, DP, m.ls, base_s, B))) return rc;
     for (int g = 0; g < G; ++g) {
-      const int64_t jg = (int64_t)j * G + g;
       PathWorkspace ws{};
-      if ((rc = launch_path_weights(ctx, m, S, F, omega + jg * F * d, phase + jg * F, weights + jg * S * F, eps_j + (int64_t)g * S * N,
-                                    0, &ws)))
-        return rc;
+      if ((rc = greedy_path_weights(ctx, draws, m, j, g, &ws))) return rc;
       const int64_t row = (int64_t)j * T + (int64_t)g * S;
       if ((rc = launch_paths_over(ctx, m, ws, y_mean[j], y_std[j], S, F, ctx->Xcs, M, vals + row * M, M))) return rc;
       if (B > 0 && (rc = launch_paths_over(ctx, m, ws, y_mean[j], y_std[j], S, F, base_s, B, basev + row * b.ldb, b.ldb))) return rc;
     }
-    eps_j += (int64_t)G * S * N;
   }
-  qnehvi_mark(ctx, 1);
+  greedy_mark(ctx, ctx->qnehvi_clock, 1);
   const dim3 block(QNEI_BLOCK);
   qnehvi_front_kernel<<<dim3((unsigned)T), block, 0, ctx->stream>>>(basev, basev + (int64_t)T * b.ldb, b.ldb, B, ref[0], ref[1], T, front,
                                                                     front0, size, size0, flag);
   GPBO_HIP(ctx, hipGetLastError());
-  qnehvi_mark(ctx, 2);
-  // the greedy steps, all on the stream
+  greedy_mark(ctx, ctx->qnehvi_clock, 2);
   const int items = qnei_items(M);
   const dim3 grid((unsigned)qnei_score_blocks(M));
-  for (int j = 0; j < q; ++j) {
-    if (items == 2) qnehvi_score_kernel<2><<<grid, block, 0, ctx->stream>>>(vals, M, T, front, size, ref[0], ref[1], mask, ctx->ys);
-    else qnehvi_score_kernel<1><<<grid, block, 0, ctx->stream>>>(vals, M, T, front, size, ref[0], ref[1], mask, ctx->ys);
-    GPBO_HIP(ctx, hipGetLastError());
-    if (keys_out)
-      GPBO_HIP(ctx, hipMemcpyAsync(keys_out + (int64_t)j * M, ctx->ys, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    const SelState* st; const Key* first;
-    if ((rc = enqueue_values_select(ctx, M, &st, &first))) return rc;
-    qnehvi_update_kernel<<<dim3(1), block, 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, ref[0], ref[1], front, size, mask,
-                                                             rec, flag);
-    GPBO_HIP(ctx, hipGetLastError());
-  }
-  qnehvi_mark(ctx, 3);
-  QnehviRecord* hrec = (QnehviRecord*)((char*)ctx->pinned_aux + PIN_AUX_SEL_OUT);
+  rc = greedy_steps(
+      ctx, M, q, keys_out,
+      [&] {
+        if (items == 2) qnehvi_score_kernel<2><<<grid, block, 0, ctx->stream>>>(vals, M, T, front, size, ref[0], ref[1], mask, ctx->ys);
+        else qnehvi_score_kernel<1><<<grid, block, 0, ctx->stream>>>(vals, M, T, front, size, ref[0], ref[1], mask, ctx->ys);
+      },
+      [&](const SelState* st, const Key* first, int j) {
+        qnehvi_update_kernel<<<dim3(1), block, 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, ref[0], ref[1], front, size,
+                                                                 mask, rec, flag);
+      });
+  if (rc) return rc;
+  greedy_mark(ctx, ctx->qnehvi_clock, 3);
+  const GreedyRecord* hrec;
   int over = 0;
   const size_t front_bytes = (size_t)T * QNEHVI_FRONT * 2 * sizeof(double);
-  GPBO_HIP(ctx, hipMemcpyAsync(hrec, rec, sizeof(QnehviRecord) * (size_t)q, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = greedy_fetch(ctx, rec, q, &hrec))) return rc;
   GPBO_HIP(ctx, hipMemcpyAsync(&over, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   if (front_size_out) {
     GPBO_HIP(ctx, hipMemcpyAsync(front_size_out, size0, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));

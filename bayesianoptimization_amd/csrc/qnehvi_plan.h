@@ -26,7 +26,7 @@ inline int qnehvi_chunk_draws(int T) { return T < QNEHVI_CHUNK ? T : QNEHVI_CHUN
 inline int qnehvi_chunks(int T) { return (T + QNEHVI_CHUNK - 1) / QNEHVI_CHUNK; }
 constexpr int64_t QNEHVI_LDS_BYTES = (int64_t)QNEHVI_CHUNK * QNEHVI_STRIPS * 16 + QNEHVI_CHUNK * 4;
 
-// The workspace (ctx->qnehvi), offsets in doubles from its start, every part at an even offset (the blocks and the fronts are read
+// The workspace (in ctx->greedy), offsets in doubles from its start, every part at an even offset (the blocks and the fronts are read
 // 16 bytes at a time); objective j = slot j, T draws, M candidates, B = n_base:
 //   vals [2][T][M]        the draws' values over the candidates, objective-major: 16 T M bytes — 4 GiB at T = 256, M = 2^20
 //   basev [2][T][ldb]     the draws' values at the B base points, ldb = B

@@ -20,19 +20,15 @@
 // and fmax(m_t, -inf) = m_t.  New for it:
 //   cnei_update_kernel     qnei_update_kernel's work (the one device function both call) plus the share of draws that call the
 //                          pick feasible, in a record {gain, index, feasible} of its own
-#include "gpbo_internal.h"
+#include "greedy.h"
 
 #include <cmath>
 #include <limits>
 
 namespace gpbo {
 
-struct QneiRecord { double gain; int64_t idx; };
-static_assert(sizeof(QneiRecord) == 16, "a record is two doubles of the workspace");
-static_assert(sizeof(QneiRecord) * GPBO_MAX_SEEDS <= PIN_AUX_SEL_OUT_BYTES, "the picks' records outgrew the selection's pinned window");
-struct CneiRecord { double gain; int64_t idx; double feasible; };      // gpbo_cnei_greedy's
+struct CneiRecord { double gain; int64_t idx; double feasible; };      // gpbo_cnei_greedy's (greedy_fetch checks its room)
 static_assert(sizeof(CneiRecord) == 24, "a record is three doubles of the workspace");
-static_assert(sizeof(CneiRecord) * GPBO_MAX_SEEDS <= PIN_AUX_SEL_ROOM, "the picks' records outgrew the room behind the selection's pinned window");
 
 // m[t] = m0[t] = fmax fold of (y_best unless noisy) and base[t][c0 .. ldb): lane l takes c0 + l, c0 + l + 64, ..., the 64 partial
 // maxima meet in a butterfly.  fmax drops a NaN operand and orders numbers totally up to a zero's sign, so the fold's value is the
@@ -89,32 +85,23 @@ __global__ __launch_bounds__(QNEI_BLOCK) void qnei_score_kernel(const double* __
   }
 }
 
-// Behind step j's selection, for both update kernels: the pick (the first NaN wins, else the selection's first pick), the mask, the
-// incumbents.  Hands back the record's gain and index, and the pick's local index — -1 where it touches nothing.
-__device__ __forceinline__ int64_t qnei_absorb_pick(const SelState* __restrict__ st, const Key* __restrict__ first,
-                                                    const double* __restrict__ vals, int64_t M, int T, int64_t offset,
-                                                    double* __restrict__ m, uint8_t* __restrict__ mask, bool* nan_out, double* gain,
-                                                    int64_t* idx) {
-  const bool nan = st->first_nan != INT64_MAX;
-  const int64_t pick = nan ? st->first_nan : first->i;
-  const bool valid = pick >= 0 && pick < M;      // (always, with q <= M: a pick outside the candidates touches nothing)
-  *nan_out = nan;
-  *gain = (nan || !valid) ? std::numeric_limits<double>::quiet_NaN() : -first->v;
-  *idx = valid ? pick + offset : -1;
-  if (!valid) return -1;
-  if (threadIdx.x == 0) mask[pick] = 1;
-  for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) m[t] = fmax(m[t], vals[(int64_t)t * M + pick]);
-  return pick;
+// Behind step j's selection, for both update kernels: the pick (greedy_pick) marked in the mask and absorbed into the incumbents
+__device__ __forceinline__ GreedyPick qnei_absorb_pick(const SelState* __restrict__ st, const Key* __restrict__ first,
+                                                       const double* __restrict__ vals, int64_t M, int T, int64_t offset,
+                                                       double* __restrict__ m, uint8_t* __restrict__ mask) {
+  const GreedyPick p = greedy_pick(st, first, M, offset);
+  if (p.local < 0) return p;
+  if (threadIdx.x == 0) mask[p.local] = 1;
+  for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) m[t] = fmax(m[t], vals[(int64_t)t * M + p.local]);
+  return p;
 }
 
 __global__ __launch_bounds__(QNEI_BLOCK) void qnei_update_kernel(const SelState* __restrict__ st, const Key* __restrict__ first,
                                                                  const double* __restrict__ vals, int64_t M, int T, int64_t offset, int j,
                                                                  double* __restrict__ m, uint8_t* __restrict__ mask,
-                                                                 QneiRecord* __restrict__ rec) {
-  bool nan;
-  QneiRecord r;
-  (void)qnei_absorb_pick(st, first, vals, M, T, offset, m, mask, &nan, &r.gain, &r.idx);
-  if (threadIdx.x == 0) rec[j] = r;
+                                                                 GreedyRecord* __restrict__ rec) {
+  const GreedyPick p = qnei_absorb_pick(st, first, vals, M, T, offset, m, mask);
+  if (threadIdx.x == 0) rec[j] = GreedyRecord{p.gain, p.idx};
 }
 
 // ... and, over the masked block, feasible = (the number of draws t whose value at the pick is > -inf) / T: NaN for a NaN pick
@@ -125,71 +112,27 @@ __global__ __launch_bounds__(QNEI_BLOCK) void cnei_update_kernel(const SelState*
   __shared__ int count;
   if (threadIdx.x == 0) count = 0;
   __syncthreads();
-  bool nan;
-  CneiRecord r;
-  const int64_t pick = qnei_absorb_pick(st, first, vals, M, T, offset, m, mask, &nan, &r.gain, &r.idx);
-  if (pick >= 0) {
+  const GreedyPick p = qnei_absorb_pick(st, first, vals, M, T, offset, m, mask);
+  if (p.local >= 0) {
     int mine = 0;
-    for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) mine += vals[(int64_t)t * M + pick] > -std::numeric_limits<double>::infinity();
+    for (int t = threadIdx.x; t < T; t += QNEI_BLOCK) mine += vals[(int64_t)t * M + p.local] > -std::numeric_limits<double>::infinity();
     if (mine) atomicAdd(&count, mine);
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    r.feasible = (nan || pick < 0) ? std::numeric_limits<double>::quiet_NaN() : (double)count / (double)T;
-    rec[j] = r;
-  }
+  if (threadIdx.x == 0)
+    rec[j] = CneiRecord{p.gain, p.idx, (p.nan || p.local < 0) ? std::numeric_limits<double>::quiet_NaN() : (double)count / (double)T};
 }
 
-// debug build: an event before the draws, between the baselines and the steps, and behind the last step of the last call, per
-// entry point (ev / used: ctx->qnei_ev, ctx->cnei_ev and their flags); the product records nothing
-static inline void stage_mark(gpbo_ctx* ctx, hipEvent_t* ev, bool* used, int i) {
-#ifdef GPBO_DEBUG
-  if (!ev[i]) (void)hipEventCreate(&ev[i]);
-  (void)hipEventRecord(ev[i], ctx->stream);
-  *used = (i == 2);
-#else
-  (void)ctx; (void)ev; (void)used; (void)i;
-#endif
-}
-static inline void qnei_mark(gpbo_ctx* ctx, int i) { stage_mark(ctx, ctx->qnei_ev, &ctx->qnei_ev_used, i); }
-static inline void cnei_mark(gpbo_ctx* ctx, int i) { stage_mark(ctx, ctx->cnei_ev, &ctx->cnei_ev_used, i); }
-
-#ifdef GPBO_DEBUG
-// ms[0] the draws and baselines, ms[1] the steps of the call the three events belong to (gpbo_debug_qnei_stage_ms / _cnei_)
-static int stage_ms(gpbo_ctx* ctx, const hipEvent_t* ev, bool used, const char* who, const char* call, float* ms) {
-  if (!used) GPBO_FAIL(ctx, GPBO_ERR_STATE, std::string(who) + ": no " + call + " call to report");
-  GPBO_HIP(ctx, hipEventSynchronize(ev[2]));
-  for (int i = 0; i < 2; ++i) GPBO_HIP(ctx, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-  return GPBO_OK;
-}
-int debug_qnei_stage_ms(gpbo_ctx* ctx, float* ms) {
-  return stage_ms(ctx, ctx->qnei_ev, ctx->qnei_ev_used, "debug_qnei_stage_ms", "gpbo_qnei_greedy", ms);
-}
-int debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms) {
-  return stage_ms(ctx, ctx->cnei_ev, ctx->cnei_ev_used, "debug_cnei_stage_ms", "gpbo_cnei_greedy", ms);
-}
-#endif
-
-// The q greedy steps of both entry points, all on the stream: the keys of step j into ctx->ys, the selection's one pick, and
-// `update(st, first, j)` — the launch of the caller's update kernel behind it.
+// The q greedy steps of both entry points (greedy_steps) over the block `vals`; `update(st, first, j)` launches the caller's update kernel
 template <class Update>
 static int qnei_steps(gpbo_ctx* ctx, const double* vals, int64_t M, int T, const double* mt, const uint8_t* mask, int q,
                       double* keys_out, Update update) {
-  int rc;
   const int items = qnei_items(M);
   const dim3 grid((unsigned)qnei_score_blocks(M)), block(QNEI_BLOCK);
-  for (int j = 0; j < q; ++j) {
+  return greedy_steps(ctx, M, q, keys_out, [&] {
     if (items == 2) qnei_score_kernel<2><<<grid, block, 0, ctx->stream>>>(vals, M, T, mt, mask, ctx->ys);
     else qnei_score_kernel<1><<<grid, block, 0, ctx->stream>>>(vals, M, T, mt, mask, ctx->ys);
-    GPBO_HIP(ctx, hipGetLastError());
-    if (keys_out)
-      GPBO_HIP(ctx, hipMemcpyAsync(keys_out + (int64_t)j * M, ctx->ys, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    const SelState* st; const Key* first;
-    if ((rc = enqueue_values_select(ctx, M, &st, &first))) return rc;
-    update(st, first, j);
-    GPBO_HIP(ctx, hipGetLastError());
-  }
-  return GPBO_OK;
+  }, update);
 }
 
 int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, double y_std, int G, int S, int F, const double* omega,
@@ -199,15 +142,15 @@ int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, 
   int rc;
   const int N = (int)m.N, d = m.d, T = G * S;
   const QneiBlock b = qnei_block(T, M, N, P, d, m.DP, q);
-  if ((rc = ensure(ctx, &ctx->qnei, &ctx->cap_qnei, b.doubles))) return rc;
-  double* w = ctx->qnei;
+  if ((rc = ensure(ctx, &ctx->greedy, &ctx->cap_greedy, b.doubles))) return rc;
+  double* w = ctx->greedy;
   double *vals = w + b.vals, *base = w + b.base, *mt = w + b.m, *pend_s = w + b.pend_s;
   uint8_t* mask = (uint8_t*)(w + b.mask);
-  QneiRecord* rec = (QneiRecord*)(w + b.rec);
+  GreedyRecord* rec = (GreedyRecord*)(w + b.rec);
   // the scaled candidates (the draws' workspace of the context, as gpbo_sample_paths fills it) and the scaled pending points
   const int64_t Mp = round_up(M, POST_CANDS);
   if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * m.DP))) return rc;
-  qnei_mark(ctx, 0);
+  greedy_mark(ctx, ctx->qnei_clock, 0);
   if ((rc = launch_prescale(ctx, ctx->Xc, M, d, m.DP, m.ls, ctx->Xcs, Mp))) return rc;
   if (P > 0) {
     GPBO_HIP(ctx, hipMemcpyAsync(w + b.pend, pending, (size_t)P * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -216,11 +159,11 @@ int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, 
   if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, M))) return rc;
   GPBO_HIP(ctx, hipMemsetAsync(mask, 0, (size_t)((M + 7) / 8 * 8), ctx->stream));
   // the draws, group by group: the group's inputs and path weights into the paths workspace, then its S rows of each buffer
+  const Model* one = &m;
+  const GreedyDraws draws = greedy_draws(1, &one, G, S, F, omega, phase, weights, eps);
   for (int g = 0; g < G; ++g) {
     PathWorkspace ws{};
-    if ((rc = launch_path_weights(ctx, m, S, F, omega + (int64_t)g * F * d, phase + (int64_t)g * F, weights + (int64_t)g * S * F,
-                                  eps + (int64_t)g * S * N, 0, &ws)))
-      return rc;
+    if ((rc = greedy_path_weights(ctx, draws, m, 0, g, &ws))) return rc;
     if ((rc = launch_paths_over(ctx, m, ws, y_mean, y_std, S, F, ctx->Xcs, M, vals + (int64_t)g * S * M, M))) return rc;
     double* rows = base + (int64_t)g * S * b.ldb;
     if (noisy && (rc = launch_paths_over(ctx, m, ws, y_mean, y_std, S, F, m.Xs, N, rows, b.ldb))) return rc;
@@ -228,14 +171,14 @@ int launch_qnei_greedy(gpbo_ctx* ctx, const Model& m, int64_t M, double y_mean, 
   }
   qnei_baseline_kernel<<<dim3((unsigned)T), dim3(64), 0, ctx->stream>>>(base, b.ldb, noisy ? 0 : N, noisy, y_best, mt, w + b.m0);
   GPBO_HIP(ctx, hipGetLastError());
-  qnei_mark(ctx, 1);
+  greedy_mark(ctx, ctx->qnei_clock, 1);
   if ((rc = qnei_steps(ctx, vals, M, T, mt, mask, q, keys_out, [&](const SelState* st, const Key* first, int j) {
         qnei_update_kernel<<<dim3(1), dim3(QNEI_BLOCK), 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, mt, mask, rec);
       })))
     return rc;
-  qnei_mark(ctx, 2);
-  QneiRecord* hrec = (QneiRecord*)((char*)ctx->pinned_aux + PIN_AUX_SEL_OUT);
-  GPBO_HIP(ctx, hipMemcpyAsync(hrec, rec, sizeof(QneiRecord) * (size_t)q, hipMemcpyDeviceToHost, ctx->stream));
+  greedy_mark(ctx, ctx->qnei_clock, 2);
+  const GreedyRecord* hrec;
+  if ((rc = greedy_fetch(ctx, rec, q, &hrec))) return rc;
   GPBO_HIP(ctx, hipMemcpyAsync(baseline_out, w + b.m0, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (values_out)
     GPBO_HIP(ctx, hipMemcpyAsync(values_out, vals, (size_t)T * (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -254,8 +197,8 @@ int launch_cnei_greedy(gpbo_ctx* ctx, int C, const Model* const* ms, int64_t M, 
   int rc;
   const int d = ms[0]->d, DP = ms[0]->DP, T = G * S;
   const CneiBlock b = cnei_block(T, S, M, B, d, DP, q, values_out != nullptr, base_values_out != nullptr && B > 0);
-  if ((rc = ensure(ctx, &ctx->cnei, &ctx->cap_cnei, b.doubles))) return rc;
-  double* w = ctx->cnei;
+  if ((rc = ensure(ctx, &ctx->greedy, &ctx->cap_greedy, b.doubles))) return rc;
+  double* w = ctx->greedy;
   double *vals = w + b.vals, *base = w + b.base, *mt = w + b.m, *viol = w + b.viol, *violb = w + b.violb, *pts_s = w + b.pts_s;
   double* stage = values_out ? w + b.stage : nullptr;
   double* stageb = (base_values_out && B > 0) ? w + b.stageb : nullptr;
@@ -264,15 +207,10 @@ int launch_cnei_greedy(gpbo_ctx* ctx, int C, const Model* const* ms, int64_t M, 
   const int64_t Mp = round_up(M, POST_CANDS);
   if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * DP))) return rc;
   if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, M))) return rc;
-  cnei_mark(ctx, 0);
+  greedy_mark(ctx, ctx->cnei_clock, 0);
   GPBO_HIP(ctx, hipMemsetAsync(mask, 0, (size_t)((M + 7) / 8 * 8), ctx->stream));
   if (B > 0) GPBO_HIP(ctx, hipMemcpyAsync(w + b.pts, base_pts, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  // slot j's (G, S, N_j) block of eps
-  const double* eps_of[GPBO_MAX_MODELS];
-  {
-    const double* e = eps;
-    for (int j = 0; j <= C; ++j) { eps_of[j] = e; e += (int64_t)G * S * ms[j]->N; }
-  }
+  const GreedyDraws draws = greedy_draws(C + 1, ms, G, S, F, omega, phase, weights, eps);
   // the draws, group by group; per group the constraints in slot order (the violation's sum order), the objective last: per slot
   // the group's path weights, the candidates and the base points scaled by THAT slot's length scales, one pass over each
   const size_t cand_bytes = (size_t)S * (size_t)M * sizeof(double), base_bytes = (size_t)S * (size_t)B * sizeof(double);
@@ -281,11 +219,8 @@ int launch_cnei_greedy(gpbo_ctx* ctx, int C, const Model* const* ms, int64_t M, 
     for (int k = 1; k <= C + 1; ++k) {
       const int j = k <= C ? k : 0;
       const Model& m = *ms[j];
-      const int64_t jg = (int64_t)j * G + g;
       PathWorkspace ws{};
-      if ((rc = launch_path_weights(ctx, m, S, F, omega + jg * F * d, phase + jg * F, weights + jg * S * F,
-                                    eps_of[j] + (int64_t)g * S * m.N, 0, &ws)))
-        return rc;
+      if ((rc = greedy_path_weights(ctx, draws, m, j, g, &ws))) return rc;
       if ((rc = launch_prescale(ctx, ctx->Xc, M, d, DP, m.ls, ctx->Xcs, Mp))) return rc;
       const int epilogue = j == 0 ? (int)PATH_MASKED : path_epilogue(j);
       const double lo = j ? lb[j - 1] : 0.0, hi = j ? ub[j - 1] : 0.0;
@@ -308,14 +243,14 @@ int launch_cnei_greedy(gpbo_ctx* ctx, int C, const Model* const* ms, int64_t M, 
   }
   qnei_baseline_kernel<<<dim3((unsigned)T), dim3(64), 0, ctx->stream>>>(base, b.ldb, 0, 0, y_floor, mt, w + b.m0);
   GPBO_HIP(ctx, hipGetLastError());
-  cnei_mark(ctx, 1);
+  greedy_mark(ctx, ctx->cnei_clock, 1);
   if ((rc = qnei_steps(ctx, vals, M, T, mt, mask, q, keys_out, [&](const SelState* st, const Key* first, int j) {
         cnei_update_kernel<<<dim3(1), dim3(QNEI_BLOCK), 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, mt, mask, rec);
       })))
     return rc;
-  cnei_mark(ctx, 2);
-  CneiRecord* hrec = (CneiRecord*)((char*)ctx->pinned_aux + PIN_AUX_SEL_OUT);      // (behind the last selection: its records are read)
-  GPBO_HIP(ctx, hipMemcpyAsync(hrec, rec, sizeof(CneiRecord) * (size_t)q, hipMemcpyDeviceToHost, ctx->stream));
+  greedy_mark(ctx, ctx->cnei_clock, 2);
+  const CneiRecord* hrec;
+  if ((rc = greedy_fetch(ctx, rec, q, &hrec))) return rc;
   GPBO_HIP(ctx, hipMemcpyAsync(baseline_out, w + b.m0, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int j = 0; j < q; ++j) { pick_idx[j] = hrec[j].idx; pick_gain[j] = hrec[j].gain; pick_feasible[j] = hrec[j].feasible; }

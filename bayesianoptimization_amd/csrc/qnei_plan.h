@@ -26,7 +26,7 @@ inline int64_t qnei_score_blocks(int64_t M) {
   return (M + per_block - 1) / per_block;
 }
 
-// The workspace (ctx->qnei), offsets in doubles from its start, every part at an even offset (the block is read as double2, the
+// The workspace (in ctx->greedy), offsets in doubles from its start, every part at an even offset (the block is read as double2, the
 // scaled pending points too):
 //   vals [T][M]      the draws' values over the candidates, row t = g S + s: 8 T M bytes — 2 GiB at T = 256, M = 2^20
 //   base [T][ldb]    the draws' values at the N training points | the P pending points, ldb = N + P

@@ -994,6 +994,42 @@ class GpEngine:
                                                 C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
         return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
 
+    @staticmethod
+    def _greedy_groups(who, draws, message):
+        """G of `draws` — per slot a list of tuples (omega, phase, weights, eps), G >= 1 of them in every slot —, else ValueError:
+        `message` for lists that are not that, then G's range."""
+        G = len(draws[0])
+        if G < 1 or any(len(groups) != G for groups in draws) or any(len(t) != 4 for groups in draws for t in groups):
+            raise ValueError(f"{who}: {message}")
+        if G > _lib.MAX_QNEI_GROUPS:
+            raise ValueError(f"{who}: n_groups out of range [1, {_lib.MAX_QNEI_GROUPS}]")
+        return G
+
+    def _greedy_inputs(self, who, slotted):
+        """The draws of a greedy call as it hands them down: `slotted`, a list of (slot, that slot's groups), each group checked as
+        `_path_inputs` checks it against its slot and all of one S and F.  Returns (omega, phase, weights, eps, S, F, d), the four
+        flat and concatenated slot-major, then group-major (csrc/greedy.h: GreedyDraws)."""
+        parts = [self._path_inputs(who, *t, slot) for slot, groups in slotted for t in groups]
+        F, S = parts[0][0].shape[0], parts[0][2].shape[0]
+        if any(p[0].shape[0] != F or p[2].shape[0] != S for p in parts):
+            raise ValueError(f"{who}: every group's draws must have the same S and F")
+        omega, phase, weights, eps = (np.ascontiguousarray(np.concatenate([p[k].ravel() for p in parts])) for k in range(4))
+        return omega, phase, weights, eps, int(S), int(F), int(parts[0][4][1])
+
+    @staticmethod
+    def _greedy_points(who, points, d, noun, count, whose):
+        """A greedy call's point set (`noun`: pending / base; `count`: what its docstring calls their number) as (float64 array or
+        None, number of points); it must be (n, d) to fit `whose` (the slot's model / the slots' models)."""
+        if points is None:
+            return None, 0
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        if points.ndim != 2:
+            raise ValueError(f"{who}: {noun} must be two-dimensional ({count}, d)")
+        n = int(points.shape[0])
+        if n and points.shape[1] != d:
+            raise ValueError(f"{who}: {noun} ({count}, {points.shape[1]}) does not fit the {whose} in {d} dimensions")
+        return (points, n) if n else (None, 0)
+
     def qnei_greedy(self, groups, q, noisy=True, y_best=0.0, pending=None, slot=0, y_mean=0.0, y_std=1.0, index_offset=0,
                     return_values=False, return_keys=False):
         """A batch of q resident candidates by greedy noisy expected improvement over T joint posterior draws (gpbo_qnei_greedy;
@@ -1005,31 +1041,9 @@ class GpEngine:
         `sample_paths`."""
         who = "qnei_greedy"
         groups = list(groups)
-        G = len(groups)
-        if G < 1 or any(len(t) != 4 for t in groups):
-            raise ValueError(f"{who}: groups must be a non-empty list of tuples (omega, phase, weights, eps)")
-        if G > _lib.MAX_QNEI_GROUPS:
-            raise ValueError(f"{who}: n_groups out of range [1, {_lib.MAX_QNEI_GROUPS}]")
-        parts = [self._path_inputs(who, *t, slot) for t in groups]
-        F, S = parts[0][0].shape[0], parts[0][2].shape[0]
-        if any(p[0].shape[0] != F or p[2].shape[0] != S for p in parts):
-            raise ValueError(f"{who}: every group's draws must have the same S and F")
-        d = parts[0][4][1]
-        if pending is None:
-            P = 0
-        else:
-            pending = np.ascontiguousarray(np.asarray(pending, dtype=np.float64))
-            if pending.ndim != 2:
-                raise ValueError(f"{who}: pending must be two-dimensional (P, d)")
-            P = int(pending.shape[0])
-            if P and pending.shape[1] != d:
-                raise ValueError(f"{who}: pending (P, {pending.shape[1]}) does not fit the slot's model in {d} dimensions")
-            if P == 0:
-                pending = None
-        omega = np.ascontiguousarray(np.concatenate([p[0].ravel() for p in parts]))
-        phase = np.ascontiguousarray(np.concatenate([p[1] for p in parts]))
-        weights = np.ascontiguousarray(np.concatenate([p[2].ravel() for p in parts]))
-        eps = np.ascontiguousarray(np.concatenate([p[3].ravel() for p in parts]))
+        G = self._greedy_groups(who, [groups], "groups must be a non-empty list of tuples (omega, phase, weights, eps)")
+        omega, phase, weights, eps, S, F, d = self._greedy_inputs(who, [(slot, groups)])
+        pending, P = self._greedy_points(who, pending, d, "pending", "P", "slot's model")
         q = int(q)
         T, M = G * S, max(int(self.n_candidates), 0)
         n = max(q, 1)
@@ -1059,32 +1073,9 @@ class GpEngine:
         draws = [list(g) for g in draws]
         if len(draws) != 2:
             raise ValueError(f"{who}: draws must hold two lists of groups, one per objective")
-        G = len(draws[0])
-        if G < 1 or len(draws[1]) != G or any(len(t) != 4 for groups in draws for t in groups):
-            raise ValueError(f"{who}: each objective needs the same non-empty list of tuples (omega, phase, weights, eps)")
-        if G > _lib.MAX_QNEI_GROUPS:
-            raise ValueError(f"{who}: n_groups out of range [1, {_lib.MAX_QNEI_GROUPS}]")
-        parts = [[self._path_inputs(who, *t, j) for t in groups] for j, groups in enumerate(draws)]
-        F, S = parts[0][0][0].shape[0], parts[0][0][2].shape[0]
-        if any(p[0].shape[0] != F or p[2].shape[0] != S for ps in parts for p in ps):
-            raise ValueError(f"{who}: every group's draws must have the same S and F")
-        d = parts[0][0][4][1]
-        if base is None:
-            B = 0
-        else:
-            base = np.ascontiguousarray(np.asarray(base, dtype=np.float64))
-            if base.ndim != 2:
-                raise ValueError(f"{who}: base must be two-dimensional (n_base, d)")
-            B = int(base.shape[0])
-            if B and base.shape[1] != d:
-                raise ValueError(f"{who}: base (n_base, {base.shape[1]}) does not fit the slots' models in {d} dimensions")
-            if B == 0:
-                base = None
-        flat = [p for ps in parts for p in ps]
-        omega = np.ascontiguousarray(np.concatenate([p[0].ravel() for p in flat]))
-        phase = np.ascontiguousarray(np.concatenate([p[1] for p in flat]))
-        weights = np.ascontiguousarray(np.concatenate([p[2].ravel() for p in flat]))
-        eps = np.ascontiguousarray(np.concatenate([p[3].ravel() for p in flat]))
+        G = self._greedy_groups(who, draws, "each objective needs the same non-empty list of tuples (omega, phase, weights, eps)")
+        omega, phase, weights, eps, S, F, d = self._greedy_inputs(who, list(enumerate(draws)))
+        base, B = self._greedy_points(who, base, d, "base", "n_base", "slots' models")
         ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).ravel())
         y_mean = np.ascontiguousarray(np.asarray(y_mean, dtype=np.float64).ravel())
         y_std = np.ascontiguousarray(np.asarray(y_std, dtype=np.float64).ravel())
@@ -1127,38 +1118,15 @@ class GpEngine:
             raise ValueError(f"{who}: draws must hold 1 + C lists of groups, C >= 1: the objective's, then each constraint's")
         if n_slots > _lib.MAX_MODELS:
             raise ValueError(f"{who}: n_constraints out of range [1, {_lib.MAX_MODELS - 1}]")
-        G = len(draws[0])
-        if G < 1 or any(len(groups) != G for groups in draws) or any(len(t) != 4 for groups in draws for t in groups):
-            raise ValueError(f"{who}: each slot needs the same non-empty list of tuples (omega, phase, weights, eps)")
-        if G > _lib.MAX_QNEI_GROUPS:
-            raise ValueError(f"{who}: n_groups out of range [1, {_lib.MAX_QNEI_GROUPS}]")
+        G = self._greedy_groups(who, draws, "each slot needs the same non-empty list of tuples (omega, phase, weights, eps)")
         lb = np.ascontiguousarray(lb, dtype=np.float64).ravel()
         ub = np.ascontiguousarray(ub, dtype=np.float64).ravel()
         y_mean = np.zeros(n_slots) if y_mean is None else np.ascontiguousarray(y_mean, dtype=np.float64).ravel()
         y_std = np.ones(n_slots) if y_std is None else np.ascontiguousarray(y_std, dtype=np.float64).ravel()
         if lb.shape[0] != n_slots - 1 or ub.shape[0] != n_slots - 1 or y_mean.shape[0] != n_slots or y_std.shape[0] != n_slots:
             raise ValueError(f"{who}: lb / ub must have {n_slots - 1} entries, y_mean / y_std {n_slots}")
-        parts = [[self._path_inputs(who, *t, j) for t in groups] for j, groups in enumerate(draws)]
-        F, S = parts[0][0][0].shape[0], parts[0][0][2].shape[0]
-        if any(p[0].shape[0] != F or p[2].shape[0] != S for ps in parts for p in ps):
-            raise ValueError(f"{who}: every group's draws must have the same S and F")
-        d = parts[0][0][4][1]
-        if base is None:
-            B = 0
-        else:
-            base = np.ascontiguousarray(np.asarray(base, dtype=np.float64))
-            if base.ndim != 2:
-                raise ValueError(f"{who}: base must be two-dimensional (n_base, d)")
-            B = int(base.shape[0])
-            if B and base.shape[1] != d:
-                raise ValueError(f"{who}: base (n_base, {base.shape[1]}) does not fit the slots' models in {d} dimensions")
-            if B == 0:
-                base = None
-        flat = [p for ps in parts for p in ps]
-        omega = np.ascontiguousarray(np.concatenate([p[0].ravel() for p in flat]))
-        phase = np.ascontiguousarray(np.concatenate([p[1] for p in flat]))
-        weights = np.ascontiguousarray(np.concatenate([p[2].ravel() for p in flat]))
-        eps = np.ascontiguousarray(np.concatenate([p[3].ravel() for p in flat]))
+        omega, phase, weights, eps, S, F, d = self._greedy_inputs(who, list(enumerate(draws)))
+        base, B = self._greedy_points(who, base, d, "base", "n_base", "slots' models")
         q = int(q)
         T, M = G * S, max(int(self.n_candidates), 0)
         n = max(q, 1)

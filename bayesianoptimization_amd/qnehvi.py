@@ -26,8 +26,7 @@ import warnings
 import numpy as np
 
 from . import _suggest as S
-from ._lib import MAX_PATH_FEATURES as MAX_FEATURES, MAX_QNEHVI_BASE as MAX_BASE, MAX_SEEDS as MAX_Q
-from .qnei import MAX_DRAWS, _pending_rows, draw_layout
+from ._lib import MAX_QNEHVI_BASE as MAX_BASE
 
 
 def suggest_qnehvi(pareto, q: int, n_random: int = 10_000, n_draws: int = 64, n_features: int = 1024, pending=None,
@@ -59,17 +58,9 @@ def suggest_qnehvi(pareto, q: int, n_random: int = 10_000, n_draws: int = 64, n_
     n_features outside [1, 4096], pending of another shape or not finite.  NotImplementedError also when a draw's front outgrows
     128 points (gpbo_qnhvi_greedy never thins a front)."""
     who = "suggest_qnehvi"
-    q = S.count(q, 1, MAX_Q, f"q must be an integer in [1, {MAX_Q}]")
-    n_random, n_features = int(n_random), int(n_features)
-    if n_random < 1:
-        raise ValueError("n_random must be >= 1")
-    if q > n_random:
-        raise ValueError("q must not exceed n_random")
-    n_draws = S.count(n_draws, 1, MAX_DRAWS, f"n_draws must be an integer in [1, {MAX_DRAWS}]")
-    if not 1 <= n_features <= MAX_FEATURES:
-        raise ValueError(f"n_features must be in [1, {MAX_FEATURES}]")
+    q, n_random, n_draws, n_features = S.greedy_counts(q, n_random, n_draws, n_features)
     d = int(pareto.bounds.shape[0])
-    pending = _pending_rows(pending, pareto, d)
+    pending = S.pending_rows(pending, pareto, d)
     if pareto.n_objectives != 2:
         raise NotImplementedError(f"{who}: {pareto.n_objectives} objectives; a draw's front is a staircase for two objectives "
                                   "only (gpbo_qnhvi_greedy serves m = 2 and approximates nothing)")
@@ -89,15 +80,13 @@ def suggest_qnehvi(pareto, q: int, n_random: int = 10_000, n_draws: int = 64, n_
                 gp.fit(pareto.params, pareto.targets[:, j])
     models = [S.read_model(gp, pareto, who) for gp in pareto._gps]
     eng.generate_candidates_like(n_random, pareto.bounds[:, 0], pareto.bounds[:, 1], rng)
-    G, n_paths = draw_layout(n_draws)
+    G, n_paths = S.draw_layout(n_draws)
     draws = [S.group_inputs(gp, rng, model, G, n_paths, n_features) for gp, model in zip(pareto._gps, models)]
     for gp in pareto._gps:
         gp._ensure_resident()
     out = eng.qnehvi_greedy(draws, q, pareto.ref_point, base=np.ascontiguousarray(base, dtype=np.float64),
                             y_mean=[m.y_mean for m in models], y_std=[m.y_std for m in models], return_fronts=True)
-    index = np.asarray(out["index"], dtype=np.int64)
-    rows = np.asarray(eng.get_candidate_rows(index, d), dtype=np.float64)
-    picks = [dict(zip(pareto.keys, x)) for x in rows]
+    index, picks = S.picked_params(eng, out["index"], d, lambda x: dict(zip(pareto.keys, x)))
     if return_info:
         sizes = np.asarray(out["front_size"])
         return picks, {"gain": np.asarray(out["gain"], dtype=np.float64), "index": index,

@@ -19,36 +19,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _suggest as S
-from ._lib import (MAX_PATH_FEATURES as MAX_FEATURES, MAX_PATHS, MAX_QNEI_GROUPS as MAX_GROUPS, MAX_QNEI_POINTS as MAX_PENDING,
-                   MAX_SEEDS as MAX_Q)
-
-MAX_DRAWS = MAX_GROUPS * MAX_PATHS
-
-
-def draw_layout(n_draws: int):
-    """(G, S): `n_draws` as G = ceil(n_draws / 16) groups of S = ceil(n_draws / G) draws each — every group the same size, as the
-    engine call wants them, so T = G * S >= n_draws (17 -> 2 x 9 = 18, 20 -> 2 x 10, 33 -> 3 x 11, 64 -> 4 x 16, 250 -> 16 x 16)."""
-    G = -(-int(n_draws) // MAX_PATHS)
-    return G, -(-int(n_draws) // G)
-
-
-def _pending_rows(pending, space, d: int):
-    """`pending` (a list of parameter dicts, or an array (P, d)) as a float64 (P, d) array, None for no point"""
-    if pending is None:
-        return None
-    if isinstance(pending, (list, tuple)) and len(pending) and all(isinstance(p, dict) for p in pending):
-        try:
-            pending = [[p[k] for k in space.keys] for p in pending]
-        except KeyError as e:
-            raise ValueError(f"pending: a point lacks the parameter {e.args[0]!r}") from None
-    rows = np.asarray(pending, dtype=np.float64)
-    if rows.size == 0:
-        return None
-    if rows.ndim != 2 or rows.shape[1] != d:
-        raise ValueError(f"pending must be a list of parameter dicts or an array (P, {d})")
-    if not np.isfinite(rows).all():
-        raise ValueError("pending must be finite")
-    return np.ascontiguousarray(rows)
+from ._lib import MAX_QNEI_POINTS as MAX_PENDING
+from ._suggest import MAX_DRAWS, draw_layout  # noqa: F401  (their home is _suggest.py; they stay importable from here)
 
 
 def suggest_qnei(optimizer, q: int, n_random: int = 10_000, n_draws: int = 64, n_features: int = 1024, noisy: bool = True,
@@ -80,20 +52,12 @@ def suggest_qnei(optimizer, q: int, n_random: int = 10_000, n_draws: int = 64, n
     n_features outside [1, 4096], more than 64 pending points, pending of another shape or not finite.  TargetSpaceEmptyError on an
     empty space, ConstraintNotSupportedError with a constraint.  NotImplementedError, never a host fallback, for: a GP that is not
     on the engine's slot 0, a space with an input transform (int / categorical parameters), a model in host mode, a device group."""
-    q = S.count(q, 1, MAX_Q, f"q must be an integer in [1, {MAX_Q}]")
-    n_random, n_features = int(n_random), int(n_features)
-    if n_random < 1:
-        raise ValueError("n_random must be >= 1")
-    if q > n_random:
-        raise ValueError("q must not exceed n_random")
-    n_draws = S.count(n_draws, 1, MAX_DRAWS, f"n_draws must be an integer in [1, {MAX_DRAWS}]")
-    if not 1 <= n_features <= MAX_FEATURES:
-        raise ValueError(f"n_features must be in [1, {MAX_FEATURES}]")
+    q, n_random, n_draws, n_features = S.greedy_counts(q, n_random, n_draws, n_features)
     if pending is not None and len(pending) > MAX_PENDING:
         raise ValueError(f"pending must hold at most {MAX_PENDING} points")
     gp, space, eng = S.gate(optimizer, "suggest_qnei", "sampled", ("sample_paths", "qnei_greedy"),
                             "a device group has no path sampler; use a single device")
-    pending = _pending_rows(pending, space, int(space.bounds.shape[0]))
+    pending = S.pending_rows(pending, space, int(space.bounds.shape[0]))
     rng = optimizer._random_state
 
     model = S.fit_model(gp, space, "suggest_qnei")
@@ -103,9 +67,7 @@ def suggest_qnei(optimizer, q: int, n_random: int = 10_000, n_draws: int = 64, n
     gp._ensure_resident()
     index, gain, baseline, _values, _keys = eng.qnei_greedy(groups, q, noisy=bool(noisy), y_best=float(np.max(space.target)),
                                                             pending=pending, slot=gp.slot, y_mean=model.y_mean, y_std=model.y_std)
-    index = np.asarray(index, dtype=np.int64)
-    rows = np.asarray(eng.get_candidate_rows(index, model.d), dtype=np.float64)
-    picks = [space.array_to_params(x) for x in rows]
+    index, picks = S.picked_params(eng, index, model.d, space.array_to_params)
     if return_info:
         return picks, {"gain": np.asarray(gain, dtype=np.float64), "index": index, "baseline": np.asarray(baseline, dtype=np.float64),
                        "n_draws": G * n_paths}

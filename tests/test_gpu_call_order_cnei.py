@@ -3,8 +3,9 @@ its base state (two fitted slots — slot 0 the objective, slot 1 the constraint
 
   a. gpbo_cnei_greedy before and after each other reader of the path family (CS.CALLS' sample_paths, sample_paths_constrained,
      ascend_paths with resident and with given starts, qnei_greedy, qnehvi_greedy) on ONE context gives the bits a fresh context
-     gives — and so does the other call: they share ctx->paths, ctx->Xcs, ctx->ys and the selection's records, and each keeps a
-     workspace of its own (ctx->cnei, ctx->qnei, ctx->qnehvi, ctx->cpaths) whose contents must not leak.
+     gives — and so does the other call: they share ctx->paths, ctx->Xcs, ctx->ys and the selection's records, the three greedy
+     calls lay their workspaces out in ONE buffer (ctx->greedy) and the constrained sampler keeps its own (ctx->cpaths); what one
+     call leaves in either must not leak into the next.
   b. after a writer of the candidates (set_candidates) or of a slot (a refit of the constraint's slot on other targets) it answers
      for the new state: the fresh context's bits for that state, which differ from the old state's.
 
