@@ -1,6 +1,6 @@
 """MI355X-native GP-posterior + acquisition engine for bayes_opt's suggest() hot path.
 
-Hand-written HIP (gfx950) behind a C ABI (include/gpbo.h), loaded with ctypes.  No PyTorch, no
+Hand-written HIP (gfx950) behind a C ABI (include/gpbo.h, include/gpmo.h), loaded with ctypes.  No PyTorch, no
 Triton, no CPU fallback: importing the host classes works anywhere, creating an engine requires the
 built library and an AMD GPU.
 """
@@ -12,7 +12,7 @@ __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate
            "suggest_mes", "suggest_kg", "suggest_turbo", "TrustRegion", "sobol_tables",
            "suggest_constrained_thompson", "suggest_scbo", "ConstrainedTrustRegion",
            "ParetoOptimizer", "pareto_front", "hypervolume", "box_decomposition", "suggest_qnei", "suggest_qnehvi",
-           "suggest_constrained_qnei"]
+           "suggest_constrained_qnei", "suggest_constrained_qnehvi"]
 
 
 def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must not need sklearn/scipy
@@ -58,6 +58,9 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name == "suggest_constrained_qnei":
         from .cqnei import suggest_constrained_qnei
         return suggest_constrained_qnei
+    if name == "suggest_constrained_qnehvi":
+        from .cqnehvi import suggest_constrained_qnehvi
+        return suggest_constrained_qnehvi
     if name == "suggest_qnehvi":
         from .qnehvi import suggest_qnehvi
         return suggest_qnehvi

@@ -1,4 +1,4 @@
-"""ctypes binding of libgpbo.so (the C ABI declared in include/gpbo.h).
+"""ctypes binding of libgpbo.so (the C ABI declared in include/gpbo.h and, for the constrained multi-objective calls, include/gpmo.h).
 
 There is NO CPU fallback: if the HIP library is missing or no AMD GPU is visible, loading or context
 creation raises.  Nothing in this package imports the test oracle.
@@ -166,6 +166,17 @@ SIGNATURES = {
     "gpbo_hbm_copy_peak": (C.c_int, [C.c_void_p, C.c_int64, _c_double_p]),
 }
 
+# name -> (restype, argtypes) of the constrained multi-objective family; must list every symbol include/gpmo.h declares (tests check this)
+MO_SIGNATURES = {
+    "gpmo_cehvi_argbest": (C.c_int, [C.c_void_p, C.c_int, _c_int_p, _c_double_p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                     C.c_int, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, _c_double_p,
+                                     _c_int64_p, _c_double_p, _c_double_p]),
+    "gpmo_cnhvi_greedy": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int,
+                                    _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int,
+                                    C.c_int, C.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_int_p, _c_double_p, _c_double_p,
+                                    _c_double_p, _c_double_p, _c_double_p]),
+}
+
 # entry points only libgpbo_dbg.so exports (include/gpbo.h, "#ifdef GPBO_DEBUG")
 DEBUG_SIGNATURES = {
     "gpbo_debug_minimize_box": (C.c_int, [C.c_void_p, C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int,
@@ -180,6 +191,7 @@ DEBUG_SIGNATURES = {
     "gpbo_debug_kg_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "gpbo_debug_qnei_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "gpbo_debug_qnehvi_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "gpbo_debug_cnhvi_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "gpbo_debug_cnei_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "gpbo_debug_qnehvi_fronts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_int_p,
                                            _c_double_p]),
@@ -245,7 +257,7 @@ def load_library(path: str | None = None):
         raise ImportError(
             f"{path} not found: the HIP extension has not been built. Run "
             "`python -m bayesianoptimization_amd.build` (needs hipcc). There is no CPU fallback.")
-    lib = _bind(path, SIGNATURES)
+    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES})
     if not explicit:
         _lib = lib
     return lib
@@ -262,7 +274,7 @@ def load_debug_library():
                 build_debug(verbose=False)
             except Exception as e:  # noqa: BLE001
                 raise ImportError(f"{DEBUG_LIB_PATH} not found and building it failed ({e})") from e
-        _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **DEBUG_SIGNATURES})
+        _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **DEBUG_SIGNATURES})
     return _debug_lib
 
 

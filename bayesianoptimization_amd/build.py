@@ -48,9 +48,9 @@ SOURCES = {
     "acq_kernels.hip": ["-ffp-contract=off"],  # elementwise formulas follow NumPy op by op
     "mes.hip": ["-ffp-contract=off"],         # gpbo_mes_argbest: max-value entropy search values (acq_formulas.h's pieces, the bits they have in acq_kernels.hip)
     "kg.hip": ["-ffp-contract=off"],          # gpbo_kg_argbest: knowledge gradient values (candidate x point covariances, upper envelope of J + 1 lines; acq_formulas.h's pieces)
-    "ehvi.hip": ["-ffp-contract=off"],        # gpbo_ehvi_argbest: expected hypervolume improvement values (per-candidate level tables in LDS, the sum over the boxes; acq_formulas.h's pieces)
+    "ehvi.hip": ["-ffp-contract=off"],        # gpbo_ehvi_argbest: expected hypervolume improvement values (per-candidate level tables in LDS, the sum over the boxes; acq_formulas.h's pieces); gpmo_cehvi_argbest: the same kernel body with the log-feasibility epilogue
     "qnei.hip": ["-ffp-contract=off"],        # gpbo_qnei_greedy: greedy batch noisy expected improvement over a resident (T, M) block of posterior draws (the score kernel streams it once per pick; incumbents updated in-stream); gpbo_cnei_greedy: the same stream over draws masked by their constraint draws
-    "qnehvi.hip": ["-ffp-contract=off"],      # gpbo_qnhvi_greedy: greedy batch noisy expected hypervolume improvement, m = 2: per-draw fronts from the draws' values at the observed and pending points, a score kernel that streams the (2, T, M) block against the fronts' strips in LDS, fronts updated in-stream
+    "qnehvi.hip": ["-ffp-contract=off"],      # gpbo_qnhvi_greedy: greedy batch noisy expected hypervolume improvement, m = 2: per-draw fronts from the draws' values at the observed and pending points, a score kernel that streams the (2, T, M) block against the fronts' strips in LDS, fronts updated in-stream; gpmo_cnhvi_greedy: the same stream over objective 0 masked by the constraint draws
     "candidates.hip": [],
     "trust_region.hip": ["-ffp-contract=off"],  # gpbo_generate_candidates_trust_region: lo + (hi - lo) * u as NumPy computes it (scrambled Sobol points under a Philox mask)
     "mt19937.hip": ["-ffp-contract=off"],      # lo + (hi - lo) * u as NumPy computes it
@@ -113,7 +113,7 @@ def _code_only(src: str) -> str:
 
 def _fingerprint() -> str:
     h = hashlib.sha256()
-    names = sorted(os.listdir(CSRC)) + ["../../include/gpbo.h"]
+    names = sorted(os.listdir(CSRC)) + ["../../include/gpbo.h", "../../include/gpmo.h"]
     for n in names:
         p = os.path.normpath(os.path.join(CSRC, n))
         if os.path.isfile(p):

@@ -33,6 +33,12 @@
 // THE ORDER OF THE SUM: each chunk runs k ascending into one accumulator that starts at 0; the chunk sums are then added
 // g = 0 .. G - 1 in that order into one accumulator that starts at chunk 0's sum.  C, G and P are functions of m, the level counts
 // and K alone: a candidate's bits depend neither on M, nor on the grid, nor on the other candidates.  fp64 whatever a slot's precision.
+//
+// gpmo_cehvi_argbest (include/gpmo.h) is the same kernel body with an epilogue: behind the box sum the lane that holds a candidate's
+// EHVI E — the bits above — forms s = sum_j log p_j from the constraint slots' resident (cm, cs), j ascending into one accumulator
+// from 0, by GPBO_ACQ_LOG_FEAS's function (acq_formulas.h: log_interval_dev), and stores -(E exp(s)) or -(log E + s).  Once per
+// candidate, nothing through HBM, no second pass.  FORM = 0 is gpbo_ehvi_argbest's instance: its kernel keeps its name, its
+// arguments and its code.
 #include "gpbo_internal.h"
 #include "acq_formulas.h"
 
@@ -63,6 +69,15 @@ struct EhviDev {
   int64_t M;
 };
 
+// gpmo_cehvi_argbest's constraints: slot m + j's resident posterior and bounds, j < n
+struct EhviFeas {
+  int n;
+  const double* cm[GPBO_MAX_MODELS];
+  const double* cs[GPBO_MAX_MODELS];
+  double lb[GPBO_MAX_MODELS], ub[GPBO_MAX_MODELS];
+};
+enum EhviForm : int { EHVI_PLAIN = 0, EHVI_PRODUCT = 1, EHVI_LOG = 2 };
+
 // g(a) = E[(Y - a)^+], Y ~ N(mean, sd^2); sd == 0: (mean - a)^+.  The caller has dealt with a NaN mean or sd.
 __device__ __forceinline__ double ehvi_g_dev(double mean, double sd, double a) {
   if (sd == 0.0) {
@@ -76,8 +91,8 @@ __device__ __forceinline__ double ehvi_g_dev(double mean, double sd, double a) {
   return sd * (pdf * log_ei_ratio(z, DevErfcx()));
 }
 
-template <int C, int NOBJ>
-__global__ __launch_bounds__(EHVI_THREADS) void ehvi_kernel(EhviDev a, double* __restrict__ ys) {
+template <int C, int NOBJ, int FORM>
+__device__ __forceinline__ void ehvi_body(const EhviDev& a, const EhviFeas* __restrict__ feas, double* __restrict__ ys) {
   extern __shared__ __attribute__((aligned(16))) double ehvi_tab[];
   constexpr int G = EHVI_THREADS / C;
   const int c = threadIdx.x % C;
@@ -120,9 +135,27 @@ __global__ __launch_bounds__(EHVI_THREADS) void ehvi_kernel(EhviDev a, double* _
       if (g == 0)
         for (int q = 1; q < G; ++q) acc = acc + ehvi_tab[q * C + c];
     }
-    if (g == 0 && live) ys[i] = is_nan ? NAN : -acc;
+    if (g == 0 && live) {
+      double key = -acc;
+      if (FORM != EHVI_PLAIN) {
+        double s = 0.0;
+        for (int j = 0; j < feas->n; ++j) s = s + log_interval_dev(feas->lb[j], feas->ub[j], feas->cm[j][i], feas->cs[j][i]);
+        key = FORM == EHVI_PRODUCT ? -(acc * exp(s)) : -(log(acc) + s);
+      }
+      ys[i] = is_nan ? NAN : key;
+    }
     __syncthreads();                         // the next tile overwrites the tables
   }
+}
+
+template <int C, int NOBJ>
+__global__ __launch_bounds__(EHVI_THREADS) void ehvi_kernel(EhviDev a, double* __restrict__ ys) {
+  ehvi_body<C, NOBJ, EHVI_PLAIN>(a, nullptr, ys);
+}
+
+template <int C, int NOBJ, int FORM>
+__global__ __launch_bounds__(EHVI_THREADS) void cehvi_kernel(EhviDev a, EhviFeas feas, double* __restrict__ ys) {
+  ehvi_body<C, NOBJ, FORM>(a, &feas, ys);
 }
 
 constexpr int64_t EHVI_MAX_BLOCKS = 8192;     // the tile loop takes the rest
@@ -138,23 +171,27 @@ static inline void ehvi_mark(gpbo_ctx* ctx, int i) {
 #endif
 }
 
+// feas == nullptr: gpbo_ehvi_argbest's kernel; else the constrained one in product (log_form == 0) or log form
 template <int C, int NOBJ>
-static int ehvi_launch(gpbo_ctx* ctx, const EhviDev& a, size_t lds) {
+static int ehvi_launch(gpbo_ctx* ctx, const EhviDev& a, size_t lds, const EhviFeas* feas, int log_form) {
   const int64_t tiles = (a.M + C - 1) / C;
+  const dim3 grid((unsigned)(tiles < EHVI_MAX_BLOCKS ? tiles : EHVI_MAX_BLOCKS)), block(EHVI_THREADS);
   ehvi_mark(ctx, 0);
-  ehvi_kernel<C, NOBJ><<<dim3((unsigned)(tiles < EHVI_MAX_BLOCKS ? tiles : EHVI_MAX_BLOCKS)), dim3(EHVI_THREADS), lds, ctx->stream>>>(a, ctx->ys);
+  if (!feas) ehvi_kernel<C, NOBJ><<<grid, block, lds, ctx->stream>>>(a, ctx->ys);
+  else if (log_form) cehvi_kernel<C, NOBJ, EHVI_LOG><<<grid, block, lds, ctx->stream>>>(a, *feas, ctx->ys);
+  else cehvi_kernel<C, NOBJ, EHVI_PRODUCT><<<grid, block, lds, ctx->stream>>>(a, *feas, ctx->ys);
   GPBO_HIP(ctx, hipGetLastError());
   ehvi_mark(ctx, 1);
   return GPBO_OK;
 }
 
 template <int NOBJ>
-static int ehvi_launch_tile(gpbo_ctx* ctx, const EhviDev& a, int C, size_t lds) {
+static int ehvi_launch_tile(gpbo_ctx* ctx, const EhviDev& a, int C, size_t lds, const EhviFeas* feas, int log_form) {
   switch (C) {
-    case 256: return ehvi_launch<256, NOBJ>(ctx, a, lds);
-    case 128: return ehvi_launch<128, NOBJ>(ctx, a, lds);
-    case 64: return ehvi_launch<64, NOBJ>(ctx, a, lds);
-    default: return ehvi_launch<32, NOBJ>(ctx, a, lds);
+    case 256: return ehvi_launch<256, NOBJ>(ctx, a, lds, feas, log_form);
+    case 128: return ehvi_launch<128, NOBJ>(ctx, a, lds, feas, log_form);
+    case 64: return ehvi_launch<64, NOBJ>(ctx, a, lds, feas, log_form);
+    default: return ehvi_launch<32, NOBJ>(ctx, a, lds, feas, log_form);
   }
 }
 
@@ -170,11 +207,30 @@ static int ehvi_lds_attr(gpbo_ctx* ctx) {
   ctx->func_attrs |= ATTR_EHVI;
   return GPBO_OK;
 }
-
-int launch_ehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels, const double* levels, int64_t n_cells,
-                       const uint8_t* cell_lo, const uint8_t* cell_hi) {
+// ... and the constrained instances', on gpmo_cehvi_argbest's first call
+template <int NOBJ, int FORM>
+static int cehvi_lds_attr_of(gpbo_ctx* ctx) {
+  const void* kernels[] = {
+      reinterpret_cast<const void*>(cehvi_kernel<256, NOBJ, FORM>), reinterpret_cast<const void*>(cehvi_kernel<128, NOBJ, FORM>),
+      reinterpret_cast<const void*>(cehvi_kernel<64, NOBJ, FORM>),  reinterpret_cast<const void*>(cehvi_kernel<32, NOBJ, FORM>)};
+  for (const void* k : kernels) GPBO_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, EHVI_LDS_BYTES));
+  return GPBO_OK;
+}
+static int cehvi_lds_attr(gpbo_ctx* ctx) {
+  if (ctx->func_attrs & ATTR_CEHVI) return GPBO_OK;
   int rc;
-  if ((rc = ehvi_lds_attr(ctx))) return rc;
+  if ((rc = cehvi_lds_attr_of<2, EHVI_PRODUCT>(ctx)) || (rc = cehvi_lds_attr_of<2, EHVI_LOG>(ctx)) ||
+      (rc = cehvi_lds_attr_of<3, EHVI_PRODUCT>(ctx)) || (rc = cehvi_lds_attr_of<3, EHVI_LOG>(ctx)))
+    return rc;
+  ctx->func_attrs |= ATTR_CEHVI;
+  return GPBO_OK;
+}
+
+// the values of both entry points; feas == nullptr: gpbo_ehvi_argbest's
+static int ehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels, const double* levels, int64_t n_cells,
+                       const uint8_t* cell_lo, const uint8_t* cell_hi, const EhviFeas* feas, int log_form) {
+  int rc;
+  if ((rc = feas ? cehvi_lds_attr(ctx) : ehvi_lds_attr(ctx))) return rc;
   if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, M))) return rc;
   // the call's workspace: the level rows, then one word per cell
   const int64_t n_lv = (int64_t)n_obj * GPBO_MAX_EHVI_LEVELS;
@@ -203,7 +259,24 @@ int launch_ehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels,
   a.per_group = (int)((n_cells + G - 1) / G);
   a.M = M;
   const size_t lds = (size_t)n_obj * a.l_max * C * sizeof(double);
-  return n_obj == 2 ? ehvi_launch_tile<2>(ctx, a, C, lds) : ehvi_launch_tile<3>(ctx, a, C, lds);
+  return n_obj == 2 ? ehvi_launch_tile<2>(ctx, a, C, lds, feas, log_form) : ehvi_launch_tile<3>(ctx, a, C, lds, feas, log_form);
+}
+
+int launch_ehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels, const double* levels, int64_t n_cells,
+                       const uint8_t* cell_lo, const uint8_t* cell_hi) {
+  return ehvi_values(ctx, n_obj, M, n_levels, levels, n_cells, cell_lo, cell_hi, nullptr, 0);
+}
+
+int launch_cehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels, const double* levels, int64_t n_cells,
+                        const uint8_t* cell_lo, const uint8_t* cell_hi, int n_constraints, const double* lb, const double* ub,
+                        int log_form) {
+  EhviFeas feas{};
+  feas.n = n_constraints;
+  for (int j = 0; j < n_constraints; ++j) {
+    const Model& m = ctx->models[n_obj + j];
+    feas.cm[j] = m.mu; feas.cs[j] = m.sd; feas.lb[j] = lb[j]; feas.ub[j] = ub[j];
+  }
+  return ehvi_values(ctx, n_obj, M, n_levels, levels, n_cells, cell_lo, cell_hi, &feas, log_form);
 }
 
 }  // namespace gpbo

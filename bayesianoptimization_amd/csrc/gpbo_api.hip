@@ -227,7 +227,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock})
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock})
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -1533,38 +1533,46 @@ int gpbo_kg_argbest(gpbo_ctx* ctx, const double* points, int n_points, int d, do
   return GPBO_OK;
 }
 
-int gpbo_ehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, const double* levels, int64_t n_cells,
-                      const uint8_t* cell_lo, const uint8_t* cell_hi, int k_seeds, int64_t index_offset, int64_t* best_idx,
-                      double* best_val, int64_t* seed_idx, double* seed_val, double* ys_out) {
-  if (!ctx) return GPBO_ERR_INVALID;
-  const int nobj = n_objectives;
-  if (nobj < 2 || nobj > GPBO_MAX_EHVI_OBJECTIVES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: n_objectives out of range [2, 3]");
-  if (!n_levels || !levels || !cell_lo || !cell_hi) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: NULL levels or cells");
+// The refusals gpbo_ehvi_argbest and gpmo_cehvi_argbest share, in the order the former has always had them; w: "<who>: ".
+// ... of the arguments
+static int check_ehvi_args(gpbo_ctx* ctx, const std::string& w, int nobj, const int* n_levels, const double* levels, int64_t n_cells,
+                           const uint8_t* cell_lo, const uint8_t* cell_hi, int k_seeds, const void* best_idx, const void* best_val,
+                           const void* seed_idx, const void* seed_val) {
+  if (nobj < 2 || nobj > GPBO_MAX_EHVI_OBJECTIVES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_objectives out of range [2, 3]");
+  if (!n_levels || !levels || !cell_lo || !cell_hi) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL levels or cells");
   for (int j = 0; j < nobj; ++j) {
-    if (n_levels[j] < 2 || n_levels[j] > GPBO_MAX_EHVI_LEVELS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: a level count out of range [2, 130]");
+    if (n_levels[j] < 2 || n_levels[j] > GPBO_MAX_EHVI_LEVELS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "a level count out of range [2, 130]");
     const double* row = levels + (size_t)j * GPBO_MAX_EHVI_LEVELS;
     for (int l = 0; l + 1 < n_levels[j]; ++l)
       if (!std::isfinite(row[l]) || !(row[l] < row[l + 1]))
-        GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: levels must be finite and strictly increasing up to the last");
-    if (!(row[n_levels[j] - 1] == INFINITY)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: the last level must be +inf");
+        GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "levels must be finite and strictly increasing up to the last");
+    if (!(row[n_levels[j] - 1] == INFINITY)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "the last level must be +inf");
   }
-  if (n_cells < 1 || n_cells > GPBO_MAX_EHVI_CELLS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: n_cells out of range [1, 16641]");
+  if (n_cells < 1 || n_cells > GPBO_MAX_EHVI_CELLS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_cells out of range [1, 16641]");
   for (int64_t k = 0; k < n_cells; ++k)
     for (int j = 0; j < nobj; ++j)
       if ((int)cell_hi[k * nobj + j] >= n_levels[j] || cell_lo[k * nobj + j] >= cell_hi[k * nobj + j])
-        GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: a cell needs lo < hi < the objective's level count");
-  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: k_seeds out of range [0, 64]");
-  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ehvi_argbest: NULL output");
+        GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "a cell needs lo < hi < the objective's level count");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL output");
+  return GPBO_OK;
+}
+// ... of the state of slots 0 .. n_slots - 1 (what: "every objective's slot" / "every objective's and constraint's slot")
+static int check_ehvi_slots(gpbo_ctx* ctx, const char* who, int n_slots, const char* what) {
   int rc;
-  for (int j = 0; j < nobj; ++j) {
-    if ((rc = no_pending_fit(ctx, j, "ehvi_argbest"))) return rc;
+  for (int j = 0; j < n_slots; ++j) {
+    if ((rc = no_pending_fit(ctx, j, who))) return rc;
     if ((rc = need_fitted(ctx, j))) return rc;
   }
-  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ehvi_argbest: no candidates");
-  for (int j = 0; j < nobj; ++j)
-    if (ctx->models[j].M_post != ctx->M) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ehvi_argbest: run gpbo_posterior for every objective's slot first");
-  ev_begin(ctx, T_ACQ);
-  rc = launch_ehvi_values(ctx, nobj, ctx->M, n_levels, levels, n_cells, cell_lo, cell_hi);
+  const std::string w = std::string(who) + ": ";
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "no candidates");
+  for (int j = 0; j < n_slots; ++j)
+    if (ctx->models[j].M_post != ctx->M) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "run gpbo_posterior for " + what + " first");
+  return GPBO_OK;
+}
+// ... and what follows the values in ctx->ys: the selection, the outputs, ys_out
+static int ehvi_finish(gpbo_ctx* ctx, int rc, int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx,
+                       double* seed_val, double* ys_out) {
   if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
   ev_end(ctx, T_ACQ);
   if (rc) return rc;
@@ -1573,6 +1581,42 @@ int gpbo_ehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, cons
     GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return GPBO_OK;
+}
+
+int gpbo_ehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, const double* levels, int64_t n_cells,
+                      const uint8_t* cell_lo, const uint8_t* cell_hi, int k_seeds, int64_t index_offset, int64_t* best_idx,
+                      double* best_val, int64_t* seed_idx, double* seed_val, double* ys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const int nobj = n_objectives;
+  int rc = check_ehvi_args(ctx, "ehvi_argbest: ", nobj, n_levels, levels, n_cells, cell_lo, cell_hi, k_seeds, best_idx, best_val,
+                           seed_idx, seed_val);
+  if (rc) return rc;
+  if ((rc = check_ehvi_slots(ctx, "ehvi_argbest", nobj, "every objective's slot"))) return rc;
+  ev_begin(ctx, T_ACQ);
+  rc = launch_ehvi_values(ctx, nobj, ctx->M, n_levels, levels, n_cells, cell_lo, cell_hi);
+  return ehvi_finish(ctx, rc, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val, ys_out);
+}
+
+int gpmo_cehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, const double* levels, int64_t n_cells,
+                       const uint8_t* cell_lo, const uint8_t* cell_hi, int n_constraints, const double* lb, const double* ub,
+                       int log_form, int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx,
+                       double* seed_val, double* ys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const int nobj = n_objectives, C = n_constraints;
+  const std::string w = "cehvi_argbest: ";
+  int rc = check_ehvi_args(ctx, w, nobj, n_levels, levels, n_cells, cell_lo, cell_hi, k_seeds, best_idx, best_val, seed_idx, seed_val);
+  if (rc) return rc;
+  if (C < 1 || C > GPBO_MAX_MODELS - nobj)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_constraints out of range [1, " + std::to_string(GPBO_MAX_MODELS - nobj) + "]");
+  if (!lb || !ub) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL lb or ub");
+  for (int j = 0; j < C; ++j)
+    if (lb[j] != lb[j] || ub[j] != ub[j] || !(lb[j] < ub[j]))
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "the bounds must not be NaN, with lb < ub for every constraint");
+  if (log_form != 0 && log_form != 1) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "log_form must be 0 or 1");
+  if ((rc = check_ehvi_slots(ctx, "cehvi_argbest", nobj + C, "every objective's and constraint's slot"))) return rc;
+  ev_begin(ctx, T_ACQ);
+  rc = launch_cehvi_values(ctx, nobj, ctx->M, n_levels, levels, n_cells, cell_lo, cell_hi, C, lb, ub, log_form);
+  return ehvi_finish(ctx, rc, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val, ys_out);
 }
 
 // The refusals the greedy draw batches (gpbo_qnei_greedy, gpbo_qnhvi_greedy, gpbo_cnei_greedy) share, in three pieces that each
@@ -1677,6 +1721,34 @@ int gpbo_cnei_greedy(gpbo_ctx* ctx, int n_constraints, const double* y_mean, con
   return launch_cnei_greedy(ctx, C, ms, ctx->M, y_mean, y_std, lb, ub, n_groups, n_paths, n_features, omega, phase, weights, eps,
                             y_floor, base, n_base, q, index_offset, pick_idx, pick_gain, pick_feasible, baseline_out, values_out,
                             viol_out, base_values_out, keys_out);
+}
+
+int gpmo_cnhvi_greedy(gpbo_ctx* ctx, int n_constraints, const double* y_mean, const double* y_std, const double* lb, const double* ub,
+                      int n_groups, int n_paths, int n_features, const double* omega, const double* phase, const double* weights,
+                      const double* eps, const double* ref, const double* base, int n_base, int d, int q, int64_t index_offset,
+                      int64_t* pick_idx, double* pick_gain, double* pick_feasible, int* front_size_out, double* fronts_out,
+                      double* values_out, double* viol_out, double* base_values_out, double* keys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const char* who = "cnhvi_greedy";
+  const std::string w = std::string(who) + ": ";
+  const int C = n_constraints;
+  if (C < 1 || C > GPBO_MAX_MODELS - 2) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_constraints out of range [1, 6]");
+  const bool given = y_mean && y_std && lb && ub && omega && phase && weights && eps && ref && pick_idx && pick_gain && pick_feasible;
+  const Model* ms[GPBO_MAX_MODELS];
+  int rc = check_greedy_slots(ctx, who, n_groups, n_paths, n_features, given, C + 2, y_mean, y_std, ms);
+  if (rc) return rc;
+  for (int j = 0; j < C; ++j)
+    if (lb[j] != lb[j] || ub[j] != ub[j] || !(lb[j] < ub[j]))
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "the bounds must not be NaN, with lb < ub for every constraint");
+  if (!std::isfinite(ref[0]) || !std::isfinite(ref[1])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "ref must be finite");
+  if ((rc = check_greedy_points(ctx, w, "base", base, n_base, GPBO_MAX_QNEHVI_BASE, d, ms[0]->d, "models'"))) return rc;
+  if (q < 1 || q > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q out of range [1, 64]");
+  for (int j = 1; j < C + 2; ++j)
+    if (ms[j]->d != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the slots' models differ in dimension");
+  if ((rc = check_greedy_candidates(ctx, w, C + 2, ms, "the fitted models'", q))) return rc;
+  return launch_cnhvi_greedy(ctx, C, ms, ctx->M, y_mean, y_std, lb, ub, n_groups, n_paths, n_features, omega, phase, weights, eps, ref,
+                             base, n_base, q, index_offset, pick_idx, pick_gain, pick_feasible, front_size_out, fronts_out,
+                             values_out, viol_out, base_values_out, keys_out);
 }
 
 int gpbo_set_timing(gpbo_ctx* ctx, int on) {
@@ -1862,6 +1934,11 @@ int gpbo_debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms) {
 int gpbo_debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
   return greedy_stage_ms(ctx, ctx->qnehvi_clock, "debug_qnehvi_stage_ms", "gpbo_qnhvi_greedy", ms);
+}
+
+int gpbo_debug_cnhvi_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  return greedy_stage_ms(ctx, ctx->cnhvi_clock, "debug_cnhvi_stage_ms", "gpmo_cnhvi_greedy", ms);
 }
 
 int gpbo_debug_qnehvi_fronts(gpbo_ctx* ctx, int n_draws, int n, const double* base_values, const double* ref, int n_insert,

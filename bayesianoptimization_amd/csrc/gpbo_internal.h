@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "gpbo.h"
+#include "gpmo.h"
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
@@ -190,6 +191,7 @@ struct gpbo_ctx {
   gpbo::StageClock qnei_clock{3};   // before the draws, between the baselines and the greedy steps, behind the last step of the last gpbo_qnei_greedy
   gpbo::StageClock cnei_clock{3};   // the same three events of the last gpbo_cnei_greedy
   gpbo::StageClock qnehvi_clock{4}; // before the draws, behind them, behind the front build, behind the last step of the last gpbo_qnhvi_greedy
+  gpbo::StageClock cnhvi_clock{4};  // the same four events of the last gpmo_cnhvi_greedy
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -235,7 +237,7 @@ namespace gpbo {
 
 constexpr size_t SMALL_PIN_IN = 128 * 1024, SMALL_PIN_OUT = 32 * 1024;   // bytes: candidates in; mu, sd out (each)
 constexpr size_t SMALL_PIN_BYTES = SMALL_PIN_IN + 2 * SMALL_PIN_OUT;
-constexpr unsigned ATTR_GEMM128 = 4u, ATTR_CHOL128 = 16u, ATTR_FUSED = 32u, ATTR_MID = 64u, ATTR_KINV_GRAD = 128u, ATTR_POLISH_FUSED = 256u, ATTR_GEMM_FAT = 512u, ATTR_EVOLVE = 2048u, ATTR_KG = 4096u, ATTR_EHVI = 8192u;
+constexpr unsigned ATTR_GEMM128 = 4u, ATTR_CHOL128 = 16u, ATTR_FUSED = 32u, ATTR_MID = 64u, ATTR_KINV_GRAD = 128u, ATTR_POLISH_FUSED = 256u, ATTR_GEMM_FAT = 512u, ATTR_EVOLVE = 2048u, ATTR_KG = 4096u, ATTR_EHVI = 8192u, ATTR_CEHVI = 16384u;
 // pinned staging of a small host-side fit's X (N, d) | y (N), read by the first kernel directly (one window per PIN window)
 constexpr int STAGE_NP_CAP = MID_NP_CAP;
 static_assert(STAGE_NP_CAP >= FUSED_NP_CAP, "the staging window serves both small paths");
@@ -708,6 +710,19 @@ int launch_qnehvi_greedy(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const
                          const double* eps, const double* ref, const double* base, int n_base, int q, int64_t index_offset,
                          int64_t* pick_idx, double* pick_gain, int* front_size_out, double* fronts_out, double* values_out,
                          double* base_values_out, double* keys_out);
+// ehvi.hip: gpmo_cehvi_argbest's values (include/gpmo.h): launch_ehvi_values' EHVI weighted by the feasibility of the constraints in
+// slots n_obj .. n_obj + n_constraints - 1, in the same kernel: ctx->ys[i] = -(E exp(s)) (log_form == 0) or -(log E + s)
+int launch_cehvi_values(gpbo_ctx* ctx, int n_obj, int64_t M, const int* n_levels, const double* levels, int64_t n_cells,
+                        const uint8_t* cell_lo, const uint8_t* cell_hi, int n_constraints, const double* lb, const double* ub,
+                        int log_form);
+// qnehvi.hip: gpmo_cnhvi_greedy behind its argument checks (include/gpmo.h has the rule; cmo_plan.h the workspace, in ctx->greedy):
+// ms / y_mean / y_std per slot (the two objectives, then the C constraints), the draws' inputs concatenated slot-major, then group-major
+int launch_cnhvi_greedy(gpbo_ctx* ctx, int n_constraints, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std,
+                        const double* lb, const double* ub, int n_groups, int n_paths, int n_features, const double* omega,
+                        const double* phase, const double* weights, const double* eps, const double* ref, const double* base,
+                        int n_base, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain, double* pick_feasible,
+                        int* front_size_out, double* fronts_out, double* values_out, double* viol_out, double* base_values_out,
+                        double* keys_out);
 #ifdef GPBO_DEBUG
 int debug_qnehvi_fronts(gpbo_ctx* ctx, int T, int n, const double* base_values, const double* ref, int n_insert,
                         const double* insert_values, int* front_size_out, double* fronts_out);

@@ -19,8 +19,17 @@
 //                          NaN wins), files {gain, index}, marks the mask, and thread t inserts column `pick` of the blocks into
 //                          draw t's front (qnehvi_insert)
 // No multiply-add in any of them (the file is compiled with -ffp-contract=off as well): tests replay the keys bit for bit.
+//
+// gpmo_cnhvi_greedy (the constrained form; include/gpmo.h has the rule, cmo_plan.h its workspace) lives here too, because it runs
+// the same front and score kernels — a kernel cannot be launched from another translation unit.  Its block holds objective 0's MASKED
+// draws (path_plan.h: PATH_MASKED: -inf where the draw's constraint draws call a point infeasible) and objective 1's raw ones, which
+// the three rules above take as they are: `x > ref0` fails for -inf (front build, insertion), and min(-inf, a_k) - a_{k+1} is not
+// > 0, so every strip's width is 0 and 0 h = +0 for the finite h.  New for it:
+//   cnhvi_update_kernel    qnehvi_update_kernel's work plus the share of draws that call the pick feasible, in a record
+//                          {gain, index, feasible} of its own
 #include "greedy.h"
 #include "qnehvi_plan.h"
+#include "cmo_plan.h"
 
 #include <cmath>
 #include <limits>
@@ -342,6 +351,142 @@ int launch_qnehvi_greedy(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const
   GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (over) return qnehvi_overflow(ctx, "qnehvi_greedy", T, over);
   for (int j = 0; j < q; ++j) { pick_idx[j] = hrec[j].idx; pick_gain[j] = hrec[j].gain; }
+  return GPBO_OK;
+}
+
+// ---- gpmo_cnhvi_greedy ------------------------------------------------------------------------------------------------------
+
+struct CnhviRecord { double gain; int64_t idx; double feasible; };      // gpmo_cnhvi_greedy's (greedy_fetch checks its room)
+static_assert(sizeof(CnhviRecord) == 24, "a record is three doubles of the workspace");
+
+// qnehvi_update_kernel's work over the block whose objective 0 is masked, plus feasible = (the number of draws t whose masked value
+// at the pick is > -inf) / T: NaN for a NaN pick.  An infeasible draw's (-inf, y1) fails qnehvi_insert's first test.
+__global__ __launch_bounds__(QNEI_BLOCK) void cnhvi_update_kernel(const SelState* __restrict__ st, const Key* __restrict__ first,
+                                                                  const double* __restrict__ vals, int64_t M, int T, int64_t offset,
+                                                                  int j, double ref0, double ref1, double2* __restrict__ front,
+                                                                  int* __restrict__ size, uint8_t* __restrict__ mask,
+                                                                  CnhviRecord* __restrict__ rec, int* __restrict__ flag) {
+  __shared__ int count;
+  if (threadIdx.x == 0) count = 0;
+  __syncthreads();
+  const GreedyPick p = greedy_pick(st, first, M, offset);
+  const int64_t pick = p.local;
+  const int t = threadIdx.x;
+  if (pick >= 0 && t < T) {
+    const double y0 = vals[(int64_t)t * M + pick], y1 = vals[((int64_t)T + t) * M + pick];
+    if (y0 > -std::numeric_limits<double>::infinity()) atomicAdd(&count, 1);
+    if (qnehvi_insert(front + (int64_t)t * QNEHVI_FRONT, size + t, y0, y1, ref0, ref1)) atomicMax(flag, T - t);
+  }
+  __syncthreads();
+  if (t == 0) {
+    rec[j] = CnhviRecord{p.gain, p.idx, (p.nan || pick < 0) ? std::numeric_limits<double>::quiet_NaN() : (double)count / (double)T};
+    if (pick >= 0) mask[pick] = 1;
+  }
+}
+
+int launch_cnhvi_greedy(gpbo_ctx* ctx, int C, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std,
+                        const double* lb, const double* ub, int G, int S, int F, const double* omega, const double* phase,
+                        const double* weights, const double* eps, const double* ref, const double* base_pts, int B, int q,
+                        int64_t index_offset, int64_t* pick_idx, double* pick_gain, double* pick_feasible, int* front_size_out,
+                        double* fronts_out, double* values_out, double* viol_out, double* base_values_out, double* keys_out) {
+  int rc;
+  const int d = ms[0]->d, DP = ms[0]->DP, T = G * S;
+  const bool keep_base = base_values_out != nullptr && B > 0;
+  const CmoBlock b = cmo_block(T, S, M, B, d, DP, q, values_out != nullptr, keep_base);
+  if ((rc = ensure(ctx, &ctx->greedy, &ctx->cap_greedy, b.doubles))) return rc;
+  double* w = ctx->greedy;
+  double *vals = w + b.vals, *basev = w + b.basev, *viol = w + b.viol, *violb = w + b.violb, *base_s = w + b.base_s;
+  double* stage = values_out ? w + b.stage : nullptr;
+  double* stageb = keep_base ? w + b.stageb : nullptr;
+  double2 *front = (double2*)(w + b.front), *front0 = (double2*)(w + b.front0);
+  int *size = (int*)(w + b.size), *size0 = (int*)(w + b.size0), *flag = (int*)(w + b.flag);
+  uint8_t* mask = (uint8_t*)(w + b.mask);
+  CnhviRecord* rec = (CnhviRecord*)(w + b.rec);
+  const int64_t Mp = round_up(M, POST_CANDS);
+  if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * DP))) return rc;
+  if ((rc = ensure(ctx, &ctx->ys, &ctx->cap_ys, M))) return rc;
+  greedy_mark(ctx, ctx->cnhvi_clock, 0);
+  GPBO_HIP(ctx, hipMemsetAsync(mask, 0, (size_t)((M + 7) / 8 * 8), ctx->stream));
+  GPBO_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
+  if (B > 0) GPBO_HIP(ctx, hipMemcpyAsync(w + b.base, base_pts, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const GreedyDraws draws = greedy_draws(2 + C, ms, G, S, F, omega, phase, weights, eps);
+  // the draws, group by group; per group the constraints in slot order (the violation's sum order), then objective 0 through the
+  // mask, then objective 1 as it is: per slot the group's path weights, the candidates and the base points scaled by THAT slot's
+  // length scales, one pass over each
+  const size_t cand_bytes = (size_t)S * (size_t)M * sizeof(double), base_bytes = (size_t)S * (size_t)B * sizeof(double);
+  for (int g = 0; g < G; ++g) {
+    const int64_t row = (int64_t)g * S;
+    for (int k = 0; k < C + 2; ++k) {
+      const int j = k < C ? 2 + k : k - C;      // 2 .. 1 + C, 0, 1
+      const Model& m = *ms[j];
+      PathWorkspace ws{};
+      if ((rc = greedy_path_weights(ctx, draws, m, j, g, &ws))) return rc;
+      if ((rc = launch_prescale(ctx, ctx->Xc, M, d, DP, m.ls, ctx->Xcs, Mp))) return rc;
+      if (B > 0 && (rc = launch_prescale(ctx, w + b.base, B, d, DP, m.ls, base_s, B))) return rc;
+      double* out = vals + ((int64_t)j * T + row) * M;                 // (objectives only)
+      double* outb = basev + ((int64_t)j * T + row) * b.ldb;
+      if (j == 1) {
+        if ((rc = launch_paths_over(ctx, m, ws, y_mean[j], y_std[j], S, F, ctx->Xcs, M, out, M))) return rc;
+        if (values_out)
+          GPBO_HIP(ctx, hipMemcpyAsync(values_out + ((int64_t)j * T + row) * M, out, cand_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (B > 0 && (rc = launch_paths_over(ctx, m, ws, y_mean[j], y_std[j], S, F, base_s, B, outb, b.ldb))) return rc;
+        if (keep_base)
+          GPBO_HIP(ctx, hipMemcpyAsync(base_values_out + ((int64_t)j * T + row) * B, outb, base_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        continue;
+      }
+      const int epilogue = j == 0 ? (int)PATH_MASKED : (j == 2 ? (int)PATH_VIOL_WRITE : (int)PATH_VIOL_ADD);
+      const double lo = j ? lb[j - 2] : 0.0, hi = j ? ub[j - 2] : 0.0;
+      if ((rc = launch_paths_over_fold(ctx, m, ws, y_mean[j], y_std[j], S, F, ctx->Xcs, M, j ? nullptr : out, M,
+                                       PathFold{epilogue, lo, hi, viol, stage})))
+        return rc;
+      if (values_out)      // stream order: the next pass overwrites the stage after this copy has read it
+        GPBO_HIP(ctx, hipMemcpyAsync(values_out + ((int64_t)j * T + row) * M, stage, cand_bytes, hipMemcpyDeviceToHost, ctx->stream));
+      if (B > 0) {
+        if ((rc = launch_paths_over_fold(ctx, m, ws, y_mean[j], y_std[j], S, F, base_s, B, j ? nullptr : outb, b.ldb,
+                                         PathFold{epilogue, lo, hi, violb, stageb})))
+          return rc;
+        if (keep_base)
+          GPBO_HIP(ctx, hipMemcpyAsync(base_values_out + ((int64_t)j * T + row) * B, stageb, base_bytes, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      if (j == 0 && viol_out) GPBO_HIP(ctx, hipMemcpyAsync(viol_out + row * M, viol, cand_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+  }
+  greedy_mark(ctx, ctx->cnhvi_clock, 1);
+  const dim3 block(QNEI_BLOCK);
+  qnehvi_front_kernel<<<dim3((unsigned)T), block, 0, ctx->stream>>>(basev, basev + (int64_t)T * b.ldb, b.ldb, B, ref[0], ref[1], T, front,
+                                                                    front0, size, size0, flag);
+  GPBO_HIP(ctx, hipGetLastError());
+  greedy_mark(ctx, ctx->cnhvi_clock, 2);
+  const int items = qnei_items(M);
+  const dim3 grid((unsigned)qnei_score_blocks(M));
+  rc = greedy_steps(
+      ctx, M, q, keys_out,
+      [&] {
+        if (items == 2) qnehvi_score_kernel<2><<<grid, block, 0, ctx->stream>>>(vals, M, T, front, size, ref[0], ref[1], mask, ctx->ys);
+        else qnehvi_score_kernel<1><<<grid, block, 0, ctx->stream>>>(vals, M, T, front, size, ref[0], ref[1], mask, ctx->ys);
+      },
+      [&](const SelState* st, const Key* first, int j) {
+        cnhvi_update_kernel<<<dim3(1), block, 0, ctx->stream>>>(st, first, vals, M, T, index_offset, j, ref[0], ref[1], front, size,
+                                                                mask, rec, flag);
+      });
+  if (rc) return rc;
+  greedy_mark(ctx, ctx->cnhvi_clock, 3);
+  const CnhviRecord* hrec;
+  int over = 0;
+  const size_t front_bytes = (size_t)T * QNEHVI_FRONT * 2 * sizeof(double);
+  if ((rc = greedy_fetch(ctx, rec, q, &hrec))) return rc;
+  GPBO_HIP(ctx, hipMemcpyAsync(&over, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  if (front_size_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(front_size_out, size0, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipMemcpyAsync(front_size_out + T, size, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (fronts_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(fronts_out, front0, front_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipMemcpyAsync(fronts_out + (size_t)T * QNEHVI_FRONT * 2, front, front_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (over) return qnehvi_overflow(ctx, "cnhvi_greedy", T, over);
+  for (int j = 0; j < q; ++j) { pick_idx[j] = hrec[j].idx; pick_gain[j] = hrec[j].gain; pick_feasible[j] = hrec[j].feasible; }
   return GPBO_OK;
 }
 

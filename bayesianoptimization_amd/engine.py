@@ -964,34 +964,64 @@ class GpEngine:
         seed_val, ys|None) as `mes_argbest`.  A reader: the fits, the resident posteriors and the candidates stay as they were.  A
         fit pending on one of the slots (`overlapped_fits`) is waited for first, as every reader of a slot does; the new fit has no
         posterior over the candidates, so the call is then refused as such."""
-        rows = [np.asarray(r, dtype=np.float64).ravel() for r in levels]
-        m = len(rows)
-        rows = [r[:int(np.argmax(np.isposinf(r))) + 1] if np.isposinf(r).any() else r for r in rows]      # a row ends at its first +inf
-        if not 2 <= m <= _lib.MAX_EHVI_OBJECTIVES:
-            raise ValueError("ehvi_argbest: levels must have 2 or 3 rows, one per objective")
-        if any(not 2 <= r.shape[0] <= _lib.MAX_EHVI_LEVELS for r in rows):
-            raise ValueError(f"ehvi_argbest: a row of levels needs 2 to {_lib.MAX_EHVI_LEVELS} entries")
-        lo = np.ascontiguousarray(np.asarray(cell_lo, dtype=np.int64))
-        hi = np.ascontiguousarray(np.asarray(cell_hi, dtype=np.int64))
-        if lo.ndim != 2 or lo.shape != hi.shape or lo.shape[1] != m:
-            raise ValueError("ehvi_argbest: cell_lo and cell_hi must both be (K, m)")
-        if lo.size and (min(lo.min(), hi.min()) < 0 or max(lo.max(), hi.max()) > 255):
-            raise ValueError("ehvi_argbest: a cell index is not a level index")
-        table = np.zeros((m, _lib.MAX_EHVI_LEVELS))
-        n_levels = np.zeros(m, dtype=np.intc)
-        for j, r in enumerate(rows):
-            table[j, :r.shape[0]] = r
-            n_levels[j] = r.shape[0]
-        lo8, hi8 = lo.astype(np.uint8), hi.astype(np.uint8)
+        m, n_levels, table, lo8, hi8 = self._ehvi_frame("ehvi_argbest", levels, cell_lo, cell_hi)
         k_seeds = int(k_seeds)
         for j in range(m):
             self._settle(j)
         _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
         best_idx, best_val = C.c_int64(0), C.c_double(0.0)
         u8 = C.POINTER(C.c_uint8)
-        self._check(self._lib.gpbo_ehvi_argbest(self._h, m, n_levels.ctypes.data_as(C.POINTER(C.c_int)), dptr(table), int(lo.shape[0]),
+        self._check(self._lib.gpbo_ehvi_argbest(self._h, m, n_levels.ctypes.data_as(C.POINTER(C.c_int)), dptr(table), int(lo8.shape[0]),
                                                 lo8.ctypes.data_as(u8), hi8.ctypes.data_as(u8), k_seeds, int(index_offset),
                                                 C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
+        return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
+
+    @staticmethod
+    def _ehvi_frame(who, levels, cell_lo, cell_hi):
+        """The levels and boxes of `ehvi_argbest` / `cehvi_argbest` as the library reads them: (m, n_levels (m,) intc, the level table
+        (m, GPBO_MAX_EHVI_LEVELS), cell_lo, cell_hi (K, m) uint8), else ValueError."""
+        rows = [np.asarray(r, dtype=np.float64).ravel() for r in levels]
+        m = len(rows)
+        rows = [r[:int(np.argmax(np.isposinf(r))) + 1] if np.isposinf(r).any() else r for r in rows]      # a row ends at its first +inf
+        if not 2 <= m <= _lib.MAX_EHVI_OBJECTIVES:
+            raise ValueError(f"{who}: levels must have 2 or 3 rows, one per objective")
+        if any(not 2 <= r.shape[0] <= _lib.MAX_EHVI_LEVELS for r in rows):
+            raise ValueError(f"{who}: a row of levels needs 2 to {_lib.MAX_EHVI_LEVELS} entries")
+        lo = np.ascontiguousarray(np.asarray(cell_lo, dtype=np.int64))
+        hi = np.ascontiguousarray(np.asarray(cell_hi, dtype=np.int64))
+        if lo.ndim != 2 or lo.shape != hi.shape or lo.shape[1] != m:
+            raise ValueError(f"{who}: cell_lo and cell_hi must both be (K, m)")
+        if lo.size and (min(lo.min(), hi.min()) < 0 or max(lo.max(), hi.max()) > 255):
+            raise ValueError(f"{who}: a cell index is not a level index")
+        table = np.zeros((m, _lib.MAX_EHVI_LEVELS))
+        n_levels = np.zeros(m, dtype=np.intc)
+        for j, r in enumerate(rows):
+            table[j, :r.shape[0]] = r
+            n_levels[j] = r.shape[0]
+        return m, n_levels, table, np.ascontiguousarray(lo.astype(np.uint8)), np.ascontiguousarray(hi.astype(np.uint8))
+
+    def cehvi_argbest(self, levels, cell_lo, cell_hi, lb, ub, log_form: bool = True, k_seeds: int = 0, index_offset: int = 0,
+                      return_values: bool = False):
+        """Feasibility-weighted expected hypervolume improvement over the resident candidates (gpmo_cehvi_argbest; include/gpmo.h has
+        the formulas, the conventions and the order of every sum): `ehvi_argbest`'s EHVI E for the same `levels` / `cell_lo` /
+        `cell_hi`, and s = the sum of the C constraints' log feasibilities — constraint j from slot m + j's resident posterior and
+        (lb[j], ub[j]), infinite sides allowed.  log_form: ys = -(log E + s); else ys = -(E exp(s)).  Returns (best_idx, best_val,
+        seed_idx, seed_val, ys|None) as `ehvi_argbest`.  A reader: the fits, the resident posteriors and the candidates stay as they
+        were; a fit pending on one of the slots is waited for first."""
+        who = "cehvi_argbest"
+        m, n_levels, table, lo8, hi8 = self._ehvi_frame(who, levels, cell_lo, cell_hi)
+        k_seeds = int(k_seeds)
+        lb, ub, n_c, seed_idx, seed_val, ys = _argbest_frame(lb, ub, k_seeds, self.n_candidates if return_values else None)
+        if n_c < 1:
+            raise ValueError(f"{who}: lb and ub must name at least one constraint")
+        for j in range(min(m + n_c, _lib.MAX_MODELS)):
+            self._settle(j)
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.gpmo_cehvi_argbest(self._h, m, n_levels.ctypes.data_as(C.POINTER(C.c_int)), dptr(table), int(lo8.shape[0]),
+                                                 lo8.ctypes.data_as(u8), hi8.ctypes.data_as(u8), n_c, dptr(lb), dptr(ub),
+                                                 int(bool(log_form)), k_seeds, int(index_offset), C.byref(best_idx),
+                                                 C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
         return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
 
     @staticmethod
@@ -1145,6 +1175,64 @@ class GpEngine:
                                                dptr(keys)))
         return {"index": pick_idx[:q], "gain": pick_gain[:q], "feasible": pick_feasible[:q], "baseline": baseline[:T],
                 "values": values, "viol": viol, "base_values": base_values, "keys": keys}
+
+    def cnehvi_greedy(self, draws, q, lb, ub, ref, base=None, y_mean=None, y_std=None, index_offset=0, return_values=False,
+                      return_keys=False, return_fronts=False):
+        """A batch of q resident candidates by greedy noisy expected hypervolume improvement of two objectives UNDER NOISY
+        CONSTRAINTS, over T joint posterior draws of every slot (gpmo_cnhvi_greedy; include/gpmo.h has the rule).  `draws`: 2 + C
+        lists, slot j's G <= 16 tuples (omega, phase, weights, eps) as `qnei_greedy` takes them — the objectives in slots 0 and 1,
+        constraint j in slot 2 + j —, all with the same G, S <= 16 and F.  lb / ub (C,); ref (2,) finite; y_mean / y_std (2 + C,)
+        (None: 0 / 1 everywhere); base (n_base <= 16384, d) or None: the observed points followed by the pending ones.
+        Returns a dict as `cnei_greedy`'s — "index" (q,) int64, "gain" (q,), "feasible" (q,) the share of draws that call each pick
+        feasible, and, None unless asked for, "values" (2 + C, T, M) the RAW draws, "viol" (T, M), "base_values" (2 + C, T, n_base)
+        (with `return_values`), "keys" (q, M) — plus the fronts as `qnehvi_greedy`'s: "front_size" (2, T) int32 and "fronts"
+        (2, T, 128, 2).  A front of more than 128 points is NotImplementedError.  A reader, as `sample_paths`."""
+        who = "cnehvi_greedy"
+        draws = [list(g) for g in draws]
+        n_slots = len(draws)
+        if n_slots < 3:
+            raise ValueError(f"{who}: draws must hold 2 + C lists of groups, C >= 1: the two objectives', then each constraint's")
+        if n_slots > _lib.MAX_MODELS:
+            raise ValueError(f"{who}: n_constraints out of range [1, {_lib.MAX_MODELS - 2}]")
+        G = self._greedy_groups(who, draws, "each slot needs the same non-empty list of tuples (omega, phase, weights, eps)")
+        lb = np.ascontiguousarray(lb, dtype=np.float64).ravel()
+        ub = np.ascontiguousarray(ub, dtype=np.float64).ravel()
+        ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).ravel())
+        y_mean = np.zeros(n_slots) if y_mean is None else np.ascontiguousarray(y_mean, dtype=np.float64).ravel()
+        y_std = np.ones(n_slots) if y_std is None else np.ascontiguousarray(y_std, dtype=np.float64).ravel()
+        if lb.shape[0] != n_slots - 2 or ub.shape[0] != n_slots - 2 or y_mean.shape[0] != n_slots or y_std.shape[0] != n_slots:
+            raise ValueError(f"{who}: lb / ub must have {n_slots - 2} entries, y_mean / y_std {n_slots}")
+        if ref.shape[0] != 2:
+            raise ValueError(f"{who}: ref must hold one value per objective")
+        omega, phase, weights, eps, S, F, d = self._greedy_inputs(who, list(enumerate(draws)))
+        base, B = self._greedy_points(who, base, d, "base", "n_base", "slots' models")
+        q = int(q)
+        T, M = G * S, max(int(self.n_candidates), 0)
+        n = max(q, 1)
+        L = _lib.MAX_QNEHVI_FRONT
+        pick_idx = np.empty(n, dtype=np.int64)
+        pick_gain, pick_feasible = np.empty(n), np.empty(n)
+        keep = return_values and T >= 1 and M >= 1
+        values = np.empty((n_slots, T, M)) if keep else None
+        viol = np.empty((T, M)) if keep else None
+        base_values = np.empty((n_slots, T, B)) if return_values else None
+        keys = np.empty((q, M)) if return_keys and q >= 1 and M >= 1 else None
+        front_size = np.zeros((2, T), dtype=np.int32) if return_fronts else None
+        fronts = np.empty((2, T, L, 2)) if return_fronts else None
+        self._check(self._lib.gpmo_cnhvi_greedy(self._h, n_slots - 2, dptr(y_mean), dptr(y_std), dptr(lb), dptr(ub), G, int(S), int(F),
+                                                dptr(omega), dptr(phase), dptr(weights), dptr(eps), dptr(ref), dptr(base), B, int(d),
+                                                q, int(index_offset), iptr(pick_idx), dptr(pick_gain), dptr(pick_feasible),
+                                                None if front_size is None else front_size.ctypes.data_as(C.POINTER(C.c_int)),
+                                                dptr(fronts), dptr(values), dptr(viol), dptr(base_values) if B else None, dptr(keys)))
+        return {"index": pick_idx[:q], "gain": pick_gain[:q], "feasible": pick_feasible[:q], "values": values, "viol": viol,
+                "base_values": base_values, "keys": keys, "front_size": front_size, "fronts": fronts}
+
+    def debug_cnhvi_stage_ms(self):
+        """gpbo_debug_cnhvi_stage_ms (debug build): kernel ms of the last `cnehvi_greedy`'s stages, (draws, front build, greedy steps)."""
+        self._need_debug("gpbo_debug_cnhvi_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gpbo_debug_cnhvi_stage_ms(self._h, ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def debug_cnei_stage_ms(self):
         """gpbo_debug_cnei_stage_ms (debug build): kernel ms of the last `cnei_greedy`'s stages, (draws and baselines, greedy steps)."""
@@ -1688,6 +1776,16 @@ class GroupEngine(GpEngine):
                     return_keys=False):
         raise NotImplementedError("a device group has no constrained batch noisy expected improvement (gpbo_cnei_greedy is per "
                                   "context); use a single device")
+
+    def cehvi_argbest(self, levels, cell_lo, cell_hi, lb, ub, log_form: bool = True, k_seeds: int = 0, index_offset: int = 0,
+                      return_values: bool = False):
+        raise NotImplementedError("a device group has no constrained expected hypervolume improvement (gpmo_cehvi_argbest is per "
+                                  "context); use a single device")
+
+    def cnehvi_greedy(self, draws, q, lb, ub, ref, base=None, y_mean=None, y_std=None, index_offset=0, return_values=False,
+                      return_keys=False, return_fronts=False):
+        raise NotImplementedError("a device group has no constrained batch noisy expected hypervolume improvement (gpmo_cnhvi_greedy "
+                                  "is per context); use a single device")
 
     def posterior_refresh(self, slot=0, y_mean=0.0, y_std=1.0, fetch=True, return_route=False):
         raise NotImplementedError("a device group has no posterior refresh path (gpbo_posterior_refresh is per context); "

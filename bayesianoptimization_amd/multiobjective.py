@@ -16,8 +16,13 @@ evaluated over, the conventions and the order of the sum).
 
 `pareto_front`, `hypervolume` and `box_decomposition` are the host side: plain NumPy, no device.
 
-Out of scope here: constraint weighting, m > 3, a local-search stage.  Batches of q > 1 points and the noisy-front variant (NEHVI)
-are `suggest_qnehvi` (qnehvi.py) for m = 2; for m = 3 they are out of scope too.
+Black-box constraints: `ParetoOptimizer(..., constraints=[(lb, ub), ...])` gives every constraint a GP of its own in the slots behind
+the objectives', keeps `front` and `hypervolume` to the FEASIBLE observations, and `suggest` weights the EHVI by the probability
+that every constraint holds, in log form: log EHVI(x) + sum_j log p_j(x) (the engine's `cehvi_argbest`, gpmo_cehvi_argbest;
+include/gpmo.h has the formulas).
+
+Out of scope here: m > 3, a local-search stage.  Batches of q > 1 points and the noisy-front variant (NEHVI) are `suggest_qnehvi`
+(qnehvi.py) and, under constraints, `suggest_constrained_qnehvi` (cqnehvi.py), both for m = 2; for m = 3 they are out of scope too.
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ import warnings
 
 import numpy as np
 
-from ._lib import MAX_EHVI_CELLS, MAX_EHVI_LEVELS, MAX_EHVI_OBJECTIVES
+from ._lib import MAX_EHVI_CELLS, MAX_EHVI_LEVELS, MAX_EHVI_OBJECTIVES, MAX_MODELS
 
 #: the largest front `ParetoOptimizer.suggest` serves: GPBO_MAX_EHVI_LEVELS less r_j and +inf
 MAX_FRONT = MAX_EHVI_LEVELS - 2
@@ -140,13 +145,19 @@ class ParetoOptimizer:
     (`random_state`) shared by the theta searches and the candidate draws.  `flags`: `matern_family` / `scaled_kernels` /
     `scaled_lanes` / `precision`, passed to every HipGPR.
 
-    Out of scope: constraint weighting, m > 3, a local-search stage — the pick is among the candidates.  Batches of q > 1 points
-    and the noisy-front variant (NEHVI): `suggest_qnehvi(self, q)` for m = 2, out of scope for m = 3."""
+    `constraints`: None, or a sequence of C (lb, ub) pairs, lb < ub, infinite sides allowed, m + C <= 8: black-box constraints
+    c_j(x) that hold where lb_j <= c_j(x) <= ub_j.  Constraint j gets a HipGPR of the objectives' construction in slot m + j;
+    `register` then takes the C measured constraint values too, `feasible` is the mask of the observations whose measured values
+    hold, `front` and `hypervolume` are over those alone, and `suggest` weights the EHVI by the feasibility (below).
+
+    Out of scope: m > 3, a local-search stage — the pick is among the candidates.  Batches of q > 1 points and the noisy-front
+    variant (NEHVI): `suggest_qnehvi(self, q)` — with constraints `suggest_constrained_qnehvi(self, q)` — for m = 2, out of scope
+    for m = 3."""
 
     _FLAGS = ("matern_family", "scaled_kernels", "scaled_lanes", "precision")
 
     def __init__(self, pbounds, n_objectives, ref_point, kernel=None, alpha=1e-6, n_restarts_optimizer=5, random_state=None,
-                 engine=None, device=0, **flags):
+                 engine=None, device=0, constraints=None, **flags):
         from sklearn.base import clone
         from sklearn.gaussian_process.kernels import Matern
 
@@ -167,6 +178,17 @@ class ParetoOptimizer:
         self.bounds = np.array([[float(lo), float(hi)] for lo, hi in pbounds.values()], dtype=np.float64)
         if self.bounds.shape[0] < 1 or not np.all(self.bounds[:, 0] < self.bounds[:, 1]):
             raise ValueError("pbounds must give lo < hi for at least one parameter")
+        self.constraints = None
+        if constraints is not None:
+            try:
+                pairs = np.array([[float(lo), float(hi)] for lo, hi in constraints], dtype=np.float64).reshape(-1, 2)
+            except (TypeError, ValueError):
+                raise ValueError("constraints must be a sequence of (lb, ub) pairs") from None
+            if pairs.shape[0] < 1 or np.isnan(pairs).any() or not np.all(pairs[:, 0] < pairs[:, 1]):
+                raise ValueError("constraints must be at least one (lb, ub) pair, without a NaN and with lb < ub")
+            if self.n_objectives + pairs.shape[0] > MAX_MODELS:
+                raise ValueError(f"n_objectives + the number of constraints must not exceed {MAX_MODELS}, the engine's model slots")
+            self.constraints = pairs
         self._random_state = ensure_rng(random_state)
         self._engine_arg, self._device = engine, device
         self._params = np.empty((0, self.bounds.shape[0]))
@@ -174,6 +196,11 @@ class ParetoOptimizer:
         self._gps = [HipGPR(kernel=Matern(nu=2.5) if kernel is None else clone(kernel), alpha=alpha, normalize_y=True,
                             n_restarts_optimizer=n_restarts_optimizer, random_state=self._random_state, engine=engine, slot=j,
                             **flags) for j in range(self.n_objectives)]
+        n_c = 0 if self.constraints is None else self.constraints.shape[0]
+        self._constraint_values = np.empty((0, n_c))
+        self._cgps = [HipGPR(kernel=Matern(nu=2.5) if kernel is None else clone(kernel), alpha=alpha, normalize_y=True,
+                             n_restarts_optimizer=n_restarts_optimizer, random_state=self._random_state, engine=engine,
+                             slot=self.n_objectives + j, **flags) for j in range(n_c)]
 
     # -- the store ------------------------------------------------------------------------------------------------------------
     def __len__(self):
@@ -187,8 +214,14 @@ class ParetoOptimizer:
     def targets(self):
         return self._targets
 
-    def register(self, params, targets):
-        """One observation: `params` a {name: value} dict or a (d,) array in `pbounds`' order, `targets` (m,) finite values."""
+    @property
+    def constraint_values(self):
+        """(n, C) the measured constraint values ((n, 0) without constraints)"""
+        return self._constraint_values if self.constraints is not None else np.empty((len(self), 0))
+
+    def register(self, params, targets, constraint_values=None):
+        """One observation: `params` a {name: value} dict or a (d,) array in `pbounds`' order, `targets` (m,) finite values; with
+        `constraints`, `constraint_values` (C,) the finite measured values of the constraints (without: None)."""
         if isinstance(params, dict):
             if set(params) != set(self.keys):
                 raise ValueError(f"params must have exactly the keys {self.keys}")
@@ -200,21 +233,45 @@ class ParetoOptimizer:
             raise ValueError("params must hold one finite value per parameter")
         if y.shape[0] != self.n_objectives or not np.all(np.isfinite(y)):
             raise ValueError("targets must hold one finite value per objective")
+        if self.constraints is None:
+            if constraint_values is not None:
+                raise ValueError("constraint_values given, but the optimizer has no constraints")
+        else:
+            c = np.empty(0) if constraint_values is None else np.asarray(constraint_values, dtype=np.float64).ravel()
+            if c.shape[0] != self.constraints.shape[0] or not np.all(np.isfinite(c)):
+                raise ValueError("constraint_values must hold one finite value per constraint")
+            self._constraint_values = np.concatenate([self._constraint_values, c[None]])
         self._params = np.concatenate([self._params, x[None]])
         self._targets = np.concatenate([self._targets, y[None]])
 
     @property
+    def feasible(self):
+        """(n,) bool: the observations whose measured constraint values all lie in their [lb, ub]; all True without constraints."""
+        if self.constraints is None:
+            return np.ones(len(self), dtype=bool)
+        c = self._constraint_values
+        return np.all((c >= self.constraints[:, 0]) & (c <= self.constraints[:, 1]), axis=1)
+
+    def _feasible_observations(self):
+        """(params, targets) of the feasible observations: all of them without constraints"""
+        if self.constraints is None:
+            return self._params, self._targets
+        ok = self.feasible
+        return self._params[ok], self._targets[ok]
+
+    @property
     def front(self):
         """(params (k, d), targets (k, m)) of the non-dominated observations strictly above `ref_point` (`pareto_front`: equal
-        targets once, at their first observation; order of first appearance)."""
-        P = pareto_front(self._targets, self.ref_point)
-        rows = [int(np.flatnonzero(np.all(self._targets == p, axis=1))[0]) for p in P]
-        return self._params[rows], P
+        targets once, at their first observation; order of first appearance).  With `constraints`: of the FEASIBLE observations."""
+        params, targets = self._feasible_observations()
+        P = pareto_front(targets, self.ref_point)
+        rows = [int(np.flatnonzero(np.all(targets == p, axis=1))[0]) for p in P]
+        return params[rows], P
 
     @property
     def hypervolume(self):
-        """The hypervolume the observations dominate above `ref_point`."""
-        return hypervolume(self._targets, self.ref_point)
+        """The hypervolume the observations dominate above `ref_point`.  With `constraints`: the FEASIBLE observations."""
+        return hypervolume(self._feasible_observations()[1], self.ref_point)
 
     # -- the suggestion -------------------------------------------------------------------------------------------------------
     def _engine(self):
@@ -222,9 +279,19 @@ class ParetoOptimizer:
             from .gpr import shared_engine
 
             self._engine_arg = shared_engine(self._device)
-            for gp in self._gps:
+            for gp in self._gps + self._cgps:
                 gp.engine = self._engine_arg
         return self._engine_arg
+
+    def _constraint_host_reason(self):
+        """(j, reason) of the first constraint whose model would run on the host, else None"""
+        from sklearn.base import clone
+
+        for j, gp in enumerate(self._cgps):
+            reason = gp._unsupported_reason(clone(gp.kernel), self._constraint_values[:, j], self._params)
+            if reason is not None:
+                return j, reason
+        return None
 
     def suggest(self, n_random: int = 10_000, return_info: bool = False):
         """One parameter dict to probe next: the candidate of the largest expected hypervolume improvement.  In this order:
@@ -244,8 +311,15 @@ class ParetoOptimizer:
         Nothing else draws from the RandomState.  `return_info=True`: (params, info), info = {"value": the pick's EHVI, "index": its
         candidate index, "n_cells": K, "front_size": the front's size}.
 
-        Out of scope: constraint weighting, m > 3, a local-search stage (the pick is AMONG THE CANDIDATES); q > 1 and NEHVI are
-        `suggest_qnehvi` for m = 2."""
+        With `constraints` (C of them) the same order, and in addition: in 2. NotImplementedError for an engine without
+        `cehvi_argbest` and for a constraint whose model would run on the host, and the front is the FEASIBLE observations'; in 3.
+        the C constraint fits follow the objectives' in slot order m .. m + C - 1, their theta searches' draws after the
+        objectives', in slot order; in 5. their posterior passes follow too; 6. is `cehvi_argbest` in log form over the boxes of the
+        feasible front — none feasible yet: the one box [r, +inf), "improve on r, weighted by feasibility" —, and info["value"] is
+        log EHVI + sum_j log p_j at the pick.
+
+        Out of scope: m > 3, a local-search stage (the pick is AMONG THE CANDIDATES); q > 1 and NEHVI are `suggest_qnehvi` /
+        `suggest_constrained_qnehvi` for m = 2."""
         from sklearn.base import clone
 
         from . import fused_acquisition as A
@@ -265,7 +339,14 @@ class ParetoOptimizer:
             if reason is not None:
                 raise NotImplementedError(f"ParetoOptimizer.suggest: objective {j}'s model runs on the host ({reason}); only models "
                                           "on the device path are served")
-        P = pareto_front(self._targets, self.ref_point)
+        if self.constraints is not None:
+            if not hasattr(eng, "cehvi_argbest"):
+                raise NotImplementedError("ParetoOptimizer.suggest: the engine has no cehvi_argbest")
+            host = self._constraint_host_reason()
+            if host is not None:
+                raise NotImplementedError(f"ParetoOptimizer.suggest: constraint {host[0]}'s model runs on the host ({host[1]}); only "
+                                          "models on the device path are served")
+        P = pareto_front(self._feasible_observations()[1], self.ref_point)
         if P.shape[0] > MAX_FRONT:
             raise NotImplementedError(f"ParetoOptimizer.suggest: the front has {P.shape[0]} points, more than the {MAX_FRONT} "
                                       "gpbo_ehvi_argbest's level lists hold; the front is never thinned")
@@ -275,14 +356,20 @@ class ParetoOptimizer:
             with overlap:
                 for j, gp in enumerate(self._gps):
                     gp.fit(self._params, self._targets[:, j])
-        if any(gp._host_mode for gp in self._gps):      # (unreachable after the refusals; a host model must not get this far silently)
+                for j, gp in enumerate(self._cgps):
+                    gp.fit(self._params, self._constraint_values[:, j])
+        if any(gp._host_mode for gp in self._gps + self._cgps):      # (unreachable after the refusals; a host model must not get this far silently)
             raise NotImplementedError("ParetoOptimizer.suggest: a model was fitted on the host")
         eng.generate_candidates_like(n_random, self.bounds[:, 0], self.bounds[:, 1], self._random_state)
-        for gp in self._gps:
+        for gp in self._gps + self._cgps:
             gp._ensure_resident()
             eng.posterior(slot=gp.slot, y_mean=float(gp._y_train_mean), y_std=float(gp._y_train_std), fetch=False)
         _n_levels, levels, cell_lo, cell_hi = box_decomposition(P, self.ref_point)
-        index, value, _seed_idx, _seed_val, _ys = eng.ehvi_argbest(levels, cell_lo, cell_hi)
+        if self.constraints is None:
+            index, value, _seed_idx, _seed_val, _ys = eng.ehvi_argbest(levels, cell_lo, cell_hi)
+        else:
+            index, value, _seed_idx, _seed_val, _ys = eng.cehvi_argbest(levels, cell_lo, cell_hi, self.constraints[:, 0],
+                                                                        self.constraints[:, 1], log_form=True)
         row = np.asarray(eng.get_candidate_rows(np.array([index], dtype=np.int64), self.bounds.shape[0]), dtype=np.float64)[0]
         params = dict(zip(self.keys, row))
         if return_info:

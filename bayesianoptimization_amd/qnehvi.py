@@ -16,7 +16,9 @@ include/gpbo.h has the formulas and the conventions): the draws stay on the devi
 there, and the q scoring passes, selections and front updates run on the stream without a host round trip.
 
 m = 2 only: at two objectives a front is a staircase and the improvement a sum over its strips.  Three objectives need a box
-decomposition per draw on the device; they are refused, not approximated.
+decomposition per draw on the device; they are refused, not approximated.  Black-box constraints are served by
+`suggest_constrained_qnehvi` (cqnehvi.py), which masks objective 0's draw by the draw's own constraint draws; this function scores
+fronts built from every observed point and refuses nothing on their account.
 """
 from __future__ import annotations
 

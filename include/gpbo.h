@@ -942,8 +942,9 @@ int gpbo_debug_kg_stage_ms(gpbo_ctx* ctx, float* ms);
 /* Kernel milliseconds (HIP events) of the generator kernel of the context's last gpbo_generate_candidates or
  * gpbo_generate_candidates_trust_region call: the launch alone, without the call's argument upload and synchronise. */
 int gpbo_debug_generate_ms(gpbo_ctx* ctx, float* ms);
-/* Kernel milliseconds (HIP events) of the value kernel of the context's last gpbo_ehvi_argbest: the tables and the sum over the
- * boxes, without the upload of levels and boxes and without the selection. */
+/* Kernel milliseconds (HIP events) of the value kernel of the context's last gpbo_ehvi_argbest or gpmo_cehvi_argbest (include/gpmo.h;
+ * with its feasibility epilogue): the tables and the sum over the boxes, without the upload of levels and boxes and without the
+ * selection. */
 int gpbo_debug_ehvi_ms(gpbo_ctx* ctx, float* ms);
 /* Kernel milliseconds (HIP events) of the two stages of the context's last gpbo_qnei_greedy: ms[0] the draws — the candidates'
  * and the pending points' scaling, per group the path weights and the passes over candidates, training and pending points, the
@@ -958,6 +959,10 @@ int gpbo_debug_cnei_stage_ms(gpbo_ctx* ctx, float* ms);
  * slot and group the path weights and the passes over candidates and base points —, ms[1] the front build, ms[2] the q greedy steps
  * (score, selection, update; with keys_out their copies too).  The fetch of the results and the synchronise are in none. */
 int gpbo_debug_qnehvi_stage_ms(gpbo_ctx* ctx, float* ms);
+/* The same three stages of the context's last gpmo_cnhvi_greedy (include/gpmo.h): ms[0] the draws — per group and slot the path
+ * weights, the scalings and the passes over candidates and base points, with values_out / viol_out / base_values_out their copies
+ * too —, ms[1] the front build, ms[2] the q greedy steps. */
+int gpbo_debug_cnhvi_stage_ms(gpbo_ctx* ctx, float* ms);
 /* gpbo_qnhvi_greedy's front build and update rule alone, on host-given values: qnehvi_front_kernel on base_values (2, n_draws, n)
  * — objective-major, as base_values_out — against ref (2,), then the update rule n_insert times per draw, in order, with
  * insert_values (2, n_draws, n_insert).  front_size_out (n_draws,), fronts_out (n_draws, GPBO_MAX_QNEHVI_FRONT, 2).  n_draws in
