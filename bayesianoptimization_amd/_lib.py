@@ -1,4 +1,4 @@
-"""ctypes binding of libgpbo.so (the C ABI declared in include/gpbo.h and, for the constrained multi-objective calls, include/gpmo.h).
+"""ctypes binding of libgpbo.so (the C ABI declared in include/gpbo.h and, for the constrained multi-objective calls, include/gpmo.h, and for the three-objective batch include/gpmo3.h).
 
 There is NO CPU fallback: if the HIP library is missing or no AMD GPU is visible, loading or context
 creation raises.  Nothing in this package imports the test oracle.
@@ -177,6 +177,20 @@ MO_SIGNATURES = {
                                     _c_double_p, _c_double_p, _c_double_p]),
 }
 
+# name -> (restype, argtypes) of the three-objective batch; must list every product symbol include/gpmo3.h declares (tests check this)
+MO3_SIGNATURES = {
+    "gpmo3_nhvi_greedy": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int, _c_double_p, _c_double_p,
+                                    _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                    _c_int64_p, _c_double_p, _c_int_p, _c_double_p, _c_int_p, _c_double_p, _c_double_p, _c_double_p,
+                                    _c_double_p]),
+}
+# ... and its debug part (libgpbo_dbg.so only)
+MO3_DEBUG_SIGNATURES = {
+    "gpmo3_debug_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "gpmo3_debug_cells": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_int_p, _c_double_p,
+                                    _c_int_p, _c_double_p]),
+}
+
 # entry points only libgpbo_dbg.so exports (include/gpbo.h, "#ifdef GPBO_DEBUG")
 DEBUG_SIGNATURES = {
     "gpbo_debug_minimize_box": (C.c_int, [C.c_void_p, C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int,
@@ -257,7 +271,7 @@ def load_library(path: str | None = None):
         raise ImportError(
             f"{path} not found: the HIP extension has not been built. Run "
             "`python -m bayesianoptimization_amd.build` (needs hipcc). There is no CPU fallback.")
-    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES})
+    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES})
     if not explicit:
         _lib = lib
     return lib
@@ -274,7 +288,7 @@ def load_debug_library():
                 build_debug(verbose=False)
             except Exception as e:  # noqa: BLE001
                 raise ImportError(f"{DEBUG_LIB_PATH} not found and building it failed ({e})") from e
-        _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **DEBUG_SIGNATURES})
+        _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **DEBUG_SIGNATURES, **MO3_DEBUG_SIGNATURES})
     return _debug_lib
 
 

@@ -51,6 +51,7 @@ SOURCES = {
     "ehvi.hip": ["-ffp-contract=off"],        # gpbo_ehvi_argbest: expected hypervolume improvement values (per-candidate level tables in LDS, the sum over the boxes; acq_formulas.h's pieces); gpmo_cehvi_argbest: the same kernel body with the log-feasibility epilogue
     "qnei.hip": ["-ffp-contract=off"],        # gpbo_qnei_greedy: greedy batch noisy expected improvement over a resident (T, M) block of posterior draws (the score kernel streams it once per pick; incumbents updated in-stream); gpbo_cnei_greedy: the same stream over draws masked by their constraint draws
     "qnehvi.hip": ["-ffp-contract=off"],      # gpbo_qnhvi_greedy: greedy batch noisy expected hypervolume improvement, m = 2: per-draw fronts from the draws' values at the observed and pending points, a score kernel that streams the (2, T, M) block against the fronts' strips in LDS, fronts updated in-stream; gpmo_cnhvi_greedy: the same stream over objective 0 masked by the constraint draws
+    "qnehvi3.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # gpmo3_nhvi_greedy: the same greedy batch for m = 3: per-draw fronts by repeated arg-max, a height-map sweep into <= 2 n + 1 cells per draw (one wave, staircase in LDS), a score kernel that streams the (3, T, M) block against cells staged in LDS by the draws' cell counts, a wave per draw that inserts and re-sweeps
     "candidates.hip": [],
     "trust_region.hip": ["-ffp-contract=off"],  # gpbo_generate_candidates_trust_region: lo + (hi - lo) * u as NumPy computes it (scrambled Sobol points under a Philox mask)
     "mt19937.hip": ["-ffp-contract=off"],      # lo + (hi - lo) * u as NumPy computes it
@@ -113,7 +114,7 @@ def _code_only(src: str) -> str:
 
 def _fingerprint() -> str:
     h = hashlib.sha256()
-    names = sorted(os.listdir(CSRC)) + ["../../include/gpbo.h", "../../include/gpmo.h"]
+    names = sorted(os.listdir(CSRC)) + ["../../include/gpbo.h", "../../include/gpmo.h", "../../include/gpmo3.h"]
     for n in names:
         p = os.path.normpath(os.path.join(CSRC, n))
         if os.path.isfile(p):

@@ -227,7 +227,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock})
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock})
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -1751,6 +1751,28 @@ int gpmo_cnhvi_greedy(gpbo_ctx* ctx, int n_constraints, const double* y_mean, co
                              values_out, viol_out, base_values_out, keys_out);
 }
 
+int gpmo3_nhvi_greedy(gpbo_ctx* ctx, const double* y_mean, const double* y_std, int n_groups, int n_paths, int n_features,
+                      const double* omega, const double* phase, const double* weights, const double* eps, const double* ref,
+                      const double* base, int n_base, int d, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain,
+                      int* front_size_out, double* fronts_out, int* cell_count_out, double* cells_out, double* values_out,
+                      double* base_values_out, double* keys_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const char* who = "nhvi3_greedy";
+  const std::string w = std::string(who) + ": ";
+  const bool given = y_mean && y_std && omega && phase && weights && eps && ref && pick_idx && pick_gain;
+  const Model* ms[3];
+  int rc = check_greedy_slots(ctx, who, n_groups, n_paths, n_features, given, 3, y_mean, y_std, ms);
+  if (rc) return rc;
+  if (!std::isfinite(ref[0]) || !std::isfinite(ref[1]) || !std::isfinite(ref[2])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "ref must be finite");
+  if ((rc = check_greedy_points(ctx, w, "base", base, n_base, GPBO_MAX_QNEHVI_BASE, d, ms[0]->d, "models'"))) return rc;
+  if (q < 1 || q > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "q out of range [1, 64]");
+  if (ms[1]->d != ms[0]->d || ms[2]->d != ms[0]->d) GPBO_FAIL(ctx, GPBO_ERR_STATE, w + "the three objectives' models differ in dimension");
+  if ((rc = check_greedy_candidates(ctx, w, 3, ms, "the fitted models'", q))) return rc;
+  return launch_qnehvi3_greedy(ctx, ms, ctx->M, y_mean, y_std, n_groups, n_paths, n_features, omega, phase, weights, eps, ref, base,
+                               n_base, q, index_offset, pick_idx, pick_gain, front_size_out, fronts_out, cell_count_out, cells_out,
+                               values_out, base_values_out, keys_out);
+}
+
 int gpbo_set_timing(gpbo_ctx* ctx, int on) {
   if (!ctx) return GPBO_ERR_INVALID;
   ctx->timing_off = !on;
@@ -1950,6 +1972,23 @@ int gpbo_debug_qnehvi_fronts(gpbo_ctx* ctx, int n_draws, int n, const double* ba
     GPBO_FAIL(ctx, GPBO_ERR_INVALID, "debug_qnehvi_fronts: bad arguments");
   GPBO_HIP(ctx, hipSetDevice(ctx->device));
   return debug_qnehvi_fronts(ctx, n_draws, n, base_values, ref, n_insert, insert_values, front_size_out, fronts_out);
+}
+
+int gpmo3_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  return greedy_stage_ms(ctx, ctx->qnehvi3_clock, "gpmo3_debug_stage_ms", "gpmo3_nhvi_greedy", ms);
+}
+
+int gpmo3_debug_cells(gpbo_ctx* ctx, int n_draws, int n, const double* base_values, const double* ref, int n_insert,
+                      const double* insert_values, int* front_size_out, double* fronts_out, int* cell_count_out, double* cells_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (n_draws < 1 || n_draws > 4096 || n < 0 || n > GPBO_MAX_QNEHVI_BASE || n_insert < 0 || n_insert > 4096 || !ref ||
+      !std::isfinite(ref[0]) || !std::isfinite(ref[1]) || !std::isfinite(ref[2]) || (n > 0 && !base_values) ||
+      (n_insert > 0 && !insert_values) || !front_size_out || !fronts_out || !cell_count_out || !cells_out)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpmo3_debug_cells: bad arguments");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  return debug_qnehvi3_cells(ctx, n_draws, n, base_values, ref, n_insert, insert_values, front_size_out, fronts_out, cell_count_out,
+                             cells_out);
 }
 
 #endif  // GPBO_DEBUG

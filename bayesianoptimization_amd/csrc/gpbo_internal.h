@@ -14,6 +14,7 @@
 
 #include "gpbo.h"
 #include "gpmo.h"
+#include "gpmo3.h"
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
@@ -182,7 +183,7 @@ struct gpbo_ctx {
   int64_t cap_kg = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
-  double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
+  double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h), gpmo3_nhvi_greedy (qnehvi3_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
   int64_t cap_greedy = 0;
   hipEvent_t kg_ev[4] = {};   // debug build: around the three stages of the last gpbo_kg_argbest (the fields exist in both builds: one layout)
   bool kg_ev_used = false;
@@ -192,6 +193,7 @@ struct gpbo_ctx {
   gpbo::StageClock cnei_clock{3};   // the same three events of the last gpbo_cnei_greedy
   gpbo::StageClock qnehvi_clock{4}; // before the draws, behind them, behind the front build, behind the last step of the last gpbo_qnhvi_greedy
   gpbo::StageClock cnhvi_clock{4};  // the same four events of the last gpmo_cnhvi_greedy
+  gpbo::StageClock qnehvi3_clock{4}; // the same four events of the last gpmo3_nhvi_greedy (the front build includes the cells)
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -723,7 +725,16 @@ int launch_cnhvi_greedy(gpbo_ctx* ctx, int n_constraints, const Model* const* ms
                         int n_base, int q, int64_t index_offset, int64_t* pick_idx, double* pick_gain, double* pick_feasible,
                         int* front_size_out, double* fronts_out, double* values_out, double* viol_out, double* base_values_out,
                         double* keys_out);
+// qnehvi3.hip: gpmo3_nhvi_greedy behind its argument checks (include/gpmo3.h has the rule; qnehvi3_plan.h the workspace, in
+// ctx->greedy): ms / y_mean / y_std / ref per objective, the draws' inputs concatenated in slot order
+int launch_qnehvi3_greedy(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std, int n_groups,
+                          int n_paths, int n_features, const double* omega, const double* phase, const double* weights,
+                          const double* eps, const double* ref, const double* base, int n_base, int q, int64_t index_offset,
+                          int64_t* pick_idx, double* pick_gain, int* front_size_out, double* fronts_out, int* cell_count_out,
+                          double* cells_out, double* values_out, double* base_values_out, double* keys_out);
 #ifdef GPBO_DEBUG
+int debug_qnehvi3_cells(gpbo_ctx* ctx, int T, int n, const double* base_values, const double* ref, int n_insert,
+                        const double* insert_values, int* front_size_out, double* fronts_out, int* cell_count_out, double* cells_out);
 int debug_qnehvi_fronts(gpbo_ctx* ctx, int T, int n, const double* base_values, const double* ref, int n_insert,
                         const double* insert_values, int* front_size_out, double* fronts_out);
 int debug_kg_lines(gpbo_ctx* ctx, const double* a, const double* b, int64_t R, int n_lines, double* out);

@@ -1130,6 +1130,81 @@ class GpEngine:
         return {"index": pick_idx[:q], "gain": pick_gain[:q], "values": values, "base_values": base_values, "keys": keys,
                 "front_size": front_size, "fronts": fronts}
 
+    def qnehvi3_greedy(self, draws, q, ref, base=None, y_mean=(0.0, 0.0, 0.0), y_std=(1.0, 1.0, 1.0), index_offset=0,
+                       return_values=False, return_keys=False, return_fronts=False):
+        """A batch of q resident candidates by greedy noisy expected hypervolume improvement over T joint posterior draws of THREE
+        objectives (gpmo3_nhvi_greedy; include/gpmo3.h has the rule, the conventions and the order of every sum).  `draws`: three
+        lists, objective j's (slot j's) G <= 16 tuples (omega, phase, weights, eps) as `qnei_greedy` takes them, all with the same
+        G, S <= 16 and F.  ref, y_mean, y_std (3,); base (n_base <= 16384, d) or None: the observed points followed by the pending
+        ones.  Returns a dict: "index" (q,) int64, "gain" (q,), and — None unless asked for — "values" (3, T, M), "base_values"
+        (3, T, n_base) (with `return_values`), "keys" (q, M), and with `return_fronts` "front_size" (2, T) int32, "fronts"
+        (2, T, 128, 3) in the stored order (objective 2, then 0, then 1, all descending), "cell_count" (2, T) int32 and "cells"
+        (2, T, 257, 5) rows (x_lo, x_hi, y_lo, y_hi, h) (before the first pick | after the last; rows past a count are
+        unspecified).  A front of more than 128 points is NotImplementedError.  A reader, as `sample_paths`."""
+        who = "qnehvi3_greedy"
+        draws = [list(g) for g in draws]
+        if len(draws) != 3:
+            raise ValueError(f"{who}: draws must hold three lists of groups, one per objective")
+        G = self._greedy_groups(who, draws, "each objective needs the same non-empty list of tuples (omega, phase, weights, eps)")
+        omega, phase, weights, eps, S, F, d = self._greedy_inputs(who, list(enumerate(draws)))
+        base, B = self._greedy_points(who, base, d, "base", "n_base", "slots' models")
+        ref, y_mean, y_std = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (ref, y_mean, y_std))
+        if ref.shape[0] != 3 or y_mean.shape[0] != 3 or y_std.shape[0] != 3:
+            raise ValueError(f"{who}: ref, y_mean and y_std must hold one value per objective")
+        q = int(q)
+        T, M = G * S, max(int(self.n_candidates), 0)
+        n = max(q, 1)
+        L = _lib.MAX_QNEHVI_FRONT
+        ints = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+        pick_idx = np.empty(n, dtype=np.int64)
+        pick_gain = np.empty(n)
+        values = np.empty((3, T, M)) if return_values and M >= 1 else None
+        base_values = np.empty((3, T, B)) if return_values else None
+        keys = np.empty((q, M)) if return_keys and q >= 1 and M >= 1 else None
+        front_size = np.zeros((2, T), dtype=np.int32) if return_fronts else None
+        fronts = np.empty((2, T, L, 3)) if return_fronts else None
+        cell_count = np.zeros((2, T), dtype=np.int32) if return_fronts else None
+        cells = np.empty((2, T, 2 * L + 1, 5)) if return_fronts else None
+        self._check(self._lib.gpmo3_nhvi_greedy(self._h, dptr(y_mean), dptr(y_std), G, int(S), int(F), dptr(omega), dptr(phase),
+                                                dptr(weights), dptr(eps), dptr(ref), dptr(base), B, int(d), q, int(index_offset),
+                                                iptr(pick_idx), dptr(pick_gain), ints(front_size), dptr(fronts), ints(cell_count),
+                                                dptr(cells), dptr(values), dptr(base_values) if B else None, dptr(keys)))
+        return {"index": pick_idx[:q], "gain": pick_gain[:q], "values": values, "base_values": base_values, "keys": keys,
+                "front_size": front_size, "fronts": fronts, "cell_count": cell_count, "cells": cells}
+
+    def debug_qnehvi3_cells(self, base_values, ref, insert_values=None):
+        """gpmo3_debug_cells (debug build): the product's front build and sweep on base_values (3, T, n) against ref (3,), then its
+        update rule with insert_values (3, T, n_insert), in order: (front_size (T,) int32, fronts (T, 128, 3), cell_count (T,) int32,
+        cells (T, 257, 5))."""
+        self._need_debug("gpmo3_debug_cells")
+        bv = np.ascontiguousarray(np.asarray(base_values, dtype=np.float64))
+        if bv.ndim != 3 or bv.shape[0] != 3:
+            raise ValueError("debug_qnehvi3_cells: base_values must be (3, T, n)")
+        T, n = int(bv.shape[1]), int(bv.shape[2])
+        iv, n_insert = None, 0
+        if insert_values is not None:
+            iv = np.ascontiguousarray(np.asarray(insert_values, dtype=np.float64))
+            if iv.ndim != 3 or iv.shape[:2] != (3, T):
+                raise ValueError("debug_qnehvi3_cells: insert_values must be (3, T, n_insert)")
+            n_insert = int(iv.shape[2])
+        ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).ravel())
+        L = _lib.MAX_QNEHVI_FRONT
+        size, count = np.zeros(max(T, 1), dtype=np.int32), np.zeros(max(T, 1), dtype=np.int32)
+        fronts, cells = np.empty((max(T, 1), L, 3)), np.empty((max(T, 1), 2 * L + 1, 5))
+        ints = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._check(self._lib.gpmo3_debug_cells(self._h, T, n, dptr(bv) if n else None, dptr(ref) if ref.shape[0] == 3 else None,
+                                                n_insert, dptr(iv) if n_insert else None, ints(size), dptr(fronts), ints(count),
+                                                dptr(cells)))
+        return size[:T], fronts[:T], count[:T], cells[:T]
+
+    def debug_qnehvi3_stage_ms(self):
+        """gpmo3_debug_stage_ms (debug build): kernel ms of the last `qnehvi3_greedy`'s stages, (draws, front and cell build, greedy
+        steps)."""
+        self._need_debug("gpmo3_debug_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gpmo3_debug_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
     def cnei_greedy(self, draws, q, lb, ub, y_floor, base=None, y_mean=None, y_std=None, index_offset=0, return_values=False,
                     return_keys=False):
         """A batch of q resident candidates by greedy noisy expected improvement UNDER CONSTRAINTS, over T joint posterior draws of
@@ -1771,6 +1846,11 @@ class GroupEngine(GpEngine):
                       return_keys=False, return_fronts=False):
         raise NotImplementedError("a device group has no batch noisy expected hypervolume improvement (gpbo_qnhvi_greedy is per "
                                   "context); use a single device")
+
+    def qnehvi3_greedy(self, draws, q, ref, base=None, y_mean=(0.0, 0.0, 0.0), y_std=(1.0, 1.0, 1.0), index_offset=0,
+                       return_values=False, return_keys=False, return_fronts=False):
+        raise NotImplementedError("a device group has no three-objective batch noisy expected hypervolume improvement "
+                                  "(gpmo3_nhvi_greedy is per context); use a single device")
 
     def cnei_greedy(self, draws, q, lb, ub, y_floor, base=None, y_mean=None, y_std=None, index_offset=0, return_values=False,
                     return_keys=False):

@@ -22,7 +22,7 @@ that every constraint holds, in log form: log EHVI(x) + sum_j log p_j(x) (the en
 include/gpmo.h has the formulas).
 
 Out of scope here: m > 3, a local-search stage.  Batches of q > 1 points and the noisy-front variant (NEHVI) are `suggest_qnehvi`
-(qnehvi.py) and, under constraints, `suggest_constrained_qnehvi` (cqnehvi.py), both for m = 2; for m = 3 they are out of scope too.
+(qnehvi.py) and, under constraints, `suggest_constrained_qnehvi` (cqnehvi.py), both for m = 2, and `suggest_qnehvi3` (qnehvi3.py) for m = 3 without constraints.
 """
 from __future__ import annotations
 
@@ -151,8 +151,8 @@ class ParetoOptimizer:
     hold, `front` and `hypervolume` are over those alone, and `suggest` weights the EHVI by the feasibility (below).
 
     Out of scope: m > 3, a local-search stage — the pick is among the candidates.  Batches of q > 1 points and the noisy-front
-    variant (NEHVI): `suggest_qnehvi(self, q)` — with constraints `suggest_constrained_qnehvi(self, q)` — for m = 2, out of scope
-    for m = 3."""
+    variant (NEHVI): `suggest_qnehvi(self, q)` — with constraints `suggest_constrained_qnehvi(self, q)` — for m = 2, and
+    `suggest_qnehvi3(self, q)` for m = 3 without constraints."""
 
     _FLAGS = ("matern_family", "scaled_kernels", "scaled_lanes", "precision")
 

@@ -681,7 +681,8 @@ int gpbo_qnei_greedy(gpbo_ctx* ctx, int slot, double y_mean, double y_std,
  * expected hypervolume improvement", in its greedy, cached-draws form).  Every draw carries a Pareto front of its own — the draw's
  * values at the observed and the pending points, not the noisy readings —, a candidate is worth the mean over the draws of the
  * hypervolume it adds to the draw's front, and after a pick every draw's front absorbs the draw's values there: the next pick is
- * scored jointly with the earlier ones, no observation is made up, nothing is refitted.  m = 3 is not served (and not approximated).
+ * scored jointly with the earlier ones, no observation is made up, nothing is refitted.  m = 3 is served by gpmo3_nhvi_greedy
+ * (include/gpmo3.h: a box decomposition per draw, built on the device); this call refuses nothing on that account, it takes two slots.
  * Objectives and draws.  Objective j is slot j, j = 0, 1; both are MAXIMISED, raw target units; y_mean / y_std (2,) per objective.
  * Both slots are fitted with the candidates' d; N, kernel kind, length scales, scale and precision may differ.  T = G S draws per
  * objective, G = n_groups <= GPBO_MAX_QNEI_GROUPS, S = n_paths <= GPBO_MAX_PATHS, F = n_features.  The per-slot inputs of
