@@ -191,6 +191,17 @@ MO3_DEBUG_SIGNATURES = {
                                     _c_int_p, _c_double_p]),
 }
 
+# name -> (restype, argtypes) of the integrated variance reduction; must list every product symbol include/gpiv.h declares
+IV_SIGNATURES = {
+    "gpiv_ivr_argbest": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int64,
+                                   _c_int64_p, _c_double_p, _c_int64_p, _c_double_p, _c_double_p]),
+}
+# ... and its debug part (libgpbo_dbg.so only)
+IV_DEBUG_SIGNATURES = {
+    "gpiv_debug_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+}
+MAX_IVR_POINTS = 4096    # GPIV_MAX_POINTS
+
 # entry points only libgpbo_dbg.so exports (include/gpbo.h, "#ifdef GPBO_DEBUG")
 DEBUG_SIGNATURES = {
     "gpbo_debug_minimize_box": (C.c_int, [C.c_void_p, C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int,
@@ -271,7 +282,7 @@ def load_library(path: str | None = None):
         raise ImportError(
             f"{path} not found: the HIP extension has not been built. Run "
             "`python -m bayesianoptimization_amd.build` (needs hipcc). There is no CPU fallback.")
-    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES})
+    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **IV_SIGNATURES})
     if not explicit:
         _lib = lib
     return lib
@@ -288,7 +299,8 @@ def load_debug_library():
                 build_debug(verbose=False)
             except Exception as e:  # noqa: BLE001
                 raise ImportError(f"{DEBUG_LIB_PATH} not found and building it failed ({e})") from e
-        _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **DEBUG_SIGNATURES, **MO3_DEBUG_SIGNATURES})
+        _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **DEBUG_SIGNATURES, **MO3_DEBUG_SIGNATURES,
+                                           **IV_SIGNATURES, **IV_DEBUG_SIGNATURES})
     return _debug_lib
 
 

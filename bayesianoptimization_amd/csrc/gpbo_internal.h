@@ -15,6 +15,7 @@
 #include "gpbo.h"
 #include "gpmo.h"
 #include "gpmo3.h"
+#include "gpiv.h"
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
@@ -181,6 +182,8 @@ struct gpbo_ctx {
   int64_t cap_ys = 0;
   double* kg = nullptr;    // gpbo_kg_argbest: the call's points, their solves and the candidate x point covariances (kg.hip)
   int64_t cap_kg = 0;
+  double* iv = nullptr;    // gpiv_ivr_argbest: the call's points, weights, their solves in column groups and the packed V (ivr_plan.h: ivr_block)
+  int64_t cap_iv = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
   double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h), gpmo3_nhvi_greedy (qnehvi3_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
@@ -194,6 +197,7 @@ struct gpbo_ctx {
   gpbo::StageClock qnehvi_clock{4}; // before the draws, behind them, behind the front build, behind the last step of the last gpbo_qnhvi_greedy
   gpbo::StageClock cnhvi_clock{4};  // the same four events of the last gpmo_cnhvi_greedy
   gpbo::StageClock qnehvi3_clock{4}; // the same four events of the last gpmo3_nhvi_greedy (the front build includes the cells)
+  gpbo::StageClock iv_clock{4};     // around the three stages of the last gpiv_ivr_argbest (points, scores, selection)
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -688,6 +692,12 @@ int launch_mes_values(gpbo_ctx* ctx, const Model& m, int64_t M, int n_samples, c
 // every argument.  The call's workspace is ctx->kg (kg.hip: kg_block).
 int launch_kg_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, int J, double y_mean, double y_std,
                      double* mu_points_out);
+// ivr.hip: ctx->ys[i] = -IVR(x_i), the negated integrated posterior variance reduction of the M resident candidates over the J
+// integration points `points` (J, d; host, parameter space) with `weights` (J,; host) or null = 1 / J, from m's resident mu / sd
+// (include/gpiv.h has the formulas).  The caller has checked every argument.  The call's workspace is ctx->iv (ivr_plan.h).
+// ivr_mark_end: the debug build's event behind the caller's selection.
+int launch_ivr_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, const double* weights, int J, double y_std);
+void ivr_mark_end(gpbo_ctx* ctx);
 // ehvi.hip: ctx->ys[i] = -EHVI(x_i), the negated expected hypervolume improvement of the M resident candidates from the resident
 // mu / sd of slots 0 .. n_obj - 1, the level rows `levels` (n_obj, GPBO_MAX_EHVI_LEVELS) and the boxes cell_lo / cell_hi (n_cells, n_obj)
 // of level indices (all host).  The caller has checked every argument.  The call's workspace is ctx->ehvi.

@@ -955,6 +955,31 @@ class GpEngine:
         out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
         return out + (mu_points,) if return_point_means else out
 
+    def ivr_argbest(self, points, weights=None, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
+                    return_values: bool = False):
+        """Integrated posterior variance reduction over the resident candidates (gpiv_ivr_argbest; include/gpiv.h has the formulas):
+        ys = -IVR, how much one noisy observation at the candidate lowers the latent posterior variance, summed with `weights`
+        (J,) — None: 1 / J each — over the J <= 4096 integration `points` (J, d), parameter space; raw target units squared, from
+        slot 0's resident posterior; `y_mean` / `y_std` are those of the pass that left it.  Returns (best_idx, best_val, seed_idx,
+        seed_val, ys|None) as `acq_argbest`.  A reader: the fit, the resident posterior and the candidates stay as they were.  A
+        fit pending on slot 0 (`overlapped_fits`) is waited for first, as every reader of a slot does; the new fit has no posterior
+        over the candidates, so the call is then refused as such."""
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        if points.ndim != 2:
+            raise ValueError("ivr_argbest: points must be two-dimensional (J, d)")
+        if weights is not None:
+            weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+            if weights.shape != (points.shape[0],):
+                raise ValueError("ivr_argbest: weights must be one-dimensional (J,)")
+        k_seeds = int(k_seeds)
+        self._settle(0)
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        self._check(self._lib.gpiv_ivr_argbest(self._h, dptr(points), dptr(weights), int(points.shape[0]), int(points.shape[1]),
+                                               float(y_mean), float(y_std), k_seeds, int(index_offset), C.byref(best_idx),
+                                               C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
+        return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
+
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         """Expected hypervolume improvement over the resident candidates (gpbo_ehvi_argbest; include/gpbo.h has the formulas, the
         conventions and the order of the sum): ys = -EHVI for m = 2 or 3 maximised objectives, objective j from slot j's resident
@@ -1371,6 +1396,13 @@ class GpEngine:
         self._need_debug("gpbo_debug_kg_stage_ms")
         ms = (C.c_float * 3)()
         self._check(self._lib.gpbo_debug_kg_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+    def debug_ivr_stage_ms(self):
+        """gpiv_debug_stage_ms (debug build): kernel ms of the last `ivr_argbest`'s stages, (points, scores, selection)."""
+        self._need_debug("gpiv_debug_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gpiv_debug_stage_ms(self._h, ms))
         return tuple(float(v) for v in ms)
 
     def debug_qnei_stage_ms(self):
@@ -1832,6 +1864,11 @@ class GroupEngine(GpEngine):
     def kg_argbest(self, points, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                    return_values: bool = False, return_point_means: bool = False):
         raise NotImplementedError("a device group has no knowledge gradient (gpbo_kg_argbest is per context); use a single device")
+
+    def ivr_argbest(self, points, weights=None, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
+                    return_values: bool = False):
+        raise NotImplementedError("a device group has no integrated variance reduction (gpiv_ivr_argbest is per context); "
+                                  "use a single device")
 
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         raise NotImplementedError("a device group has no expected hypervolume improvement (gpbo_ehvi_argbest is per context); "
