@@ -202,6 +202,18 @@ IV_DEBUG_SIGNATURES = {
 }
 MAX_IVR_POINTS = 4096    # GPIV_MAX_POINTS
 
+# name -> (restype, argtypes) of joint entropy search; must list every product symbol include/gpje.h declares
+JE_SIGNATURES = {
+    "gpje_jes_argbest": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int64,
+                                   _c_int64_p, _c_double_p, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+}
+# ... and its debug part (libgpbo_dbg.so only)
+JE_DEBUG_SIGNATURES = {
+    "gpje_debug_r2": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, _c_double_p]),
+    "gpje_debug_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+}
+MAX_JES_SAMPLES = 64     # GPJE_MAX_SAMPLES
+
 # entry points only libgpbo_dbg.so exports (include/gpbo.h, "#ifdef GPBO_DEBUG")
 DEBUG_SIGNATURES = {
     "gpbo_debug_minimize_box": (C.c_int, [C.c_void_p, C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int,
@@ -282,7 +294,7 @@ def load_library(path: str | None = None):
         raise ImportError(
             f"{path} not found: the HIP extension has not been built. Run "
             "`python -m bayesianoptimization_amd.build` (needs hipcc). There is no CPU fallback.")
-    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **IV_SIGNATURES})
+    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **IV_SIGNATURES, **JE_SIGNATURES})
     if not explicit:
         _lib = lib
     return lib
@@ -300,7 +312,7 @@ def load_debug_library():
             except Exception as e:  # noqa: BLE001
                 raise ImportError(f"{DEBUG_LIB_PATH} not found and building it failed ({e})") from e
         _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **DEBUG_SIGNATURES, **MO3_DEBUG_SIGNATURES,
-                                           **IV_SIGNATURES, **IV_DEBUG_SIGNATURES})
+                                           **IV_SIGNATURES, **IV_DEBUG_SIGNATURES, **JE_SIGNATURES, **JE_DEBUG_SIGNATURES})
     return _debug_lib
 
 

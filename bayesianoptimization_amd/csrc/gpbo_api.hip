@@ -227,7 +227,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock})
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock})
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -239,7 +239,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1576,6 +1576,42 @@ int gpiv_ivr_argbest(gpbo_ctx* ctx, const double* points, const double* weights,
   return GPBO_OK;
 }
 
+int gpje_jes_argbest(gpbo_ctx* ctx, const double* x_star, const double* f_star, int n_samples, int d, double y_mean, double y_std,
+                     int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val,
+                     double* ys_out, double* mu_star_out, double* var_star_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (n_samples < 1 || n_samples > GPJE_MAX_SAMPLES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: n_samples out of range [1, 64]");
+  if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: d out of range");
+  if (!x_star || !f_star) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: NULL x_star or f_star");
+  for (int64_t e = 0; e < (int64_t)n_samples * d; ++e)
+    if (!std::isfinite(x_star[e])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: x_star must be finite");
+  for (int s = 0; s < n_samples; ++s)
+    if (!std::isfinite(f_star[s])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: f_star must be finite");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: NULL output");
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: y_std must be finite and positive, y_mean finite");
+  int rc = no_pending_fit(ctx, 0, "jes_argbest");
+  if (rc) return rc;
+  if ((rc = need_fitted(ctx, 0))) return rc;
+  const Model& m = ctx->models[0];
+  if (d != m.d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: the samples' dimension differs from the fitted model's");
+  if (ctx->M < 1 || m.M_post != ctx->M) GPBO_FAIL(ctx, GPBO_ERR_STATE, "jes_argbest: run gpbo_posterior for slot 0 first");
+  if (y_std != m.ystd_post)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "jes_argbest: y_std is not the one the resident posterior was scaled with");
+  ev_begin(ctx, T_ACQ);
+  rc = launch_jes_values(ctx, m, ctx->M, x_star, f_star, n_samples, y_mean, y_std, mu_star_out, var_star_out);
+  if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  if (!rc) jes_mark_end(ctx);
+  ev_end(ctx, T_ACQ);
+  if (rc) return rc;
+  if (ys_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(ys_out, ctx->ys, (size_t)ctx->M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GPBO_OK;
+}
+
 // The refusals gpbo_ehvi_argbest and gpmo_cehvi_argbest share, in the order the former has always had them; w: "<who>: ".
 // ... of the arguments
 static int check_ehvi_args(gpbo_ctx* ctx, const std::string& w, int nobj, const int* n_levels, const double* levels, int64_t n_cells,
@@ -2025,6 +2061,18 @@ int gpmo3_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
 int gpiv_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
   return greedy_stage_ms(ctx, ctx->iv_clock, "gpiv_debug_stage_ms", "gpiv_ivr_argbest", ms);
+}
+
+int gpje_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  return greedy_stage_ms(ctx, ctx->je_clock, "gpje_debug_stage_ms", "gpje_jes_argbest", ms);
+}
+
+int gpje_debug_r2(gpbo_ctx* ctx, const double* beta, int n, double* out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!beta || !out || n < 1 || n > (1 << 20)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "gpje_debug_r2: bad arguments");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  return debug_jes_r2(ctx, beta, n, out);
 }
 
 int gpmo3_debug_cells(gpbo_ctx* ctx, int n_draws, int n, const double* base_values, const double* ref, int n_insert,

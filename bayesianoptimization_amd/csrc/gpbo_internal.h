@@ -16,6 +16,7 @@
 #include "gpmo.h"
 #include "gpmo3.h"
 #include "gpiv.h"
+#include "gpje.h"
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
@@ -184,6 +185,8 @@ struct gpbo_ctx {
   int64_t cap_kg = 0;
   double* iv = nullptr;    // gpiv_ivr_argbest: the call's points, weights, their solves in column groups and the packed V (ivr_plan.h: ivr_block)
   int64_t cap_iv = 0;
+  double* je = nullptr;    // gpje_jes_argbest: the call's sampled optima, their solves and scalars and the packed V (jes_plan.h: jes_block)
+  int64_t cap_je = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
   double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h), gpmo3_nhvi_greedy (qnehvi3_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
@@ -198,6 +201,7 @@ struct gpbo_ctx {
   gpbo::StageClock cnhvi_clock{4};  // the same four events of the last gpmo_cnhvi_greedy
   gpbo::StageClock qnehvi3_clock{4}; // the same four events of the last gpmo3_nhvi_greedy (the front build includes the cells)
   gpbo::StageClock iv_clock{4};     // around the three stages of the last gpiv_ivr_argbest (points, scores, selection)
+  gpbo::StageClock je_clock{4};     // the same four events of the last gpje_jes_argbest
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -698,6 +702,16 @@ int launch_kg_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* poi
 // ivr_mark_end: the debug build's event behind the caller's selection.
 int launch_ivr_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, const double* weights, int J, double y_std);
 void ivr_mark_end(gpbo_ctx* ctx);
+// jes.hip: ctx->ys[i] = -a(x_i), the negated joint entropy search value of the M resident candidates over the S sampled optima
+// x_star (S, d; host, parameter space) / f_star (S,; host, raw units) from m's resident mu / sd (include/gpje.h has the formulas);
+// mu_star_out / var_star_out (S,; host) or null.  The caller has checked every argument.  The call's workspace is ctx->je
+// (jes_plan.h).  jes_mark_end: the debug build's event behind the caller's selection.  debug_jes_r2: the device's r2 over n values.
+int launch_jes_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* x_star, const double* f_star, int S, double y_mean,
+                      double y_std, double* mu_star_out, double* var_star_out);
+void jes_mark_end(gpbo_ctx* ctx);
+#ifdef GPBO_DEBUG
+int debug_jes_r2(gpbo_ctx* ctx, const double* beta, int n, double* out);
+#endif
 // ehvi.hip: ctx->ys[i] = -EHVI(x_i), the negated expected hypervolume improvement of the M resident candidates from the resident
 // mu / sd of slots 0 .. n_obj - 1, the level rows `levels` (n_obj, GPBO_MAX_EHVI_LEVELS) and the boxes cell_lo / cell_hi (n_cells, n_obj)
 // of level indices (all host).  The caller has checked every argument.  The call's workspace is ctx->ehvi.

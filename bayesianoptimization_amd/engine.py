@@ -980,6 +980,33 @@ class GpEngine:
                                                C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
         return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
 
+    def jes_argbest(self, x_star, f_star, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
+                    return_values: bool = False, return_star: bool = False):
+        """Joint entropy search, lower bound, over the resident candidates (gpje_jes_argbest; include/gpje.h has the formulas): ys =
+        -a, a the entropy in nats that observing the candidate takes from the joint of the optimum's location and value, averaged
+        over the S <= 64 sampled optima `x_star` (S, d), parameter space, with values `f_star` (S,), raw target units — what
+        `ascend_paths` returns as x_out / f_out; from slot 0's resident posterior; `y_mean` / `y_std` are those of the pass that
+        left it.  Returns (best_idx, best_val, seed_idx, seed_val, ys|None) as `acq_argbest`; `return_star=True` appends the
+        posterior mean and latent variance at the x_star, (S,) each, raw units.  A reader, as `ivr_argbest`."""
+        x_star = np.ascontiguousarray(np.asarray(x_star, dtype=np.float64))
+        f_star = np.ascontiguousarray(np.asarray(f_star, dtype=np.float64))
+        if x_star.ndim != 2:
+            raise ValueError("jes_argbest: x_star must be two-dimensional (S, d)")
+        if f_star.shape != (x_star.shape[0],):
+            raise ValueError("jes_argbest: f_star must be one-dimensional (S,)")
+        k_seeds = int(k_seeds)
+        self._settle(0)
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        mu_star = np.empty(x_star.shape[0]) if return_star else None
+        var_star = np.empty(x_star.shape[0]) if return_star else None
+        self._check(self._lib.gpje_jes_argbest(self._h, dptr(x_star), dptr(f_star), int(x_star.shape[0]), int(x_star.shape[1]),
+                                               float(y_mean), float(y_std), k_seeds, int(index_offset), C.byref(best_idx),
+                                               C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys), dptr(mu_star),
+                                               dptr(var_star)))
+        out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
+        return out + (mu_star, var_star) if return_star else out
+
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         """Expected hypervolume improvement over the resident candidates (gpbo_ehvi_argbest; include/gpbo.h has the formulas, the
         conventions and the order of the sum): ys = -EHVI for m = 2 or 3 maximised objectives, objective j from slot j's resident
@@ -1404,6 +1431,21 @@ class GpEngine:
         ms = (C.c_float * 3)()
         self._check(self._lib.gpiv_debug_stage_ms(self._h, ms))
         return tuple(float(v) for v in ms)
+
+    def debug_jes_stage_ms(self):
+        """gpje_debug_stage_ms (debug build): kernel ms of the last `jes_argbest`'s stages, (points, scores, selection)."""
+        self._need_debug("gpje_debug_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gpje_debug_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+    def debug_jes_r2(self, beta):
+        """gpje_debug_r2 (debug build): the device's r2 (include/gpje.h) over the values `beta`."""
+        self._need_debug("gpje_debug_r2")
+        beta = np.ascontiguousarray(np.asarray(beta, dtype=np.float64).ravel())
+        out = np.empty_like(beta)
+        self._check(self._lib.gpje_debug_r2(self._h, dptr(beta), int(beta.size), dptr(out)))
+        return out
 
     def debug_qnei_stage_ms(self):
         """gpbo_debug_qnei_stage_ms (debug build): kernel ms of the last `qnei_greedy`'s stages, (draws and baselines, greedy steps)."""
@@ -1869,6 +1911,10 @@ class GroupEngine(GpEngine):
                     return_values: bool = False):
         raise NotImplementedError("a device group has no integrated variance reduction (gpiv_ivr_argbest is per context); "
                                   "use a single device")
+
+    def jes_argbest(self, x_star, f_star, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
+                    return_values: bool = False, return_star: bool = False):
+        raise NotImplementedError("a device group has no joint entropy search (gpje_jes_argbest is per context); use a single device")
 
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         raise NotImplementedError("a device group has no expected hypervolume improvement (gpbo_ehvi_argbest is per context); "
