@@ -76,6 +76,20 @@ __device__ __forceinline__ double log_ei_dev(double aa, double sd) {
   return log(sd) + log_h_dev(aa / sd);
 }
 
+// g(a) = E[(Y - a)^+], Y ~ N(mean, sd^2), in the two-range form ehvi.hip's header states (z > -1 as written, below it phi(z) r(z));
+// sd == 0: (mean - a)^+.  NaN for a NaN mean, sd or a with sd != 0; ehvi.hip's caller has dealt with those, lookahead.hip's wants them.
+__device__ __forceinline__ double ehvi_g_dev(double mean, double sd, double a) {
+  if (sd == 0.0) {
+    const double diff = mean - a;
+    return diff > 0.0 ? diff : 0.0;
+  }
+  const double z = (mean - a) / sd;
+  if (z > -1.0) return sd * (norm_pdf_dev(z) + z * ndtr_dev(z));
+  const double pdf = norm_pdf_dev(z);
+  if (pdf == 0.0) return 0.0;
+  return sd * (pdf * log_ei_ratio(z, DevErfcx()));
+}
+
 // ---- log feasibility (GPBO_ACQ_LOG_CEI / GPBO_ACQ_LOG_FEAS; include/gpbo.h has the definition and the conventions) ---------------
 // log p_j = log(Phi(b) - Phi(a)), a = (lb - cm) / cs, b = (ub - cm) / cs, without the subtraction of two numbers near 0 or near 1
 // that makes the product form's p_j exactly 0 a few sigma outside the band.  `ndtr_of` / `erfcx_of` are the caller's Phi and scaled

@@ -78,19 +78,6 @@ struct EhviFeas {
 };
 enum EhviForm : int { EHVI_PLAIN = 0, EHVI_PRODUCT = 1, EHVI_LOG = 2 };
 
-// g(a) = E[(Y - a)^+], Y ~ N(mean, sd^2); sd == 0: (mean - a)^+.  The caller has dealt with a NaN mean or sd.
-__device__ __forceinline__ double ehvi_g_dev(double mean, double sd, double a) {
-  if (sd == 0.0) {
-    const double diff = mean - a;
-    return diff > 0.0 ? diff : 0.0;
-  }
-  const double z = (mean - a) / sd;
-  if (z > -1.0) return sd * (norm_pdf_dev(z) + z * ndtr_dev(z));
-  const double pdf = norm_pdf_dev(z);
-  if (pdf == 0.0) return 0.0;
-  return sd * (pdf * log_ei_ratio(z, DevErfcx()));
-}
-
 template <int C, int NOBJ, int FORM>
 __device__ __forceinline__ void ehvi_body(const EhviDev& a, const EhviFeas* __restrict__ feas, double* __restrict__ ys) {
   extern __shared__ __attribute__((aligned(16))) double ehvi_tab[];

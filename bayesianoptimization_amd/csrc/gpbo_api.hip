@@ -227,7 +227,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock})
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock})
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -239,7 +239,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1612,6 +1612,52 @@ int gpje_jes_argbest(gpbo_ctx* ctx, const double* x_star, const double* f_star, 
   return GPBO_OK;
 }
 
+int gpla_ei2_argbest(gpbo_ctx* ctx, const double* points, int n_points, int d, const double* nodes, const double* weights, int n_nodes,
+                     double y_best, double y_mean, double y_std, int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val,
+                     int64_t* seed_idx, double* seed_val, double* ys_out, double* mu_points_out, double* var_points_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (n_points < 1 || n_points > GPLA_MAX_POINTS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: n_points out of range [1, 64]");
+  if (n_nodes < 1 || n_nodes > GPLA_MAX_NODES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: n_nodes out of range [1, 32]");
+  if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: d out of range");
+  if (!points || !nodes || !weights) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: NULL points, nodes or weights");
+  for (int64_t e = 0; e < (int64_t)n_points * d; ++e)
+    if (!std::isfinite(points[e])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: points must be finite");
+  for (int h = 0; h < n_nodes; ++h)
+    if (!std::isfinite(nodes[h])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: nodes must be finite");
+  for (int h = 0; h < n_nodes; ++h)
+    if (!std::isfinite(weights[h])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: weights must be finite");
+  double weight_sum = 0.0;
+  for (int h = 0; h < n_nodes; ++h) {
+    if (weights[h] < 0.0) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: weights must not be negative");
+    weight_sum += weights[h];
+  }
+  if (!(weight_sum > 0.0)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: weights must not all be zero");
+  if (!std::isfinite(y_best)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: y_best must be finite");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: NULL output");
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: y_std must be finite and positive, y_mean finite");
+  int rc = no_pending_fit(ctx, 0, "ei2_argbest");
+  if (rc) return rc;
+  if ((rc = need_fitted(ctx, 0))) return rc;
+  const Model& m = ctx->models[0];
+  if (d != m.d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: the points' dimension differs from the fitted model's");
+  if (ctx->M < 1 || m.M_post != ctx->M) GPBO_FAIL(ctx, GPBO_ERR_STATE, "ei2_argbest: run gpbo_posterior for slot 0 first");
+  if (y_std != m.ystd_post)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "ei2_argbest: y_std is not the one the resident posterior was scaled with");
+  ev_begin(ctx, T_ACQ);
+  rc = launch_la_values(ctx, m, ctx->M, points, n_points, nodes, weights, n_nodes, y_best, y_mean, y_std, mu_points_out, var_points_out);
+  if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  if (!rc) la_mark_end(ctx);
+  ev_end(ctx, T_ACQ);
+  if (rc) return rc;
+  if (ys_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(ys_out, ctx->ys, (size_t)ctx->M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GPBO_OK;
+}
+
 // The refusals gpbo_ehvi_argbest and gpmo_cehvi_argbest share, in the order the former has always had them; w: "<who>: ".
 // ... of the arguments
 static int check_ehvi_args(gpbo_ctx* ctx, const std::string& w, int nobj, const int* n_levels, const double* levels, int64_t n_cells,
@@ -2066,6 +2112,11 @@ int gpiv_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
 int gpje_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
   return greedy_stage_ms(ctx, ctx->je_clock, "gpje_debug_stage_ms", "gpje_jes_argbest", ms);
+}
+
+int gpla_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  return greedy_stage_ms(ctx, ctx->la_clock, "gpla_debug_stage_ms", "gpla_ei2_argbest", ms);
 }
 
 int gpje_debug_r2(gpbo_ctx* ctx, const double* beta, int n, double* out) {

@@ -17,6 +17,7 @@
 #include "gpmo3.h"
 #include "gpiv.h"
 #include "gpje.h"
+#include "gpla.h"
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
@@ -187,6 +188,8 @@ struct gpbo_ctx {
   int64_t cap_iv = 0;
   double* je = nullptr;    // gpje_jes_argbest: the call's sampled optima, their solves and scalars and the packed V (jes_plan.h: jes_block)
   int64_t cap_je = 0;
+  double* la = nullptr;    // gpla_ei2_argbest: the call's reference points, their solves and scalars, the packed V, the nodes and weights (lookahead_plan.h: la_block)
+  int64_t cap_la = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
   double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h), gpmo3_nhvi_greedy (qnehvi3_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
@@ -202,6 +205,7 @@ struct gpbo_ctx {
   gpbo::StageClock qnehvi3_clock{4}; // the same four events of the last gpmo3_nhvi_greedy (the front build includes the cells)
   gpbo::StageClock iv_clock{4};     // around the three stages of the last gpiv_ivr_argbest (points, scores, selection)
   gpbo::StageClock je_clock{4};     // the same four events of the last gpje_jes_argbest
+  gpbo::StageClock la_clock{4};     // the same four events of the last gpla_ei2_argbest
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -712,6 +716,20 @@ void jes_mark_end(gpbo_ctx* ctx);
 #ifdef GPBO_DEBUG
 int debug_jes_r2(gpbo_ctx* ctx, const double* beta, int n, double* out);
 #endif
+// ... and its points stage for lookahead.hip: into the workspace ws laid out by b (jes_plan.h) k*, V = -K'^-1 k*, m_s / p_s and the
+// packed V of the S points x_star; f_star null: taken as 0.  Event 0 of `clock` is recorded in front of the kernels (jes_mark: the
+// debug build's event i of a stage clock).
+struct JesBlock;
+int launch_jes_points(gpbo_ctx* ctx, const Model& m, double* ws, const JesBlock& b, const double* x_star, const double* f_star, int S,
+                      double y_mean, double y_std, StageClock& clock);
+void jes_mark(gpbo_ctx* ctx, StageClock& clock, int i);
+// lookahead.hip: ctx->ys[i] = -(y_std a(x_i)), the negated two-step lookahead EI of the M resident candidates over the J reference
+// points (J, d; host, parameter space) and the H quadrature nodes / weights (host) against y_best, from m's resident mu / sd
+// (include/gpla.h has the formulas); mu_points_out / var_points_out (J,; host) or null.  The caller has checked every argument.  The
+// call's workspace is ctx->la (lookahead_plan.h).  la_mark_end: the debug build's event behind the caller's selection.
+int launch_la_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, int J, const double* nodes, const double* weights,
+                     int H, double y_best, double y_mean, double y_std, double* mu_points_out, double* var_points_out);
+void la_mark_end(gpbo_ctx* ctx);
 // ehvi.hip: ctx->ys[i] = -EHVI(x_i), the negated expected hypervolume improvement of the M resident candidates from the resident
 // mu / sd of slots 0 .. n_obj - 1, the level rows `levels` (n_obj, GPBO_MAX_EHVI_LEVELS) and the boxes cell_lo / cell_hi (n_cells, n_obj)
 // of level indices (all host).  The caller has checked every argument.  The call's workspace is ctx->ehvi.

@@ -33,12 +33,11 @@
 #include "gpbo_internal.h"
 #include "acq_formulas.h"
 #include "jes_plan.h"
+#include "jes_product.h"
 
 #include <cmath>
 
 namespace gpbo {
-
-typedef double je_d4 __attribute__((ext_vector_type(4)));
 
 // r2(b) = 1 - b h - h^2, h = phi(b) / Phi(b): the variance of a unit normal truncated to (-inf, b].  include/gpje.h has the ranges.
 __device__ __forceinline__ double jes_r2_dev(const double b) {
@@ -167,114 +166,17 @@ struct JesScoreArgs {
   double amplitude, y_mean, y_std, lambda, white;
 };
 
-// wave w's 8 rows of the stage in xs -> its 8 rows of the k-major block: ab[row][candidate]
-template <int DP, int KERNEL>
-__device__ __forceinline__ void jes_generate(const double (&xc)[DP], const double* xs, double* ab, const int wave, const int lane) {
-#pragma unroll 2
-  for (int q = 0; q < JES_KC / 4; q += 2) {
-    const int row = wave * (JES_KC / 4) + q;
-    const double* xr = xs + row * DP;          // the same address in every lane: LDS broadcast
-    double d2a = 0.0, d2b = 0.0;
-#pragma unroll
-    for (int t = 0; t < DP; ++t) {
-      const double da = xc[t] - xr[t], db = xc[t] - xr[DP + t];
-      d2a = fma(da, da, d2a);
-      d2b = fma(db, db, d2b);
-    }
-    ab[row * JES_PITCH + lane] = gpbo_kernel_value<KERNEL>(d2a);
-    ab[(row + 1) * JES_PITCH + lane] = gpbo_kernel_value<KERNEL>(d2b);
-  }
-}
-
-template <int DP>
-__device__ __forceinline__ void jes_stage_points(const double* __restrict__ src, double* xs, const int tid) {
-  const double2* s2 = reinterpret_cast<const double2*>(src);
-  double2* d2 = reinterpret_cast<double2*>(xs);
-  for (int e = tid; e < JES_KC * DP / 2; e += 256) d2[e] = s2[e];
-}
-
 template <int DP, int KERNEL, int SPLIT>
 __global__ __launch_bounds__(256) void jes_score_kernel(const JesScoreArgs a) {
   constexpr int NFMAX = SPLIT == 4 ? 1 : (SPLIT == 2 ? 2 : 4);
-  constexpr int KSW = 8 / SPLIT;      // k-steps of a stage this wave multiplies
   __shared__ __attribute__((aligned(16))) double lds[jes_lds_doubles(DP, NFMAX)];
   __shared__ double star[3][JES_STAR];      // rho_s | g_s | fn_s
-  double* xs = lds;                        // the stage's train points (or 32 of the samples' own points)
-  double* ab = lds + JES_KC * DP;          // k* of the stage, k-major: the A operand
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int lk = lane >> 4, lc = lane & 15;
-  const int u = wave / SPLIT, part = wave % SPLIT;
-  const bool active = u < a.nf;            // wave-uniform: at split 1 a wave without a fragment only generates
   const int64_t m0 = (int64_t)blockIdx.x * JES_ROWS;
-  const int64_t mrow = m0 + lane < a.M ? m0 + lane : a.M - 1;
-  double xc[DP];
-  {
-    const double* xcp = a.P + mrow * DP;
-#pragma unroll
-    for (int t = 0; t < DP; t += 2) {
-      const double2 v = *reinterpret_cast<const double2*>(xcp + t);
-      xc[t] = v.x;
-      xc[t + 1] = v.y;
-    }
-  }
-  if (tid < 3 * JES_STAR) star[tid >> 6][lane] = a.star[2 * JES_STAR + tid];      // read behind the barriers below
-  je_d4 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = je_d4{0.0, 0.0, 0.0, 0.0};
-  const double* vp = a.Vp + ((int64_t)(active ? u : 0) * 8 + part * KSW) * 64 + lane;
-  const int64_t stage_stride = (int64_t)a.nf * 8 * 64;
-  for (int kc = 0; kc < a.Kp; kc += JES_KC) {
-    // this stage's B fragments: asked for now, used behind the generation
-    double vb[KSW];
-#pragma unroll
-    for (int ks = 0; ks < KSW; ++ks) vb[ks] = active ? vp[ks * 64] : 0.0;
-    vp += stage_stride;
-    jes_stage_points<DP>(a.Xs + (int64_t)kc * DP, xs, tid);
-    __syncthreads();      // xs is whole; every wave is done with the previous stage's ab
-    jes_generate<DP, KERNEL>(xc, xs, ab, wave, lane);
-    __syncthreads();      // ab is whole; everyone is done with xs
-    if (active) {
-#pragma unroll
-      for (int ks = 0; ks < KSW; ++ks) {
-        const double* ar = ab + ((part * KSW + ks) * 4 + lk) * JES_PITCH + lc;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[16 * t], vb[ks], acc[t], 0, 0, 0);
-      }
-    }
-  }
-  // the samples' own points, 32 at a time: row r of block q is sample 32 q + r, fragment 2 q + (r >> 4)
-  for (int q = 0; q < (a.nf + 1) / 2; ++q) {
-    jes_stage_points<DP>(a.As + (int64_t)q * JES_KC * DP, xs, tid);
-    __syncthreads();
-    jes_generate<DP, KERNEL>(xc, xs, ab, wave, lane);
-    __syncthreads();
-    if (active && part == SPLIT - 1 && (u >> 1) == q) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const double unit = (4 * j + lk == lc) ? 1.0 : 0.0;      // B[k][column] = 1 where "train point" k is the column's sample
-        const double* ar = ab + (16 * (u & 1) + 4 * j + lk) * JES_PITCH + lc;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[16 * t], unit, acc[t], 0, 0, 0);
-      }
-    }
-  }
-  __syncthreads();      // xs and ab are dead: the same LDS is now sums [64][pitch]
+  if (tid < 3 * JES_STAR) star[tid >> 6][lane] = a.star[2 * JES_STAR + tid];      // read behind the product's barriers
+  const int64_t mrow = jes_product<DP, KERNEL, SPLIT>(a.Xs, a.Vp, a.P, a.As, a.M, a.Kp, a.nf, lds);
   double* sums = lds;
   const int pitch = 16 * a.nf + 1;
-#pragma unroll
-  for (int pp = 0; pp < SPLIT; ++pp) {
-    if (active && part == pp) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          double* dst = sums + (16 * t + 4 * r + lk) * pitch + 16 * u + lc;
-          *dst = pp == 0 ? acc[t][r] : *dst + acc[t][r];
-        }
-      }
-    }
-    __syncthreads();
-  }
   // thread (wave, lane): candidate `lane`, samples wave, wave + 4, ...
   const double mean = a.mu[mrow], sd = a.sd[mrow];
   const double qv = sd / a.y_std;
@@ -299,15 +201,15 @@ __global__ __launch_bounds__(256) void jes_score_kernel(const JesScoreArgs a) {
   a.ys[i] = -(0.5 * log(vo) - total / (double)a.S);
 }
 
-// debug build: an event before and after each stage of the last call (gpje_debug_stage_ms); the product records nothing
-static inline void jes_mark(gpbo_ctx* ctx, int i) {
+// debug build: an event before and after each stage of the last call on its clock (gpje_debug_stage_ms, gpla_debug_stage_ms); the
+// product records nothing
+void jes_mark(gpbo_ctx* ctx, StageClock& c, int i) {
 #ifdef GPBO_DEBUG
-  StageClock& c = ctx->je_clock;
   if (!c.ev[i]) (void)hipEventCreate(&c.ev[i]);
   (void)hipEventRecord(c.ev[i], ctx->stream);
   c.used = (i == c.n - 1);
 #else
-  (void)ctx; (void)i;
+  (void)ctx; (void)c; (void)i;
 #endif
 }
 
@@ -322,19 +224,18 @@ static int launch_jes_score(gpbo_ctx* ctx, const Model& m, const JesScoreArgs& a
   });
 }
 
-int launch_jes_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* x_star, const double* f_star, int S, double y_mean,
-                      double y_std, double* mu_star_out, double* var_star_out) {
+// The points stage into the workspace ws laid out by b: k*(a_s), V_s = -K'^-1 k*(a_s), the points' scalars (jes_star_kernel) and the
+// packed V, event 0 of `clock` in front of its kernels.  f_star null: the values are taken as 0 (lookahead.hip reads m_s and p_s only).
+int launch_jes_points(gpbo_ctx* ctx, const Model& m, double* ws, const JesBlock& b, const double* x_star, const double* f_star, int S,
+                      double y_mean, double y_std, StageClock& clock) {
   const int N = (int)m.N, NP = (int)m.NP, d = m.d, DP = m.DP;
   int rc;
-  const JesBlock b = jes_block(S, d, DP, N, NP);
-  if ((rc = ensure(ctx, &ctx->je, &ctx->cap_je, b.doubles))) return rc;
-  double* ws = ctx->je;
   GPBO_HIP(ctx, hipMemcpyAsync(ws + b.raw, x_star, (size_t)S * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  GPBO_HIP(ctx, hipMemcpyAsync(ws + b.fraw, f_star, (size_t)S * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (f_star) GPBO_HIP(ctx, hipMemcpyAsync(ws + b.fraw, f_star, (size_t)S * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   GPBO_HIP(ctx, hipMemsetAsync(ws + b.zero, 0, (size_t)b.n_zero * sizeof(double), ctx->stream));
   if ((rc = launch_prescale(ctx, ws + b.raw, S, d, DP, m.ls, ws + b.As, JES_STAR))) return rc;
   // stage 1: k*(x*_s), V_s, the samples' scalars, the packed V
-  jes_mark(ctx, 0);
+  jes_mark(ctx, clock, 0);
   rc = with_dp_kernel(ctx, DP, m.kernel, [&](auto dp, auto k) {
     jes_points_kernel<decltype(dp)::value, decltype(k)::value><<<dim3((unsigned)S), dim3(256), 0, ctx->stream>>>(m.Xs, ws + b.As,
                                                                                                                 ws + b.KS, N, NP);
@@ -343,13 +244,24 @@ int launch_jes_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* x_
   });
   if (rc) return rc;
   if ((rc = launch_path_solve(ctx, m, S, ws + b.KS, ws + b.zero, ws + b.zero, ws + b.T, ws + b.V))) return rc;
-  jes_star_kernel<<<dim3(JES_STAR), dim3(256), 0, ctx->stream>>>(ws + b.KS, ws + b.V, m.alpha, ws + b.fraw, S, N, NP, m.amplitude, y_mean,
-                                                                 y_std, ws + b.star);
+  jes_star_kernel<<<dim3(JES_STAR), dim3(256), 0, ctx->stream>>>(ws + b.KS, ws + b.V, m.alpha, f_star ? ws + b.fraw : ws + b.zero, S, N, NP,
+                                                                 m.amplitude, y_mean, y_std, ws + b.star);
   GPBO_HIP(ctx, hipGetLastError());
   jes_pack_kernel<<<dim3((unsigned)((b.n_Vp + 255) / 256)), dim3(256), 0, ctx->stream>>>(ws + b.V, ws + b.Vp, b.n_Vp, S, N, NP, b.nf);
   GPBO_HIP(ctx, hipGetLastError());
+  return GPBO_OK;
+}
+
+int launch_jes_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* x_star, const double* f_star, int S, double y_mean,
+                      double y_std, double* mu_star_out, double* var_star_out) {
+  const int d = m.d, DP = m.DP;
+  int rc;
+  const JesBlock b = jes_block(S, d, DP, m.N, m.NP);
+  if ((rc = ensure(ctx, &ctx->je, &ctx->cap_je, b.doubles))) return rc;
+  double* ws = ctx->je;
+  if ((rc = launch_jes_points(ctx, m, ws, b, x_star, f_star, S, y_mean, y_std, ctx->je_clock))) return rc;
   // stage 2: the scores
-  jes_mark(ctx, 1);
+  jes_mark(ctx, ctx->je_clock, 1);
   const int64_t Mp = round_up(M, POST_CANDS);
   if ((rc = ensure(ctx, &ctx->Xcs, &ctx->cap_Xcs, Mp * DP))) return rc;
   if ((rc = launch_prescale(ctx, ctx->Xc, M, d, DP, m.ls, ctx->Xcs, Mp))) return rc;
@@ -364,7 +276,7 @@ int launch_jes_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* x_
     default: rc = launch_jes_score<1>(ctx, m, s); break;
   }
   if (rc) return rc;
-  jes_mark(ctx, 2);      // stage 3, the selection, is the caller's; it records event 3 behind it (jes_mark_end)
+  jes_mark(ctx, ctx->je_clock, 2);      // stage 3, the selection, is the caller's; it records event 3 behind it (jes_mark_end)
   if (mu_star_out || var_star_out) {
     double host[2 * JES_STAR];
     GPBO_HIP(ctx, hipMemcpyAsync(host, ws + b.star, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
@@ -377,7 +289,7 @@ int launch_jes_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* x_
   return GPBO_OK;
 }
 
-void jes_mark_end(gpbo_ctx* ctx) { jes_mark(ctx, 3); }
+void jes_mark_end(gpbo_ctx* ctx) { jes_mark(ctx, ctx->je_clock, 3); }
 
 #ifdef GPBO_DEBUG
 __global__ void jes_r2_kernel(const double* __restrict__ beta, int n, double* __restrict__ out) {

@@ -1007,6 +1007,35 @@ class GpEngine:
         out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
         return out + (mu_star, var_star) if return_star else out
 
+    def ei2_argbest(self, points, nodes, weights, y_best: float, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0,
+                    y_std: float = 1.0, return_values: bool = False, return_point_moments: bool = False):
+        """Two-step lookahead expected improvement over the resident candidates (gpla_ei2_argbest; include/gpla.h has the formulas):
+        ys = -a, a the EI of observing the candidate against `y_best` (raw target units) plus the best EI left over the candidate
+        itself and the J <= 64 reference `points` (J, d), parameter space, once that observation is absorbed, in expectation over
+        the observation by the quadrature rule `nodes` / `weights` (H <= 32,) of a unit normal; from slot 0's resident posterior;
+        `y_mean` / `y_std` are those of the pass that left it.  Returns (best_idx, best_val, seed_idx, seed_val, ys|None) as
+        `acq_argbest`; `return_point_moments=True` appends the posterior mean and latent variance at the points, (J,) each, raw
+        units.  A reader, as `jes_argbest`."""
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        nodes = np.ascontiguousarray(np.asarray(nodes, dtype=np.float64))
+        weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if points.ndim != 2:
+            raise ValueError("ei2_argbest: points must be two-dimensional (J, d)")
+        if nodes.ndim != 1 or weights.shape != nodes.shape:
+            raise ValueError("ei2_argbest: nodes and weights must be one-dimensional (H,) each")
+        k_seeds = int(k_seeds)
+        self._settle(0)
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        mu_points = np.empty(points.shape[0]) if return_point_moments else None
+        var_points = np.empty(points.shape[0]) if return_point_moments else None
+        self._check(self._lib.gpla_ei2_argbest(self._h, dptr(points), int(points.shape[0]), int(points.shape[1]), dptr(nodes),
+                                               dptr(weights), int(nodes.shape[0]), float(y_best), float(y_mean), float(y_std), k_seeds,
+                                               int(index_offset), C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val),
+                                               dptr(ys), dptr(mu_points), dptr(var_points)))
+        out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
+        return out + (mu_points, var_points) if return_point_moments else out
+
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         """Expected hypervolume improvement over the resident candidates (gpbo_ehvi_argbest; include/gpbo.h has the formulas, the
         conventions and the order of the sum): ys = -EHVI for m = 2 or 3 maximised objectives, objective j from slot j's resident
@@ -1437,6 +1466,13 @@ class GpEngine:
         self._need_debug("gpje_debug_stage_ms")
         ms = (C.c_float * 3)()
         self._check(self._lib.gpje_debug_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+    def debug_ei2_stage_ms(self):
+        """gpla_debug_stage_ms (debug build): kernel ms of the last `ei2_argbest`'s stages, (points, scores, selection)."""
+        self._need_debug("gpla_debug_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gpla_debug_stage_ms(self._h, ms))
         return tuple(float(v) for v in ms)
 
     def debug_jes_r2(self, beta):
@@ -1915,6 +1951,10 @@ class GroupEngine(GpEngine):
     def jes_argbest(self, x_star, f_star, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                     return_values: bool = False, return_star: bool = False):
         raise NotImplementedError("a device group has no joint entropy search (gpje_jes_argbest is per context); use a single device")
+
+    def ei2_argbest(self, points, nodes, weights, y_best: float, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0,
+                    y_std: float = 1.0, return_values: bool = False, return_point_moments: bool = False):
+        raise NotImplementedError("a device group has no two-step lookahead EI (gpla_ei2_argbest is per context); use a single device")
 
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         raise NotImplementedError("a device group has no expected hypervolume improvement (gpbo_ehvi_argbest is per context); "
