@@ -227,6 +227,20 @@ LA_DEBUG_SIGNATURES = {
 MAX_LA_POINTS = 64       # GPLA_MAX_POINTS
 MAX_LA_NODES = 32        # GPLA_MAX_NODES
 
+# name -> (restype, argtypes) of Pareto-frontier entropy search; must list every product symbol include/gppf.h declares
+PF_SIGNATURES = {
+    "gppf_pfes_argbest": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int, C.c_int, C.c_int, _c_double_p, _c_double_p,
+                                    _c_double_p, _c_double_p, C.c_int, _c_int_p, _c_double_p, C.c_int, C.c_int64, _c_int64_p,
+                                    _c_double_p, _c_int64_p, _c_double_p, _c_double_p, _c_int_p, _c_double_p]),
+}
+# ... and its debug part (libgpbo_dbg.so only)
+PF_DEBUG_SIGNATURES = {
+    "gppf_debug_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+}
+MAX_PFES_SAMPLES = 64            # GPPF_MAX_SAMPLES
+MAX_PFES_FRONT = 128             # GPPF_MAX_FRONT
+MAX_PFES_FRONT_CANDIDATES = 16384  # GPPF_MAX_FRONT_CANDIDATES
+
 # entry points only libgpbo_dbg.so exports (include/gpbo.h, "#ifdef GPBO_DEBUG")
 DEBUG_SIGNATURES = {
     "gpbo_debug_minimize_box": (C.c_int, [C.c_void_p, C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int,
@@ -307,7 +321,7 @@ def load_library(path: str | None = None):
         raise ImportError(
             f"{path} not found: the HIP extension has not been built. Run "
             "`python -m bayesianoptimization_amd.build` (needs hipcc). There is no CPU fallback.")
-    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **IV_SIGNATURES, **JE_SIGNATURES, **LA_SIGNATURES})
+    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **IV_SIGNATURES, **JE_SIGNATURES, **LA_SIGNATURES, **PF_SIGNATURES})
     if not explicit:
         _lib = lib
     return lib
@@ -326,7 +340,7 @@ def load_debug_library():
                 raise ImportError(f"{DEBUG_LIB_PATH} not found and building it failed ({e})") from e
         _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **DEBUG_SIGNATURES, **MO3_DEBUG_SIGNATURES,
                                            **IV_SIGNATURES, **IV_DEBUG_SIGNATURES, **JE_SIGNATURES, **JE_DEBUG_SIGNATURES, **LA_SIGNATURES,
-                                           **LA_DEBUG_SIGNATURES})
+                                           **LA_DEBUG_SIGNATURES, **PF_SIGNATURES, **PF_DEBUG_SIGNATURES})
     return _debug_lib
 
 

@@ -227,7 +227,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock})
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock, &ctx->pf_clock})
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -239,7 +239,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->pf, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1744,6 +1744,59 @@ int gpmo_cehvi_argbest(gpbo_ctx* ctx, int n_objectives, const int* n_levels, con
   return ehvi_finish(ctx, rc, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val, ys_out);
 }
 
+int gppf_pfes_argbest(gpbo_ctx* ctx, const double* y_mean, const double* y_std, int n_groups, int n_paths, int n_features,
+                      const double* omega, const double* phase, const double* weights, const double* eps, int n_samples,
+                      const int* front_size_in, const double* fronts_in, int k_seeds, int64_t index_offset, int64_t* best_idx,
+                      double* best_val, int64_t* seed_idx, double* seed_val, double* ys_out, int* front_size_out, double* fronts_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  const std::string w = "pfes_argbest: ";
+  if (!omega) {
+    if (n_samples < 1 || n_samples > GPPF_MAX_SAMPLES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_samples out of range [1, 64]");
+    if (!front_size_in || !fronts_in) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL front_size_in or fronts_in without draws");
+  } else {
+    if (n_groups < 1 || n_groups > GPBO_MAX_QNEI_GROUPS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups out of range [1, 16]");
+    if (n_paths < 1 || n_paths > GPBO_MAX_PATHS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_paths out of range [1, 16]");
+    if (n_features < 1 || n_features > GPBO_MAX_PATH_FEATURES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_features out of range [1, 4096]");
+    if (n_groups * n_paths > GPPF_MAX_SAMPLES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "n_groups * n_paths exceeds 64 draws");
+    if (!phase || !weights || !eps) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL phase, weights or eps");
+  }
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "k_seeds out of range [0, 64]");
+  if (!y_mean || !y_std || !best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val)))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "NULL y_mean, y_std or output");
+  for (int j = 0; j < 2; ++j)
+    if (!std::isfinite(y_std[j]) || !(y_std[j] > 0.0) || !std::isfinite(y_mean[j]))
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "y_std must be finite and positive, y_mean finite");
+  if (!omega)
+    for (int s = 0; s < n_samples; ++s) {
+      const int n = front_size_in[s];
+      if (n < 1 || n > GPPF_MAX_FRONT) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "a front size out of range [1, 128]");
+      const double* f = fronts_in + (size_t)s * GPPF_MAX_FRONT * 2;
+      for (int k = 0; k < n; ++k) {
+        if (!std::isfinite(f[2 * k]) || !std::isfinite(f[2 * k + 1])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "a front must be finite");
+        if (k > 0 && (!(f[2 * k] < f[2 * k - 2]) || !(f[2 * k + 1] > f[2 * k - 1])))
+          GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "a front needs objective 0 strictly descending and objective 1 strictly ascending");
+      }
+    }
+  int rc;
+  if ((rc = check_ehvi_slots(ctx, "pfes_argbest", 2, "both objectives' slots"))) return rc;
+  const Model* ms[2] = {&ctx->models[0], &ctx->models[1]};
+  for (int j = 0; j < 2; ++j)
+    if (y_std[j] != ms[j]->ystd_post)
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, w + "y_std is not the one the resident posterior was scaled with");
+  ev_begin(ctx, T_ACQ);
+  rc = launch_pfes_values(ctx, ms, ctx->M, y_mean, y_std, n_groups, n_paths, n_features, omega, phase, weights, eps, n_samples,
+                          front_size_in, fronts_in, front_size_out, fronts_out);
+  if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  if (!rc) pfes_mark_end(ctx);
+  ev_end(ctx, T_ACQ);
+  if (rc) return rc;
+  if (ys_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(ys_out, ctx->ys, (size_t)ctx->M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GPBO_OK;
+}
+
 // The refusals the greedy draw batches (gpbo_qnei_greedy, gpbo_qnhvi_greedy, gpbo_cnei_greedy) share, in three pieces that each
 // entry point calls in its own order; w: "<who>: ".
 // ... of the entry points over several slots: the counts (as check_path_args orders them), a NULL argument, then check_path_args
@@ -2117,6 +2170,11 @@ int gpje_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
 int gpla_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
   return greedy_stage_ms(ctx, ctx->la_clock, "gpla_debug_stage_ms", "gpla_ei2_argbest", ms);
+}
+
+int gppf_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  return greedy_stage_ms(ctx, ctx->pf_clock, "gppf_debug_stage_ms", "gppf_pfes_argbest", ms);
 }
 
 int gpje_debug_r2(gpbo_ctx* ctx, const double* beta, int n, double* out) {

@@ -18,6 +18,7 @@
 #include "gpiv.h"
 #include "gpje.h"
 #include "gpla.h"
+#include "gppf.h"
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
@@ -190,6 +191,8 @@ struct gpbo_ctx {
   int64_t cap_je = 0;
   double* la = nullptr;    // gpla_ei2_argbest: the call's reference points, their solves and scalars, the packed V, the nodes and weights (lookahead_plan.h: la_block)
   int64_t cap_la = 0;
+  double* pf = nullptr;    // gppf_pfes_argbest: the joint draws at the first candidates, the sampled fronts and their sizes (pfes_plan.h: pfes_block)
+  int64_t cap_pf = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
   double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h), gpmo3_nhvi_greedy (qnehvi3_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
@@ -206,6 +209,7 @@ struct gpbo_ctx {
   gpbo::StageClock iv_clock{4};     // around the three stages of the last gpiv_ivr_argbest (points, scores, selection)
   gpbo::StageClock je_clock{4};     // the same four events of the last gpje_jes_argbest
   gpbo::StageClock la_clock{4};     // the same four events of the last gpla_ei2_argbest
+  gpbo::StageClock pf_clock{4};     // around the three stages of the last gppf_pfes_argbest (draws and fronts, scores, selection)
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -730,6 +734,20 @@ void jes_mark(gpbo_ctx* ctx, StageClock& clock, int i);
 int launch_la_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, int J, const double* nodes, const double* weights,
                      int H, double y_best, double y_mean, double y_std, double* mu_points_out, double* var_points_out);
 void la_mark_end(gpbo_ctx* ctx);
+// qnehvi.hip: qnehvi_front_kernel for another translation unit: the front of each of T draws from its n value pairs (v0[t ld + i],
+// v1[t ld + i]) above (ref0, ref1) — -inf: no reference point —, as gpbo_qnhvi_greedy builds it; front / front0 [T][128], size / size0
+// [T], *flag raised for a front beyond 128 points (the caller has cleared it)
+int launch_qnehvi_fronts(gpbo_ctx* ctx, const double* v0, const double* v1, int64_t ld, int n, double ref0, double ref1, int T,
+                         double2* front, double2* front0, int* size, int* size0, int* flag);
+// pfes.hip: ctx->ys[i] = -a(x_i), the negated Pareto-frontier entropy search value of the M resident candidates from the resident
+// mu / sd of ms[0], ms[1] (include/gppf.h has the formulas) over the fronts given (omega null: n_samples of them, front_size_in /
+// fronts_in, host) or built on the device from G groups of Sp joint draws at the first candidates; front_size_out / fronts_out
+// (host) or null.  The caller has checked every argument.  The call's workspace is ctx->pf (pfes_plan.h).  pfes_mark_end: the debug
+// build's event behind the caller's selection.
+int launch_pfes_values(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const double* y_mean, const double* y_std, int G, int Sp,
+                       int F, const double* omega, const double* phase, const double* weights, const double* eps, int n_samples,
+                       const int* front_size_in, const double* fronts_in, int* front_size_out, double* fronts_out);
+void pfes_mark_end(gpbo_ctx* ctx);
 // ehvi.hip: ctx->ys[i] = -EHVI(x_i), the negated expected hypervolume improvement of the M resident candidates from the resident
 // mu / sd of slots 0 .. n_obj - 1, the level rows `levels` (n_obj, GPBO_MAX_EHVI_LEVELS) and the boxes cell_lo / cell_hi (n_cells, n_obj)
 // of level indices (all host).  The caller has checked every argument.  The call's workspace is ctx->ehvi.

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(QNEI_BLOCK) void qnehvi_front_kernel(const double* 
   const int t = blockIdx.x, tid = threadIdx.x;
   const double* r0 = v0 + (int64_t)t * ld;
   const double* r1 = v1 + (int64_t)t * ld;
-  const double none = -std::numeric_limits<double>::infinity();      // ref0 is finite: every admitted pair is above it
+  const double none = -std::numeric_limits<double>::infinity();      // ref0 is finite, or -inf itself (no reference point): every admitted pair is above it
   double floor_c = ref1;
   int count = 0;
   for (;;) {
@@ -93,6 +93,14 @@ __global__ __launch_bounds__(QNEI_BLOCK) void qnehvi_front_kernel(const double* 
     floor_c = c;
   }
   if (tid == 0) { size[t] = count; size0[t] = count; }
+}
+
+int launch_qnehvi_fronts(gpbo_ctx* ctx, const double* v0, const double* v1, int64_t ld, int n, double ref0, double ref1, int T,
+                         double2* front, double2* front0, int* size, int* size0, int* flag) {
+  qnehvi_front_kernel<<<dim3((unsigned)T), dim3(QNEI_BLOCK), 0, ctx->stream>>>(v0, v1, ld, n, ref0, ref1, T, front, front0, size, size0,
+                                                                              flag);
+  GPBO_HIP(ctx, hipGetLastError());
+  return GPBO_OK;
 }
 
 // The update rule of one front f[0 .. *n) (objective 0 descending, objective 1 ascending) for y = (y0, y1): unchanged if y has a NaN,

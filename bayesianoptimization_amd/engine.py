@@ -1036,6 +1036,67 @@ class GpEngine:
         out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
         return out + (mu_points, var_points) if return_point_moments else out
 
+    def pfes_argbest(self, fronts=None, front_size=None, draws=None, k_seeds: int = 0, index_offset: int = 0, y_mean=(0.0, 0.0),
+                     y_std=(1.0, 1.0), return_values: bool = False, return_fronts: bool = False):
+        """Pareto-frontier entropy search over the resident candidates for two maximised objectives (gppf_pfes_argbest;
+        include/gppf.h has the formulas, the conventions and the order of every sum): ys = -a, a the mean over S <= 64 sampled
+        Pareto fronts of the entropy the observation at a candidate loses once it is known to be dominated by the front; objective j
+        from slot j's resident posterior, `y_mean` / `y_std` (2,) those of the passes that left them.  Either `fronts` — a list of S
+        arrays (n_s <= 128, 2), or an array (S, 128, 2) with `front_size` (S,) — each front finite, objective 0 strictly
+        descending and objective 1 strictly ascending, raw target units; or `draws` — two lists, objective j's G tuples (omega,
+        phase, weights, eps) as `qnehvi_greedy` takes them, G S <= 64: every joint draw's front is built on the device from the
+        draw's values at the first min(M, 16384) candidates.  Returns (best_idx, best_val, seed_idx, seed_val, ys|None) as
+        `acq_argbest`; `return_fronts=True` appends the fronts scored, front_size (S,) int32 and fronts (S, 128, 2) (rows past a
+        front's size unspecified).  A front of more than 128 points is NotImplementedError.  A reader, as `jes_argbest`."""
+        who = "pfes_argbest"
+        if (fronts is None) == (draws is None):
+            raise ValueError(f"{who}: give either fronts or draws")
+        L = _lib.MAX_PFES_FRONT
+        G = S_g = F = 0
+        omega = phase = weights = eps = sizes = None
+        if draws is not None:
+            draws = [list(g) for g in draws]
+            if len(draws) != 2:
+                raise ValueError(f"{who}: draws must hold two lists of groups, one per objective")
+            G = self._greedy_groups(who, draws, "each objective needs the same non-empty list of tuples (omega, phase, weights, eps)")
+            omega, phase, weights, eps, S_g, F, _d = self._greedy_inputs(who, list(enumerate(draws)))
+            S = G * S_g
+        elif front_size is None:
+            fronts = [np.asarray(f, dtype=np.float64) for f in fronts]
+            if any(f.ndim != 2 or f.shape[1] != 2 for f in fronts):
+                raise ValueError(f"{who}: every front must be two-dimensional (n, 2)")
+            S = len(fronts)
+            sizes = np.array([f.shape[0] for f in fronts], dtype=np.int32)
+            packed = np.zeros((S, L, 2))
+            for s, f in enumerate(fronts):
+                packed[s, :min(f.shape[0], L)] = f[:L]
+            fronts = packed
+        else:
+            fronts = np.ascontiguousarray(np.asarray(fronts, dtype=np.float64))
+            sizes = np.ascontiguousarray(np.asarray(front_size, dtype=np.int32).ravel())
+            S = int(sizes.shape[0])
+            if fronts.shape != (S, L, 2):
+                raise ValueError(f"{who}: fronts must be (S, {L}, 2) with front_size (S,)")
+        y_mean = np.ascontiguousarray(np.asarray(y_mean, dtype=np.float64).ravel())
+        y_std = np.ascontiguousarray(np.asarray(y_std, dtype=np.float64).ravel())
+        if y_mean.shape[0] != 2 or y_std.shape[0] != 2:
+            raise ValueError(f"{who}: y_mean and y_std must hold one value per objective")
+        k_seeds = int(k_seeds)
+        for slot in (0, 1):
+            self._settle(slot)
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        size_out = np.zeros(max(S, 1), dtype=np.int32) if return_fronts else None
+        fronts_out = np.empty((max(S, 1), L, 2)) if return_fronts else None
+        int_p = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))      # noqa: E731
+        self._check(self._lib.gppf_pfes_argbest(self._h, dptr(y_mean), dptr(y_std), G, int(S_g), int(F), dptr(omega), dptr(phase),
+                                                dptr(weights), dptr(eps), 0 if draws is not None else S, int_p(sizes),
+                                                dptr(fronts) if draws is None else None, k_seeds, int(index_offset),
+                                                C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys),
+                                                int_p(size_out), dptr(fronts_out)))
+        out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
+        return out + (size_out[:S], fronts_out[:S]) if return_fronts else out
+
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         """Expected hypervolume improvement over the resident candidates (gpbo_ehvi_argbest; include/gpbo.h has the formulas, the
         conventions and the order of the sum): ys = -EHVI for m = 2 or 3 maximised objectives, objective j from slot j's resident
@@ -1473,6 +1534,13 @@ class GpEngine:
         self._need_debug("gpla_debug_stage_ms")
         ms = (C.c_float * 3)()
         self._check(self._lib.gpla_debug_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+    def debug_pfes_stage_ms(self):
+        """gppf_debug_stage_ms (debug build): kernel ms of the last `pfes_argbest`'s stages, (draws and fronts, scores, selection)."""
+        self._need_debug("gppf_debug_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gppf_debug_stage_ms(self._h, ms))
         return tuple(float(v) for v in ms)
 
     def debug_jes_r2(self, beta):
@@ -1955,6 +2023,11 @@ class GroupEngine(GpEngine):
     def ei2_argbest(self, points, nodes, weights, y_best: float, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0,
                     y_std: float = 1.0, return_values: bool = False, return_point_moments: bool = False):
         raise NotImplementedError("a device group has no two-step lookahead EI (gpla_ei2_argbest is per context); use a single device")
+
+    def pfes_argbest(self, fronts=None, front_size=None, draws=None, k_seeds: int = 0, index_offset: int = 0, y_mean=(0.0, 0.0),
+                     y_std=(1.0, 1.0), return_values: bool = False, return_fronts: bool = False):
+        raise NotImplementedError("a device group has no Pareto-frontier entropy search (gppf_pfes_argbest is per context); "
+                                  "use a single device")
 
     def ehvi_argbest(self, levels, cell_lo, cell_hi, k_seeds: int = 0, index_offset: int = 0, return_values: bool = False):
         raise NotImplementedError("a device group has no expected hypervolume improvement (gpbo_ehvi_argbest is per context); "
