@@ -241,6 +241,18 @@ MAX_PFES_SAMPLES = 64            # GPPF_MAX_SAMPLES
 MAX_PFES_FRONT = 128             # GPPF_MAX_FRONT
 MAX_PFES_FRONT_CANDIDATES = 16384  # GPPF_MAX_FRONT_CANDIDATES
 
+# name -> (restype, argtypes) of multi-fidelity max-value entropy search; must list every product symbol include/gpmf.h declares
+MF_SIGNATURES = {
+    "gpmf_mes_argbest": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, _c_double_p, C.c_int, C.c_double, C.c_double,
+                                   C.c_int, C.c_int64, _c_int64_p, _c_double_p, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
+                                   _c_double_p, _c_double_p]),
+}
+# ... and its debug part (libgpbo_dbg.so only)
+MF_DEBUG_SIGNATURES = {
+    "gpmf_debug_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+}
+MAX_MF_SAMPLES = 64      # GPMF_MAX_SAMPLES
+
 # entry points only libgpbo_dbg.so exports (include/gpbo.h, "#ifdef GPBO_DEBUG")
 DEBUG_SIGNATURES = {
     "gpbo_debug_minimize_box": (C.c_int, [C.c_void_p, C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int,
@@ -321,7 +333,8 @@ def load_library(path: str | None = None):
         raise ImportError(
             f"{path} not found: the HIP extension has not been built. Run "
             "`python -m bayesianoptimization_amd.build` (needs hipcc). There is no CPU fallback.")
-    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **IV_SIGNATURES, **JE_SIGNATURES, **LA_SIGNATURES, **PF_SIGNATURES})
+    lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **IV_SIGNATURES, **JE_SIGNATURES, **LA_SIGNATURES, **PF_SIGNATURES,
+                       **MF_SIGNATURES})
     if not explicit:
         _lib = lib
     return lib
@@ -340,7 +353,8 @@ def load_debug_library():
                 raise ImportError(f"{DEBUG_LIB_PATH} not found and building it failed ({e})") from e
         _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **DEBUG_SIGNATURES, **MO3_DEBUG_SIGNATURES,
                                            **IV_SIGNATURES, **IV_DEBUG_SIGNATURES, **JE_SIGNATURES, **JE_DEBUG_SIGNATURES, **LA_SIGNATURES,
-                                           **LA_DEBUG_SIGNATURES, **PF_SIGNATURES, **PF_DEBUG_SIGNATURES})
+                                           **LA_DEBUG_SIGNATURES, **PF_SIGNATURES, **PF_DEBUG_SIGNATURES, **MF_SIGNATURES,
+                                           **MF_DEBUG_SIGNATURES})
     return _debug_lib
 
 

@@ -51,6 +51,7 @@ SOURCES = {
     "ivr.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # gpiv_ivr_argbest: integrated posterior variance reduction: the candidate x integration-point covariance product on fp64 MFMA with k* generated into LDS, the squared weighted row sum behind it in registers (no M x J block anywhere)
     "jes.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # gpje_jes_argbest: joint entropy search: the candidate x sampled-optimum covariance product on fp64 MFMA with the stage's k-steps split over the waves that share a 16-column fragment, the conditioning / truncated-variance / log chain per entry from LDS
     "lookahead.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # gpla_ei2_argbest: two-step lookahead EI: jes.hip's candidate x point covariance product (jes_product.h), then from LDS the slopes and residual sds per (candidate, point), the best second-step EI per (candidate, node) with the nodes dealt over the four waves, the weighted sum per candidate
+    "mfmes.hip": ["-ffp-contract=off"],       # gpmf_mes_argbest: multi-fidelity max-value entropy search (GIBBON): the paired posterior pass on fp64 MFMA — a workgroup owns 32 candidate pairs (z, z at the target fidelity) and walks every row chunk of W itself, k and k' from one shared distance as two B fragments over the same candidates, |Wk|^2, |Wk'|^2 and Wk.Wk' reduced lane-locally, the score (jes_r2.h's r2) per candidate from LDS
     "pfes.hip": ["-ffp-contract=off"],        # gppf_pfes_argbest: Pareto-frontier entropy search, m = 2: lane = candidate, four waves on the same 64 candidates with the sampled fronts' draws dealt over them, the fronts staged in LDS as staircases, (Phi, z phi) of a strip's lower level carried in registers into the next strip; device-front mode draws by posterior_paths.hip and builds the fronts by qnehvi.hip's front kernel
     "ehvi.hip": ["-ffp-contract=off"],        # gpbo_ehvi_argbest: expected hypervolume improvement values (per-candidate level tables in LDS, the sum over the boxes; acq_formulas.h's pieces); gpmo_cehvi_argbest: the same kernel body with the log-feasibility epilogue
     "qnei.hip": ["-ffp-contract=off"],        # gpbo_qnei_greedy: greedy batch noisy expected improvement over a resident (T, M) block of posterior draws (the score kernel streams it once per pick; incumbents updated in-stream); gpbo_cnei_greedy: the same stream over draws masked by their constraint draws
@@ -118,7 +119,7 @@ def _code_only(src: str) -> str:
 
 def _fingerprint() -> str:
     h = hashlib.sha256()
-    names = sorted(os.listdir(CSRC)) + ["../../include/gpbo.h", "../../include/gpmo.h", "../../include/gpmo3.h", "../../include/gpiv.h", "../../include/gpje.h", "../../include/gpla.h", "../../include/gppf.h"]
+    names = sorted(os.listdir(CSRC)) + ["../../include/gpbo.h", "../../include/gpmo.h", "../../include/gpmo3.h", "../../include/gpiv.h", "../../include/gpje.h", "../../include/gpla.h", "../../include/gppf.h", "../../include/gpmf.h"]
     for n in names:
         p = os.path.normpath(os.path.join(CSRC, n))
         if os.path.isfile(p):

@@ -227,7 +227,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock, &ctx->pf_clock})
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock, &ctx->pf_clock, &ctx->mf_clock})
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -239,7 +239,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->pf, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->pf, ctx->mf, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1612,6 +1612,45 @@ int gpje_jes_argbest(gpbo_ctx* ctx, const double* x_star, const double* f_star, 
   return GPBO_OK;
 }
 
+int gpmf_mes_argbest(gpbo_ctx* ctx, int fid_col, double fid_target, double cost0, double cost1, const double* y_star, int n_samples,
+                     double y_mean, double y_std, int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val,
+                     int64_t* seed_idx, double* seed_val, double* ys_out, double* rho_out, double* mu_t_out, double* sd_t_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (n_samples < 1 || n_samples > GPMF_MAX_SAMPLES) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: n_samples out of range [1, 64]");
+  if (!y_star) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: NULL y_star");
+  for (int s = 0; s < n_samples; ++s)
+    if (!std::isfinite(y_star[s])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: y_star must be finite");
+  if (fid_col < 0 || fid_col >= GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: fid_col out of range");
+  if (!std::isfinite(fid_target)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: fid_target must be finite");
+  if (!std::isfinite(cost0) || !(cost0 > 0.0)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: cost0 must be finite and positive");
+  if (!std::isfinite(cost1) || cost1 < 0.0) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: cost1 must be finite and not negative");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: NULL output");
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: y_std must be finite and positive, y_mean finite");
+  int rc = no_pending_fit(ctx, 0, "mf_mes_argbest");
+  if (rc) return rc;
+  if ((rc = need_fitted(ctx, 0))) return rc;
+  const Model& m = ctx->models[0];
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "mf_mes_argbest: no candidates");
+  if (ctx->d_c != m.d) GPBO_FAIL(ctx, GPBO_ERR_STATE, "mf_mes_argbest: the candidates' dimension differs from the fitted model's");
+  if (fid_col >= m.d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "mf_mes_argbest: fid_col is not a column of the model");
+  const bool parts = rho_out || mu_t_out || sd_t_out;
+  const int64_t M = ctx->M;
+  ev_begin(ctx, T_ACQ);
+  rc = launch_mf_values(ctx, m, M, fid_col, fid_target, cost0, cost1, y_star, n_samples, y_mean, y_std, parts);
+  if (!rc) rc = launch_values_argbest(ctx, M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  if (!rc) mf_mark_end(ctx);
+  ev_end(ctx, T_ACQ);
+  if (rc) return rc;
+  double* const host[4] = {ys_out, rho_out, mu_t_out, sd_t_out};
+  const double* const dev[4] = {ctx->ys, ctx->mf + MF_PARTS_AT, ctx->mf + MF_PARTS_AT + M, ctx->mf + MF_PARTS_AT + 2 * M};
+  for (int t = 0; t < 4; ++t)
+    if (host[t]) GPBO_HIP(ctx, hipMemcpyAsync(host[t], dev[t], (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (ys_out || parts) GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return GPBO_OK;
+}
+
 int gpla_ei2_argbest(gpbo_ctx* ctx, const double* points, int n_points, int d, const double* nodes, const double* weights, int n_nodes,
                      double y_best, double y_mean, double y_std, int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val,
                      int64_t* seed_idx, double* seed_val, double* ys_out, double* mu_points_out, double* var_points_out) {
@@ -2175,6 +2214,11 @@ int gpla_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
 int gppf_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
   return greedy_stage_ms(ctx, ctx->pf_clock, "gppf_debug_stage_ms", "gppf_pfes_argbest", ms);
+}
+
+int gpmf_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  return greedy_stage_ms(ctx, ctx->mf_clock, "gpmf_debug_stage_ms", "gpmf_mes_argbest", ms);
 }
 
 int gpje_debug_r2(gpbo_ctx* ctx, const double* beta, int n, double* out) {

@@ -19,6 +19,7 @@
 #include "gpje.h"
 #include "gpla.h"
 #include "gppf.h"
+#include "gpmf.h"
 #include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
@@ -193,6 +194,8 @@ struct gpbo_ctx {
   int64_t cap_la = 0;
   double* pf = nullptr;    // gppf_pfes_argbest: the joint draws at the first candidates, the sampled fronts and their sizes (pfes_plan.h: pfes_block)
   int64_t cap_pf = 0;
+  double* mf = nullptr;    // gpmf_mes_argbest: the call's sampled maxima [64], then the optional per-candidate parts rho | mu_t | sd_t (mfmes.hip)
+  int64_t cap_mf = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
   double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h), gpmo3_nhvi_greedy (qnehvi3_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
@@ -210,6 +213,7 @@ struct gpbo_ctx {
   gpbo::StageClock je_clock{4};     // the same four events of the last gpje_jes_argbest
   gpbo::StageClock la_clock{4};     // the same four events of the last gpla_ei2_argbest
   gpbo::StageClock pf_clock{4};     // around the three stages of the last gppf_pfes_argbest (draws and fronts, scores, selection)
+  gpbo::StageClock mf_clock{3};     // around the two stages of the last gpmf_mes_argbest (pair pass, selection)
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -748,6 +752,14 @@ int launch_pfes_values(gpbo_ctx* ctx, const Model* const* ms, int64_t M, const d
                        int F, const double* omega, const double* phase, const double* weights, const double* eps, int n_samples,
                        const int* front_size_in, const double* fronts_in, int* front_size_out, double* fronts_out);
 void pfes_mark_end(gpbo_ctx* ctx);
+// mfmes.hip: ctx->ys[i] = -a(z_i) / cost(z_i), the negated multi-fidelity max-value entropy search value per cost of the M resident
+// candidates from m's fit alone (include/gpmf.h has the formulas): fidelity column fid_col, target fid_target, the S sampled maxima
+// y_star (host, raw units).  with_parts: rho | mu_t | sd_t, M doubles each, are left on the device MF_PARTS_AT doubles into ctx->mf.
+// The caller has checked every argument.  mf_mark_end: the debug build's event behind the caller's selection.
+constexpr int64_t MF_PARTS_AT = 64;
+int launch_mf_values(gpbo_ctx* ctx, const Model& m, int64_t M, int fid_col, double fid_target, double cost0, double cost1,
+                     const double* y_star, int S, double y_mean, double y_std, bool with_parts);
+void mf_mark_end(gpbo_ctx* ctx);
 // ehvi.hip: ctx->ys[i] = -EHVI(x_i), the negated expected hypervolume improvement of the M resident candidates from the resident
 // mu / sd of slots 0 .. n_obj - 1, the level rows `levels` (n_obj, GPBO_MAX_EHVI_LEVELS) and the boxes cell_lo / cell_hi (n_cells, n_obj)
 // of level indices (all host).  The caller has checked every argument.  The call's workspace is ctx->ehvi.

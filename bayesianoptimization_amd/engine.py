@@ -1007,6 +1007,31 @@ class GpEngine:
         out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
         return out + (mu_star, var_star) if return_star else out
 
+    def mf_mes_argbest(self, y_star, fid_col: int, fid_target: float, cost0: float = 1.0, cost1: float = 0.0, k_seeds: int = 0,
+                       index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0, return_values: bool = False,
+                       return_parts: bool = False):
+        """Multi-fidelity max-value entropy search per cost over the resident candidates (gpmf_mes_argbest; include/gpmf.h has the
+        formulas): column `fid_col` of a candidate is its fidelity s, ys = -a / (cost0 + cost1 s), a the GIBBON lower bound in nats
+        on what a noisy observation at the candidate tells about the maximum of f(., fid_target), averaged over the S <= 64 sampled
+        maxima `y_star` (raw target units) of the target fidelity.  From slot 0's FIT and the candidates alone: no resident posterior
+        is needed, and none is touched.  Returns (best_idx, best_val, seed_idx, seed_val, ys|None) as `acq_argbest`;
+        `return_parts=True` appends (rho, mu_t, sd_t), (M,) each: the correlation of the observation at the candidate with
+        f at its target-fidelity twin, and the twin's posterior mean and latent sd in raw units.  A reader, as `jes_argbest`."""
+        y_star = np.ascontiguousarray(np.atleast_1d(np.asarray(y_star, dtype=np.float64)))
+        if y_star.ndim != 1:
+            raise ValueError("mf_mes_argbest: y_star must be one-dimensional")
+        k_seeds = int(k_seeds)
+        self._settle(0)
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        parts = tuple(np.empty(self.n_candidates) for _ in range(3)) if return_parts else (None, None, None)
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        self._check(self._lib.gpmf_mes_argbest(self._h, int(fid_col), float(fid_target), float(cost0), float(cost1), dptr(y_star),
+                                               int(y_star.shape[0]), float(y_mean), float(y_std), k_seeds, int(index_offset),
+                                               C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys),
+                                               dptr(parts[0]), dptr(parts[1]), dptr(parts[2])))
+        out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
+        return out + parts if return_parts else out
+
     def ei2_argbest(self, points, nodes, weights, y_best: float, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0,
                     y_std: float = 1.0, return_values: bool = False, return_point_moments: bool = False):
         """Two-step lookahead expected improvement over the resident candidates (gpla_ei2_argbest; include/gpla.h has the formulas):
@@ -1543,6 +1568,13 @@ class GpEngine:
         self._check(self._lib.gppf_debug_stage_ms(self._h, ms))
         return tuple(float(v) for v in ms)
 
+    def debug_mf_stage_ms(self):
+        """gpmf_debug_stage_ms (debug build): kernel ms of the last `mf_mes_argbest`'s stages, (pair pass, selection)."""
+        self._need_debug("gpmf_debug_stage_ms")
+        ms = (C.c_float * 2)()
+        self._check(self._lib.gpmf_debug_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
     def debug_jes_r2(self, beta):
         """gpje_debug_r2 (debug build): the device's r2 (include/gpje.h) over the values `beta`."""
         self._need_debug("gpje_debug_r2")
@@ -2019,6 +2051,12 @@ class GroupEngine(GpEngine):
     def jes_argbest(self, x_star, f_star, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                     return_values: bool = False, return_star: bool = False):
         raise NotImplementedError("a device group has no joint entropy search (gpje_jes_argbest is per context); use a single device")
+
+    def mf_mes_argbest(self, y_star, fid_col: int, fid_target: float, cost0: float = 1.0, cost1: float = 0.0, k_seeds: int = 0,
+                       index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0, return_values: bool = False,
+                       return_parts: bool = False):
+        raise NotImplementedError("a device group has no multi-fidelity entropy search (gpmf_mes_argbest is per context); "
+                                  "use a single device")
 
     def ei2_argbest(self, points, nodes, weights, y_best: float, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0,
                     y_std: float = 1.0, return_values: bool = False, return_point_moments: bool = False):
