@@ -227,7 +227,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock, &ctx->pf_clock, &ctx->mf_clock})
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock, &ctx->pf_clock, &ctx->mf_clock, &ctx->ls_clock})
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -239,7 +239,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->pf, ctx->mf, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->pf, ctx->mf, ctx->ls, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1576,6 +1576,50 @@ int gpiv_ivr_argbest(gpbo_ctx* ctx, const double* points, const double* weights,
   return GPBO_OK;
 }
 
+int gpls_sur_argbest(gpbo_ctx* ctx, const double* points, const double* weights, int n_points, int d, double level, double y_mean,
+                     double y_std, int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx,
+                     double* seed_val, double* ys_out, double* p_out, double* unc_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (n_points < 1 || n_points > GPLS_MAX_POINTS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: n_points out of range [1, 4096]");
+  if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: d out of range");
+  if (!points) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: NULL points");
+  for (int64_t e = 0; e < (int64_t)n_points * d; ++e)
+    if (!std::isfinite(points[e])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: points must be finite");
+  if (weights) {
+    double sum = 0.0;
+    for (int j = 0; j < n_points; ++j) {
+      if (!std::isfinite(weights[j]) || weights[j] < 0.0)
+        GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: weights must be finite and not negative");
+      sum += weights[j];
+    }
+    if (!(sum > 0.0)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: the weights' sum must be positive");
+  }
+  if (!std::isfinite(level)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: level must be finite");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: NULL output");
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: y_std must be finite and positive, y_mean finite");
+  int rc = no_pending_fit(ctx, 0, "sur_argbest");
+  if (rc) return rc;
+  if ((rc = need_fitted(ctx, 0))) return rc;
+  const Model& m = ctx->models[0];
+  if (d != m.d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: the points' dimension differs from the fitted model's");
+  if (ctx->M < 1 || m.M_post != ctx->M) GPBO_FAIL(ctx, GPBO_ERR_STATE, "sur_argbest: run gpbo_posterior for slot 0 first");
+  if (y_std != m.ystd_post)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "sur_argbest: y_std is not the one the resident posterior was scaled with");
+  ev_begin(ctx, T_ACQ);
+  rc = launch_sur_values(ctx, m, ctx->M, points, weights, n_points, level, y_mean, y_std, p_out, unc_out);
+  if (!rc) rc = launch_values_argbest(ctx, ctx->M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  if (!rc) sur_mark_end(ctx);
+  ev_end(ctx, T_ACQ);
+  if (rc) return rc;
+  if (ys_out) {
+    GPBO_HIP(ctx, hipMemcpyAsync(ys_out, ctx->ys, (size_t)ctx->M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GPBO_OK;
+}
+
 int gpje_jes_argbest(gpbo_ctx* ctx, const double* x_star, const double* f_star, int n_samples, int d, double y_mean, double y_std,
                      int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val,
                      double* ys_out, double* mu_star_out, double* var_star_out) {
@@ -2199,6 +2243,11 @@ int gpmo3_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
 int gpiv_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
   return greedy_stage_ms(ctx, ctx->iv_clock, "gpiv_debug_stage_ms", "gpiv_ivr_argbest", ms);
+}
+
+int gpls_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  return greedy_stage_ms(ctx, ctx->ls_clock, "gpls_debug_stage_ms", "gpls_sur_argbest", ms);
 }
 
 int gpje_debug_stage_ms(gpbo_ctx* ctx, float* ms) {

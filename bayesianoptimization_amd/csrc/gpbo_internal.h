@@ -20,7 +20,8 @@
 #include "gpla.h"
 #include "gppf.h"
 #include "gpmf.h"
-#include "fit_plan.h"         // the fit's size rule, its block size NB and a model's buffer sizes
+#include "gpls.h"
+#include "fit_plan.h"        // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
 #include "path_plan.h"        // the posterior function draws' workspace layout and dispatch rules
@@ -196,6 +197,8 @@ struct gpbo_ctx {
   int64_t cap_pf = 0;
   double* mf = nullptr;    // gpmf_mes_argbest: the call's sampled maxima [64], then the optional per-candidate parts rho | mu_t | sd_t (mfmes.hip)
   int64_t cap_mf = 0;
+  double* ls = nullptr;    // gpls_sur_argbest: gpiv_ivr_argbest's layout for the call's points, then h_j^2 | 1 / s_j^2 | p_j per column (sur_plan.h: sur_block)
+  int64_t cap_ls = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
   double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h), gpmo3_nhvi_greedy (qnehvi3_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
@@ -214,6 +217,7 @@ struct gpbo_ctx {
   gpbo::StageClock la_clock{4};     // the same four events of the last gpla_ei2_argbest
   gpbo::StageClock pf_clock{4};     // around the three stages of the last gppf_pfes_argbest (draws and fronts, scores, selection)
   gpbo::StageClock mf_clock{3};     // around the two stages of the last gpmf_mes_argbest (pair pass, selection)
+  gpbo::StageClock ls_clock{4};     // around the three stages of the last gpls_sur_argbest (points, scores, selection)
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -714,6 +718,21 @@ int launch_kg_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* poi
 // ivr_mark_end: the debug build's event behind the caller's selection.
 int launch_ivr_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, const double* weights, int J, double y_std);
 void ivr_mark_end(gpbo_ctx* ctx);
+// ... and its points stage for sur.hip: into the workspace ws laid out by b (ivr_plan.h) the scaled points, omega and, a group of
+// IVR_GROUP columns at a time, k*(a_j), V_j = -K'^-1 k*(a_j) and the packed V.  after_group (or null) runs behind each group's solve,
+// while KS / V [cols][NP] hold the columns g0 .. g0 + cols - 1.  Event 0 of `clock` is recorded in front of the groups (jes_mark).
+struct IvrBlock;
+typedef int (*IvrGroupHook)(gpbo_ctx* ctx, const Model& m, const double* KS, const double* V, int g0, int cols, void* user);
+int launch_ivr_points(gpbo_ctx* ctx, const Model& m, double* ws, const IvrBlock& b, const double* points, const double* weights, int J,
+                      StageClock& clock, IvrGroupHook after_group, void* user);
+// sur.hip: ctx->ys[i] = -SUR(x_i), the negated expected reduction of the excursion set's classification uncertainty of the M resident
+// candidates over the J integration points `points` (J, d; host, parameter space) with `weights` (J,; host) or null = 1 / J, for the
+// level `level` (raw units), from m's resident mu / sd (include/gpls.h has the formulas); p_out (J,; host) / unc_out (1,; host) or
+// null.  The caller has checked every argument.  The call's workspace is ctx->ls (sur_plan.h).  sur_mark_end: the debug build's
+// event behind the caller's selection.
+int launch_sur_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, const double* weights, int J, double level,
+                      double y_mean, double y_std, double* p_out, double* unc_out);
+void sur_mark_end(gpbo_ctx* ctx);
 // jes.hip: ctx->ys[i] = -a(x_i), the negated joint entropy search value of the M resident candidates over the S sampled optima
 // x_star (S, d; host, parameter space) / f_star (S,; host, raw units) from m's resident mu / sd (include/gpje.h has the formulas);
 // mu_star_out / var_star_out (S,; host) or null.  The caller has checked every argument.  The call's workspace is ctx->je

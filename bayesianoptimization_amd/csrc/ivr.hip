@@ -28,12 +28,11 @@
 // sum above has a fixed order.  Rows from M on repeat row M - 1 and are not written.
 #include "gpbo_internal.h"
 #include "ivr_plan.h"
+#include "ivr_product.h"
 
 #include <cmath>
 
 namespace gpbo {
-
-typedef double iv_d4 __attribute__((ext_vector_type(4)));
 
 // KS[j][i] = k(a_j, X_i) for i < N, 0 up to NP.  Workgroup = point; thread t takes the train points t, t + 256, ...
 template <int DP, int KERNEL>
@@ -92,105 +91,22 @@ struct IvrScoreArgs {
   double amplitude, y_std, lambda, white;
 };
 
-// wave w's 8 rows of the stage in xs -> its 8 rows of the k-major block: ab[row][candidate]
-template <int DP, int KERNEL>
-__device__ __forceinline__ void ivr_generate(const double (&xc)[DP], const double* xs, double* ab, const int wave, const int lane) {
-#pragma unroll 2
-  for (int q = 0; q < IVR_KC / 4; q += 2) {
-    const int row = wave * (IVR_KC / 4) + q;
-    const double* xr = xs + row * DP;          // the same address in every lane: LDS broadcast
-    double d2a = 0.0, d2b = 0.0;
-#pragma unroll
-    for (int t = 0; t < DP; ++t) {
-      const double da = xc[t] - xr[t], db = xc[t] - xr[DP + t];
-      d2a = fma(da, da, d2a);
-      d2b = fma(db, db, d2b);
-    }
-    ab[row * IVR_PITCH + lane] = gpbo_kernel_value<KERNEL>(d2a);
-    ab[(row + 1) * IVR_PITCH + lane] = gpbo_kernel_value<KERNEL>(d2b);
-  }
-}
-
 template <int DP, int KERNEL, int NSUB>
 __global__ __launch_bounds__(256) void ivr_score_kernel(const IvrScoreArgs a) {
   __shared__ __attribute__((aligned(16))) double xs[IVR_KC * DP];           // the stage's train points (or the tile's own points)
   __shared__ __attribute__((aligned(16))) double ab[IVR_KC * IVR_PITCH];    // k* of the stage, k-major: the A operand
   __shared__ double red[4][IVR_ROWS];
-  constexpr int KSTEPS = IVR_KC / 4;      // k-steps per stage
   constexpr int NWC = 16 * NSUB;          // columns per wave
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int lk = lane >> 4, lc = lane & 15;
   const int64_t m0 = (int64_t)blockIdx.x * IVR_ROWS;
   double xc[DP];
-  {
-    const int64_t m = m0 + lane < a.M ? m0 + lane : a.M - 1;
-    const double* xcp = a.P + m * DP;
-#pragma unroll
-    for (int t = 0; t < DP; t += 2) {
-      const double2 v = *reinterpret_cast<const double2*>(xcp + t);
-      xc[t] = v.x;
-      xc[t + 1] = v.y;
-    }
-  }
-  const int64_t tile_stride = (int64_t)(a.Kp / 4) * 4 * NSUB * 64;
+  ivr_load_candidate<DP>(a.P, m0, a.M, lane, xc);
   double total = 0.0;      // threads 0 .. 63: candidate tid's sum over the tiles so far
   for (int tile = 0; tile < a.n_tiles; ++tile) {
     iv_d4 acc[4][NSUB];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int u = 0; u < NSUB; ++u) acc[t][u] = iv_d4{0.0, 0.0, 0.0, 0.0};
-    const double* vp = a.Vp + tile * tile_stride + (int64_t)wave * NSUB * 64 + lane;
-    for (int kc = 0; kc < a.Kp; kc += IVR_KC) {
-      // this stage's B fragments: asked for now, used behind the generation
-      double vb[KSTEPS][NSUB];
-#pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks)
-#pragma unroll
-        for (int u = 0; u < NSUB; ++u) vb[ks][u] = vp[(ks * 4 * NSUB + u) * 64];
-      vp += KSTEPS * 4 * NSUB * 64;
-      {
-        const double2* src = reinterpret_cast<const double2*>(a.Xs + (int64_t)kc * DP);
-        double2* dst = reinterpret_cast<double2*>(xs);
-        for (int e = tid; e < IVR_KC * DP / 2; e += 256) dst[e] = src[e];
-      }
-      __syncthreads();      // xs is whole; every wave is done with the previous stage's ab
-      ivr_generate<DP, KERNEL>(xc, xs, ab, wave, lane);
-      __syncthreads();      // ab is whole; everyone is done with xs
-#pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) {
-        const double* ar = ab + (ks * 4 + lk) * IVR_PITCH + lc;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const double av = ar[16 * t];
-#pragma unroll
-          for (int u = 0; u < NSUB; ++u) acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, vb[ks][u], acc[t][u], 0, 0, 0);
-        }
-      }
-    }
-    // the tile's own points, 8 of the wave's columns at a time: row 8 w + q of the stage = column 16 NSUB w + 16 u + 8 h + q of the tile
+    ivr_tile_product<DP, KERNEL, NSUB>(a.Xs, a.Vp, a.As, a.Kp, tile, xc, xs, ab, acc);      // ivr_product.h
     const int64_t j0 = (int64_t)tile * (4 * NWC);
-#pragma unroll
-    for (int u = 0; u < NSUB; ++u) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        for (int e = tid; e < IVR_KC * DP / 2; e += 256) {
-          const int row = e / (DP / 2), t2 = e - row * (DP / 2);
-          const int64_t j = j0 + (row >> 3) * NWC + 16 * u + 8 * h + (row & 7);
-          reinterpret_cast<double2*>(xs)[e] = reinterpret_cast<const double2*>(a.As + j * DP)[t2];
-        }
-        __syncthreads();
-        ivr_generate<DP, KERNEL>(xc, xs, ab, wave, lane);
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const double unit = (8 * h + 4 * s + lk == lc) ? 1.0 : 0.0;      // B[k][column] = 1 where train "point" k is the column
-          const double* ar = ab + (wave * 8 + 4 * s + lk) * IVR_PITCH + lc;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[16 * t], unit, acc[t][u], 0, 0, 0);
-        }
-      }
-    }
     // c, square, omega; the wave's columns; the four waves; the tiles
     double om[NSUB];
 #pragma unroll
@@ -248,12 +164,13 @@ static int launch_ivr_score(gpbo_ctx* ctx, const Model& m, const IvrScoreArgs& a
   });
 }
 
-int launch_ivr_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, const double* weights, int J, double y_std) {
+// The points stage into the workspace ws laid out by b: the scaled points, omega, and per group of columns k*(a_j), V_j and its packed
+// image, event 0 of `clock` in front of the groups.  after_group (or null) runs behind each group's solve, while KS and V still
+// hold that group's columns (sur.hip takes the points' means and variances there).
+int launch_ivr_points(gpbo_ctx* ctx, const Model& m, double* ws, const IvrBlock& b, const double* points, const double* weights, int J,
+                      StageClock& clock, IvrGroupHook after_group, void* user) {
   const int N = (int)m.N, NP = (int)m.NP, d = m.d, DP = m.DP;
   int rc;
-  const IvrBlock b = ivr_block(J, d, DP, N, NP);
-  if ((rc = ensure(ctx, &ctx->iv, &ctx->cap_iv, b.doubles))) return rc;
-  double* ws = ctx->iv;
   GPBO_HIP(ctx, hipMemcpyAsync(ws + b.raw, points, (size_t)J * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (weights) GPBO_HIP(ctx, hipMemcpyAsync(ws + b.wraw, weights, (size_t)J * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   GPBO_HIP(ctx, hipMemsetAsync(ws + b.zero, 0, (size_t)b.n_zero * sizeof(double), ctx->stream));
@@ -262,7 +179,7 @@ int launch_ivr_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* po
                                                                                      (int)b.Jp, ws + b.omega);
   GPBO_HIP(ctx, hipGetLastError());
   // stage 1: k*(a_j), V_j, packed, a group of columns at a time
-  ivr_mark(ctx, 0);
+  jes_mark(ctx, clock, 0);
   for (int g0 = 0; g0 < J; g0 += IVR_GROUP) {
     const int cols = J - g0 < IVR_GROUP ? J - g0 : IVR_GROUP;
     rc = with_dp_kernel(ctx, DP, m.kernel, [&](auto dp, auto k) {
@@ -273,6 +190,7 @@ int launch_ivr_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* po
     });
     if (rc) return rc;
     if ((rc = launch_path_solve(ctx, m, cols, ws + b.KS, ws + b.zero, ws + b.zero, ws + b.T, ws + b.V))) return rc;
+    if (after_group && (rc = after_group(ctx, m, ws + b.KS, ws + b.V, g0, cols, user))) return rc;
     // the last group also writes the zero columns up to Jp
     const int pcols = g0 + cols == J ? (int)(b.Jp - g0) : cols;
     const int64_t n = (int64_t)pcols * b.Kp;
@@ -280,6 +198,16 @@ int launch_ivr_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* po
                                                                                    (int)b.Kp, b.nsub);
     GPBO_HIP(ctx, hipGetLastError());
   }
+  return GPBO_OK;
+}
+
+int launch_ivr_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, const double* weights, int J, double y_std) {
+  const int d = m.d, DP = m.DP;
+  int rc;
+  const IvrBlock b = ivr_block(J, d, DP, m.N, m.NP);
+  if ((rc = ensure(ctx, &ctx->iv, &ctx->cap_iv, b.doubles))) return rc;
+  double* ws = ctx->iv;
+  if ((rc = launch_ivr_points(ctx, m, ws, b, points, weights, J, ctx->iv_clock, nullptr, nullptr))) return rc;
   // stage 2: the scores
   ivr_mark(ctx, 1);
   const int64_t Mp = round_up(M, POST_CANDS);

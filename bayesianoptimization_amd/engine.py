@@ -980,6 +980,33 @@ class GpEngine:
                                                C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys)))
         return best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys
 
+    def sur_argbest(self, points, level, weights=None, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
+                    return_values: bool = False, return_points: bool = False):
+        """SUR for the excursion set {f > level} over the resident candidates (gpls_sur_argbest; include/gpls.h has the formulas):
+        ys = -SUR, the expected drop of the classification uncertainty sum_j omega_j p_j (1 - p_j), p_j = P(f(a_j) > level), after
+        one noisy observation at the candidate, over the J <= 4096 integration `points` (J, d), parameter space, with `weights`
+        (J,) — None: 1 / J each; `level` in raw target units; from slot 0's resident posterior; `y_mean` / `y_std` are those of the
+        pass that left it.  Returns (best_idx, best_val, seed_idx, seed_val, ys|None) as `acq_argbest`; `return_points=True` appends
+        p (J,) and the uncertainty itself.  A reader, as `ivr_argbest`."""
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        if points.ndim != 2:
+            raise ValueError("sur_argbest: points must be two-dimensional (J, d)")
+        if weights is not None:
+            weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+            if weights.shape != (points.shape[0],):
+                raise ValueError("sur_argbest: weights must be one-dimensional (J,)")
+        k_seeds = int(k_seeds)
+        self._settle(0)
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, self.n_candidates if return_values else None)
+        p = np.empty(points.shape[0]) if return_points else None
+        best_idx, best_val, unc = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        self._check(self._lib.gpls_sur_argbest(self._h, dptr(points), dptr(weights), int(points.shape[0]), int(points.shape[1]),
+                                               float(level), float(y_mean), float(y_std), k_seeds, int(index_offset),
+                                               C.byref(best_idx), C.byref(best_val), iptr(seed_idx), dptr(seed_val), dptr(ys), dptr(p),
+                                               C.byref(unc) if return_points else None))
+        out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
+        return out + (p, unc.value) if return_points else out
+
     def jes_argbest(self, x_star, f_star, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                     return_values: bool = False, return_star: bool = False):
         """Joint entropy search, lower bound, over the resident candidates (gpje_jes_argbest; include/gpje.h has the formulas): ys =
@@ -1547,6 +1574,13 @@ class GpEngine:
         self._check(self._lib.gpiv_debug_stage_ms(self._h, ms))
         return tuple(float(v) for v in ms)
 
+    def debug_sur_stage_ms(self):
+        """gpls_debug_stage_ms (debug build): kernel ms of the last `sur_argbest`'s stages, (points, scores, selection)."""
+        self._need_debug("gpls_debug_stage_ms")
+        ms = (C.c_float * 3)()
+        self._check(self._lib.gpls_debug_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
     def debug_jes_stage_ms(self):
         """gpje_debug_stage_ms (debug build): kernel ms of the last `jes_argbest`'s stages, (points, scores, selection)."""
         self._need_debug("gpje_debug_stage_ms")
@@ -2047,6 +2081,10 @@ class GroupEngine(GpEngine):
                     return_values: bool = False):
         raise NotImplementedError("a device group has no integrated variance reduction (gpiv_ivr_argbest is per context); "
                                   "use a single device")
+
+    def sur_argbest(self, points, level, weights=None, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
+                    return_values: bool = False, return_points: bool = False):
+        raise NotImplementedError("a device group has no level-set acquisition (gpls_sur_argbest is per context); use a single device")
 
     def jes_argbest(self, x_star, f_star, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                     return_values: bool = False, return_star: bool = False):
