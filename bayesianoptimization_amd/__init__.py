@@ -1,6 +1,6 @@
 """MI355X-native GP-posterior + acquisition engine for bayes_opt's suggest() hot path.
 
-Hand-written HIP (gfx950) behind a C ABI (include/gpbo.h, include/gpmo.h, include/gpmo3.h, include/gpiv.h, include/gpje.h, include/gpla.h, include/gppf.h, include/gpmf.h, include/gpls.h), loaded with ctypes.  No PyTorch, no
+Hand-written HIP (gfx950) behind a C ABI (include/gpbo.h, include/gpmo.h, include/gpmo3.h, include/gpiv.h, include/gpje.h, include/gpla.h, include/gppf.h, include/gpmf.h, include/gpls.h, include/gpnn.h), loaded with ctypes.  No PyTorch, no
 Triton, no CPU fallback: importing the host classes works anywhere, creating an engine requires the
 built library and an AMD GPU.
 """
@@ -13,7 +13,7 @@ __all__ = ["GpEngine", "HipGPR", "HipConstraintModel", "FloatSpace", "accelerate
            "suggest_constrained_thompson", "suggest_scbo", "ConstrainedTrustRegion",
            "ParetoOptimizer", "pareto_front", "hypervolume", "box_decomposition", "suggest_qnei", "suggest_qnehvi",
            "suggest_constrained_qnei", "suggest_constrained_qnehvi", "suggest_qnehvi3", "suggest_ivr", "suggest_jes",
-           "suggest_lookahead", "suggest_pfes", "suggest_multifidelity", "suggest_levelset"]
+           "suggest_lookahead", "suggest_pfes", "suggest_multifidelity", "suggest_levelset", "suggest_local"]
 
 
 def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must not need sklearn/scipy
@@ -77,6 +77,9 @@ def __getattr__(name):  # lazy: `import bayesianoptimization_amd.workloads` must
     if name == "suggest_levelset":
         from .levelset import suggest_levelset
         return suggest_levelset
+    if name == "suggest_local":
+        from .localgp import suggest_local
+        return suggest_local
     if name == "suggest_jes":
         from .jes import suggest_jes
         return suggest_jes

@@ -264,6 +264,20 @@ LS_DEBUG_SIGNATURES = {
 }
 MAX_LS_POINTS = 4096     # GPLS_MAX_POINTS
 
+# name -> (restype, argtypes) of the nearest-neighbour GP scoring; must list every product symbol include/gpnn.h declares
+NN_SIGNATURES = {
+    "gpnn_acq_argbest": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, C.c_int, C.c_double,
+                                   C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                   C.c_int64, _c_int64_p, _c_double_p, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                   _c_int64_p]),
+}
+# ... and its debug part (libgpbo_dbg.so only)
+NN_DEBUG_SIGNATURES = {
+    "gpnn_debug_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+}
+MAX_NN_NEIGHBORS = 64    # GPNN_MAX_NEIGHBORS
+MAX_NN_N = 1 << 20       # GPNN_MAX_N
+
 # entry points only libgpbo_dbg.so exports (include/gpbo.h, "#ifdef GPBO_DEBUG")
 DEBUG_SIGNATURES = {
     "gpbo_debug_minimize_box": (C.c_int, [C.c_void_p, C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_int,
@@ -345,7 +359,7 @@ def load_library(path: str | None = None):
             f"{path} not found: the HIP extension has not been built. Run "
             "`python -m bayesianoptimization_amd.build` (needs hipcc). There is no CPU fallback.")
     lib = _bind(path, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **IV_SIGNATURES, **JE_SIGNATURES, **LA_SIGNATURES, **PF_SIGNATURES,
-                       **MF_SIGNATURES, **LS_SIGNATURES})
+                       **MF_SIGNATURES, **LS_SIGNATURES, **NN_SIGNATURES})
     if not explicit:
         _lib = lib
     return lib
@@ -365,7 +379,8 @@ def load_debug_library():
         _debug_lib = _bind(DEBUG_LIB_PATH, {**SIGNATURES, **MO_SIGNATURES, **MO3_SIGNATURES, **DEBUG_SIGNATURES, **MO3_DEBUG_SIGNATURES,
                                            **IV_SIGNATURES, **IV_DEBUG_SIGNATURES, **JE_SIGNATURES, **JE_DEBUG_SIGNATURES, **LA_SIGNATURES,
                                            **LA_DEBUG_SIGNATURES, **PF_SIGNATURES, **PF_DEBUG_SIGNATURES, **MF_SIGNATURES,
-                                           **MF_DEBUG_SIGNATURES, **LS_SIGNATURES, **LS_DEBUG_SIGNATURES})
+                                           **MF_DEBUG_SIGNATURES, **LS_SIGNATURES, **LS_DEBUG_SIGNATURES, **NN_SIGNATURES,
+                                           **NN_DEBUG_SIGNATURES})
     return _debug_lib
 
 

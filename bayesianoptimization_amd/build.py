@@ -50,6 +50,7 @@ SOURCES = {
     "kg.hip": ["-ffp-contract=off"],          # gpbo_kg_argbest: knowledge gradient values (candidate x point covariances, upper envelope of J + 1 lines; acq_formulas.h's pieces)
     "ivr.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # gpiv_ivr_argbest: integrated posterior variance reduction: the candidate x integration-point covariance product on fp64 MFMA with k* generated into LDS, the squared weighted row sum behind it in registers (no M x J block anywhere)
     "sur.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # gpls_sur_argbest: SUR for excursion sets: ivr.hip's covariance product (ivr_product.h), and behind each column tile a bivariate normal probability per accumulator entry as a 12-node quadrature in registers, four entries side by side per lane
+    "nngp.hip": ["-ffp-contract=off"],        # gpnn_acq_argbest: nearest-neighbour GP scoring for 10^4 .. 10^6 observations: a brute-force fp64 k-nearest-neighbour search (lane = candidate, rows broadcast from LDS, each candidate's k-list of (d2, index) in LDS) and a batched k x k Cholesky with both right-hand sides in the sweep (one wave per 64 / k candidates, lane = row, the triangle in LDS)
     "jes.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # gpje_jes_argbest: joint entropy search: the candidate x sampled-optimum covariance product on fp64 MFMA with the stage's k-steps split over the waves that share a 16-column fragment, the conditioning / truncated-variance / log chain per entry from LDS
     "lookahead.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # gpla_ei2_argbest: two-step lookahead EI: jes.hip's candidate x point covariance product (jes_product.h), then from LDS the slopes and residual sds per (candidate, point), the best second-step EI per (candidate, node) with the nodes dealt over the four waves, the weighted sum per candidate
     "mfmes.hip": ["-ffp-contract=off"],       # gpmf_mes_argbest: multi-fidelity max-value entropy search (GIBBON): the paired posterior pass on fp64 MFMA — a workgroup owns 32 candidate pairs (z, z at the target fidelity) and walks every row chunk of W itself, k and k' from one shared distance as two B fragments over the same candidates, |Wk|^2, |Wk'|^2 and Wk.Wk' reduced lane-locally, the score (jes_r2.h's r2) per candidate from LDS
@@ -120,7 +121,7 @@ def _code_only(src: str) -> str:
 
 def _fingerprint() -> str:
     h = hashlib.sha256()
-    names = sorted(os.listdir(CSRC)) + ["../../include/gpbo.h", "../../include/gpmo.h", "../../include/gpmo3.h", "../../include/gpiv.h", "../../include/gpje.h", "../../include/gpla.h", "../../include/gppf.h", "../../include/gpmf.h", "../../include/gpls.h"]
+    names = sorted(os.listdir(CSRC)) + ["../../include/gpbo.h", "../../include/gpmo.h", "../../include/gpmo3.h", "../../include/gpiv.h", "../../include/gpje.h", "../../include/gpla.h", "../../include/gppf.h", "../../include/gpmf.h", "../../include/gpls.h", "../../include/gpnn.h"]
     for n in names:
         p = os.path.normpath(os.path.join(CSRC, n))
         if os.path.isfile(p):

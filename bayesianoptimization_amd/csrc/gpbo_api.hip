@@ -9,6 +9,7 @@
 
 #include "gpbo_internal.h"
 #include "scaled_kernel.h"    // a scaled model c * k + white * I as the unit model at noise (white + alpha) / c
+#include "nngp_plan.h"        // gpnn_acq_argbest's neighbour counts and workspace layout
 
 namespace gpbo {
 
@@ -227,7 +228,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   for (auto& st : ctx->slot_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (ctx->small_ev) (void)hipEventDestroy(ctx->small_ev);
   for (auto ev : ctx->kg_ev) if (ev) (void)hipEventDestroy(ev);
-  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock, &ctx->pf_clock, &ctx->mf_clock, &ctx->ls_clock})
+  for (StageClock* c : {&ctx->qnei_clock, &ctx->cnei_clock, &ctx->qnehvi_clock, &ctx->cnhvi_clock, &ctx->qnehvi3_clock, &ctx->iv_clock, &ctx->je_clock, &ctx->la_clock, &ctx->pf_clock, &ctx->mf_clock, &ctx->ls_clock, &ctx->nn_clock})
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->gen_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : ctx->ehvi_ev) if (ev) (void)hipEventDestroy(ev);
@@ -239,7 +240,7 @@ int gpbo_destroy(gpbo_ctx* ctx) {
   if (ctx->lml_slab) (void)hipFree(ctx->lml_slab);
   if (ctx->lml_X) (void)hipFree(ctx->lml_X);
   if (ctx->lml_y) (void)hipFree(ctx->lml_y);
-  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->pf, ctx->mf, ctx->ls, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
+  void* ptrs[] = {ctx->Xc, ctx->Xc_raw, ctx->Xcs, ctx->part, ctx->mu_part, ctx->ys, ctx->paths, ctx->cpaths, ctx->kg, ctx->iv, ctx->je, ctx->la, ctx->pf, ctx->mf, ctx->ls, ctx->nn, ctx->ehvi, ctx->greedy, ctx->red, ctx->info_dev, ctx->comm_buf, ctx->kst, ctx->stage};
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   if (ctx->mt_work) (void)hipFree(ctx->mt_work);
   if (ctx->mt_bits) (void)hipFree(ctx->mt_bits);
@@ -1620,6 +1621,67 @@ int gpls_sur_argbest(gpbo_ctx* ctx, const double* points, const double* weights,
   return GPBO_OK;
 }
 
+int gpnn_acq_argbest(gpbo_ctx* ctx, const double* X, const double* y_norm, int64_t N, int d, int kernel, const double* length_scale,
+                     int n_ls, double amplitude, double white, double alpha, int k, int acq, double kappa_or_xi, double y_max,
+                     double y_mean, double y_std, int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val,
+                     int64_t* seed_idx, double* seed_val, double* ys_out, double* mu_out, double* sd_out, int64_t* nbr_out) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  if (!nn_k_ok(k)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: k must be 16, 32 or 64");
+  if (N < k || N > GPNN_MAX_N) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: N out of range [k, 1048576]");
+  if (d < 1 || d > GPBO_MAX_DIM) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: d out of range [1, 64]");
+  if (n_ls != 1 && n_ls != d) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: length_scale must have 1 or d entries");
+  if (kernel != GPBO_KERNEL_RBF && kernel != GPBO_KERNEL_MATERN25 && kernel != GPBO_KERNEL_MATERN15 && kernel != GPBO_KERNEL_MATERN05)
+    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "nn_acq_argbest: kernel must be RBF or Matern(nu=2.5, 1.5 or 0.5)");
+  if (acq != GPBO_ACQ_UCB && acq != GPBO_ACQ_EI && acq != GPBO_ACQ_POI && acq != GPBO_ACQ_LOG_EI)
+    GPBO_FAIL(ctx, GPBO_ERR_UNSUPPORTED, "nn_acq_argbest: acq must be UCB, EI, POI or LOG_EI");
+  if (!X || !y_norm || !length_scale) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: NULL input");
+  for (int t = 0; t < n_ls; ++t)
+    if (!(length_scale[t] > 0.0) || !std::isfinite(length_scale[t]))
+      GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: length_scale must be positive and finite");
+  if (!scaled_args_ok(amplitude, white) || !std::isfinite(alpha) || alpha < 0.0)
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: amplitude must be positive, white and alpha not negative, all finite");
+  if (!std::isfinite(kappa_or_xi) || !std::isfinite(y_max)) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: kappa_or_xi and y_max must be finite");
+  if (!std::isfinite(y_std) || !(y_std > 0.0) || !std::isfinite(y_mean))
+    GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: y_std must be finite and positive, y_mean finite");
+  if (k_seeds < 0 || k_seeds > GPBO_MAX_SEEDS) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: k_seeds out of range [0, 64]");
+  if (!best_idx || !best_val || (k_seeds > 0 && (!seed_idx || !seed_val))) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: NULL output");
+  for (int64_t e = 0; e < N * d; ++e)
+    if (!std::isfinite(X[e])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: X must be finite");
+  for (int64_t i = 0; i < N; ++i)
+    if (!std::isfinite(y_norm[i])) GPBO_FAIL(ctx, GPBO_ERR_INVALID, "nn_acq_argbest: y_norm must be finite");
+  if (ctx->M < 1) GPBO_FAIL(ctx, GPBO_ERR_STATE, "nn_acq_argbest: no candidates resident (call gpbo_set_candidates)");
+  if (ctx->d_c != d) GPBO_FAIL(ctx, GPBO_ERR_STATE, "nn_acq_argbest: the candidates' dimension differs from d");
+  GPBO_HIP(ctx, hipSetDevice(ctx->device));
+  double ls[GPBO_MAX_DIM];
+  for (int t = 0; t < GPBO_MAX_DIM; ++t) ls[t] = (t < d) ? (n_ls == 1 ? length_scale[0] : length_scale[t]) : 1.0;
+  const int64_t M = ctx->M;
+  NnCall c{};
+  c.X = X; c.y = y_norm; c.ls = ls; c.N = N; c.d = d; c.kernel = kernel; c.k = k; c.acq = acq;
+  c.amplitude = amplitude; c.white = white; c.alpha = alpha; c.param = kappa_or_xi; c.y_max = y_max; c.y_mean = y_mean; c.y_std = y_std;
+  ev_begin(ctx, T_ACQ);
+  int rc = launch_nn_values(ctx, c);
+  if (!rc) rc = launch_values_argbest(ctx, M, k_seeds, index_offset, best_idx, best_val, seed_idx, seed_val);
+  if (!rc) nn_mark_end(ctx);
+  ev_end(ctx, T_ACQ);
+  if (rc) {
+    (void)hipStreamSynchronize(ctx->stream);      // the uploads read the caller's arrays and `ls`
+    return rc;
+  }
+  const NnBlock b = nn_block(N, d, pad_dim(d), M, k);
+  double* const host[3] = {ys_out, mu_out, sd_out};
+  const double* const dev[3] = {ctx->ys, ctx->nn + b.mu, ctx->nn + b.sd};
+  for (int t = 0; t < 3; ++t)
+    if (host[t]) GPBO_HIP(ctx, hipMemcpyAsync(host[t], dev[t], (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<int> nbr32;
+  if (nbr_out) {
+    nbr32.resize((size_t)M * k);
+    GPBO_HIP(ctx, hipMemcpyAsync(nbr32.data(), ctx->nn + b.nbr, nbr32.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (ys_out || mu_out || sd_out || nbr_out) GPBO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t e = 0; e < nbr32.size(); ++e) nbr_out[e] = nbr32[e];
+  return GPBO_OK;
+}
+
 int gpje_jes_argbest(gpbo_ctx* ctx, const double* x_star, const double* f_star, int n_samples, int d, double y_mean, double y_std,
                      int k_seeds, int64_t index_offset, int64_t* best_idx, double* best_val, int64_t* seed_idx, double* seed_val,
                      double* ys_out, double* mu_star_out, double* var_star_out) {
@@ -2248,6 +2310,11 @@ int gpiv_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
 int gpls_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
   if (!ctx) return GPBO_ERR_INVALID;
   return greedy_stage_ms(ctx, ctx->ls_clock, "gpls_debug_stage_ms", "gpls_sur_argbest", ms);
+}
+
+int gpnn_debug_stage_ms(gpbo_ctx* ctx, float* ms) {
+  if (!ctx) return GPBO_ERR_INVALID;
+  return greedy_stage_ms(ctx, ctx->nn_clock, "gpnn_debug_stage_ms", "gpnn_acq_argbest", ms);
 }
 
 int gpje_debug_stage_ms(gpbo_ctx* ctx, float* ms) {

@@ -21,6 +21,7 @@
 #include "gppf.h"
 #include "gpmf.h"
 #include "gpls.h"
+#include "gpnn.h"
 #include "fit_plan.h"        // the fit's size rule, its block size NB and a model's buffer sizes
 #include "posterior_plan.h"   // the posterior's path rule and its row / candidate granules (POST_ROWS, POST_CANDS)
 #include "search_plan.h"      // the one-launch searches' serve rule, LDS layouts and host / device blocks
@@ -108,11 +109,11 @@ struct EventPair {
   hipEvent_t a = nullptr, b = nullptr;
   bool used = false;
 };
-// debug build: the n <= 4 events around the stages of an entry point's last call (greedy.h: greedy_mark; gpbo_api.hip: greedy_stage_ms); the
+// debug build: the n <= 5 events around the stages of an entry point's last call (greedy.h: greedy_mark; gpbo_api.hip: greedy_stage_ms); the
 // product records nothing.  The fields exist in both builds: one layout.
 struct StageClock {
   int n = 0;
-  hipEvent_t ev[4] = {};
+  hipEvent_t ev[5] = {};
   bool used = false;
 };
 
@@ -199,6 +200,8 @@ struct gpbo_ctx {
   int64_t cap_mf = 0;
   double* ls = nullptr;    // gpls_sur_argbest: gpiv_ivr_argbest's layout for the call's points, then h_j^2 | 1 / s_j^2 | p_j per column (sur_plan.h: sur_block)
   int64_t cap_ls = 0;
+  double* nn = nullptr;    // gpnn_acq_argbest: the call's rows, targets, scaled images, mu / sd and neighbour lists (nngp_plan.h: nn_block)
+  int64_t cap_nn = 0;
   double* ehvi = nullptr;  // gpbo_ehvi_argbest: the call's level rows, then one 8-byte word per cell (ehvi.hip)
   int64_t cap_ehvi = 0;
   double* greedy = nullptr;  // the workspace of whichever greedy draw batch runs — gpbo_qnei_greedy (qnei_plan.h), gpbo_cnei_greedy (cnei_plan.h), gpbo_qnhvi_greedy (qnehvi_plan.h), gpmo3_nhvi_greedy (qnehvi3_plan.h): each call writes every part of its layout before it reads it, nothing is carried between calls
@@ -218,6 +221,7 @@ struct gpbo_ctx {
   gpbo::StageClock pf_clock{4};     // around the three stages of the last gppf_pfes_argbest (draws and fronts, scores, selection)
   gpbo::StageClock mf_clock{3};     // around the two stages of the last gpmf_mes_argbest (pair pass, selection)
   gpbo::StageClock ls_clock{4};     // around the three stages of the last gpls_sur_argbest (points, scores, selection)
+  gpbo::StageClock nn_clock{5};     // around the four stages of the last gpnn_acq_argbest (upload and scaling, search, solves, selection)
   hipEvent_t ehvi_ev[2] = {}; // debug build: around the value kernel of the last gpbo_ehvi_argbest (ehvi.hip: ehvi_mark)
   bool ehvi_ev_used = false;
   double* paths = nullptr; // gpbo_sample_paths: features, weights and noise draws of the call | g(X) | W u | V (posterior_paths.hip)
@@ -733,6 +737,20 @@ int launch_ivr_points(gpbo_ctx* ctx, const Model& m, double* ws, const IvrBlock&
 int launch_sur_values(gpbo_ctx* ctx, const Model& m, int64_t M, const double* points, const double* weights, int J, double level,
                       double y_mean, double y_std, double* p_out, double* unc_out);
 void sur_mark_end(gpbo_ctx* ctx);
+// nngp.hip: ctx->ys[i] = -acq of the M resident candidates under the nearest-neighbour GP of the call's own observations and
+// hyper-parameters (include/gpnn.h has the formulas); mu, sd and the sorted neighbour lists stay in ctx->nn (nngp_plan.h: nn_block).
+// X (N, d), y (N,), ls [64] (the length scale per dimension, 1 beyond d): host.  The caller has checked every argument.
+// nn_mark_end: the debug build's event behind the caller's selection.
+struct NnCall {
+  const double* X;
+  const double* y;
+  const double* ls;
+  int64_t N;
+  int d, kernel, k, acq;
+  double amplitude, white, alpha, param, y_max, y_mean, y_std;
+};
+int launch_nn_values(gpbo_ctx* ctx, const NnCall& c);
+void nn_mark_end(gpbo_ctx* ctx);
 // jes.hip: ctx->ys[i] = -a(x_i), the negated joint entropy search value of the M resident candidates over the S sampled optima
 // x_star (S, d; host, parameter space) / f_star (S,; host, raw units) from m's resident mu / sd (include/gpje.h has the formulas);
 // mu_star_out / var_star_out (S,; host) or null.  The caller has checked every argument.  The call's workspace is ctx->je

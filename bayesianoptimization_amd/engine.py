@@ -1007,6 +1007,34 @@ class GpEngine:
         out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
         return out + (p, unc.value) if return_points else out
 
+    def nn_acq_argbest(self, X, y_norm, kernel: int, length_scale, noise: float, k: int, acq: int, param: float, y_max: float = 0.0,
+                       amplitude: float = 1.0, white: float = 0.0, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0,
+                       y_std: float = 1.0, return_values: bool = False, return_posterior: bool = False,
+                       return_neighbors: bool = False):
+        """Nearest-neighbour GP scoring of the resident candidates (gpnn_acq_argbest; include/gpnn.h has the formulas): every
+        candidate's posterior is the exact GP's conditioned on its `k` (16, 32 or 64) nearest rows of `X` (N, d), k <= N <= 2^20,
+        in the metric of `length_scale`, at the FIXED hyper-parameters given — `noise` the estimator's alpha, `amplitude` / `white`
+        the scaled model amplitude * (k + white * I) + noise * I —, and ys = -acq(mu, sd) for `acq` in UCB / EI / POI / LOG_EI
+        with `param` and `y_max` as `acq_argbest`.  `y_norm` (N,): the normalised targets; `y_mean` / `y_std` put mu and sd back into
+        raw units.  No slot is read or written: no fit is needed, and none is disturbed.  Returns (best_idx, best_val, seed_idx,
+        seed_val, ys|None) as `acq_argbest`; `return_posterior=True` appends mu (M,) and sd (M,), `return_neighbors=True` the
+        neighbours' row indices (M, k), nearest first."""
+        X, y_norm, ls = _model_arrays(X, y_norm, length_scale)
+        k, k_seeds, M = int(k), int(k_seeds), self.n_candidates
+        _lb, _ub, _n_c, seed_idx, seed_val, ys = _argbest_frame(None, None, k_seeds, M if return_values else None)
+        mu, sd = (np.empty(M), np.empty(M)) if return_posterior else (None, None)
+        nbr = np.empty((M, max(k, 0)), dtype=np.int64) if return_neighbors else None
+        best_idx, best_val = C.c_int64(0), C.c_double(0.0)
+        self._check(self._lib.gpnn_acq_argbest(self._h, dptr(X), dptr(y_norm), int(X.shape[0]), int(X.shape[1]), int(kernel), dptr(ls),
+                                               int(ls.shape[0]), float(amplitude), float(white), float(noise), k, int(acq),
+                                               float(param), float(y_max if y_max is not None else 0.0), float(y_mean), float(y_std),
+                                               k_seeds, int(index_offset), C.byref(best_idx), C.byref(best_val), iptr(seed_idx),
+                                               dptr(seed_val), dptr(ys), dptr(mu), dptr(sd), iptr(nbr)))
+        out = (best_idx.value, best_val.value, seed_idx[:k_seeds], seed_val[:k_seeds], ys)
+        if return_posterior:
+            out += (mu, sd)
+        return out + (nbr,) if return_neighbors else out
+
     def jes_argbest(self, x_star, f_star, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                     return_values: bool = False, return_star: bool = False):
         """Joint entropy search, lower bound, over the resident candidates (gpje_jes_argbest; include/gpje.h has the formulas): ys =
@@ -1581,6 +1609,14 @@ class GpEngine:
         self._check(self._lib.gpls_debug_stage_ms(self._h, ms))
         return tuple(float(v) for v in ms)
 
+    def debug_nn_stage_ms(self):
+        """gpnn_debug_stage_ms (debug build): kernel ms of the last `nn_acq_argbest`'s stages, (upload and scaling, neighbour
+        search, local solves, selection)."""
+        self._need_debug("gpnn_debug_stage_ms")
+        ms = (C.c_float * 4)()
+        self._check(self._lib.gpnn_debug_stage_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
     def debug_jes_stage_ms(self):
         """gpje_debug_stage_ms (debug build): kernel ms of the last `jes_argbest`'s stages, (points, scores, selection)."""
         self._need_debug("gpje_debug_stage_ms")
@@ -2085,6 +2121,10 @@ class GroupEngine(GpEngine):
     def sur_argbest(self, points, level, weights=None, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                     return_values: bool = False, return_points: bool = False):
         raise NotImplementedError("a device group has no level-set acquisition (gpls_sur_argbest is per context); use a single device")
+
+    def nn_acq_argbest(self, X, y_norm, kernel: int, length_scale, noise: float, k: int, acq: int, param: float, **kw):
+        raise NotImplementedError("a device group has no nearest-neighbour GP scoring (gpnn_acq_argbest is per context); use a "
+                                  "single device")
 
     def jes_argbest(self, x_star, f_star, k_seeds: int = 0, index_offset: int = 0, y_mean: float = 0.0, y_std: float = 1.0,
                     return_values: bool = False, return_star: bool = False):
